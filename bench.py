@@ -9,6 +9,9 @@ N_gpus * sum(U) / max-over-ranks(step time), in GiB/s.  Multi-GPU: one process p
 rank works on its own 4096 blocks (weak scaling), no data-path collective; the int32 size vector
 is all-gathered once outside the timed region.
 
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last step returned as DIR/<name>.npy (dump_outputs()); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 Extra objects on the JSON line:
   roofline      dominant kernel (the encoder: k4_parse_kernel, which decides the sequences and writes the blocks
                 out) -- algorithmic bytes per launch (sum(U)+sum(C)+12N) / median launch duration measured
@@ -110,10 +113,55 @@ def strong(args):
     dist.destroy_process_group()
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: the files' total size at most
+DUMP_SAMPLE_BLOCKS = 64
+DUMP_SEED = 1
+
+
+def dump_outputs(out_dir, comp, clen, back, dlen, bound, bs):
+    """--dump-outputs DIR: what the timed path handed its caller after the last step, so that two builds can be compared output
+    for output on the same inputs.  Every block's compressed and decoded length and the Adler-32 of its compressed and decoded
+    bytes (float64, exact); the bytes themselves (float32, exact) for a fixed seeded sample of blocks, one row per block, zero
+    past the block's length.  At most DUMP_BYTES in all."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(clen.numel())
+    clen_h = clen.cpu().numpy().astype(np.int64)
+    dlen_h = dlen.cpu().numpy().astype(np.int64)
+    comp_h, coff_h = comp.data.cpu().numpy(), comp.off.cpu().numpy().astype(np.int64)
+    back_h, boff_h = back.data.cpu().numpy(), back.off.cpu().numpy().astype(np.int64)
+
+    def view(buf, off, length, cap, i):
+        o = int(off[i])
+        return buf[o:o + max(0, min(int(length[i]), cap))]
+
+    arrays = {
+        "encoded_length": clen_h.astype(np.float64),
+        "decoded_length": dlen_h.astype(np.float64),
+        "encoded_adler32": np.array([zlib.adler32(view(comp_h, coff_h, clen_h, bound, i)) for i in range(n)], np.float64),
+        "decoded_adler32": np.array([zlib.adler32(view(back_h, boff_h, dlen_h, bs, i)) for i in range(n)], np.float64),
+    }
+    room = DUMP_BYTES - 4 * n * 8 - (1 << 16)          # the per-block vectors, the sample's index and the .npy headers
+    k = int(min(n, DUMP_SAMPLE_BLOCKS, max(1, room // ((bound + bs) * 4))))
+    w_enc, w_dec = (bound, bs) if k * (bound + bs) * 4 <= room else (room // 8, room // 8)   # one block over the budget: its head
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    enc = np.zeros((k, w_enc), np.float32)
+    dec = np.zeros((k, w_dec), np.float32)
+    for row, i in enumerate(pick):
+        e = view(comp_h, coff_h, clen_h, bound, i)[:w_enc]
+        d = view(back_h, boff_h, dlen_h, bs, i)[:w_dec]
+        enc[row, :e.size] = e
+        dec[row, :d.size] = d
+    arrays.update(sample_block_index=pick.astype(np.float64), encoded_bytes_sample=enc, decoded_bytes_sample=dec)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --strong times one pass and takes none)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=4096)
     ap.add_argument("--block-size", type=int, default=65536)
@@ -124,9 +172,19 @@ def main():
                     help="ONE configs[3] batch (LZ4Pickler over --messages variable-length messages) split over the ranks by bytes; "
                          "not the headline metric, reported as its own line")
     ap.add_argument("--messages", type=int, default=100000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (compressed and decoded lengths and "
+                         "Adler-32 of every block, the bytes of a seeded sample of blocks) as DIR/<name>.npy, float64 / float32")
     args = ap.parse_args()
     if args.strong:
+        # one timed pass over one batch: neither a step count nor the headline path's outputs apply
+        if args.steps is not None or args.dump_outputs:
+            ap.error("--strong times one pass and writes no outputs: --steps and --dump-outputs do not apply")
         return strong(args)
+    if args.steps is None:
+        args.steps = 20
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -202,6 +260,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=on)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, comp, clen, back, dlen, bound, bs)
 
     enc_ms = np.array([e[0].elapsed_time(e[1]) for e in events])
     dec_ms = np.array([e[1].elapsed_time(e[2]) for e in events])

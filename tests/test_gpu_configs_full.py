@@ -532,3 +532,67 @@ def test_headline_bench_with_two_ranks_is_the_command_the_scaling_run_launches(o
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and lines, p.stderr[-2000:]
     assert json.loads(lines[-1])["bit_exact"] is False
+
+
+def test_bench_dump_outputs_are_what_the_timed_path_returned(oracle, tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's outputs as .npy (float64 / float32, 64 MB at most) -- every block's
+    compressed and decoded length and Adler-32, the bytes of a seeded sample of blocks -- equal the oracle's encode of the
+    same seeded inputs and the inputs themselves (the step count itself: the test below)"""
+    import json, subprocess, sys, zlib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nb = 96
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--blocks", str(nb), "--steps", "2", "--warmup", "1",
+           "--no-host-path", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k != "K4LZ4_CORPUS_DIR"}
+    p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert p.returncode == 0 and lines, p.stderr[-2000:]
+    r = json.loads(lines[-1])
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["bit_exact"] is True
+    d = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(d) == {"encoded_length", "decoded_length", "encoded_adler32", "decoded_adler32", "sample_block_index",
+                      "encoded_bytes_sample", "decoded_bytes_sample"}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
+    blocks = corpus.silesia_like_blocks(nb, 65536, seed=2)
+    want = [oracle.encode(b) for b in blocks]
+    assert d["encoded_length"].tolist() == [len(w) for w in want]
+    assert d["encoded_adler32"].tolist() == [zlib.adler32(w) for w in want]
+    assert (d["decoded_length"] == 65536).all()
+    assert d["decoded_adler32"].tolist() == [zlib.adler32(b.tobytes()) for b in blocks]
+    idx = d["sample_block_index"].astype(np.int64)
+    assert idx.size == 64 and np.array_equal(d["decoded_bytes_sample"], blocks[idx].astype(np.float32))
+    for row, i in enumerate(idx):
+        w = np.frombuffer(want[i], np.uint8).astype(np.float32)
+        e = d["encoded_bytes_sample"][row]
+        assert np.array_equal(e[:w.size], w) and not e[w.size:].any(), i
+
+
+def test_bench_steps_sets_the_number_of_timed_steps(monkeypatch, capsys):
+    """`--steps K --warmup W` on the headline path: the encoder and the decoder are called W + K times, K of those steps
+    bracketed by timing events (3 per step), and the line reports K and the window over K"""
+    import json, sys
+    import torch
+    import bench
+    from k4os.compression.lz4_amd.device import DeviceCodec
+    calls = {"encode": 0, "decode": 0, "events": 0}
+    for name in ("encode", "decode"):
+        def counted(self, *a, _real=getattr(DeviceCodec, name), _name=name, **k):
+            calls[_name] += 1
+            return _real(self, *a, **k)
+        monkeypatch.setattr(DeviceCodec, name, counted)
+
+    def counted_event(*a, _real=torch.cuda.Event, **k):
+        calls["events"] += 1
+        return _real(*a, **k)
+
+    monkeypatch.setattr(torch.cuda, "Event", counted_event)
+    monkeypatch.delenv("K4LZ4_CORPUS_DIR", raising=False)
+    nb, steps, warmup = 64, 5, 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--blocks", str(nb), "--steps", str(steps), "--warmup", str(warmup),
+                                      "--no-host-path", "--no-cpu-baseline", "--no-verify"])
+    bench.main()
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    r = json.loads(lines[-1])
+    assert calls == {"encode": warmup + steps, "decode": warmup + steps, "events": 3 * steps}
+    assert r["steps"] == steps and r["ms_per_step"] > 0
+    assert abs(r["value"] - nb * 65536 / 2 ** 30 / (r["ms_per_step"] * 1e-3)) < 0.01 * r["value"]
