@@ -64,6 +64,14 @@ namespace K4os.Compression.LZ4.Engine
 		[DllImport(Lib)] public static extern int k4lz4_decode_chain_batch(
 			IntPtr ctx, byte* src, ulong* blkOff, uint* blkLen, long nBlocks, ulong* firstBlk, uint* nBlk, int* blockSize, byte* chained,
 			byte* dst, ulong* dstOff, ulong* dstCap, long* outLen, long nStreams);
+		// chained HC streams: LZ4HighChainEncoder(level, blockSize, extraBlocks) over whole contents, every block of every stream in
+		// one launch sequence; dictLen (may be null): ring-buffer bytes in front of each content's first new block
+		[DllImport(Lib)] public static extern int k4lz4_encode_hc_chain_batch(
+			IntPtr ctx, byte* src, ulong* srcOff, long* srcLen, int* blockSize, int* extraBlocks, int* dictLen, long nStreams,
+			byte* dst, ulong* dstOff, int* outLen, long nBlocks, int level, int flags);
+		[DllImport(Lib)] public static extern int k4lz4_encode_hc_chain_batch_device(
+			IntPtr ctx, IntPtr src, ulong* srcOff, long* srcLen, int* blockSize, int* extraBlocks, int* dictLen, long nStreams,
+			IntPtr dst, ulong* dstOff, IntPtr outLen, long nBlocks, int level, int flags, IntPtr stream);
 
 		// ---- device-resident variants: every pointer is a device pointer of the context's GPU, stream = hipStream_t
 		[DllImport(Lib)] public static extern int k4lz4_encode_batch_device(

@@ -1,8 +1,10 @@
 // Streams/Frames/LZ4FrameBatch.cs -- whole-buffer frames through the batch calls: what LZ4FrameWriter / LZ4FrameReader do one
 // block at a time (Frames/LZ4FrameWriter.async.cs:15-90: length word with raw bit, payload, optional block checksum, EndMark,
 // optional content checksum; Frames/LZ4FrameReader.async.cs:108-136), done for all blocks of a frame -- or of many frames -- with
-// one encode / decode launch and one XXH32 launch.  Frames of independent blocks only (LZ4EncoderSettings.ChainBlocks = false):
-// chained blocks depend on each other and do not batch (the reader side does decode them, in order, k4lz4_decode_chain_batch).
+// one encode / decode launch and one XXH32 launch.  Chained frames (ChainBlocks = true, the reference's default) at L03_HC and up
+// are LZ4HighChainEncoder's blocks, from k4lz4_encode_hc_chain_batch: a chained HC block needs the bytes before it, not the parse
+// of the block before it (DESIGN.md).  Chained L00_FAST frames stay with LZ4FrameWriter (LZ4FastChainEncoder's table depends on
+// its parse: serial per stream).  The reader side decodes both, chained blocks in order (k4lz4_decode_chain_batch).
 // Byte layout and header arithmetic are LZ4FrameWriter.cs:57-108,:159-189.  Compile-unverified.
 using System;
 using System.Buffers.Binary;
@@ -17,16 +19,39 @@ namespace K4os.Compression.LZ4.Streams.Frames
 
 		/// <summary>One LZ4 frame (independent blocks) around content, byte-identical to what LZ4FrameWriter writes for the same
 		/// settings when its input arrives in one piece.</summary>
+		/// <summary>LZ4HighChainEncoder(level, blockSize, extraBlocks) over the whole content (Streams/Extensions.cs:18-36), one native
+		/// call: block i to arena[i * slot], encoded[i] as LZ4EncoderBase.Encode(allowCopy: true) returns it.</summary>
+		private static void EncodeChained(ReadOnlySpan<byte> content, LZ4EncoderSettings settings, int blockSize, byte[] arena, int[] encoded, int n)
+		{
+			if (n == 0) return;
+			var extra = Math.Max(settings.ExtraMemory > 0 ? blockSize : 0, settings.ExtraMemory) / blockSize;
+			ulong srcOff = 0, dstOff = 0;
+			long srcLen = content.Length;
+			using var lease = NativeContext.Rent();
+			fixed (byte* src = content)
+			fixed (byte* dst = arena)
+			fixed (int* outLen = encoded)
+				LLNative.ThrowIfFailed(LLNative.k4lz4_encode_hc_chain_batch(lease.Handle, src, &srcOff, &srcLen, &blockSize, &extra, null, 1,
+					dst, &dstOff, outLen, n, (int) settings.CompressionLevel, LLNative.FLAG_ALLOW_COPY), lease.Handle);
+		}
+
 		public static byte[] Encode(ReadOnlySpan<byte> content, LZ4EncoderSettings settings)
 		{
-			if (settings.ChainBlocks) throw new NotSupportedException("chained blocks are encoded one after the other: use LZ4FrameWriter");
+			var chained = settings.ChainBlocks;
+			if (chained && settings.CompressionLevel < LZ4Level.L03_HC)
+				throw new NotSupportedException("chained L00_FAST blocks depend on each other's parse: use LZ4FrameWriter");
 			var blockSize = MaxBlockSize(settings.BlockSize, out var bdCode);
-			var n = (int) (((long) content.Length + blockSize - 1) / blockSize);
-			var slot = LZ4Codec.MaximumOutputSize(blockSize);
+			// the chained encoder's blocks are its ring buffer's: the block size rounded up to a whole KiB (LZ4EncoderBase.cs:23)
+			var encoderBlock = chained ? (Math.Max(blockSize, 1024) + 1023) / 1024 * 1024 : blockSize;
+			var n = (int) (((long) content.Length + encoderBlock - 1) / encoderBlock);
+			var slot = LZ4Codec.MaximumOutputSize(encoderBlock);
 			var arena = new byte[Math.Max(1, (long) n * slot)];
-			var encoded = new int[n];
-			using (var encoder = new LZ4BlockEncoder(settings.CompressionLevel, blockSize))
-				encoder.EncodeBlocks(content, arena, encoded, allowCopy: true);
+			var encoded = new int[Math.Max(1, n)];
+			if (chained)
+				EncodeChained(content, settings, blockSize, arena, encoded, n);
+			else
+				using (var encoder = new LZ4BlockEncoder(settings.CompressionLevel, blockSize))
+					encoder.EncodeBlocks(content, arena, encoded, allowCopy: true);
 
 			// sizes: header 7 (+8 content length), per block 4 + stored (+4), EndMark 4 (+4)
 			long total = 7 + (settings.ContentLength.HasValue ? 8 : 0) + 4 + (settings.ContentChecksum ? 4 : 0);
@@ -35,7 +60,7 @@ namespace K4os.Compression.LZ4.Streams.Frames
 			var at = 0;
 			BinaryPrimitives.WriteUInt32LittleEndian(frame.AsSpan(at), Magic); at += 4;
 			var headerStart = at;
-			frame[at++] = (byte) ((1 << 6) | (1 << 5) /* independent */ | (settings.BlockChecksum ? 1 << 4 : 0) |
+			frame[at++] = (byte) ((1 << 6) | (chained ? 0 : 1 << 5) /* FLG bit 5: independent blocks */ | (settings.BlockChecksum ? 1 << 4 : 0) |
 				(settings.ContentLength.HasValue ? 1 << 3 : 0) | (settings.ContentChecksum ? 1 << 2 : 0));
 			frame[at++] = (byte) (bdCode << 4);
 			if (settings.ContentLength.HasValue) { BinaryPrimitives.WriteUInt64LittleEndian(frame.AsSpan(at), (ulong) settings.ContentLength.Value); at += 8; }

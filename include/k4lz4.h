@@ -259,6 +259,32 @@ K4LZ4_API int k4lz4_decode_chain_batch_device(k4lz4_ctx *ctx, const uint8_t *src
                                               const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen,
                                               int64_t nStreams, void *stream);
 
+/* Chained HC block streams: LZ4HighChainEncoder(level, blockSize, extraBlocks) (Encoders/LZ4HighChainEncoder.cs, LZ4EncoderBase.cs)
+ * fed a whole content and flushed block by block -- LZ4_compress_HC_continue over the encoder's ring buffer, LZ4_saveDictHC when it
+ * is full -- which is what LZ4Stream.Encode / LZ4Frame.Encode write at L03_HC .. L12_MAX with ChainBlocks = true (their default).
+ * Many streams per call; the blocks of all of them are encoded side by side (a block needs the bytes before it, not
+ * the parse of the block before it).  Stream s: content src + srcOff[s], srcLen[s] bytes; blockSize[s] is rounded up to a whole
+ * KiB, at least 1 KiB (call it B); extraBlocks[s] as the encoder's constructor takes it (NULL: 0 for every stream; the frame
+ * writer passes max(extraMemory > 0 ? blockSize : 0, extraMemory) / blockSize, Streams/Extensions.cs:18-19).  dictLen[s] (NULL:
+ * 0): the stream continues an encoder whose ring buffer holds the content's first dictLen[s] bytes in front of the next block
+ * (LZ4EncoderBase's buffer before _inputIndex, at most 65536 + (1 + extraBlocks) * B + 32 bytes): no block is written for them.
+ * Stream s has ceil((srcLen[s] - dictLen[s]) / B) blocks; block j of it is written to dst + dstOff[s] + j * k4lz4_compress_bound(B), its result is
+ * outLen[first(s) + j], where first(s) is the number of blocks of the streams before s (nBlocks: entries of outLen, at least
+ * the total).  outLen: bytes written, or with K4LZ4_FLAG_ALLOW_COPY (LZ4EncoderBase.Encode(allowCopy)) -length for a block
+ * stored raw.  level is clamped to 3..12 like the constructor does.  The only flag is K4LZ4_FLAG_ALLOW_COPY.  A stream whose
+ * blocks reach 2 GB (LZ4_compressHC_continue_generic renormalises there) is refused with K4LZ4_E_ARG (counted from the content's
+ * start: a caller that continues a longer stream through dictLen checks its own position).
+ * _device: src, dst and outLen are device pointers; srcOff, srcLen, blockSize, extraBlocks and dstOff stay HOST arrays (the
+ * block table is host index work, built inside the call).  Asynchronous on `stream` like the other *_device calls. */
+K4LZ4_API int k4lz4_encode_hc_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+                                          const int32_t *blockSize, const int32_t *extraBlocks, const int32_t *dictLen,
+                                          int64_t nStreams, uint8_t *dst, const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks,
+                                          int level, int flags);
+K4LZ4_API int k4lz4_encode_hc_chain_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+                                                 const int32_t *blockSize, const int32_t *extraBlocks, const int32_t *dictLen,
+                                                 int64_t nStreams, uint8_t *dst, const uint64_t *dstOff, int32_t *outLen,
+                                                 int64_t nBlocks, int level, int flags, void *stream);
+
 /* Frame writer on device-resident data: after k4lz4_encode_batch_device(..., K4LZ4_FLAG_ALLOW_COPY) and
  * k4lz4_xxh32_batch_device, lays the frames out (Frames/LZ4FrameWriter.cs:57-108 header, LZ4FrameWriter.async.cs:15-27
  * block records, :75-90 EndMark + content checksum).  The caller computes the positions (recOff, frameOff, tailOff) from

@@ -127,6 +127,11 @@ struct k4lz4_ctx {
     bool parse_pcost = false;             /* K4LZ4_PCOST: the parse's own cost estimate (k4_pcost_kernel) orders the blocks; measured: costs more than it gains */
     int parse_waves = 16;                 /* K4LZ4_PARSE_WAVES: blocks per workgroup (= per CU) of the parse kernel, at most PARSE_MAX_WAVES */
     bool trace = false;         /* K4LZ4_TRACE: host-pointer calls print where their time went (stderr) */
+    /* chained HC streams (k4lz4_encode_hc_chain_batch*): the block table, built on the host, and its copy on the device; the
+     * host copy is rewritten only after ev_chain says the previous upload of it is over */
+    std::vector<uint8_t> h_chain;
+    uint8_t *d_chain = nullptr; size_t d_chain_cap = 0;
+    hipEvent_t ev_chain = nullptr;
 };
 
 /* a few helper threads for the staging copies of big host-pointer calls (memcpy between the caller's pageable memory and
@@ -242,9 +247,11 @@ int take_device_status(k4lz4_ctx *ctx)
 /* HC levels: layout -> (sync for the scratch size) -> hash-table clear -> chain kernel -> parse kernel.
  * `pickle`: the same around the LZ4Pickler envelope (encoder slot = envelope + 5, cap U - 1). */
 /* hostLen: the blocks' lengths when the caller has them on the host (host-pointer calls), else nullptr */
+/* hist: chained HC streams (k4::HcArgs::hist, device pointer), else nullptr -- such a batch takes the memory paths: the LDS
+ * kernels are built around blocks of at most 64 KiB that start at their position 0 */
 int launch_hc(k4lz4_ctx *ctx, bool pickle, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
               const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
-              hipStream_t stream, const int32_t *hostLen)
+              hipStream_t stream, const int32_t *hostLen, const int32_t *hist = nullptr)
 {
     const int64_t chunk_max = 4096;   /* 128 KiB of hash table per block in flight */
     for (int64_t first = 0; first < n; first += chunk_max) {
@@ -266,6 +273,8 @@ int launch_hc(k4lz4_ctx *ctx, bool pickle, const uint8_t *src, const uint64_t *s
         h.dst = dst; h.dstOff = dstOff + first; h.dstCap = dstCap + first; h.outLen = outLen + first;
         h.n = cnt; h.level = level; h.flags = flags;
         h.hash = (uint32_t *)ctx->d_hc_hash; h.workOff = d_woff;
+        h.hist = hist ? hist + first : nullptr;
+        const bool lds_ok = hist == nullptr;
         k4::BatchArgs a{};
         a.src = src; a.srcOff = h.srcOff; a.srcLen = h.srcLen; a.dst = dst; a.dstOff = h.dstOff; a.dstCap = h.dstCap;
         a.outLen = h.outLen; a.n = cnt; a.level = level; a.accel = 1; a.flags = flags;
@@ -305,11 +314,11 @@ int launch_hc(k4lz4_ctx *ctx, bool pickle, const uint8_t *src, const uint64_t *s
             if (rc != K4LZ4_OK) return rc;
         }
         h.work = ctx->d_hc_work;
-        if (tail[1] <= 65536 && ctx->hc_chain_parts) {
+        if (tail[1] <= 65536 && lds_ok && ctx->hc_chain_parts) {
             /* no block over 64 KiB: eight waves per block, each with an eighth of the hash values and of the table (round 6) */
             h.nChain = cnt;
             hipLaunchKernelGGL(k4::k4_hc_chain_part_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_CHAIN_PARTS), 0, stream, h);
-        } else if (tail[1] <= 65536) {
+        } else if (tail[1] <= 65536 && lds_ok) {
             /* (rounds 3-5, K4LZ4_HC_CHAIN_OLD) no block over 64 KiB (known from the host lengths, the reservation or the device): hash tables in LDS -- two blocks
              * per CU, a wave each, which leaves the CU's other wave slots empty; so the last third of a big chunk goes through the
              * table-in-memory kernel on the second queue at the same time (its tables: 128 KiB per block, cleared here) */
@@ -333,7 +342,7 @@ int launch_hc(k4lz4_ctx *ctx, bool pickle, const uint8_t *src, const uint64_t *s
             hipLaunchKernelGGL(k4::k4_hc_chain_kernel, dim3((unsigned)((cnt + k4::HC_CHAIN_WAVES_PER_WG - 1) / k4::HC_CHAIN_WAVES_PER_WG)), dim3(64 * k4::HC_CHAIN_WAVES_PER_WG), 0, stream, h);
         }
         const bool optimal = level >= K4LZ4_L10_OPT;              /* clTable (LL64.high.cs:1124-1138): lz4opt strategy */
-        if (tail[1] >= 13 && tail[1] <= 65536 && !optimal && ctx->hc_cand_lds) {
+        if (tail[1] >= 13 && tail[1] <= 65536 && lds_ok && !optimal && ctx->hc_cand_lds) {
             /* no block over 64 KiB: the candidates' records out of LDS (k4_hc_walk_lds_kernel, k4_hc_cand_lds_kernel; round 6) */
             hipLaunchKernelGGL(k4::k4_hc_walk_lds_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_LDS_WAVES), 0, stream, h);
             hipLaunchKernelGGL(k4::k4_hc_cand_lds_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_CAND_LDS_WAVES), 0, stream, h);
@@ -355,7 +364,7 @@ int launch_hc(k4lz4_ctx *ctx, bool pickle, const uint8_t *src, const uint64_t *s
              * block) and the same wave turns them into bytes afterwards; without room for them LZ4HC_encodeSequence stays in the loop */
             /* ... by two or four waves per block while the chip has the wave slots for them (k4lz4_encode_hc.hpp, HcSegs; round 6) */
             int nseg = 1;
-            if (level <= K4LZ4_L03_HC && tail[1] <= 65536 && ctx->hc_records) {
+            if (level <= K4LZ4_L03_HC && tail[1] <= 65536 && lds_ok && ctx->hc_records) {
                 const int64_t slots = 32 * (int64_t)ctx->cu_count;
                 nseg = ctx->hc_segs > 0 ? ctx->hc_segs : (cnt * 2 <= slots ? 4 : 1);      /* (measured, profiles/r6_hc_ab.txt: four waves per block beat two even when they take turns -- 4096 blocks: 9.5 against 12.2-13.3 ms, one wave 13.9) */
                 if (tail[1] < k4::HC_SEG_MIN_LEN) nseg = 1;
@@ -1388,6 +1397,120 @@ int single(Kind kind, const uint8_t *src, uint8_t *dst, int srcLen, int dstCap, 
     return out;
 }
 
+/* ---- chained HC streams (LZ4HighChainEncoder, k4lz4_encode_hc_chain_batch) ------------------------------------------------
+ * LZ4EncoderBase's ring buffer (Encoders/LZ4EncoderBase.cs: Topup / Encode / Commit -> LZ4_saveDictHC, Engine/LL.high.cs:168) in
+ * stream coordinates.  Block k of a stream is LZ4_compress_HC_continue over [s, s + len) with everything since dictLimit in front of
+ * it.  The HC tables are a function of the data alone (k4lz4_encode_hc.hpp), so what the block needs of the blocks before it is
+ * their bytes: a window from max(dictLimit, s - 65536) on -- no search reaches further back (lowestMatchIndex, LL64.high.cs:93-94)
+ * and lowLimit == dictLimit throughout, so the extDict arm is never taken.  Every block of every stream is therefore independent
+ * of the others' parses and the whole batch is one launch sequence. */
+struct HcChainPlan {
+    int64_t nb = 0;
+    uint64_t *woff = nullptr, *boff = nullptr, *doff = nullptr;   /* window / block start in src, slot in dst */
+    int32_t *wlen = nullptr, *hist = nullptr, *blen = nullptr, *cap = nullptr;
+    static constexpr size_t PER_BLOCK = 3 * 8 + 4 * 4;
+    void place(uint8_t *base, int64_t n)
+    {
+        nb = n;
+        woff = (uint64_t *)base; boff = woff + n; doff = boff + n;
+        wlen = (int32_t *)(doff + n); hist = wlen + n; blen = hist + n; cap = blen + n;
+    }
+};
+
+/* LZ4EncoderBase's block size: rounded up to a whole KiB, at least 1 KiB (LZ4EncoderBase.cs:23) */
+int64_t hc_chain_block_size(int32_t blockSize) { const int64_t b = std::max<int64_t>(blockSize, 1024); return (b + 1023) / 1024 * 1024; }
+
+/* counts the blocks (fill == nullptr) or lays the table out in `fill`; the streams' contents start at srcOff[s], their first dictLen[s]
+ * bytes are what the encoder's ring buffer already holds (ptr = dictLen, dictLimit at the content's start), block j of stream s goes to
+ * dstOff[s] + j * k4lz4_compress_bound(B) */
+int hc_chain_table(k4lz4_ctx *ctx, const uint64_t *srcOff, const int64_t *srcLen, const int32_t *blockSize, const int32_t *extraBlocks,
+                   const int32_t *dictLen, int64_t nStreams, const uint64_t *dstOff, int64_t &nb, HcChainPlan *fill)
+{
+    int64_t k = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t N = srcLen[si];
+        const int64_t B = hc_chain_block_size(blockSize[si]);
+        const int64_t extra = extraBlocks ? std::max<int32_t>(extraBlocks[si], 0) : 0;
+        const int64_t D = dictLen ? dictLen[si] : 0;
+        if (N < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: negative content length");
+        if (D < 0 || D > N) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: dictLen outside the content");
+        if (B > k4::MAX_INPUT_SIZE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: block size above the input size limit");
+        const int64_t L = 65536 + (1 + extra) * B + 32;                   /* the ring buffer (LZ4EncoderBase.cs:25) */
+        const int64_t slot = B + B / 255 + 16;                            /* k4lz4_compress_bound(B) */
+        int64_t ptr = D, dl = 0, pos = D, j = 0;
+        while (pos < N) {
+            /* LZ4_compressHC_continue_generic renormalises once end - base > 2 GB (LL64.high.cs:1271-1276): not offered */
+            if (65536 + pos > ((int64_t)1 << 31))
+                return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
+            const int64_t len = std::min(B, N - pos);
+            const int64_t ws = std::max(dl, pos - 65536);
+            if (fill) {
+                fill->woff[k] = srcOff[si] + (uint64_t)ws; fill->boff[k] = srcOff[si] + (uint64_t)pos;
+                fill->doff[k] = dstOff[si] + (uint64_t)(j * slot);
+                fill->wlen[k] = (int32_t)(pos - ws + len); fill->hist[k] = (int32_t)(pos - ws);
+                fill->blen[k] = (int32_t)len; fill->cap[k] = (int32_t)slot;
+            }
+            k++; j++;
+            pos += len; ptr += len;
+            if (ptr + B > L) {                                            /* Commit -> LZ4_saveDictHC(ctx, buf, ptr) */
+                int64_t d = std::min<int64_t>(65536, std::min(ptr, pos - dl));
+                if (d < 4) d = 0;
+                dl = pos - d; ptr = d;
+            }
+        }
+    }
+    nb = k;
+    return K4LZ4_OK;
+}
+
+/* k4lz4_encode_hc_chain_batch_device: src / dst / outLen device pointers, the per-stream arrays host pointers */
+int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen, const int32_t *blockSize,
+                 const int32_t *extraBlocks, const int32_t *dictLen, int64_t nStreams, uint8_t *dst, const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks,
+                 int level, int flags, hipStream_t stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (nStreams < 0 || nBlocks < 0 || (nStreams > 0 && (!src || !srcOff || !srcLen || !blockSize || !dst || !dstOff || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (flags & ~(int)K4LZ4_FLAG_ALLOW_COPY) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: the only flag it takes is K4LZ4_FLAG_ALLOW_COPY");
+    level = std::max<int>(K4LZ4_L03_HC, std::min<int>(K4LZ4_L12_MAX, level));       /* LZ4HighChainEncoder's constructor */
+    int64_t nb = 0;
+    int rc = hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, nullptr);
+    if (rc != K4LZ4_OK) return rc;
+    if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: outLen has fewer entries than the streams have blocks");
+    if (nb == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->ev_chain) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_chain));        /* the previous upload of the host table is over */
+    const size_t bytes = (size_t)nb * HcChainPlan::PER_BLOCK;
+    try { ctx->h_chain.resize(bytes); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    HcChainPlan h;
+    h.place(ctx->h_chain.data(), nb);
+    rc = hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, &h);
+    if (rc != K4LZ4_OK) return rc;
+    if (bytes > ctx->d_chain_cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));     /* (grow frees the old table) */
+    if ((rc = grow(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes, false)) != K4LZ4_OK) return rc;
+    HcChainPlan d;
+    d.place(ctx->d_chain, nb);
+    if (ctx->busy && ctx->last_stream != stream) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_busy, 0));
+    K4_HIP(ctx, hipMemcpyAsync(ctx->d_chain, ctx->h_chain.data(), bytes, hipMemcpyHostToDevice, stream));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_chain, stream));
+    rc = launch_hc(ctx, false, src, d.woff, d.wlen, dst, d.doff, d.cap, outLen, nb, level, 0, stream, h.wlen, d.hist);
+    if (rc == K4LZ4_OK && (flags & K4LZ4_FLAG_ALLOW_COPY)) {
+        /* LZ4EncoderBase.Encode(allowCopy): a block that did not shrink is stored raw -- its bytes stay in the history all the same */
+        for (int64_t first = 0; first < nb; first += (int64_t)1 << 24) {
+            const int64_t cnt = std::min<int64_t>((int64_t)1 << 24, nb - first);
+            k4::BatchArgs a{};
+            a.src = src; a.srcOff = d.boff + first; a.srcLen = d.blen + first;
+            a.dst = dst; a.dstOff = d.doff + first; a.dstCap = d.cap + first; a.outLen = outLen + first; a.n = cnt;
+            hipLaunchKernelGGL(k4::k4_allow_copy_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, stream, a);
+        }
+        if (hipGetLastError() != hipSuccess) rc = fail(ctx, K4LZ4_E_HIP, "k4_allow_copy_kernel launch failed");
+    }
+    if (hipEventRecord(ctx->ev_busy, stream) == hipSuccess) { ctx->busy = true; ctx->last_stream = stream; }
+    else (void)hipGetLastError();
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1538,6 +1661,8 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_hc_hash) (void)hipFree(ctx->d_hc_hash);
     if (ctx->d_hc_work) (void)hipFree(ctx->d_hc_work);
     if (ctx->d_hc_meta) (void)hipFree(ctx->d_hc_meta);
+    if (ctx->d_chain) (void)hipFree(ctx->d_chain);
+    if (ctx->ev_chain) (void)hipEventDestroy(ctx->ev_chain);
     if (ctx->d_pk_meta) (void)hipFree(ctx->d_pk_meta);
     delete ctx;
 }
@@ -1954,6 +2079,66 @@ int k4lz4_unpickle_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64
     a.src = src; a.srcOff = srcOff; a.srcLen = srcLen; a.outLen = outLen; a.n = n;
     hipLaunchKernelGGL(k4::k4_unpickle_sizes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     K4_HIP(ctx, hipGetLastError());
+    return K4LZ4_OK;
+}
+
+int k4lz4_encode_hc_chain_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+                                       const int32_t *blockSize, const int32_t *extraBlocks, const int32_t *dictLen, int64_t nStreams,
+                                       uint8_t *dst, const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks, int level, int flags,
+                                       void *stream)
+{
+    return hc_chain_run(ctx, src, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dst, dstOff, outLen, nBlocks, level, flags,
+                        (hipStream_t)stream);
+}
+
+int k4lz4_encode_hc_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+                                const int32_t *blockSize, const int32_t *extraBlocks, const int32_t *dictLen, int64_t nStreams,
+                                uint8_t *dst, const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks, int level, int flags)
+{
+    if (nStreams < 0 || nBlocks < 0 || (nStreams > 0 && (!src || !srcOff || !srcLen || !blockSize || !dst || !dstOff || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    int64_t nb = 0;
+    int rc = hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, nullptr);    /* (host arithmetic: before the context) */
+    if (rc != K4LZ4_OK) return rc;
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: outLen has fewer entries than the streams have blocks");
+    if (nb == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* the contents packed on the device, the slots of every stream's blocks behind each other */
+    std::vector<uint64_t> d_soff((size_t)nStreams), d_doff((size_t)nStreams);
+    uint64_t stotal = 0, dtotal = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t B = hc_chain_block_size(blockSize[si]);
+        d_soff[(size_t)si] = stotal; stotal += ((uint64_t)srcLen[si] + 15u) & ~(uint64_t)15u;
+        const uint64_t fresh = (uint64_t)(srcLen[si] - (dictLen ? dictLen[si] : 0));       /* (validated by hc_chain_table) */
+        d_doff[(size_t)si] = dtotal; dtotal += ((fresh + (uint64_t)B - 1u) / (uint64_t)B) * (uint64_t)(B + B / 255 + 16);
+    }
+    if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, (size_t)stotal + 64, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)dtotal + 64, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, (size_t)nb * 4 + 64, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)dtotal + 64, true)) != K4LZ4_OK) return rc;
+    hipStream_t st = ctx->stream;
+    for (int64_t si = 0; si < nStreams; si++)
+        if (srcLen[si] > 0) K4_HIP(ctx, hipMemcpyAsync(ctx->d_src + d_soff[(size_t)si], src + srcOff[si], (size_t)srcLen[si], hipMemcpyHostToDevice, st));
+    int32_t *d_out = (int32_t *)ctx->d_meta;
+    rc = hc_chain_run(ctx, ctx->d_src, d_soff.data(), srcLen, blockSize, extraBlocks, dictLen, nStreams, ctx->d_dst, d_doff.data(), d_out, nb, level,
+                      flags, st);
+    if (rc == K4LZ4_OK) rc = hipMemcpyAsync(outLen, d_out, (size_t)nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "outLen download");
+    if (rc == K4LZ4_OK) rc = hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)dtotal, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "output download");
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc != K4LZ4_OK) { (void)take_device_status(ctx); return rc; }
+    K4_HIP(ctx, e);
+    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
+    /* exactly |outLen| bytes of every slot to the caller's */
+    int64_t k = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t B = hc_chain_block_size(blockSize[si]), slot = B + B / 255 + 16;
+        for (int64_t j = 0; j * B < srcLen[si] - (dictLen ? dictLen[si] : 0); j++, k++) {
+            const int32_t r = outLen[k];
+            const size_t nbytes = (size_t)(r < 0 ? -(int64_t)r : r);
+            if (nbytes) memcpy(dst + dstOff[si] + (uint64_t)(j * slot), ctx->h_stage + d_doff[(size_t)si] + (uint64_t)(j * slot), nbytes);
+        }
+    }
     return K4LZ4_OK;
 }
 

@@ -14,7 +14,8 @@
  *   LZ4HC_countPattern / reverseCountPattern Engine/x64/LL64.high.cs:37-68, Engine/LL.high.cs:232-254
  *   LZ4HC_Insert / LZ4HC_countBack           Engine/LL.high.cs:102-122,:216-230
  *   LZ4HC_encodeSequence                     Engine/x64/LL64.high.cs:435-510
- * with byte-identical output.
+ * with byte-identical output.  Chained streams (LZ4HighChainEncoder -> LZ4_compress_HC_continue, LL64.high.cs:1259-1311) go through
+ * the same memory-path kernels: each block as a window of the stream with its history in front (HcArgs::hist).
  *
  * Key observation: unlike the fast encoder, the HC tables do not depend on the parse.
  * LZ4HC_Insert enters EVERY position, in order, before it can be searched, so the chain of
@@ -78,6 +79,11 @@ struct HcArgs {
                                     * (k4lz4_parse.hpp: x = where the match starts, y = offset | (length - MINMATCH) << 16) -- the parse only DECIDES,
                                     * the block's bytes are written from the records afterwards (emit_block<true>); nullptr: LZ4HC_encodeSequence
                                     * inside the parse loop as before */
+    const int32_t *hist;           /* chained streams (k4lz4_encode_hc_chain_batch): block b's source is a WINDOW of the stream, srcLen[b] bytes from
+                                    * srcOff[b], whose first hist[b] bytes are the history before the block (at most 64 KiB); chains are built over
+                                    * the whole window, candidate records with lengths only behind the history, the parse starts at hist[b] and
+                                    * outLen[b] counts the block alone.  Memory paths only (k4_hc_chain_kernel, k4_hc_cand_kernel, k4_hc_parse_kernel,
+                                    * k4_hc_parse_opt_kernel).  nullptr: independent blocks */
 };
 
 /* a launch sized from a reservation (k4lz4_ctx_reserve_hc) whose batch turned out bigger: nothing is touched, every block
@@ -461,6 +467,7 @@ __global__ __launch_bounds__(256) K4_HC_CAND_ATTR void k4_hc_cand_kernel(HcArgs 
     const HcSrcMem src{a.src + a.srcOff[b]};
     const uint32_t *prev = (const uint32_t *)(a.work + a.workOff[b]);
     uint4 *rec = (uint4 *)(prev + ((U + 3u) & ~3u));
+    const uint32_t h0 = a.hist ? (uint32_t)a.hist[b] : 0u;
     /* the first four chain candidates (a chain step of 65535 or more ends the walk: LL.high.cs:114 caps the delta, and such a candidate is
      * below lowestMatchIndex) */
     for (int j = 0; j < HC_CAND_POS_PER_WG / 256; j++) {
@@ -472,6 +479,19 @@ __global__ __launch_bounds__(256) K4_HC_CAND_ATTR void k4_hc_cand_kernel(HcArgs 
         for (int k = 1; k < 4; k++) {
             const uint32_t q = c[k - 1] != HC_NONE ? prev[c[k - 1]] : HC_NONE;
             c[k] = (q != HC_NONE && c[k - 1] - q < (uint32_t)DISTANCE_MAX) ? q : HC_NONE;
+        }
+        if (p < h0) {
+            /* a position of the history: no search starts here, but a search of level 4 and up walks on through the record of its
+             * fourth candidate, which may lie here -- the distances, as hc_cand_record gives them, and no lengths */
+            uint32_t d[4];
+            bool chain_ok = true;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                chain_ok = chain_ok && c[k] != HC_NONE && p - c[k] <= (uint32_t)DISTANCE_MAX;
+                d[k] = chain_ok ? p - c[k] : 0u;
+            }
+            rec[p] = make_uint4(d[0] | (d[1] << 16), d[2] | (d[3] << 16), 0u, 0u);
+            continue;
         }
         rec[p] = hc_cand_record(src, U, p, c);
     }
@@ -1061,11 +1081,12 @@ __device__ __forceinline__ int hc_sequence_price(int litlen, int mlen)          
 }
 
 /* LZ4HC_compress_optimal for one block (limitedOutput / notLimited); returns bytes written, 0 = overflow */
+/* start: the block is [start, src_len) of the window at src, the bytes before it are history (HcArgs::hist) */
 __device__ __forceinline__ int hc_parse_block_opt(const uint8_t *src, int src_len, uint8_t *dst, int dst_cap, int level,
-                                                  const uint32_t *prev, uint32_t *lds, int lane)
+                                                  const uint32_t *prev, uint32_t *lds, int lane, uint32_t start = 0u)
 {
-    if ((uint32_t)src_len > (uint32_t)MAX_INPUT_SIZE) return 0;
-    const bool limited = dst_cap < compress_bound(src_len);
+    if ((uint32_t)(src_len - (int)start) > (uint32_t)MAX_INPUT_SIZE) return 0;
+    const bool limited = dst_cap < compress_bound(src_len - (int)start);
     const int64_t oend = dst_cap;
     const uint32_t U = (uint32_t)src_len;
     const int nb_searches = level <= 10 ? 96 : level == 11 ? 512 : 16384;         /* clTable :1134-1136; above 12: as 12 (:1160) */
@@ -1074,9 +1095,9 @@ __device__ __forceinline__ int hc_parse_block_opt(const uint8_t *src, int src_le
     const bool full_update = level >= 12;
     uint32_t *o_price = lds, *o_litlen = lds + HC_OPT_ENTRIES, *o_ml_off = lds + 2 * HC_OPT_ENTRIES;
 #define K4_OPT_SET(P, ML, OFF, LL, PR) do { o_price[(P)] = (uint32_t)(PR); o_litlen[(P)] = (uint32_t)(LL); o_ml_off[(P)] = (uint32_t)(ML) | ((uint32_t)(OFF) << 16); } while (0)
-    uint32_t ip = 0, anchor = 0;
+    uint32_t ip = start, anchor = start;
     int64_t op = 0;
-    if (src_len >= MFLIMIT + 1) {
+    if (src_len - (int)start >= MFLIMIT + 1) {
         const uint32_t mflimit = U - MFLIMIT, matchlimit = U - LASTLITERALS;
         while (ip <= mflimit) {
             const int llen = (int)(ip - anchor);
@@ -1279,8 +1300,11 @@ __device__ __forceinline__ int hc_nb_searches(int level)
 template <bool L3, bool REC = false, bool SEG = false>
 __device__ __forceinline__ int hc_parse_block(const uint8_t *src, int src_len, uint8_t *dst, int dst_cap, int level,
                                               const uint4 *cand, int lane,
-                                              uint32_t *pace = nullptr, uint32_t *pace_mine = nullptr, uint2 *recs = nullptr, const HcSegs *sg = nullptr)
+                                              uint32_t *pace = nullptr, uint32_t *pace_mine = nullptr, uint2 *recs = nullptr, const HcSegs *sg = nullptr,
+                                              uint32_t start = 0u)
 {
+    /* start: the block is [start, src_len) of the window at src, the bytes before it are history (HcArgs::hist); not with REC, whose
+     * records and emit_block<true> cover a block from its position 0 */
     static_assert(!SEG || (L3 && REC), "several waves per block: the level-3 parse with sequence records");
     uint32_t nrec = 0;
 /* one sequence: literals [anchor, ip), a match of ML bytes at REF; the cursor and the anchor move behind it */
@@ -1294,14 +1318,14 @@ __device__ __forceinline__ int hc_parse_block(const uint8_t *src, int src_len, u
 #define K4_HC_SEARCH(P, LOW, LONGEST, MPOS, SPOS) \
     (L3 ? hc_search_l3(src, cand, hc_get_rec(win, cand, (P)), (P), (LOW), matchlimit, (LONGEST), (MPOS), (SPOS), lane) \
         : hc_search(src, cand, (P), (LOW), matchlimit, (LONGEST), (MPOS), (SPOS), max_attempts, lane, prev, pattern_analysis))
-    if ((uint32_t)src_len > (uint32_t)MAX_INPUT_SIZE) return 0;      /* :1153 */
-    const bool limited = dst_cap < compress_bound(src_len);         /* :1348 */
+    if ((uint32_t)(src_len - (int)start) > (uint32_t)MAX_INPUT_SIZE) return 0;      /* :1153 */
+    const bool limited = dst_cap < compress_bound(src_len - (int)start);         /* :1348 */
     const int64_t oend = dst_cap;
     const int max_attempts = hc_nb_searches(level);
     const bool pattern_analysis = max_attempts > 128;               /* LZ4HC_compress_hashChain: patternAnalysis = (maxNbAttempts > 128), level 9 */
     const uint32_t *prev = (const uint32_t *)cand - (((uint32_t)(src_len > 0 ? src_len : 0) + 3u) & ~3u);
     const uint32_t U = (uint32_t)src_len;
-    uint32_t ip = 0, anchor = 0;
+    uint32_t ip = start, anchor = start;
     int64_t op = 0;
     HcWindow win;
     win.base = 0; win.valid = false;
@@ -1314,7 +1338,7 @@ __device__ __forceinline__ int hc_parse_block(const uint8_t *src, int src_len, u
         seg_base = hc_seg_start(U, sg->nseg, 1u);
     }
 
-    if (src_len >= MFLIMIT + 1) {
+    if (src_len - (int)start >= MFLIMIT + 1) {
         const uint32_t mflimit = U - MFLIMIT;
         const uint32_t matchlimit = U - LASTLITERALS;
         while (ip <= mflimit) {
@@ -1536,19 +1560,20 @@ __global__ __launch_bounds__(64 * HC_PARSE_WAVES_PER_WG) void k4_hc_parse_kernel
     const int src_len = a.srcLen[b];
     if (K4_HC_PACE) Pace::begin(a.pace, pace_mine, lane);
     const int cap = a.dstCap[b];
+    const int h0 = a.hist ? a.hist[b] : 0;                  /* (chained streams: the block is the window's last src_len - h0 bytes) */
     int ret = 0;
-    if ((src_len > 0 || (a.flags & FLAG_RAW_RETURN)) && hc_scratch_ok(a)) {
+    if ((src_len - h0 > 0 || (a.flags & FLAG_RAW_RETURN)) && hc_scratch_ok(a)) {
         const uint32_t *prev = (const uint32_t *)(a.work + a.workOff[b]);
         const uint32_t al = ((uint32_t)(src_len > 0 ? src_len : 0) + 3u) & ~3u;
         const uint4 *cand = (const uint4 *)(prev + al);
         const uint8_t *s = a.src + a.srcOff[b];
         uint8_t *d = a.dst + a.dstOff[b];
-        if (hc_nb_searches(a.level) <= 4) ret = hc_parse_block<true>(s, src_len, d, cap < 0 ? 0 : cap, a.level, cand, lane, a.pace, pace_mine);
-        else ret = hc_parse_block<false>(s, src_len, d, cap < 0 ? 0 : cap, a.level, cand, lane);
+        if (hc_nb_searches(a.level) <= 4) ret = hc_parse_block<true>(s, src_len, d, cap < 0 ? 0 : cap, a.level, cand, lane, a.pace, pace_mine, nullptr, nullptr, (uint32_t)h0);
+        else ret = hc_parse_block<false>(s, src_len, d, cap < 0 ? 0 : cap, a.level, cand, lane, nullptr, nullptr, nullptr, nullptr, (uint32_t)h0);
     }
     if (lane == 0) {
         int r = ret;
-        if (!(a.flags & FLAG_RAW_RETURN)) r = src_len <= 0 ? 0 : (ret <= 0 ? -1 : ret);   /* LZ4Codec.cs:45-51 */
+        if (!(a.flags & FLAG_RAW_RETURN)) r = src_len - h0 <= 0 ? 0 : (ret <= 0 ? -1 : ret);   /* LZ4Codec.cs:45-51 */
         else if (!hc_scratch_ok(a)) r = HC_NO_SCRATCH;      /* "not encoded", which 0 would not say to the pickle envelope (raw fallback) */
         a.outLen[b] = r;
     }
@@ -1650,14 +1675,15 @@ __global__ __launch_bounds__(64) void k4_hc_parse_opt_kernel(HcArgs a)
     const long long b = (long long)blockIdx.x;
     const int src_len = a.srcLen[b];
     const int cap = a.dstCap[b];
+    const int h0 = a.hist ? a.hist[b] : 0;                  /* (chained streams: the block is the window's last src_len - h0 bytes) */
     int ret = 0;
-    if ((src_len > 0 || (a.flags & FLAG_RAW_RETURN)) && hc_scratch_ok(a)) {
+    if ((src_len - h0 > 0 || (a.flags & FLAG_RAW_RETURN)) && hc_scratch_ok(a)) {
         const uint32_t *prev = (const uint32_t *)(a.work + a.workOff[b]);
-        ret = hc_parse_block_opt(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], cap < 0 ? 0 : cap, a.level, prev, opt_lds, lane);
+        ret = hc_parse_block_opt(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], cap < 0 ? 0 : cap, a.level, prev, opt_lds, lane, (uint32_t)h0);
     }
     if (lane == 0) {
         int r = ret;
-        if (!(a.flags & FLAG_RAW_RETURN)) r = src_len <= 0 ? 0 : (ret <= 0 ? -1 : ret);   /* LZ4Codec.cs:45-51 */
+        if (!(a.flags & FLAG_RAW_RETURN)) r = src_len - h0 <= 0 ? 0 : (ret <= 0 ? -1 : ret);   /* LZ4Codec.cs:45-51 */
         else if (!hc_scratch_ok(a)) r = HC_NO_SCRATCH;      /* "not encoded", which 0 would not say to the pickle envelope (raw fallback) */
         a.outLen[b] = r;
     }

@@ -5,20 +5,27 @@ Mirrors:
   ILZ4Encoder  (Topup / Encode / BlockSize / BytesReady)      Encoders/ILZ4Encoder.cs
   LZ4EncoderBase                                              Encoders/LZ4EncoderBase.cs:28-97
   LZ4BlockEncoder(level, blockSize)                           Encoders/LZ4BlockEncoder.cs:7-23
+  LZ4HighChainEncoder(level, blockSize, extraBlocks)          Encoders/LZ4HighChainEncoder.cs (-> LZ4_compress_HC_continue,
+                                                              LZ4_saveDictHC over LZ4EncoderBase's ring buffer)
   ILZ4Decoder  (Decode / Inject / Drain / Peek / BytesReady)  Encoders/ILZ4Decoder.cs
   LZ4BlockDecoder(blockSize)                                  Encoders/LZ4BlockDecoder.cs:11-106
   LZ4EncoderExtensions.TopupAndEncode / FlushAndEncode /
       DecodeAndDrain, EncoderAction                           Encoders/LZ4EncoderExtensions.cs:8-205, EncoderAction.cs
-The chained encoders (LZ4FastChainEncoder / LZ4HighChainEncoder -> *_continue) are serial across
-blocks and are not offered; chained *decoding* is (frames.py, k4lz4_decode_chain_batch).
+Chained HC blocks batch like independent ones: the HC tables are a function of the data alone, so a
+block needs the bytes before it (at most 64 KiB of them), not the parse of the block before it
+(k4lz4_encode_hc_chain_batch).  The chained FAST encoder (LZ4FastChainEncoder ->
+LZ4_compress_fast_continue) is not offered: its hash table holds only the positions its parse
+visited, so every block depends on the parse of the one before it.  Chained *decoding* is
+(frames.py, k4lz4_decode_chain_batch).
 
 `LZ4BlockEncoder.EncodeBlocks` is the batching front-end the frame writer uses: K blocks, one launch,
-with the reference's allowCopy rule applied on the device.
+with the reference's allowCopy rule applied on the device; `encode_hc_chain_packed` is the same for
+whole chained streams, `LZ4HighChainEncoder.EncodeBlocks` for the blocks of one.
 """
 from __future__ import annotations
 
 import enum
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -128,6 +135,160 @@ def encode_blocks_packed(blocks, level: LZ4Level, allow_copy: bool, ctx: Optiona
     return out, dst, doff
 
 
+# ---- chained HC streams ---------------------------------------------------------------------------------
+HC_CHAIN_LIMIT = (1 << 31) - 65536      # LZ4_compressHC_continue_generic renormalises a block that starts beyond this (LL64.high.cs:1271-1276)
+
+
+def hc_chain_blocks(length: int, blockSize: int, extraBlocks: int = 0, dictLen: int = 0) -> List[Tuple[int, int, int]]:
+    """LZ4HighChainEncoder's blocks of a content in content coordinates: (start, length, dictLimit) per block -- the model
+    LZ4EncoderBase's ring buffer reduces to (Topup / Encode / Commit -> LZ4_saveDictHC).  dictLen: the content's first bytes are
+    what the ring buffer already holds (no block for them).  The library builds the same table (k4lz4_capi.hip, hc_chain_table)."""
+    B = _round_block_size(blockSize)
+    L = 65536 + (1 + max(int(extraBlocks), 0)) * B + 32
+    ptr = s = int(dictLen)
+    dl = 0
+    out = []
+    while s < length:
+        n = min(B, length - s)
+        out.append((s, n, dl))
+        s += n
+        ptr += n
+        if ptr + B > L:                                  # Commit -> LZ4_saveDictHC(ctx, buf, ptr), LL.high.cs:168
+            d = min(65536, ptr, s - dl)
+            d = 0 if d < 4 else d
+            dl, ptr = s - d, d
+    return out
+
+
+def encode_hc_chain_packed(contents: Sequence, blockSize: Union[int, Sequence[int]], extraBlocks: Union[int, Sequence[int]],
+                           level: LZ4Level, allow_copy: bool, ctx: Optional[_native.Context] = None, dictLen=None):
+    """chained HC streams, one call (k4lz4_encode_hc_chain_batch) -> (outLen int32 per block, streams in order (negative: stored
+    raw), arena, arena offset per block, blocks per stream)"""
+    ctx = ctx or _native.default_context()
+    views = [_ro_view(c, "source") for c in contents]
+    ns = len(views)
+    bs = np.broadcast_to(np.asarray(blockSize, np.int64), (ns,)).astype(np.int32)
+    ex = np.broadcast_to(np.asarray(extraBlocks, np.int64), (ns,)).astype(np.int32)
+    dlen = np.zeros(ns, np.int32) if dictLen is None else np.asarray(dictLen, np.int32).reshape(ns)
+    src, soff, _ = pack_blocks(views)
+    slen = np.array([v.size for v in views], np.int64)
+    B = np.array([_round_block_size(int(b)) for b in bs], np.int64)
+    nblk = (slen - dlen + B - 1) // B
+    slot = B + B // 255 + 16                                   # LZ4Codec.MaximumOutputSize(B)
+    doff = np.zeros(ns, np.uint64)
+    if ns > 1:
+        doff[1:] = np.cumsum((nblk * slot)[:-1]).astype(np.uint64)
+    nb = int(nblk.sum())
+    dst = np.empty(max(int((nblk * slot).sum()), 1), np.uint8)
+    out = np.zeros(max(nb, 1), np.int32)
+    ctx.check(ctx.lib.k4lz4_encode_hc_chain_batch(ctx.handle, src.ctypes.data, soff.ctypes.data, slen.ctypes.data, bs.ctypes.data,
+                                                  ex.ctypes.data, dlen.ctypes.data, ns, dst.ctypes.data, doff.ctypes.data,
+                                                  out.ctypes.data, nb, int(level), FLAG_ALLOW_COPY if allow_copy else 0))
+    boff = np.concatenate([doff[f] + np.arange(nblk[f], dtype=np.uint64) * np.uint64(slot[f]) for f in range(ns)]) if nb else np.zeros(0, np.uint64)
+    return out[:nb], dst, boff, nblk
+
+
+class LZ4HighChainEncoder:
+    """Chained HC encoder (LZ4HighChainEncoder.cs over LZ4EncoderBase.cs): every block is LZ4_compress_HC_continue with the
+    blocks before it as history.  The ring buffer is the reference's, byte for byte (Topup / Encode / Commit); a block is encoded
+    on the device with what the buffer holds in front of it.  `EncodeBlocks` hands many blocks of the stream to one call."""
+
+    def __init__(self, level: LZ4Level = LZ4Level.L09_HC, blockSize: int = 65536, extraBlocks: int = 0):
+        level = int(level)
+        self._level = LZ4Level(min(max(level, int(LZ4Level.L03_HC)), int(LZ4Level.L12_MAX)))   # LZ4HighChainEncoder.cs:19-20
+        self._block_size = _round_block_size(blockSize)
+        self._extra = max(int(extraBlocks), 0)
+        self._length = 65536 + (1 + self._extra) * self._block_size + 32                      # LZ4EncoderBase.cs:25
+        self._input = np.zeros(self._length + 8, np.uint8)
+        self._index = 0
+        self._pointer = 0
+        self._position = 0                       # stream bytes encoded so far (the 2 GB renormalisation is not offered)
+
+    @property
+    def BlockSize(self) -> int:
+        return self._block_size
+
+    @property
+    def BytesReady(self) -> int:
+        return self._pointer - self._index
+
+    def Topup(self, source, offset: int = 0, length: Optional[int] = None) -> int:
+        """LZ4EncoderBase.cs:46-62"""
+        src = _ro_view(source, "source")
+        length = src.size - offset if length is None else int(length)
+        if length == 0:
+            return 0
+        space = self._index + self._block_size - self._pointer
+        if space <= 0:
+            return 0
+        chunk = min(space, length)
+        self._input[self._pointer:self._pointer + chunk] = src[offset:offset + chunk]
+        self._pointer += chunk
+        return chunk
+
+    def _commit(self) -> None:
+        """LZ4EncoderBase.Commit -> LZ4_saveDictHC(ctx, buffer, pointer)"""
+        self._index = self._pointer
+        if self._index + self._block_size <= self._length:
+            return
+        d = min(65536, self._pointer)
+        d = 0 if d < 4 else d
+        self._input[:d] = self._input[self._pointer - d:self._pointer].copy()
+        self._index = self._pointer = d
+
+    def Encode(self, target, offset: int = 0, length: Optional[int] = None, allowCopy: bool = False) -> int:
+        """encodes the pending bytes as one block into target; with allowCopy a block that does not shrink is stored raw and
+        -length is returned (LZ4EncoderBase.cs:66-88)"""
+        dst = _rw_view(target, "target")
+        length = dst.size - offset if length is None else int(length)
+        n = self._pointer - self._index
+        if n <= 0:
+            return 0
+        if self._position > HC_CHAIN_LIMIT:
+            raise NotImplementedError("a chained HC stream beyond 2 GB (the encoder's renormalisation) is not supported")
+        out, arena, boff, _ = encode_hc_chain_packed([self._input[:self._pointer]], self._block_size, self._extra, self._level,
+                                                     allowCopy, dictLen=[self._index])
+        encoded = int(out[0])
+        if encoded == 0 or abs(encoded) > length:
+            raise InvalidOperationException("Failed to encode chunk. Target buffer too small.")
+        dst[offset:offset + abs(encoded)] = arena[int(boff[0]):int(boff[0]) + abs(encoded)]
+        self._position += n
+        self._commit()
+        return encoded
+
+    def EncodeBlocks(self, sources: Sequence, allowCopy: bool = True,
+                     ctx: Optional[_native.Context] = None) -> List[Tuple[EncoderAction, bytes]]:
+        """the next blocks of the stream, as Topup + Encode(allowCopy) per element would produce them, in one call.  Every
+        element but the last is BlockSize bytes (the encoder's blocks are what the ring buffer cuts), the last at most that;
+        nothing may be pending."""
+        blocks = [_ro_view(s, "source") for s in sources]
+        if self.BytesReady:
+            raise InvalidOperationException("bytes are pending: Encode them first")
+        for i, b in enumerate(blocks):
+            if b.size > self._block_size or (i < len(blocks) - 1 and b.size != self._block_size):
+                raise InvalidOperationException("every block but the last must be BlockSize bytes")
+        blocks = [b for b in blocks if b.size]
+        if not blocks:
+            return [(EncoderAction.None_, b"") for _ in sources]
+        total = sum(b.size for b in blocks)
+        if self._position + total - blocks[-1].size > HC_CHAIN_LIMIT:
+            raise NotImplementedError("a chained HC stream beyond 2 GB (the encoder's renormalisation) is not supported")
+        content = np.concatenate([self._input[:self._index]] + blocks)
+        out, arena, boff, _ = encode_hc_chain_packed([content], self._block_size, self._extra, self._level, allowCopy, ctx,
+                                                     dictLen=[self._index])
+        res = []
+        for n, o in zip(out, boff):
+            if n == 0:
+                raise InvalidOperationException("Failed to encode chunk. Target buffer too small.")
+            res.append((EncoderAction.Copied if n < 0 else EncoderAction.Encoded, arena[int(o):int(o) + abs(int(n))].tobytes()))
+        # the ring buffer as the blocks one by one would have left it
+        for b in blocks:
+            self.Topup(b)
+            self._position += b.size
+            self._commit()
+        return res + [(EncoderAction.None_, b"")] * (len(sources) - len(res))
+
+
 class LZ4BlockDecoder:
     """Decoder for independent blocks (LZ4BlockDecoder.cs)."""
 
@@ -186,7 +347,7 @@ class LZ4BlockDecoder:
 
 
 # ---- LZ4EncoderExtensions ---------------------------------------------------------------------------
-def TopupAndEncode(encoder: LZ4BlockEncoder, source, target, forceEncode: bool, allowCopy: bool):
+def TopupAndEncode(encoder: Union[LZ4BlockEncoder, LZ4HighChainEncoder], source, target, forceEncode: bool, allowCopy: bool):
     """-> (action, loaded, encoded)   (LZ4EncoderExtensions.cs:117-133, :183-205)"""
     src = _ro_view(source, "source")
     loaded = encoder.Topup(src) if src.size > 0 else 0
@@ -194,7 +355,7 @@ def TopupAndEncode(encoder: LZ4BlockEncoder, source, target, forceEncode: bool, 
     return action, loaded, encoded
 
 
-def FlushAndEncode(encoder: LZ4BlockEncoder, target, forceEncode: bool = True, allowCopy: bool = True, loaded: int = 0):
+def FlushAndEncode(encoder: Union[LZ4BlockEncoder, LZ4HighChainEncoder], target, forceEncode: bool = True, allowCopy: bool = True, loaded: int = 0):
     """-> (action, encoded)"""
     if encoder.BytesReady < (1 if forceEncode else encoder.BlockSize):
         return (EncoderAction.Loaded if loaded > 0 else EncoderAction.None_), 0

@@ -11,9 +11,16 @@ What runs where: splitting into blocks, the header and the block table are host 
 encoding (with the allowCopy rule), block decoding (independent blocks as one batch, chained blocks as
 one in-order stream per wavefront) and every XXH32 -- header byte included -- run in the HIP kernels.
 
+Chained frames (ChainBlocks=True) are written at L03_HC and up: LZ4HighChainEncoder's blocks
+(k4lz4_encode_hc_chain_batch), every block of every frame of the batch side by side -- the HC tables
+depend on the data alone, so a block needs the 64 KiB before it and not the parse of the block before
+it.  ExtraMemory sets the encoder's extra blocks as the reference's writer does.
+
 Differences from the reference, all deliberate:
-  * the writer only makes frames of INDEPENDENT blocks (ChainBlocks=False); the reference's default
-    is chained blocks, whose encoder is serial (*_continue).  The READER takes both.
+  * ChainBlocks defaults to False here (the reference: True).  Chained frames at L00_FAST raise
+    NotImplementedException: LZ4FastChainEncoder's hash table holds only the positions its parse
+    visited, so each block depends on the parse of the one before it -- serial per stream.  The READER
+    takes both kinds.
   * ContentLength in the header is written when asked for (the reference's writer throws
     NotImplemented, LZ4FrameWriter.cs:86-88) and verified by the reader, like the reference's reader.
 """
@@ -27,7 +34,7 @@ import numpy as np
 
 from . import _native
 from .codec import LZ4Codec, LZ4Level, _ro_view, pack_blocks, make_arena, _batch_args
-from .encoders import encode_blocks_packed
+from .encoders import encode_blocks_packed, encode_hc_chain_packed, hc_chain_blocks, _round_block_size
 
 MAGIC = 0x184D2204
 K64, K256, M1, M4 = 64 << 10, 256 << 10, 1 << 20, 4 << 20
@@ -39,6 +46,16 @@ class InvalidDataException(Exception):
 
 class NotImplementedException(Exception):
     """System.NotImplementedException (predefined dictionaries)"""
+
+
+FAST_CHAIN_REFUSED = ("chained blocks at L00_FAST are not offered: LZ4_compress_fast_continue's hash table holds only the positions "
+                      "its parse visited, so every block depends on the parse of the one before it (serial per stream); use "
+                      "ChainBlocks=False, or CompressionLevel L03_HC and up")
+
+
+def _extra_blocks(block_size: int, extra_memory: int) -> int:
+    """Streams/Extensions.cs:18-19"""
+    return max(block_size if extra_memory > 0 else 0, extra_memory) // block_size
 
 
 @dataclass
@@ -213,28 +230,38 @@ class LZ4Frame:
         s = settings or LZ4EncoderSettings()
         if level is not None:
             s = LZ4EncoderSettings(**{**s.__dict__, "CompressionLevel": LZ4Level(level)})
-        if s.ChainBlocks:
-            raise NotImplementedException("chained blocks are encoded serially (LZ4_compress_*_continue): not offered; "
-                                          "use ChainBlocks=False")
+        if s.ChainBlocks and int(s.CompressionLevel) < int(LZ4Level.L03_HC):
+            raise NotImplementedException(FAST_CHAIN_REFUSED)
         max_block_size_code(s.BlockSize)
         ctx = ctx or _native.default_context()
         contents = [_ro_view(x, "source") for x in sources]
         bs = int(s.BlockSize)
-        blocks, owner = [], []
-        for f, c in enumerate(contents):
+        for c in contents:
             if s.ContentLength is not None and s.ContentLength != c.size:
                 raise ValueError("ContentLength does not match the source length")
-            for p in range(0, c.size, bs):
-                blocks.append(c[p:p + bs])
-                owner.append(f)
-        out, arena, aoff = encode_blocks_packed(blocks, s.CompressionLevel, True, ctx) if blocks else (np.zeros(0, np.int32), None, None)
+        blocks, owner = [], []
+        if s.ChainBlocks:
+            # LZ4HighChainEncoder per frame (Streams/Extensions.cs:28-36): its blocks are the ring buffer's, rounded to a whole KiB
+            nonempty = [f for f, c in enumerate(contents) if c.size]
+            if nonempty:
+                out, arena, aoff, nblk = encode_hc_chain_packed([contents[f] for f in nonempty], bs,
+                                                                _extra_blocks(bs, int(s.ExtraMemory)), s.CompressionLevel, True, ctx)
+                owner = list(np.repeat(np.array(nonempty), nblk))
+            else:
+                out, arena, aoff = np.zeros(0, np.int32), None, None
+        else:
+            for f, c in enumerate(contents):
+                for p in range(0, c.size, bs):
+                    blocks.append(c[p:p + bs])
+                    owner.append(f)
+            out, arena, aoff = encode_blocks_packed(blocks, s.CompressionLevel, True, ctx) if blocks else (np.zeros(0, np.int32), None, None)
         payloads, raw = [], []
-        for n, o in zip(out, aoff if blocks else []):
+        for n, o in zip(out, aoff if len(out) else []):
             if n == 0:
                 raise RuntimeError("Failed to encode chunk. Target buffer too small.")       # LZ4EncoderBase.cs:75-77
             payloads.append(arena[int(o):int(o) + abs(int(n))])
             raw.append(n < 0)
-        descs = [LZ4Descriptor(s.ContentLength, s.ContentChecksum, False, s.BlockChecksum, None, bs) for _ in contents]
+        descs = [LZ4Descriptor(s.ContentLength, s.ContentChecksum, bool(s.ChainBlocks), s.BlockChecksum, None, bs) for _ in contents]
         # every XXH32 of the batch in one launch: headers, then block payloads, then contents
         to_hash = [np.frombuffer(frame_header(d), np.uint8) for d in descs]
         if s.BlockChecksum:
@@ -242,7 +269,7 @@ class LZ4Frame:
         if s.ContentChecksum:
             to_hash += contents
         hashes = xxh32_many(to_hash, ctx)
-        nf, nb = len(contents), len(blocks)
+        nf, nb = len(contents), len(payloads)
         bh = hashes[nf:nf + nb] if s.BlockChecksum else None
         ch = hashes[nf + (nb if s.BlockChecksum else 0):] if s.ContentChecksum else None
         frames = []
@@ -391,28 +418,50 @@ def encode_frames_device(dc, data, off: np.ndarray, length: np.ndarray, settings
     from ._native import FLAG_ALLOW_COPY
     from .device import DeviceBatch, _dp
     s = settings or LZ4EncoderSettings()
-    if s.ChainBlocks:
-        raise NotImplementedException("chained blocks are encoded serially: use ChainBlocks=False")
+    if s.ChainBlocks and int(s.CompressionLevel) < int(LZ4Level.L03_HC):
+        raise NotImplementedException(FAST_CHAIN_REFUSED)
     bs = int(s.BlockSize)
     max_block_size_code(bs)
     off = np.asarray(off, dtype=np.int64)
     length = np.asarray(length, dtype=np.int64)
     nf = len(off)
-    nblk = (length + bs - 1) // bs
+    eb = _round_block_size(bs) if s.ChainBlocks else bs          # (the chained encoder's blocks: its ring buffer's, whole KiB)
+    nblk = (length + eb - 1) // eb
     first = np.concatenate(([0], np.cumsum(nblk)))[:-1]
     nb = int(nblk.sum())
     owner = np.repeat(np.arange(nf), nblk)
-    k_in = np.arange(nb) - first[owner]
-    boff = off[owner] + k_in * bs
-    blen = np.minimum(bs, length[owner] - k_in * bs).astype(np.int32)
-    bound = LZ4Codec.MaximumOutputSize(bs)
+    bound = LZ4Codec.MaximumOutputSize(eb)
     dev = dc.device
-    src = DeviceBatch(data, torch.from_numpy(boff).to(dev), torch.from_numpy(blen).to(dev))
-    arena = DeviceBatch.empty_slots(np.full(nb, bound, np.int64), dev)
-    out_len = dc.encode(src, arena, level=s.CompressionLevel, flags=FLAG_ALLOW_COPY) if nb else torch.zeros(0, dtype=torch.int32, device=dev)
+    if not s.ChainBlocks:
+        arena = DeviceBatch.empty_slots(np.full(nb, bound, np.int64), dev)
+    else:
+        # every frame one stream whose blocks' slots lie behind each other, `bound` bytes apart (k4lz4_encode_hc_chain_batch_device)
+        frame_slots = np.zeros(nf, np.int64)
+        if nf > 1:
+            frame_slots[1:] = np.cumsum((nblk * bound + 15) // 16 * 16)[:-1]
+        slot_off = frame_slots[owner] + (np.arange(nb) - first[owner]) * bound
+        arena = DeviceBatch(torch.empty(int(((nblk * bound + 15) // 16 * 16).sum()) + 64, dtype=torch.uint8, device=dev),
+                            torch.from_numpy(slot_off).to(dev), torch.full((nb,), bound, dtype=torch.int32, device=dev))
+    if not nb:
+        out_len = torch.zeros(0, dtype=torch.int32, device=dev)
+    elif s.ChainBlocks:
+        out_len = torch.empty(nb, dtype=torch.int32, device=dev)
+        c_off, c_len, c_dst = off.astype(np.uint64), np.ascontiguousarray(length), frame_slots.astype(np.uint64)
+        bsz = np.full(nf, bs, np.int32)
+        ext = np.full(nf, _extra_blocks(bs, int(s.ExtraMemory)), np.int32)
+        rc = dc.lib.k4lz4_encode_hc_chain_batch_device(dc.ctx.handle, _dp(data), c_off.ctypes.data, c_len.ctypes.data, bsz.ctypes.data,
+                                                       ext.ctypes.data, None, nf, _dp(arena.data), c_dst.ctypes.data, _dp(out_len), nb,
+                                                       int(s.CompressionLevel), FLAG_ALLOW_COPY, C.c_void_p(dc._stream()))
+        dc.ctx.check(rc)
+    else:
+        k_in = np.arange(nb) - first[owner]
+        boff = off[owner] + k_in * bs
+        blen = np.minimum(bs, length[owner] - k_in * bs).astype(np.int32)
+        src = DeviceBatch(data, torch.from_numpy(boff).to(dev), torch.from_numpy(blen).to(dev))
+        out_len = dc.encode(src, arena, level=s.CompressionLevel, flags=FLAG_ALLOW_COPY)
     stored = out_len.abs().to(torch.int64)
     # header bytes (host: two to ten bytes per frame) and every XXH32 of the batch
-    hdrs = [frame_header(LZ4Descriptor(int(length[f]) if s.ContentLength is not None else None, s.ContentChecksum, False,
+    hdrs = [frame_header(LZ4Descriptor(int(length[f]) if s.ContentLength is not None else None, s.ContentChecksum, bool(s.ChainBlocks),
                                        s.BlockChecksum, None, bs)) for f in range(nf)]
     hl = len(hdrs[0]) if nf else 2
     hdr_h = np.zeros((max(nf, 1), 16), np.uint8)
