@@ -73,6 +73,24 @@ namespace K4os.Compression.LZ4.Engine
 			IntPtr ctx, IntPtr src, ulong* srcOff, long* srcLen, int* blockSize, int* extraBlocks, int* dictLen, long nStreams,
 			IntPtr dst, ulong* dstOff, IntPtr outLen, long nBlocks, int level, int flags, IntPtr stream);
 
+		// chained fast streams: LZ4FastChainEncoder(blockSize, extraBlocks) over whole contents, one wavefront per stream; stateIn /
+		// stateOut (may be null): one k4lz4_fast_chain_state per stream (LZ4_stream_t's hashTable, currentOffset, dictSize) to continue
+		// a stream across calls, with dictLen = stateIn.dictSize ring-buffer bytes in front of each content's first new block
+		[StructLayout(LayoutKind.Sequential)]
+		public struct k4lz4_fast_chain_state
+		{
+			public fixed uint hashTable[4096];
+			public uint currentOffset;
+			public uint dictSize;
+			public fixed uint reserved[2];
+		}
+		[DllImport(Lib)] public static extern int k4lz4_encode_fast_chain_batch(
+			IntPtr ctx, byte* src, ulong* srcOff, long* srcLen, int* blockSize, int* extraBlocks, int* dictLen, long nStreams,
+			k4lz4_fast_chain_state* stateIn, k4lz4_fast_chain_state* stateOut, byte* dst, ulong* dstOff, int* outLen, long nBlocks, int flags);
+		[DllImport(Lib)] public static extern int k4lz4_encode_fast_chain_batch_device(
+			IntPtr ctx, IntPtr src, ulong* srcOff, long* srcLen, int* blockSize, int* extraBlocks, int* dictLen, long nStreams,
+			IntPtr stateIn, IntPtr stateOut, IntPtr dst, ulong* dstOff, IntPtr outLen, long nBlocks, int flags, IntPtr stream);
+
 		// ---- device-resident variants: every pointer is a device pointer of the context's GPU, stream = hipStream_t
 		[DllImport(Lib)] public static extern int k4lz4_encode_batch_device(
 			IntPtr ctx, IntPtr src, IntPtr srcOff, IntPtr srcLen, IntPtr dst, IntPtr dstOff, IntPtr dstCap, IntPtr outLen, long n, int level, int flags, IntPtr stream);

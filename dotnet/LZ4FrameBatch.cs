@@ -35,6 +35,23 @@ namespace K4os.Compression.LZ4.Streams.Frames
 					dst, &dstOff, outLen, n, (int) settings.CompressionLevel, LLNative.FLAG_ALLOW_COPY), lease.Handle);
 		}
 
+		/// <summary>LZ4FastChainEncoder's blocks of one content (the frame writer's ChainBlocks at levels below L03_HC):
+		/// block j in arena[j * slot ..], encoded[j] its length (negative: stored raw).  Encode below still refuses chained
+		/// L00_FAST frames; this is the block half of such a frame.</summary>
+		public static void EncodeFastChained(ReadOnlySpan<byte> content, LZ4EncoderSettings settings, int blockSize, byte[] arena, int[] encoded, int n)
+		{
+			if (n == 0) return;
+			var extra = Math.Max(settings.ExtraMemory > 0 ? blockSize : 0, settings.ExtraMemory) / blockSize;
+			ulong srcOff = 0, dstOff = 0;
+			long srcLen = content.Length;
+			using var lease = NativeContext.Rent();
+			fixed (byte* src = content)
+			fixed (byte* dst = arena)
+			fixed (int* outLen = encoded)
+				LLNative.ThrowIfFailed(LLNative.k4lz4_encode_fast_chain_batch(lease.Handle, src, &srcOff, &srcLen, &blockSize, &extra, null, 1,
+					null, null, dst, &dstOff, outLen, n, LLNative.FLAG_ALLOW_COPY), lease.Handle);
+		}
+
 		public static byte[] Encode(ReadOnlySpan<byte> content, LZ4EncoderSettings settings)
 		{
 			var chained = settings.ChainBlocks;

@@ -285,6 +285,37 @@ K4LZ4_API int k4lz4_encode_hc_chain_batch_device(k4lz4_ctx *ctx, const uint8_t *
                                                  int64_t nStreams, uint8_t *dst, const uint64_t *dstOff, int32_t *outLen,
                                                  int64_t nBlocks, int level, int flags, void *stream);
 
+/* Chained fast block streams: LZ4FastChainEncoder(blockSize, extraBlocks) (Encoders/LZ4FastChainEncoder.cs, LZ4EncoderBase.cs) fed
+ * a whole content and flushed block by block -- LZ4_compress_fast_continue(acceleration 1) over the encoder's ring buffer,
+ * LZ4_saveDict when it is full -- which is what LZ4Stream.Encode / LZ4Frame.Encode write below L03_HC with ChainBlocks = true.
+ * The arguments are the HC pair's (above) without level.  A stream's table holds the positions its parse visited, so its blocks are
+ * encoded in order by one wavefront; the streams run side by side.  The table is byU32 with hash5 for every block, so a
+ * fresh stream's first block is not the independent L00_FAST encoder's bytes.
+ * stateIn (NULL: every stream is fresh) / stateOut (NULL: not wanted): one k4lz4_fast_chain_state per stream, the stream context's
+ * hash table and indices word for word (LZ4_stream_t's hashTable, currentOffset, dictSize) as they stand before the first / after
+ * the last block of the call.  They are what lets an encoder continue a stream across calls: pass stateOut back as stateIn with the
+ * ring buffer's bytes in front of the next content (dictLen[s] == stateIn[s].dictSize, else K4LZ4_E_ARG; without stateIn dictLen
+ * must be 0).  The only flag is K4LZ4_FLAG_ALLOW_COPY; K4LZ4_FLAG_X32 and a process under k4lz4_set_enforce32(1) are refused with
+ * K4LZ4_E_ARG (the 32-bit engine's chained encoder is not offered).  A block that would take currentOffset past 2 GB
+ * (LZ4_renormDictT rescales the table there) is refused with K4LZ4_E_ARG.
+ * _device: src, dst, outLen, stateIn and stateOut are device pointers; the per-stream arrays stay HOST arrays.  With stateIn the call
+ * reads the states' two indices back to the host first (it waits for `stream` there), then runs asynchronously on it. */
+typedef struct k4lz4_fast_chain_state {
+    uint32_t hashTable[4096];
+    uint32_t currentOffset;
+    uint32_t dictSize;
+    uint32_t reserved[2];
+} k4lz4_fast_chain_state;
+K4LZ4_API int k4lz4_encode_fast_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+                                            const int32_t *blockSize, const int32_t *extraBlocks, const int32_t *dictLen,
+                                            int64_t nStreams, const k4lz4_fast_chain_state *stateIn, k4lz4_fast_chain_state *stateOut,
+                                            uint8_t *dst, const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks, int flags);
+K4LZ4_API int k4lz4_encode_fast_chain_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+                                                   const int32_t *blockSize, const int32_t *extraBlocks, const int32_t *dictLen,
+                                                   int64_t nStreams, const k4lz4_fast_chain_state *stateIn,
+                                                   k4lz4_fast_chain_state *stateOut, uint8_t *dst, const uint64_t *dstOff,
+                                                   int32_t *outLen, int64_t nBlocks, int flags, void *stream);
+
 /* Frame writer on device-resident data: after k4lz4_encode_batch_device(..., K4LZ4_FLAG_ALLOW_COPY) and
  * k4lz4_xxh32_batch_device, lays the frames out (Frames/LZ4FrameWriter.cs:57-108 header, LZ4FrameWriter.async.cs:15-27
  * block records, :75-90 EndMark + content checksum).  The caller computes the positions (recOff, frameOff, tailOff) from

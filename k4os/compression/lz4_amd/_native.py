@@ -74,6 +74,10 @@ SYMBOLS = {
                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
     "k4lz4_encode_hc_chain_batch_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _u8p,
                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "k4lz4_encode_fast_chain_batch": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "k4lz4_encode_fast_chain_batch_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                       C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
 }
 
 

@@ -33,6 +33,7 @@
 #include "k4lz4_pickle.hpp"
 #include "k4lz4_segments.hpp"
 #include "k4lz4_encode_hc.hpp"
+#include "k4lz4_fast_chain.hpp"
 #include "k4lz4_frame.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
@@ -1511,6 +1512,143 @@ int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, con
     return rc;
 }
 
+/* ---- chained fast streams (LZ4FastChainEncoder, k4lz4_encode_fast_chain_batch) ----------------------------------------------
+ * LZ4EncoderBase's ring buffer (Topup / Encode / Commit -> LZ4_saveDict, Engine/LL.tools.cs:195-213) in content coordinates, as for
+ * HC above.  What differs: the table holds the positions the parse visited, so a stream's blocks are encoded in order by one wave
+ * that keeps the table (k4lz4_fast_chain.hpp); per block the kernel needs its start, length and dictSize -- the ring's _inputIndex,
+ * which LZ4_compress_generic adds every block to (withPrefix64k; the first call's extDict arm sets it to the block's length, the
+ * same number) and LZ4_saveDict cuts to 64 KiB. */
+struct FastChainPlan {
+    int64_t ns = 0, nb = 0;
+    uint32_t *ticket = nullptr;
+    uint64_t *soff = nullptr, *slen = nullptr, *doff = nullptr;
+    int64_t *first = nullptr;
+    uint32_t *nblk = nullptr, *idx0 = nullptr, *dict_end = nullptr, *order = nullptr, *bpos = nullptr, *bdict = nullptr;
+    int32_t *blen = nullptr, *cap = nullptr;
+    static size_t bytes(int64_t ns, int64_t nb) { return 16 + (size_t)ns * (3 * 8 + 4 * 4) + (size_t)nb * (8 + 4 * 4); }
+    void place(uint8_t *base, int64_t s, int64_t b)
+    {
+        ns = s; nb = b;
+        ticket = (uint32_t *)base;
+        soff = (uint64_t *)(base + 16); slen = soff + s; first = (int64_t *)(slen + s); doff = (uint64_t *)(first + s);
+        nblk = (uint32_t *)(doff + b); idx0 = nblk + s; dict_end = idx0 + s; order = dict_end + s;
+        bpos = order + s; blen = (int32_t *)(bpos + b); bdict = (uint32_t *)(blen + b); cap = (int32_t *)(bdict + b);
+    }
+};
+
+/* counts the blocks (fill == nullptr) or lays the table out in `fill`.  cur0 / sdict: the streams' state (currentOffset, dictSize), or
+ * nullptr for fresh streams; the content's first dictLen[s] bytes are what the ring buffer holds (dictLen == dictSize) */
+int fast_chain_table(k4lz4_ctx *ctx, const uint64_t *srcOff, const int64_t *srcLen, const int32_t *blockSize, const int32_t *extraBlocks,
+                     const int32_t *dictLen, const uint32_t *cur0, const uint32_t *sdict, int64_t nStreams, const uint64_t *dstOff, int64_t &nb,
+                     FastChainPlan *fill)
+{
+    int64_t k = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t N = srcLen[si];
+        const int64_t B = hc_chain_block_size(blockSize[si]);
+        const int64_t extra = extraBlocks ? std::max<int32_t>(extraBlocks[si], 0) : 0;
+        const int64_t D = dictLen ? dictLen[si] : 0;
+        if (N < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: negative content length");
+        if (D < 0 || D > N) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: dictLen outside the content");
+        if (B > k4::MAX_INPUT_SIZE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: block size above the input size limit");
+        int64_t cur = 0;
+        if (cur0) {
+            if ((int64_t)sdict[si] != D) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: dictLen differs from the state's dictSize");
+            if (sdict[si] > cur0[si]) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: a state whose dictSize exceeds its currentOffset");
+            cur = cur0[si];
+        } else if (D != 0) {
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: dictLen without a state (the table is what continues a stream)");
+        }
+        const int64_t L = 65536 + (1 + extra) * B + 32;                   /* the ring buffer (LZ4EncoderBase.cs:25) */
+        const int64_t slot = B + B / 255 + 16;                            /* k4lz4_compress_bound(B) */
+        const int64_t first = k;
+        int64_t ptr = D, dict = D, pos = D, j = 0;
+        while (pos < N) {
+            const int64_t len = std::min(B, N - pos);
+            /* LZ4_renormDictT (LL64.tools.cs:157-173) rescales the table once currentOffset + inputSize > 2 GB: not offered */
+            if (cur + len > ((int64_t)1 << 31))
+                return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
+            if (fill) {
+                fill->bpos[k] = (uint32_t)pos; fill->blen[k] = (int32_t)len; fill->bdict[k] = (uint32_t)dict;
+                fill->doff[k] = dstOff[si] + (uint64_t)(j * slot); fill->cap[k] = (int32_t)slot;
+            }
+            k++; j++;
+            pos += len; ptr += len; dict += len; cur += len;
+            if (ptr + B > L) {                                            /* Commit -> LZ4_saveDict(ctx, buf, ptr); ptr == dictSize */
+                dict = std::min<int64_t>(65536, dict);
+                ptr = dict;
+            }
+        }
+        if (fill) {
+            fill->soff[si] = srcOff[si]; fill->slen[si] = (uint64_t)N; fill->first[si] = first; fill->nblk[si] = (uint32_t)(k - first);
+            fill->idx0[si] = (uint32_t)((cur0 ? (int64_t)cur0[si] : 0) - D); fill->dict_end[si] = (uint32_t)dict;
+        }
+    }
+    nb = k;
+    return K4LZ4_OK;
+}
+
+int fast_chain_flags(k4lz4_ctx *ctx, int flags)
+{
+    if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: the 32-bit engine's chained encoder (LZ4Codec.Enforce32) is not supported");
+    if (flags & ~(int)K4LZ4_FLAG_ALLOW_COPY) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: the only flag it takes is K4LZ4_FLAG_ALLOW_COPY");
+    return K4LZ4_OK;
+}
+
+/* src / dst / outLen / states: device pointers; the per-stream arrays and cur0 / sdict (the input states' two indices): host */
+int fast_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen, const int32_t *blockSize,
+                   const int32_t *extraBlocks, const int32_t *dictLen, const uint32_t *cur0, const uint32_t *sdict, int64_t nStreams,
+                   const k4lz4_fast_chain_state *stateIn, k4lz4_fast_chain_state *stateOut, uint8_t *dst, const uint64_t *dstOff,
+                   int32_t *outLen, int64_t nBlocks, int flags, hipStream_t stream)
+{
+    int64_t nb = 0;
+    int rc = fast_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, cur0, sdict, nStreams, dstOff, nb, nullptr);
+    if (rc != K4LZ4_OK) return rc;
+    if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: outLen has fewer entries than the streams have blocks");
+    if (nStreams == 0 || (nb == 0 && !stateOut)) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->ev_chain) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_chain));        /* the previous upload of the host table is over */
+    const size_t bytes = FastChainPlan::bytes(nStreams, nb);
+    try { ctx->h_chain.assign(bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    FastChainPlan h;
+    h.place(ctx->h_chain.data(), nStreams, nb);
+    rc = fast_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, cur0, sdict, nStreams, dstOff, nb, &h);
+    if (rc != K4LZ4_OK) return rc;
+    {   /* longest first: a wave that is done takes the next stream (the ticket) */
+        std::vector<uint32_t> ord((size_t)nStreams);
+        for (int64_t si = 0; si < nStreams; si++) ord[(size_t)si] = (uint32_t)si;
+        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return srcLen[x] - (dictLen ? dictLen[x] : 0) > srcLen[y] - (dictLen ? dictLen[y] : 0); });
+        memcpy(h.order, ord.data(), ord.size() * 4);
+    }
+    if (bytes > ctx->d_chain_cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));     /* (grow frees the old table) */
+    if ((rc = grow(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes, false)) != K4LZ4_OK) return rc;
+    FastChainPlan d;
+    d.place(ctx->d_chain, nStreams, nb);
+    if (ctx->busy && ctx->last_stream != stream) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_busy, 0));
+    K4_HIP(ctx, hipMemcpyAsync(ctx->d_chain, ctx->h_chain.data(), bytes, hipMemcpyHostToDevice, stream));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_chain, stream));
+    k4::FastChainArgs a{};
+    a.src = src; a.soff = d.soff; a.slen = d.slen; a.first = d.first; a.nblk = d.nblk; a.idx0 = d.idx0; a.dict_end = d.dict_end; a.order = d.order;
+    a.bpos = d.bpos; a.blen = d.blen; a.bdict = d.bdict; a.doff = d.doff; a.cap = d.cap; a.dst = dst; a.outLen = outLen;
+    a.state_in = (const k4::FastChainState *)stateIn; a.state_out = (k4::FastChainState *)stateOut;
+    a.ticket = d.ticket; a.n = nStreams; a.allow_copy = (flags & K4LZ4_FLAG_ALLOW_COPY) ? 1 : 0;
+    const int64_t wgs = std::min<int64_t>((nStreams + k4::FAST_CHAIN_WAVES_PER_WG - 1) / k4::FAST_CHAIN_WAVES_PER_WG, ctx->cu_count);
+    hipLaunchKernelGGL(k4::k4_fast_chain_kernel, dim3((unsigned)wgs), dim3(64 * k4::FAST_CHAIN_WAVES_PER_WG), 0, stream, a);
+    if (hipGetLastError() != hipSuccess) rc = fail(ctx, K4LZ4_E_HIP, "k4_fast_chain_kernel launch failed");
+    if (hipEventRecord(ctx->ev_busy, stream) == hipSuccess) { ctx->busy = true; ctx->last_stream = stream; }
+    else (void)hipGetLastError();
+    return rc;
+}
+
+/* the two indices of every input state, from the host's copy (or nullptr) */
+void fast_chain_indices(const k4lz4_fast_chain_state *st, int64_t n, std::vector<uint32_t> &cur0, std::vector<uint32_t> &sdict)
+{
+    cur0.resize((size_t)n); sdict.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) { cur0[(size_t)i] = st[i].currentOffset; sdict[(size_t)i] = st[i].dictSize; }
+}
+
 }  // namespace
 
 extern "C" {
@@ -2129,6 +2267,95 @@ int k4lz4_encode_hc_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64
     if (rc != K4LZ4_OK) { (void)take_device_status(ctx); return rc; }
     K4_HIP(ctx, e);
     if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
+    /* exactly |outLen| bytes of every slot to the caller's */
+    int64_t k = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t B = hc_chain_block_size(blockSize[si]), slot = B + B / 255 + 16;
+        for (int64_t j = 0; j * B < srcLen[si] - (dictLen ? dictLen[si] : 0); j++, k++) {
+            const int32_t r = outLen[k];
+            const size_t nbytes = (size_t)(r < 0 ? -(int64_t)r : r);
+            if (nbytes) memcpy(dst + dstOff[si] + (uint64_t)(j * slot), ctx->h_stage + d_doff[(size_t)si] + (uint64_t)(j * slot), nbytes);
+        }
+    }
+    return K4LZ4_OK;
+}
+
+
+int k4lz4_encode_fast_chain_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+                                         const int32_t *blockSize, const int32_t *extraBlocks, const int32_t *dictLen, int64_t nStreams,
+                                         const k4lz4_fast_chain_state *stateIn, k4lz4_fast_chain_state *stateOut, uint8_t *dst,
+                                         const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks, int flags, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (nStreams < 0 || nBlocks < 0 || (nStreams > 0 && (!src || !srcOff || !srcLen || !blockSize || !dst || !dstOff || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    int rc = fast_chain_flags(ctx, flags);
+    if (rc != K4LZ4_OK) return rc;
+    std::vector<uint32_t> cur0, sdict;
+    if (stateIn && nStreams > 0) {
+        /* the block table needs the two indices of every input state on the host (a strided copy: 8 bytes per state) */
+        K4_HIP(ctx, hipSetDevice(ctx->device));
+        std::vector<uint32_t> idx((size_t)nStreams * 2);
+        K4_HIP(ctx, hipMemcpy2DAsync(idx.data(), 8, &stateIn[0].currentOffset, sizeof(k4lz4_fast_chain_state), 8, (size_t)nStreams,
+                                     hipMemcpyDeviceToHost, (hipStream_t)stream));
+        K4_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
+        cur0.resize((size_t)nStreams); sdict.resize((size_t)nStreams);
+        for (int64_t i = 0; i < nStreams; i++) { cur0[(size_t)i] = idx[(size_t)(2 * i)]; sdict[(size_t)i] = idx[(size_t)(2 * i + 1)]; }
+    }
+    return fast_chain_run(ctx, src, srcOff, srcLen, blockSize, extraBlocks, dictLen, stateIn ? cur0.data() : nullptr, stateIn ? sdict.data() : nullptr,
+                          nStreams, stateIn, stateOut, dst, dstOff, outLen, nBlocks, flags, (hipStream_t)stream);
+}
+
+int k4lz4_encode_fast_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+                                  const int32_t *blockSize, const int32_t *extraBlocks, const int32_t *dictLen, int64_t nStreams,
+                                  const k4lz4_fast_chain_state *stateIn, k4lz4_fast_chain_state *stateOut, uint8_t *dst,
+                                  const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks, int flags)
+{
+    if (nStreams < 0 || nBlocks < 0 || (nStreams > 0 && (!src || !srcOff || !srcLen || !blockSize || !dst || !dstOff || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    int rc = fast_chain_flags(ctx, flags);
+    if (rc != K4LZ4_OK) return rc;
+    std::vector<uint32_t> cur0, sdict;
+    if (stateIn) fast_chain_indices(stateIn, nStreams, cur0, sdict);
+    const uint32_t *c0 = stateIn ? cur0.data() : nullptr, *sd = stateIn ? sdict.data() : nullptr;
+    int64_t nb = 0;
+    rc = fast_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, c0, sd, nStreams, dstOff, nb, nullptr);    /* (host arithmetic: before the context) */
+    if (rc != K4LZ4_OK) return rc;
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: outLen has fewer entries than the streams have blocks");
+    if (nStreams == 0 || (nb == 0 && !stateOut)) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* the contents packed on the device, the slots of every stream's blocks behind each other, the states behind the slots */
+    std::vector<uint64_t> d_soff((size_t)nStreams), d_doff((size_t)nStreams);
+    uint64_t stotal = 0, dtotal = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t B = hc_chain_block_size(blockSize[si]);
+        d_soff[(size_t)si] = stotal; stotal += ((uint64_t)srcLen[si] + 15u) & ~(uint64_t)15u;
+        const uint64_t fresh = (uint64_t)(srcLen[si] - (dictLen ? dictLen[si] : 0));       /* (validated by fast_chain_table) */
+        d_doff[(size_t)si] = dtotal; dtotal += ((fresh + (uint64_t)B - 1u) / (uint64_t)B) * (uint64_t)(B + B / 255 + 16);
+    }
+    dtotal = (dtotal + 15u) & ~(uint64_t)15u;
+    const size_t sbytes = (size_t)nStreams * sizeof(k4lz4_fast_chain_state);
+    const size_t nstate = (stateIn ? sbytes : 0) + (stateOut ? sbytes : 0);
+    if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, (size_t)stotal + 64, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)dtotal + nstate + 64, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, (size_t)nb * 4 + 64, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)dtotal + 64, true)) != K4LZ4_OK) return rc;
+    k4lz4_fast_chain_state *d_in = stateIn ? (k4lz4_fast_chain_state *)(ctx->d_dst + dtotal) : nullptr;
+    k4lz4_fast_chain_state *d_outst = stateOut ? (k4lz4_fast_chain_state *)(ctx->d_dst + dtotal + (stateIn ? sbytes : 0)) : nullptr;
+    hipStream_t st = ctx->stream;
+    for (int64_t si = 0; si < nStreams; si++)
+        if (srcLen[si] > 0) K4_HIP(ctx, hipMemcpyAsync(ctx->d_src + d_soff[(size_t)si], src + srcOff[si], (size_t)srcLen[si], hipMemcpyHostToDevice, st));
+    if (stateIn) K4_HIP(ctx, hipMemcpyAsync(d_in, stateIn, sbytes, hipMemcpyHostToDevice, st));
+    int32_t *d_out = (int32_t *)ctx->d_meta;
+    rc = fast_chain_run(ctx, ctx->d_src, d_soff.data(), srcLen, blockSize, extraBlocks, dictLen, c0, sd, nStreams, d_in, d_outst, ctx->d_dst,
+                        d_doff.data(), d_out, nb, flags, st);
+    if (rc == K4LZ4_OK && nb) rc = hipMemcpyAsync(outLen, d_out, (size_t)nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "outLen download");
+    if (rc == K4LZ4_OK && dtotal) rc = hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)dtotal, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "output download");
+    if (rc == K4LZ4_OK && stateOut) rc = hipMemcpyAsync(stateOut, d_outst, sbytes, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "state download");
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc != K4LZ4_OK) return rc;
+    K4_HIP(ctx, e);
     /* exactly |outLen| bytes of every slot to the caller's */
     int64_t k = 0;
     for (int64_t si = 0; si < nStreams; si++) {

@@ -11,16 +11,20 @@ Mirrors:
   LZ4BlockDecoder(blockSize)                                  Encoders/LZ4BlockDecoder.cs:11-106
   LZ4EncoderExtensions.TopupAndEncode / FlushAndEncode /
       DecodeAndDrain, EncoderAction                           Encoders/LZ4EncoderExtensions.cs:8-205, EncoderAction.cs
+  LZ4FastChainEncoder(blockSize, extraBlocks)                 Encoders/LZ4FastChainEncoder.cs (-> LZ4_compress_fast_continue,
+                                                              LZ4_saveDict over LZ4EncoderBase's ring buffer)
 Chained HC blocks batch like independent ones: the HC tables are a function of the data alone, so a
 block needs the bytes before it (at most 64 KiB of them), not the parse of the block before it
-(k4lz4_encode_hc_chain_batch).  The chained FAST encoder (LZ4FastChainEncoder ->
-LZ4_compress_fast_continue) is not offered: its hash table holds only the positions its parse
-visited, so every block depends on the parse of the one before it.  Chained *decoding* is
-(frames.py, k4lz4_decode_chain_batch).
+(k4lz4_encode_hc_chain_batch).  The chained FAST encoder's hash table holds only the
+positions its parse visited, so every block depends on the parse of the one before it: one wavefront
+encodes a stream's blocks in order with the table in LDS, many streams side by side
+(k4lz4_encode_fast_chain_batch); the table and indices travel between calls as a state blob
+(k4lz4_fast_chain_state).  Chained *decoding* is frames.py's (k4lz4_decode_chain_batch).
 
 `LZ4BlockEncoder.EncodeBlocks` is the batching front-end the frame writer uses: K blocks, one launch,
-with the reference's allowCopy rule applied on the device; `encode_hc_chain_packed` is the same for
-whole chained streams, `LZ4HighChainEncoder.EncodeBlocks` for the blocks of one.
+with the reference's allowCopy rule applied on the device; `encode_hc_chain_packed` / `encode_fast_chain_packed`
+are the same for whole chained streams, `LZ4HighChainEncoder.EncodeBlocks` / `LZ4FastChainEncoder.EncodeBlocks`
+for the blocks of one.
 """
 from __future__ import annotations
 
@@ -289,6 +293,230 @@ class LZ4HighChainEncoder:
         return res + [(EncoderAction.None_, b"")] * (len(sources) - len(res))
 
 
+# ---- chained fast streams ------------------------------------------------------------------------------
+FAST_CHAIN_LIMIT = 1 << 31       # LZ4_renormDictT rescales the table once currentOffset + inputSize passes this (LL64.tools.cs:157-173)
+FAST_CHAIN_STATE = np.dtype([("hashTable", "<u4", (4096,)), ("currentOffset", "<u4"), ("dictSize", "<u4"), ("reserved", "<u4", (2,))])
+"""k4lz4_fast_chain_state: LZ4_stream_t's hashTable and indices, word for word"""
+
+
+def fast_chain_blocks(length: int, blockSize: int, extraBlocks: int = 0, dictLen: int = 0,
+                      currentOffset: Optional[int] = None) -> List[Tuple[int, int, int, bool]]:
+    """LZ4FastChainEncoder's blocks of a content in content coordinates: (start, length, dictSize, dictSmall) per block -- the
+    model LZ4EncoderBase's ring buffer reduces to (Topup / Encode / Commit -> LZ4_saveDict).  dictLen: the content's first bytes are
+    what the ring buffer already holds (= the stream context's dictSize); currentOffset: the context's index at that point (default:
+    dictLen, a stream from its start).  dictSize is what the ring holds in front of the block, dictSmall LZ4_compress_fast_continue's
+    choice of dictIssue (LL64.fast.cs:617, :650).  The library builds the same table (k4lz4_capi.hip, fast_chain_table)."""
+    B = _round_block_size(blockSize)
+    L = 65536 + (1 + max(int(extraBlocks), 0)) * B + 32
+    s = ptr = d = int(dictLen)
+    cur = d if currentOffset is None else int(currentOffset)
+    out = []
+    while s < length:
+        n = min(B, length - s)
+        if cur + n > FAST_CHAIN_LIMIT:
+            raise NotImplementedError("a chained fast stream beyond 2 GB (the encoder's renormalisation) is not supported")
+        out.append((s, n, d, d < 65536 and d < cur))
+        s += n
+        ptr += n
+        d += n                                           # LZ4_compress_generic: dictSize += inputSize (the first call's extDict arm: = inputSize)
+        cur += n
+        if ptr + B > L:                                  # Commit -> LZ4_saveDict(ctx, buf, ptr): ptr == dictSize
+            d = ptr = min(65536, d)
+    return out
+
+
+def _fast_chain_args(contents, blockSize, extraBlocks, state_in, dictLen):
+    views = [_ro_view(c, "source") for c in contents]
+    ns = len(views)
+    bs = np.broadcast_to(np.asarray(blockSize, np.int64), (ns,)).astype(np.int32)
+    ex = np.broadcast_to(np.asarray(extraBlocks, np.int64), (ns,)).astype(np.int32)
+    if state_in is not None:
+        state_in = np.ascontiguousarray(state_in, FAST_CHAIN_STATE).reshape(ns)
+    if dictLen is None:
+        dlen = state_in["dictSize"].astype(np.int32) if state_in is not None else np.zeros(ns, np.int32)
+    else:
+        dlen = np.asarray(dictLen, np.int32).reshape(ns)
+    slen = np.array([v.size for v in views], np.int64)
+    B = np.array([_round_block_size(int(b)) for b in bs], np.int64)
+    nblk = np.maximum(slen - dlen + B - 1, 0) // B
+    slot = B + B // 255 + 16                                   # LZ4Codec.MaximumOutputSize(B)
+    doff = np.zeros(ns, np.uint64)
+    if ns > 1:
+        doff[1:] = np.cumsum((nblk * slot)[:-1]).astype(np.uint64)
+    return views, bs, ex, state_in, dlen, slen, nblk, slot, doff
+
+
+def _fast_chain_flags(allow_copy: bool) -> int:
+    if LZ4Codec.Enforce32:
+        raise NotImplementedError("the 32-bit engine's chained fast encoder (LZ4Codec.Enforce32) is not supported")
+    return FLAG_ALLOW_COPY if allow_copy else 0
+
+
+def encode_fast_chain_packed(contents: Sequence, blockSize: Union[int, Sequence[int]], extraBlocks: Union[int, Sequence[int]] = 0,
+                             allow_copy: bool = True, ctx: Optional[_native.Context] = None, state_in=None, want_state: bool = False,
+                             dictLen=None):
+    """chained fast streams, one call (k4lz4_encode_fast_chain_batch) -> (outLen int32 per block, streams in order (negative: stored
+    raw), arena, arena offset per block, blocks per stream, state after each stream (FAST_CHAIN_STATE) or None).  state_in: one state
+    per stream (None: fresh streams); the content's first state.dictSize bytes are then the ring buffer's (dictLen)."""
+    flags = _fast_chain_flags(allow_copy)
+    ctx = ctx or _native.default_context()
+    views, bs, ex, state_in, dlen, slen, nblk, slot, doff = _fast_chain_args(contents, blockSize, extraBlocks, state_in, dictLen)
+    ns = len(views)
+    src, soff, _ = pack_blocks(views)
+    nb = int(nblk.sum())
+    dst = np.empty(max(int((nblk * slot).sum()), 1), np.uint8)
+    out = np.zeros(max(nb, 1), np.int32)
+    st_out = np.zeros(ns, FAST_CHAIN_STATE) if want_state else None
+    ctx.check(ctx.lib.k4lz4_encode_fast_chain_batch(ctx.handle, src.ctypes.data, soff.ctypes.data, slen.ctypes.data, bs.ctypes.data,
+                                                    ex.ctypes.data, dlen.ctypes.data, ns,
+                                                    None if state_in is None else state_in.ctypes.data,
+                                                    None if st_out is None else st_out.ctypes.data,
+                                                    dst.ctypes.data, doff.ctypes.data, out.ctypes.data, nb, flags))
+    boff = np.concatenate([doff[f] + np.arange(nblk[f], dtype=np.uint64) * np.uint64(slot[f]) for f in range(ns)]) if nb else np.zeros(0, np.uint64)
+    return out[:nb], dst, boff, nblk, st_out
+
+
+def encode_fast_chain_device(dc, data, off, length, blockSize, extraBlocks=0, allow_copy: bool = True, state_in=None,
+                             want_state: bool = False, dictLen=None):
+    """encode_fast_chain_packed on HBM-resident contents (k4lz4_encode_fast_chain_batch_device): `data` a uint8 torch tensor, content s =
+    data[off[s] : off[s] + length[s]] (off / length host arrays).  state_in: a uint8 torch tensor of one state per stream on the device,
+    or None.  Returns (outLen, arena, arena offset per block (host), blocks per stream, states after the streams (uint8 tensor) or None),
+    asynchronous on the current torch stream; `dc` is a device.DeviceCodec."""
+    import torch
+    from .device import _dp
+    flags = _fast_chain_flags(allow_copy)
+    off = np.ascontiguousarray(off, np.uint64)
+    length = np.ascontiguousarray(length, np.int64)
+    ns = len(off)
+    bs = np.broadcast_to(np.asarray(blockSize, np.int64), (ns,)).astype(np.int32)
+    ex = np.broadcast_to(np.asarray(extraBlocks, np.int64), (ns,)).astype(np.int32)
+    dlen = np.zeros(ns, np.int32) if dictLen is None else np.asarray(dictLen, np.int32).reshape(ns)
+    B = np.array([_round_block_size(int(b)) for b in bs], np.int64)
+    nblk = np.maximum(length - dlen + B - 1, 0) // B
+    slot = B + B // 255 + 16
+    doff = np.zeros(ns, np.uint64)
+    if ns > 1:
+        doff[1:] = np.cumsum((nblk * slot)[:-1]).astype(np.uint64)
+    nb = int(nblk.sum())
+    dev = dc.device
+    arena = torch.empty(max(int((nblk * slot).sum()), 1) + 64, dtype=torch.uint8, device=dev)
+    out = torch.zeros(max(nb, 1), dtype=torch.int32, device=dev)
+    st_out = torch.zeros(ns * FAST_CHAIN_STATE.itemsize, dtype=torch.uint8, device=dev) if want_state else None
+    import ctypes as C
+    dc.ctx.check(dc.lib.k4lz4_encode_fast_chain_batch_device(dc.ctx.handle, _dp(data), off.ctypes.data, length.ctypes.data, bs.ctypes.data,
+                                                             ex.ctypes.data, dlen.ctypes.data, ns, _dp(state_in), _dp(st_out), _dp(arena),
+                                                             doff.ctypes.data, _dp(out), nb, flags, C.c_void_p(dc._stream())))
+    boff = np.concatenate([doff[f] + np.arange(nblk[f], dtype=np.uint64) * np.uint64(slot[f]) for f in range(ns)]) if nb else np.zeros(0, np.uint64)
+    return out[:nb], arena, boff, nblk, st_out
+
+
+class LZ4FastChainEncoder:
+    """Chained fast encoder (LZ4FastChainEncoder.cs over LZ4EncoderBase.cs): every block is LZ4_compress_fast_continue with the
+    blocks before it as history.  The ring buffer is the reference's, byte for byte (Topup / Encode / Commit -> LZ4_saveDict); the
+    stream context (hash table, currentOffset, dictSize) lives in a k4lz4_fast_chain_state blob that every call hands to the device
+    and takes back.  `EncodeBlocks` hands many blocks of the stream to one call."""
+
+    def __init__(self, blockSize: int = 65536, extraBlocks: int = 0):
+        self._block_size = _round_block_size(blockSize)
+        self._extra = max(int(extraBlocks), 0)
+        self._length = 65536 + (1 + self._extra) * self._block_size + 32                      # LZ4EncoderBase.cs:25
+        self._input = np.zeros(self._length + 8, np.uint8)
+        self._index = 0
+        self._pointer = 0
+        self._state = np.zeros(1, FAST_CHAIN_STATE)                                            # Mem.AllocZero(sizeof(LZ4_stream_t))
+
+    @property
+    def BlockSize(self) -> int:
+        return self._block_size
+
+    @property
+    def BytesReady(self) -> int:
+        return self._pointer - self._index
+
+    @property
+    def State(self) -> np.ndarray:
+        """the stream context as it stands (FAST_CHAIN_STATE, a copy)"""
+        return self._state.copy()
+
+    def Topup(self, source, offset: int = 0, length: Optional[int] = None) -> int:
+        """LZ4EncoderBase.cs:46-62"""
+        src = _ro_view(source, "source")
+        length = src.size - offset if length is None else int(length)
+        if length == 0:
+            return 0
+        space = self._index + self._block_size - self._pointer
+        if space <= 0:
+            return 0
+        chunk = min(space, length)
+        self._input[self._pointer:self._pointer + chunk] = src[offset:offset + chunk]
+        self._pointer += chunk
+        return chunk
+
+    def _commit(self) -> None:
+        """LZ4EncoderBase.Commit -> LZ4_saveDict(ctx, buffer, pointer)"""
+        self._index = self._pointer
+        if self._index + self._block_size <= self._length:
+            return
+        d = min(65536, self._pointer, int(self._state["dictSize"][0]))
+        self._input[:d] = self._input[self._pointer - d:self._pointer].copy()
+        self._state["dictSize"] = d
+        self._index = self._pointer = d
+
+    def _run(self, content: np.ndarray, allowCopy: bool, ctx=None):
+        if int(self._state["currentOffset"][0]) + content.size - self._index > FAST_CHAIN_LIMIT:
+            raise NotImplementedError("a chained fast stream beyond 2 GB (the encoder's renormalisation) is not supported")
+        out, arena, boff, _, st = encode_fast_chain_packed([content], self._block_size, self._extra, allowCopy, ctx, state_in=self._state,
+                                                           want_state=True)
+        return out, arena, boff, st
+
+    def Encode(self, target, offset: int = 0, length: Optional[int] = None, allowCopy: bool = False) -> int:
+        """encodes the pending bytes as one block into target; with allowCopy a block that does not shrink is stored raw and
+        -length is returned (LZ4EncoderBase.cs:66-88)"""
+        dst = _rw_view(target, "target")
+        length = dst.size - offset if length is None else int(length)
+        n = self._pointer - self._index
+        if n <= 0:
+            return 0
+        out, arena, boff, st = self._run(self._input[:self._pointer], allowCopy)
+        encoded = int(out[0])
+        if encoded == 0 or abs(encoded) > length:
+            raise InvalidOperationException("Failed to encode chunk. Target buffer too small.")
+        dst[offset:offset + abs(encoded)] = arena[int(boff[0]):int(boff[0]) + abs(encoded)]
+        self._state = st
+        self._commit()
+        return encoded
+
+    def EncodeBlocks(self, sources: Sequence, allowCopy: bool = True,
+                     ctx: Optional[_native.Context] = None) -> List[Tuple[EncoderAction, bytes]]:
+        """the next blocks of the stream, as Topup + Encode(allowCopy) per element would produce them, in one call.  Every
+        element but the last is BlockSize bytes (the encoder's blocks are what the ring buffer cuts), the last at most that;
+        nothing may be pending."""
+        blocks = [_ro_view(s, "source") for s in sources]
+        if self.BytesReady:
+            raise InvalidOperationException("bytes are pending: Encode them first")
+        for i, b in enumerate(blocks):
+            if b.size > self._block_size or (i < len(blocks) - 1 and b.size != self._block_size):
+                raise InvalidOperationException("every block but the last must be BlockSize bytes")
+        blocks = [b for b in blocks if b.size]
+        if not blocks:
+            return [(EncoderAction.None_, b"") for _ in sources]
+        content = np.concatenate([self._input[:self._index]] + blocks)
+        out, arena, boff, st = self._run(content, allowCopy, ctx)
+        res = []
+        for n, o in zip(out, boff):
+            if n == 0:
+                raise InvalidOperationException("Failed to encode chunk. Target buffer too small.")
+            res.append((EncoderAction.Copied if n < 0 else EncoderAction.Encoded, arena[int(o):int(o) + abs(int(n))].tobytes()))
+        # the ring buffer as the blocks one by one would have left it; the device's state is the last block's (and its save)
+        for b in blocks:
+            self.Topup(b)
+            self._state["dictSize"] += b.size
+            self._commit()
+        assert int(self._state["dictSize"][0]) == int(st["dictSize"][0])
+        self._state = st
+        return res + [(EncoderAction.None_, b"")] * (len(sources) - len(res))
+
+
 class LZ4BlockDecoder:
     """Decoder for independent blocks (LZ4BlockDecoder.cs)."""
 
@@ -347,7 +575,7 @@ class LZ4BlockDecoder:
 
 
 # ---- LZ4EncoderExtensions ---------------------------------------------------------------------------
-def TopupAndEncode(encoder: Union[LZ4BlockEncoder, LZ4HighChainEncoder], source, target, forceEncode: bool, allowCopy: bool):
+def TopupAndEncode(encoder: Union[LZ4BlockEncoder, LZ4HighChainEncoder, LZ4FastChainEncoder], source, target, forceEncode: bool, allowCopy: bool):
     """-> (action, loaded, encoded)   (LZ4EncoderExtensions.cs:117-133, :183-205)"""
     src = _ro_view(source, "source")
     loaded = encoder.Topup(src) if src.size > 0 else 0
@@ -355,7 +583,7 @@ def TopupAndEncode(encoder: Union[LZ4BlockEncoder, LZ4HighChainEncoder], source,
     return action, loaded, encoded
 
 
-def FlushAndEncode(encoder: Union[LZ4BlockEncoder, LZ4HighChainEncoder], target, forceEncode: bool = True, allowCopy: bool = True, loaded: int = 0):
+def FlushAndEncode(encoder: Union[LZ4BlockEncoder, LZ4HighChainEncoder, LZ4FastChainEncoder], target, forceEncode: bool = True, allowCopy: bool = True, loaded: int = 0):
     """-> (action, encoded)"""
     if encoder.BytesReady < (1 if forceEncode else encoder.BlockSize):
         return (EncoderAction.Loaded if loaded > 0 else EncoderAction.None_), 0

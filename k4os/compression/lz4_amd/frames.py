@@ -16,11 +16,14 @@ Chained frames (ChainBlocks=True) are written at L03_HC and up: LZ4HighChainEnco
 depend on the data alone, so a block needs the 64 KiB before it and not the parse of the block before
 it.  ExtraMemory sets the encoder's extra blocks as the reference's writer does.
 
+Chained frames below L03_HC -- LZ4FastChainEncoder's, whose hash table holds only the positions its parse
+visited, so a stream's blocks are serial -- are written by `encode_fast_chain_frames`
+(k4lz4_encode_fast_chain_batch: one wavefront per stream, many streams side by side).
+
 Differences from the reference, all deliberate:
-  * ChainBlocks defaults to False here (the reference: True).  Chained frames at L00_FAST raise
-    NotImplementedException: LZ4FastChainEncoder's hash table holds only the positions its parse
-    visited, so each block depends on the parse of the one before it -- serial per stream.  The READER
-    takes both kinds.
+  * ChainBlocks defaults to False here (the reference: True).  LZ4Frame.Encode / EncodeBatch and
+    encode_frames_device still raise NotImplementedException for chained frames at L00_FAST; the
+    chained fast writer is encode_fast_chain_frames.  The READER takes both kinds.
   * ContentLength in the header is written when asked for (the reference's writer throws
     NotImplemented, LZ4FrameWriter.cs:86-88) and verified by the reader, like the reference's reader.
 """
@@ -34,7 +37,7 @@ import numpy as np
 
 from . import _native
 from .codec import LZ4Codec, LZ4Level, _ro_view, pack_blocks, make_arena, _batch_args
-from .encoders import encode_blocks_packed, encode_hc_chain_packed, hc_chain_blocks, _round_block_size
+from .encoders import encode_blocks_packed, encode_hc_chain_packed, encode_fast_chain_packed, hc_chain_blocks, _round_block_size
 
 MAGIC = 0x184D2204
 K64, K256, M1, M4 = 64 << 10, 256 << 10, 1 << 20, 4 << 20
@@ -216,6 +219,39 @@ def xxh32_many(buffers: Sequence, ctx: Optional[_native.Context] = None) -> np.n
     return out
 
 
+def _assemble_frames(s: "LZ4EncoderSettings", contents, out, arena, aoff, owner, ctx) -> List[bytes]:
+    """the frames of a batch from its encoded blocks (outLen per block, negative: stored raw; arena slots; owning frame per block):
+    header, block records with their checksums, EndMark, content checksum -- every XXH32 in one launch"""
+    bs = int(s.BlockSize)
+    payloads, raw = [], []
+    for n, o in zip(out, aoff if len(out) else []):
+        if n == 0:
+            raise RuntimeError("Failed to encode chunk. Target buffer too small.")       # LZ4EncoderBase.cs:75-77
+        payloads.append(arena[int(o):int(o) + abs(int(n))])
+        raw.append(n < 0)
+    descs = [LZ4Descriptor(s.ContentLength, s.ContentChecksum, bool(s.ChainBlocks), s.BlockChecksum, None, bs) for _ in contents]
+    # every XXH32 of the batch in one launch: headers, then block payloads, then contents
+    to_hash = [np.frombuffer(frame_header(d), np.uint8) for d in descs]
+    if s.BlockChecksum:
+        to_hash += payloads
+    if s.ContentChecksum:
+        to_hash += contents
+    hashes = xxh32_many(to_hash, ctx)
+    nf, nb = len(contents), len(payloads)
+    bh = hashes[nf:nf + nb] if s.BlockChecksum else None
+    ch = hashes[nf + (nb if s.BlockChecksum else 0):] if s.ContentChecksum else None
+    frames = []
+    k = 0
+    for f, d in enumerate(descs):
+        k0 = k
+        while k < nb and owner[k] == f:
+            k += 1
+        frames.append(assemble_frame(d, int(hashes[f]), [payloads[i].tobytes() for i in range(k0, k)], raw[k0:k],
+                                     None if bh is None else [int(x) for x in bh[k0:k]],
+                                     None if ch is None else int(ch[f])))
+    return frames
+
+
 class LZ4Frame:
     """LZ4Frame.Encode / Decode for whole buffers, plus their batch forms."""
 
@@ -255,33 +291,7 @@ class LZ4Frame:
                     blocks.append(c[p:p + bs])
                     owner.append(f)
             out, arena, aoff = encode_blocks_packed(blocks, s.CompressionLevel, True, ctx) if blocks else (np.zeros(0, np.int32), None, None)
-        payloads, raw = [], []
-        for n, o in zip(out, aoff if len(out) else []):
-            if n == 0:
-                raise RuntimeError("Failed to encode chunk. Target buffer too small.")       # LZ4EncoderBase.cs:75-77
-            payloads.append(arena[int(o):int(o) + abs(int(n))])
-            raw.append(n < 0)
-        descs = [LZ4Descriptor(s.ContentLength, s.ContentChecksum, bool(s.ChainBlocks), s.BlockChecksum, None, bs) for _ in contents]
-        # every XXH32 of the batch in one launch: headers, then block payloads, then contents
-        to_hash = [np.frombuffer(frame_header(d), np.uint8) for d in descs]
-        if s.BlockChecksum:
-            to_hash += payloads
-        if s.ContentChecksum:
-            to_hash += contents
-        hashes = xxh32_many(to_hash, ctx)
-        nf, nb = len(contents), len(payloads)
-        bh = hashes[nf:nf + nb] if s.BlockChecksum else None
-        ch = hashes[nf + (nb if s.BlockChecksum else 0):] if s.ContentChecksum else None
-        frames = []
-        k = 0
-        for f, d in enumerate(descs):
-            k0 = k
-            while k < nb and owner[k] == f:
-                k += 1
-            frames.append(assemble_frame(d, int(hashes[f]), [payloads[i].tobytes() for i in range(k0, k)], raw[k0:k],
-                                         None if bh is None else [int(x) for x in bh[k0:k]],
-                                         None if ch is None else int(ch[f])))
-        return frames
+        return _assemble_frames(s, contents, out, arena, aoff, owner, ctx)
 
     # ---- decode -----------------------------------------------------------------------------------
     @staticmethod
@@ -496,3 +506,29 @@ def encode_frames_device(dc, data, off: np.ndarray, length: np.ndarray, settings
                                             _dp(frame_len), nf, C.c_void_p(dc._stream()))
     dc.ctx.check(rc)
     return frames, frame_off, frame_len[:nf]
+
+
+def encode_fast_chain_frames(sources: Sequence, settings: Optional[LZ4EncoderSettings] = None,
+                             ctx: Optional[_native.Context] = None) -> List[bytes]:
+    """the frames LZ4FrameWriter writes with ChainBlocks=True below L03_HC (Streams/Extensions.cs:28-36 -> LZ4FastChainEncoder(blockSize,
+    extraBlocks)): header, blocks with the allowCopy rule, block checksums, EndMark, content checksum, ContentLength when asked for.
+    Every frame is one stream of one k4lz4_encode_fast_chain_batch call; the assembly is LZ4Frame.EncodeBatch's."""
+    s = settings or LZ4EncoderSettings(ChainBlocks=True)
+    if int(s.CompressionLevel) >= int(LZ4Level.L03_HC):
+        raise ValueError("encode_fast_chain_frames writes the fast levels' frames (below L03_HC)")
+    s = LZ4EncoderSettings(**{**s.__dict__, "ChainBlocks": True})
+    max_block_size_code(s.BlockSize)
+    ctx = ctx or _native.default_context()
+    contents = [_ro_view(x, "source") for x in sources]
+    bs = int(s.BlockSize)
+    for c in contents:
+        if s.ContentLength is not None and s.ContentLength != c.size:
+            raise ValueError("ContentLength does not match the source length")
+    nonempty = [f for f, c in enumerate(contents) if c.size]
+    if nonempty:
+        out, arena, aoff, nblk, _ = encode_fast_chain_packed([contents[f] for f in nonempty], bs, _extra_blocks(bs, int(s.ExtraMemory)),
+                                                             True, ctx)
+        owner = list(np.repeat(np.array(nonempty), nblk))
+    else:
+        out, arena, aoff, owner = np.zeros(0, np.int32), None, None, []
+    return _assemble_frames(s, contents, out, arena, aoff, owner, ctx)
