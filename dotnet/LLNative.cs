@@ -64,6 +64,20 @@ namespace K4os.Compression.LZ4.Engine
 		[DllImport(Lib)] public static extern int k4lz4_decode_chain_batch(
 			IntPtr ctx, byte* src, ulong* blkOff, uint* blkLen, long nBlocks, ulong* firstBlk, uint* nBlk, int* blockSize, byte* chained,
 			byte* dst, ulong* dstOff, ulong* dstCap, long* outLen, long nStreams);
+		// frame reader (LZ4FrameReader over whole frames, DESIGN.md 4.11): outSize = the most frame f can decode to, outStatus /
+		// outLen < 0 = the FRAME_* codes below.  The _device forms take device pointers; k4lz4_decode_frames_device waits for its
+		// stream once (it reads the block count back).
+		public const int FRAME_EOF = -1, FRAME_MAGIC = -2, FRAME_VERSION = -3, FRAME_HEADER_SUM = -4, FRAME_DICTIONARY = -5,
+			FRAME_BLOCK = -6, FRAME_BLOCK_SUM = -7, FRAME_CONTENT_SUM = -8, FRAME_CAPACITY = -9, FRAME_LENGTH = -10;
+		[DllImport(Lib)] public static extern int k4lz4_frame_sizes(
+			IntPtr ctx, byte* src, ulong* frameOff, ulong* frameLen, long n, ulong* outSize, int* outStatus);
+		[DllImport(Lib)] public static extern int k4lz4_decode_frames(
+			IntPtr ctx, byte* src, ulong* frameOff, ulong* frameLen, long n, byte* dst, ulong* dstOff, ulong* dstCap, long* outLen);
+		[DllImport(Lib)] public static extern int k4lz4_frame_sizes_device(
+			IntPtr ctx, byte* src, ulong* frameOff, ulong* frameLen, long n, ulong* outSize, int* outStatus, IntPtr stream);
+		[DllImport(Lib)] public static extern int k4lz4_decode_frames_device(
+			IntPtr ctx, byte* src, ulong* frameOff, ulong* frameLen, long n, byte* dst, ulong* dstOff, ulong* dstCap, long* outLen,
+			IntPtr stream);
 		// chained HC streams: LZ4HighChainEncoder(level, blockSize, extraBlocks) over whole contents, every block of every stream in
 		// one launch sequence; dictLen (may be null): ring-buffer bytes in front of each content's first new block
 		[DllImport(Lib)] public static extern int k4lz4_encode_hc_chain_batch(

@@ -4,7 +4,8 @@
 // one encode / decode launch and one XXH32 launch.  Chained frames (ChainBlocks = true, the reference's default) at L03_HC and up
 // are LZ4HighChainEncoder's blocks, from k4lz4_encode_hc_chain_batch: a chained HC block needs the bytes before it, not the parse
 // of the block before it (DESIGN.md).  Chained L00_FAST frames stay with LZ4FrameWriter (LZ4FastChainEncoder's table depends on
-// its parse: serial per stream).  The reader side decodes both, chained blocks in order (k4lz4_decode_chain_batch).
+// its parse: serial per stream).  The reader side (Decode / DecodeBatch) is k4lz4_frame_sizes + k4lz4_decode_frames: the frames are
+// walked, checked and decoded on the device, both kinds.
 // Byte layout and header arithmetic are LZ4FrameWriter.cs:57-108,:159-189.  Compile-unverified.
 using System;
 using System.Buffers.Binary;
@@ -103,18 +104,69 @@ namespace K4os.Compression.LZ4.Streams.Frames
 			return frame;
 		}
 
-		/// <summary>Decodes one frame (independent or chained blocks) into a fresh array; InvalidDataException where LZ4FrameReader throws
-		/// (bad magic / version / header checksum, a block or content checksum that does not match, a block that does not decode).</summary>
-		public static byte[] Decode(ReadOnlySpan<byte> frame)
+		/// <summary>Decodes one frame (independent or chained blocks) into a fresh array, throwing what LZ4FrameReader throws for the
+		/// first defect it meets in stream order (bad magic / version / header checksum, dictionary, end of stream, a block checksum,
+		/// a block that does not decode, the content checksum, ContentLength).  Bytes after the frame are ignored.</summary>
+		public static byte[] Decode(ReadOnlySpan<byte> frame) => DecodeBatch(new[] { frame.ToArray() })[0];
+
+		/// <summary>Decodes whole frames, one per element, with two native calls (k4lz4_frame_sizes sizes the output without trusting
+		/// the headers, k4lz4_decode_frames walks, checks and decodes every frame on the device); throws for the lowest-index frame
+		/// that fails.</summary>
+		public static byte[][] DecodeBatch(byte[][] frames)
 		{
-			// The header walk is LZ4FrameReader.async.cs:52-105 (index arithmetic on the host); the block table it yields --
-			// offsets, stored lengths with the raw bit, at most MaxBlockSize bytes each -- goes to LZ4BlockDecoder.DecodeBlocks
-			// (independent blocks) or k4lz4_decode_chain_batch (chained), the checksums to one k4lz4_xxh32_batch call, exactly as
-			// k4os/compression/lz4_amd/frames.py does in the Python mirror of this file (LZ4Frame.Decode / DecodeBatch), which is
-			// what the parity tests run.  The slot of a block is min(MaxBlockSize, 255 * stored + 32): a header is never trusted
-			// for memory.
-			throw new NotImplementedException("see frames.py: LZ4Frame.Decode -- the same walk, to be transcribed when a C# toolchain is at hand");
+			var n = frames.Length;
+			var frameOff = new ulong[n];
+			var frameLen = new ulong[n];
+			long total = 0;
+			for (var i = 0; i < n; i++) { frameOff[i] = (ulong) total; frameLen[i] = (ulong) frames[i].Length; total += frames[i].Length; }
+			var packed = new byte[Math.Max(total, 1)];
+			for (var i = 0; i < n; i++) Buffer.BlockCopy(frames[i], 0, packed, (int) frameOff[i], frames[i].Length);
+			var size = new ulong[n];
+			var status = new int[n];
+			var outLen = new long[n];
+			using var lease = NativeContext.Rent();
+			fixed (byte* src = packed)
+			fixed (ulong* fo = frameOff)
+			fixed (ulong* fl = frameLen)
+			fixed (ulong* sz = size)
+			fixed (int* st = status)
+				LLNative.ThrowIfFailed(LLNative.k4lz4_frame_sizes(lease.Handle, src, fo, fl, n, sz, st), lease.Handle);
+			var dstOff = new ulong[n];
+			ulong outTotal = 0;
+			for (var i = 0; i < n; i++) { dstOff[i] = outTotal; outTotal += size[i]; }
+			var dst = new byte[Math.Max(outTotal, 1UL)];
+			fixed (byte* src = packed)
+			fixed (ulong* fo = frameOff)
+			fixed (ulong* fl = frameLen)
+			fixed (byte* d = dst)
+			fixed (ulong* doff = dstOff)
+			fixed (ulong* cap = size)
+			fixed (long* ol = outLen)
+				LLNative.ThrowIfFailed(LLNative.k4lz4_decode_frames(lease.Handle, src, fo, fl, n, d, doff, cap, ol), lease.Handle);
+			var result = new byte[n][];
+			for (var i = 0; i < n; i++)
+			{
+				if (outLen[i] < 0) throw FrameError(outLen[i]);
+				result[i] = dst.AsSpan((int) dstOff[i], (int) outLen[i]).ToArray();
+			}
+			return result;
 		}
+
+		/// <summary>The reference reader's exception for a K4LZ4_FRAME_* code (Frames/LZ4FrameReader.blocking.cs ReadHeader / ReadBlock,
+		/// Internal/Stash: EndOfStream).</summary>
+		private static Exception FrameError(long code) => code switch {
+			LLNative.FRAME_EOF => new System.IO.EndOfStreamException("Unexpected end of stream"),
+			LLNative.FRAME_MAGIC => new System.IO.InvalidDataException("LZ4 frame magic number expected"),
+			LLNative.FRAME_VERSION => new System.IO.InvalidDataException("LZ4 frame version unknown: 0"),
+			LLNative.FRAME_HEADER_SUM => new System.IO.InvalidDataException("Invalid LZ4 frame header checksum"),
+			LLNative.FRAME_DICTIONARY => new NotImplementedException("Predefined dictionaries feature is not implemented"),
+			LLNative.FRAME_BLOCK => new System.IO.InvalidDataException("LZ4 block does not decode"),
+			LLNative.FRAME_BLOCK_SUM => new System.IO.InvalidDataException("Invalid block checksum"),
+			LLNative.FRAME_CONTENT_SUM => new System.IO.InvalidDataException("Invalid content checksum"),
+			LLNative.FRAME_CAPACITY => new System.IO.InvalidDataException("Decoded frame does not fit its target"),
+			LLNative.FRAME_LENGTH => new System.IO.InvalidDataException("Content length does not match the frame header"),
+			_ => new InvalidOperationException($"unknown frame result {code}"),
+		};
 
 		private static int MaxBlockSize(int requested, out int bdCode)
 		{   // LZ4FrameWriter.cs:176-189

@@ -327,6 +327,51 @@ K4LZ4_API int k4lz4_frame_assemble_device(k4lz4_ctx *ctx, const uint8_t *arena, 
                                           const uint64_t *tailOff, const uint32_t *contentSum, uint8_t *frames,
                                           uint64_t *frameLen, int64_t nFrames, void *stream);
 
+/* ---- frame reader on device-resident frames: LZ4FrameReader (Frames/LZ4FrameReader.blocking.cs ReadHeader / ReadBlock) over
+ * many whole frames at once.  Frame f is src[frameOff[f] .. frameOff[f] + frameLen[f]); nothing outside that
+ * range is read, and bytes after the frame's end (EndMark, content checksum) are ignored.  Header fields, the header checksum
+ * and the block records are walked on the device, one thread per frame; block checksums, decoding and the content checksum
+ * are the batch kernels' (independent-block frames: every block decoded in parallel straight into its place; chained frames,
+ * and independent frames whose blocks are not all full but the last: in order, one stream per frame).
+ *
+ * Per-frame results (outLen, outStatus).  A frame reports the first defect the reference's reader meets in stream order: header
+ * fields, header checksum, dictionary, then per block truncation, block checksum, decoding; then EndMark and content checksum;
+ * then ContentLength.  -6 and -9 are the chain API's (k4lz4_decode_chain_batch). */
+#define K4LZ4_FRAME_EOF            (-1)   /* the frame ends early (header, block record or trailer): EndOfStream */
+#define K4LZ4_FRAME_MAGIC          (-2)   /* "LZ4 frame magic number expected" */
+#define K4LZ4_FRAME_VERSION        (-3)   /* "LZ4 frame version unknown" ((FLG >> 6) & 0x11 != 1, as the reader tests it) */
+#define K4LZ4_FRAME_HEADER_SUM     (-4)   /* "Invalid LZ4 frame header checksum" */
+#define K4LZ4_FRAME_DICTIONARY     (-5)   /* predefined dictionary: NotImplementedException */
+#define K4LZ4_FRAME_BLOCK          (-6)   /* a block does not decode */
+#define K4LZ4_FRAME_BLOCK_SUM      (-7)   /* "Invalid block checksum" */
+#define K4LZ4_FRAME_CONTENT_SUM    (-8)   /* "Invalid content checksum" */
+#define K4LZ4_FRAME_CAPACITY       (-9)   /* dstCap[f] is too small for what the frame produces */
+#define K4LZ4_FRAME_LENGTH         (-10)  /* the output does not match the declared ContentLength (also: it would pass a ContentLength
+                                             that is <= dstCap[f], which is this code and not -9) */
+
+/* outSize[f] = what frame f may decode to at most, without trusting its header: per block min(blockSize, 255 * stored + 32), the
+ * stored length for a raw block, the total capped by ContentLength when the frame declares one (what LZ4Frame.DecodeBatch allows);
+ * outStatus[f] = 0, or the header / structure defect the walk found (-1 .. -5; with -1 after the header, outSize covers the
+ * complete blocks before the end).  Every pointer is a device pointer.  Asynchronous on `stream`.  Mirrors
+ * k4lz4_unpickle_sizes_device. */
+K4LZ4_API int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen,
+                                       int64_t n, uint64_t *outSize, int32_t *outStatus, void *stream);
+/* Decodes frame f into dst + dstOff[f] (at most dstCap[f] bytes; outSize of k4lz4_frame_sizes_device always suffices);
+ * outLen[f] = bytes produced, or a K4LZ4_FRAME_* code.  Bytes of a slot past outLen[f] may be written (with blocks that later
+ * turn out not to fit, or with blocks of a failing frame) but nothing outside [dstOff[f], dstOff[f] + dstCap[f]) is.  Every
+ * pointer is a device pointer.  The number of blocks is known only on the device: the call reads it back once to size its
+ * grow-only block table (56 bytes per block, plus 105 bytes per frame), so it WAITS FOR `stream` there, after the walk; everything
+ * else is enqueued on `stream`. */
+K4LZ4_API int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen,
+                                         int64_t n, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen,
+                                         void *stream);
+/* The same on host memory (staged through the GPU like k4lz4_decode_chain_batch; the staging is sized by the sum of dstCap):
+ * exactly outLen[f] bytes are written to dst + dstOff[f] for a frame that decodes, none for one that fails.  Synchronous. */
+K4LZ4_API int k4lz4_frame_sizes(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                                uint64_t *outSize, int32_t *outStatus);
+K4LZ4_API int k4lz4_decode_frames(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                                  uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,11 +7,13 @@ from .pickler import LZ4Pickler, InvalidDataException
 from .encoders import (LZ4BlockEncoder, LZ4HighChainEncoder, LZ4FastChainEncoder, LZ4BlockDecoder, EncoderAction, InvalidOperationException, TopupAndEncode,
                        FlushAndEncode, DecodeAndDrain, encode_fast_chain_packed, encode_fast_chain_device, fast_chain_blocks,
                        FAST_CHAIN_STATE)
-from .frames import LZ4Frame, LZ4EncoderSettings, LZ4Descriptor, parse_frame, xxh32_many, encode_fast_chain_frames
+from .frames import (LZ4Frame, LZ4EncoderSettings, LZ4Descriptor, parse_frame, xxh32_many, encode_fast_chain_frames,
+                     frame_sizes_device, decode_frames_device, frame_exception)
 from ._native import NativeLibraryError, Context, load_library, default_context, host_register, host_unregister
 
 __all__ = ["LZ4Codec", "LZ4Level", "LZ4Pickler", "InvalidDataException", "NativeLibraryError", "Context",
            "load_library", "default_context", "host_register", "host_unregister", "pack_blocks", "make_arena", "LZ4BlockEncoder", "LZ4HighChainEncoder", "LZ4FastChainEncoder", "LZ4BlockDecoder",
            "EncoderAction", "InvalidOperationException", "TopupAndEncode", "FlushAndEncode", "DecodeAndDrain", "LZ4Frame",
            "LZ4EncoderSettings", "LZ4Descriptor", "parse_frame", "xxh32_many", "encode_fast_chain_packed", "encode_fast_chain_device",
-           "fast_chain_blocks", "FAST_CHAIN_STATE", "encode_fast_chain_frames"]
+           "fast_chain_blocks", "FAST_CHAIN_STATE", "encode_fast_chain_frames",
+           "frame_sizes_device", "decode_frames_device", "frame_exception"]

@@ -70,6 +70,11 @@ SYMBOLS = {
     "k4lz4_frame_assemble_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_int64, C.c_void_p]),
     "k4lz4_unpickle_sizes_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "k4lz4_frame_sizes_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_decode_frames_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "k4lz4_frame_sizes": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "k4lz4_decode_frames": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "k4lz4_encode_hc_chain_batch": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _u8p,
                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
     "k4lz4_encode_hc_chain_batch_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _u8p,

@@ -35,6 +35,7 @@
 #include "k4lz4_encode_hc.hpp"
 #include "k4lz4_fast_chain.hpp"
 #include "k4lz4_frame.hpp"
+#include "k4lz4_frame_read.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 
@@ -133,6 +134,9 @@ struct k4lz4_ctx {
     std::vector<uint8_t> h_chain;
     uint8_t *d_chain = nullptr; size_t d_chain_cap = 0;
     hipEvent_t ev_chain = nullptr;
+    /* frame reader (k4lz4_frame_read.hpp): per-frame words and the block table, both grow-only */
+    uint8_t *d_fr = nullptr; size_t d_fr_cap = 0;
+    uint8_t *d_fb = nullptr; size_t d_fb_cap = 0;
 };
 
 /* a few helper threads for the staging copies of big host-pointer calls (memcpy between the caller's pageable memory and
@@ -1649,6 +1653,87 @@ void fast_chain_indices(const k4lz4_fast_chain_state *st, int64_t n, std::vector
     for (int64_t i = 0; i < n; i++) { cur0[(size_t)i] = st[i].currentOffset; sdict[(size_t)i] = st[i].dictSize; }
 }
 
+/* ---- frame reader scratch (k4lz4_frame_read.hpp): per-frame words behind 64 bytes of counters, and the block table.
+ * Grow-only; a table that has to grow waits for the context's earlier work first (grow frees the old one). */
+constexpr size_t FRAME_BYTES = 8 * 8 + 10 * 4 + 1, BLOCK_BYTES = 3 * 8 + 8 * 4;
+
+int frame_scratch(k4lz4_ctx *ctx, int64_t n, k4::FrameTab *t, unsigned long long **counters)
+{
+    const size_t need = 64 + (size_t)n * FRAME_BYTES + 64;
+    int rc;
+    if (need > ctx->d_fr_cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
+    if ((rc = grow(ctx, &ctx->d_fr, &ctx->d_fr_cap, need, false)) != K4LZ4_OK) return rc;
+    uint8_t *m = ctx->d_fr;
+    const size_t w8 = (size_t)n * 8, w4 = (size_t)n * 4;
+    *counters = (unsigned long long *)m;         m += 64;
+    t->bound = (uint64_t *)m;                    m += w8;
+    t->demand = (uint64_t *)m;                   m += w8;
+    t->clen = (uint64_t *)m;                     m += w8;
+    t->first = (uint64_t *)m;                    m += w8;
+    t->produced = (uint64_t *)m;                 m += w8;
+    t->hashLen = (uint64_t *)m;                  m += w8;
+    t->res = (int64_t *)m;                       m += w8;
+    t->serialOut = (int64_t *)m;                 m += w8;
+    t->nblk = (uint32_t *)m;                     m += w4;
+    t->status = (int32_t *)m;                    m += w4;
+    t->desc = (uint32_t *)m;                     m += w4;
+    t->bsize = (int32_t *)m;                     m += w4;
+    t->csum = (uint32_t *)m;                     m += w4;
+    t->hdrEnd = (uint32_t *)m;                   m += w4;
+    t->kbad = (uint32_t *)m;                     m += w4;
+    t->irregular = (uint32_t *)m;                m += w4;
+    t->nSerial = (uint32_t *)m;                  m += w4;
+    t->sum = (uint32_t *)m;                      m += w4;
+    t->chained = m;
+    return K4LZ4_OK;
+}
+
+int block_scratch(k4lz4_ctx *ctx, int64_t nb, k4::BlockTab *b)
+{
+    const size_t need = (size_t)std::max<int64_t>(nb, 1) * BLOCK_BYTES + 64;
+    int rc;
+    if (need > ctx->d_fb_cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
+    if ((rc = grow(ctx, &ctx->d_fb, &ctx->d_fb_cap, need, false)) != K4LZ4_OK) return rc;
+    uint8_t *m = ctx->d_fb;
+    const size_t w8 = (size_t)std::max<int64_t>(nb, 1) * 8, w4 = w8 / 2;
+    b->off = (uint64_t *)m;                      m += w8;
+    b->hlen = (uint64_t *)m;                     m += w8;
+    b->dstOff = (uint64_t *)m;                   m += w8;
+    b->len = (uint32_t *)m;                      m += w4;
+    b->owner = (uint32_t *)m;                    m += w4;
+    b->idx = (uint32_t *)m;                      m += w4;
+    b->sum = (uint32_t *)m;                      m += w4;
+    b->got = (uint32_t *)m;                      m += w4;
+    b->srcLen = (int32_t *)m;                    m += w4;
+    b->dstCap = (int32_t *)m;                    m += w4;
+    b->outLen = (int32_t *)m;
+    return K4LZ4_OK;
+}
+
+/* host-pointer frame calls: the frames' span goes up to ctx->d_src, their rebased offsets and lengths to d_off / d_len */
+int frame_stage(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n, size_t extra_meta,
+                uint64_t **d_off, uint64_t **d_len, uint8_t **meta_rest)
+{
+    uint64_t lo = UINT64_MAX, hi = 0;
+    for (int64_t i = 0; i < n; i++)
+        if (frameLen[i]) { lo = std::min(lo, frameOff[i]); hi = std::max(hi, frameOff[i] + frameLen[i]); }
+    if (lo == UINT64_MAX) { lo = 0; hi = 0; }
+    std::vector<uint64_t> h_off((size_t)n);
+    for (int64_t i = 0; i < n; i++) h_off[(size_t)i] = frameLen[i] ? frameOff[i] - lo : 0;
+    const size_t span = (size_t)(hi - lo);
+    int rc;
+    if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, span + 64, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, (size_t)n * 16 + extra_meta + 64, false)) != K4LZ4_OK) return rc;
+    *d_off = (uint64_t *)ctx->d_meta;
+    *d_len = *d_off + n;
+    *meta_rest = (uint8_t *)(*d_len + n);
+    hipStream_t st = ctx->stream;
+    if (span) K4_HIP(ctx, hipMemcpyAsync(ctx->d_src, src + lo, span, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipMemcpyAsync(*d_off, h_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipMemcpyAsync(*d_len, frameLen, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    return K4LZ4_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1794,6 +1879,8 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_src) (void)hipFree(ctx->d_src);
     if (ctx->d_dst) (void)hipFree(ctx->d_dst);
     if (ctx->d_meta) (void)hipFree(ctx->d_meta);
+    if (ctx->d_fr) (void)hipFree(ctx->d_fr);
+    if (ctx->d_fb) (void)hipFree(ctx->d_fb);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->d_sched) (void)hipFree(ctx->d_sched);
     if (ctx->d_hc_hash) (void)hipFree(ctx->d_hc_hash);
@@ -2366,6 +2453,143 @@ int k4lz4_encode_fast_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint
             if (nbytes) memcpy(dst + dstOff[si] + (uint64_t)(j * slot), ctx->h_stage + d_doff[(size_t)si] + (uint64_t)(j * slot), nbytes);
         }
     }
+    return K4LZ4_OK;
+}
+
+
+/* ---- frame reader (k4lz4_frame_read.hpp) ---------------------------------------------------------------- */
+int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                             uint64_t *outSize, int32_t *outStatus, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    k4::FrameTab t;
+    unsigned long long *cnt;
+    int rc;
+    if ((rc = frame_scratch(ctx, n, &t, &cnt)) != K4LZ4_OK) return rc;
+    k4::FrameWalkArgs w{src, frameOff, frameLen, n, t, nullptr, outSize, outStatus};
+    hipLaunchKernelGGL(k4::k4_frame_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w);
+    K4_HIP(ctx, hipGetLastError());
+    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
+    else (void)hipGetLastError();
+    return K4LZ4_OK;
+}
+
+int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                               uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !dst || !dstOff || !dstCap || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    k4::FrameTab t;
+    k4::BlockTab b;
+    unsigned long long *cnt;
+    int rc;
+    if ((rc = frame_scratch(ctx, n, &t, &cnt)) != K4LZ4_OK) return rc;
+    const unsigned fgrid = (unsigned)((n + 255) / 256);
+    K4_HIP(ctx, hipMemsetAsync(cnt, 0, 64, st));
+    k4::FrameWalkArgs w{src, frameOff, frameLen, n, t, cnt, nullptr, nullptr};
+    hipLaunchKernelGGL(k4::k4_frame_walk_kernel, dim3(fgrid), dim3(256), 0, st, w);
+    hipLaunchKernelGGL(k4::k4_frame_scan_kernel, dim3(1), dim3(k4::FRAME_SCAN_THREADS), 0, st, t.nblk, t.first, (long long)n, cnt);
+    K4_HIP(ctx, hipGetLastError());
+    /* the one wait: the block count sizes the table (and says which passes have work) */
+    unsigned long long h[k4::FRC_COUNT];
+    K4_HIP(ctx, hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    const int64_t nb = (int64_t)h[k4::FRC_BLOCKS];
+    if ((rc = block_scratch(ctx, nb, &b)) != K4LZ4_OK) return rc;
+    k4::FrameFillArgs fa{src, frameOff, dstOff, dstCap, n, t, b};
+    hipLaunchKernelGGL(k4::k4_frame_fill_kernel, dim3(fgrid), dim3(256), 0, st, fa);
+    K4_HIP(ctx, hipGetLastError());
+    if (nb && h[k4::FRC_BSUM_FRAMES]) {
+        if ((rc = k4lz4_xxh32_batch_device(ctx, src, b.off, b.hlen, b.got, nb, 0, st)) != K4LZ4_OK) return rc;
+        hipLaunchKernelGGL(k4::k4_frame_bsum_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, t, b, (long long)nb);
+    }
+    if (nb && h[k4::FRC_INDEP_BLOCKS]) {
+        if ((rc = launch(ctx, KIND_DECODE, src, b.off, b.srcLen, dst, b.dstOff, b.dstCap, b.outLen, nb, 0, 0, st)) != K4LZ4_OK) return rc;
+    }
+    if (nb) hipLaunchKernelGGL(k4::k4_frame_place_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, src, dst, t, b, (long long)nb);
+    hipLaunchKernelGGL(k4::k4_frame_route_kernel, dim3(fgrid), dim3(256), 0, st, t, (long long)n);
+    K4_HIP(ctx, hipGetLastError());
+    /* chained frames, and independent ones whose blocks did not fill their places: in order, one stream per frame (frames
+     * without such work have no blocks there) */
+    if ((rc = k4lz4_decode_chain_batch_device(ctx, src, b.off, b.len, t.first, t.nSerial, t.bsize, t.chained, dst, dstOff, dstCap,
+                                              t.serialOut, n, st)) != K4LZ4_OK)
+        return rc;
+    hipLaunchKernelGGL(k4::k4_frame_settle_kernel, dim3(fgrid), dim3(256), 0, st, t, dstCap, (long long)n);
+    if (h[k4::FRC_CSUM_FRAMES]) {
+        if ((rc = k4lz4_xxh32_batch_device(ctx, dst, dstOff, t.hashLen, t.sum, n, 0, st)) != K4LZ4_OK) return rc;
+    }
+    hipLaunchKernelGGL(k4::k4_frame_finish_kernel, dim3(fgrid), dim3(256), 0, st, t, outLen, (long long)n,
+                       h[k4::FRC_CSUM_FRAMES] ? 1 : 0);
+    K4_HIP(ctx, hipGetLastError());
+    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
+    else (void)hipGetLastError();
+    return K4LZ4_OK;
+}
+
+int k4lz4_frame_sizes(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                      uint64_t *outSize, int32_t *outStatus)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    uint64_t *d_off, *d_len;
+    uint8_t *m;
+    int rc;
+    if ((rc = frame_stage(ctx, src, frameOff, frameLen, n, (size_t)n * 12, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
+    uint64_t *d_size = (uint64_t *)m;
+    int32_t *d_status = (int32_t *)(d_size + n);
+    hipStream_t st = ctx->stream;
+    if ((rc = k4lz4_frame_sizes_device(ctx, ctx->d_src, d_off, d_len, n, d_size, d_status, st)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipMemcpyAsync(outSize, d_size, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipMemcpyAsync(outStatus, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    return take_device_status(ctx);
+}
+
+int k4lz4_decode_frames(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                        uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !dst || !dstOff || !dstCap || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> h_doff((size_t)n);
+    uint64_t dtotal = 0;
+    for (int64_t i = 0; i < n; i++) {
+        h_doff[(size_t)i] = dtotal;
+        dtotal += (dstCap[i] + 15u) & ~(uint64_t)15u;
+    }
+    uint64_t *d_off, *d_len;
+    uint8_t *m;
+    int rc;
+    if ((rc = frame_stage(ctx, src, frameOff, frameLen, n, (size_t)n * 24, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
+    uint64_t *d_doff = (uint64_t *)m, *d_dcap = d_doff + n;
+    int64_t *d_out = (int64_t *)(d_dcap + n);
+    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)dtotal + 64, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)dtotal + 64, true)) != K4LZ4_OK) return rc;
+    hipStream_t st = ctx->stream;
+    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipMemcpyAsync(d_dcap, dstCap, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipMemsetAsync(ctx->d_dst, 0, (size_t)dtotal, st));      /* (as k4lz4_decode_chain_batch: no earlier call's bytes) */
+    if ((rc = k4lz4_decode_frames_device(ctx, ctx->d_src, d_off, d_len, n, ctx->d_dst, d_doff, d_dcap, d_out, st)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (dtotal) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)dtotal, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (outLen[i] > 0 && (uint64_t)outLen[i] <= dstCap[i]) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
     return K4LZ4_OK;
 }
 

@@ -20,6 +20,9 @@ Chained frames below L03_HC -- LZ4FastChainEncoder's, whose hash table holds onl
 visited, so a stream's blocks are serial -- are written by `encode_fast_chain_frames`
 (k4lz4_encode_fast_chain_batch: one wavefront per stream, many streams side by side).
 
+Frames that sit in device memory are read by `decode_frames_device` (k4lz4_decode_frames_device): header walk,
+block table, checksums and decoding all on the device, with one wait for the batch's block count.
+
 Differences from the reference, all deliberate:
   * ChainBlocks defaults to False here (the reference: True).  LZ4Frame.Encode / EncodeBatch and
     encode_frames_device still raise NotImplementedException for chained frames at L00_FAST; the
@@ -506,6 +509,90 @@ def encode_frames_device(dc, data, off: np.ndarray, length: np.ndarray, settings
                                             _dp(frame_len), nf, C.c_void_p(dc._stream()))
     dc.ctx.check(rc)
     return frames, frame_off, frame_len[:nf]
+
+
+# per-frame codes of the device reader (include/k4lz4.h K4LZ4_FRAME_*) and what the reference's reader raises for each
+FRAME_EOF, FRAME_MAGIC, FRAME_VERSION, FRAME_HEADER_SUM, FRAME_DICTIONARY = -1, -2, -3, -4, -5
+FRAME_BLOCK, FRAME_BLOCK_SUM, FRAME_CONTENT_SUM, FRAME_CAPACITY, FRAME_LENGTH = -6, -7, -8, -9, -10
+
+
+def frame_exception(code: int) -> Exception:
+    """the exception LZ4FrameReader raises for a K4LZ4_FRAME_* code"""
+    return {FRAME_EOF: lambda: EOFError("Unexpected end of stream"),
+            FRAME_MAGIC: lambda: InvalidDataException("LZ4 frame magic number expected"),
+            FRAME_VERSION: lambda: InvalidDataException("LZ4 frame version unknown: 0"),      # (FLG >> 6) & 0x11 is 0 or 1
+            FRAME_HEADER_SUM: lambda: InvalidDataException("Invalid LZ4 frame header checksum"),
+            FRAME_DICTIONARY: lambda: NotImplementedException("Predefined dictionaries feature is not implemented"),
+            FRAME_BLOCK: lambda: InvalidDataException("LZ4 block does not decode"),
+            FRAME_BLOCK_SUM: lambda: InvalidDataException("Invalid block checksum"),
+            FRAME_CONTENT_SUM: lambda: InvalidDataException("Invalid content checksum"),
+            FRAME_CAPACITY: lambda: InvalidDataException("Decoded frame does not fit its target"),
+            FRAME_LENGTH: lambda: InvalidDataException("Content length does not match the frame header"),
+            }.get(int(code), lambda: RuntimeError(f"unknown frame result {int(code)}"))()
+
+
+def _dev_i64(x, dev):
+    """host array or device tensor -> contiguous int64 device tensor (uint64 offsets / lengths)"""
+    import torch
+    if isinstance(x, torch.Tensor):
+        return x.to(device=dev, dtype=torch.int64).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.int64))).to(dev)
+
+
+def frame_sizes_device(dc, frames, off, length):
+    """k4lz4_frame_sizes_device: frame f = frames[off[f] : off[f]+length[f]] (frames: uint8 device tensor; off / length: host arrays or
+    device tensors).  Returns (size, status), int64 / int32 device tensors: the most frame f can decode to without trusting its
+    header (per block min(blockSize, 255 * stored + 32), stored if raw; capped by ContentLength), and 0 or the walk's K4LZ4_FRAME_*
+    code.  Asynchronous on the current torch stream."""
+    import ctypes as C
+    import torch
+    from .device import _dp
+    dev = dc.device
+    off_d, len_d = _dev_i64(off, dev), _dev_i64(length, dev)
+    n = off_d.numel()
+    size = torch.zeros(n, dtype=torch.int64, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    dc.ctx.check(dc.lib.k4lz4_frame_sizes_device(dc.ctx.handle, _dp(frames), _dp(off_d), _dp(len_d), n, _dp(size), _dp(status),
+                                                 C.c_void_p(dc._stream())))
+    return size, status
+
+
+def decode_frames_device(dc, frames, off, length, out=None, raise_errors: bool = True):
+    """LZ4Frame.DecodeBatch on HBM-resident frames, nothing goes through the host: frame f = frames[off[f] : off[f]+length[f]]
+    (off / length: host arrays or device tensors, e.g. encode_frames_device's frame_off and frame_len as they are).
+    out: None, or (buffer, out_off, out_cap) -- a uint8 device tensor and per-frame positions / capacities (host arrays or device
+    tensors).  Without it the output is sized by frame_sizes_device, which costs one synchronisation, and out_off is a host array.
+    Returns (out, out_off, out_len): frame f decoded = out[out_off[f] : out_off[f]+out_len[f]], out_len an int64 device tensor
+    holding a negative K4LZ4_FRAME_* code for a frame that does not decode.  k4lz4_decode_frames_device waits for the stream once
+    (it reads the batch's block count back).  raise_errors: raise what LZ4FrameReader raises for the lowest-index failing frame
+    (reads out_len back); otherwise the caller reads out_len."""
+    import ctypes as C
+    import torch
+    from .device import _dp
+    dev = dc.device
+    off_d, len_d = _dev_i64(off, dev), _dev_i64(length, dev)
+    n = off_d.numel()
+    if out is None:
+        size, _ = frame_sizes_device(dc, frames, off_d, len_d)
+        cap = size.cpu().numpy() if n else np.zeros(0, np.int64)
+        out_off = np.zeros(n, np.int64)
+        if n > 1:
+            out_off[1:] = np.cumsum((cap + 15) // 16 * 16)[:-1]
+        buf = torch.empty(int(((cap + 15) // 16 * 16).sum()) + 64, dtype=torch.uint8, device=dev)
+        off_o, cap_o = torch.from_numpy(out_off).to(dev), size
+    else:
+        buf, out_off, out_cap = out
+        off_o, cap_o = _dev_i64(out_off, dev), _dev_i64(out_cap, dev)
+    out_len = torch.zeros(n, dtype=torch.int64, device=dev)
+    if n:
+        dc.ctx.check(dc.lib.k4lz4_decode_frames_device(dc.ctx.handle, _dp(frames), _dp(off_d), _dp(len_d), n, _dp(buf), _dp(off_o),
+                                                       _dp(cap_o), _dp(out_len), C.c_void_p(dc._stream())))
+    if raise_errors and n:
+        got = out_len.cpu().numpy()
+        bad = np.flatnonzero(got < 0)
+        if bad.size:
+            raise frame_exception(int(got[bad[0]]))
+    return buf, out_off, out_len
 
 
 def encode_fast_chain_frames(sources: Sequence, settings: Optional[LZ4EncoderSettings] = None,
