@@ -78,6 +78,40 @@ namespace K4os.Compression.LZ4.Engine
 		[DllImport(Lib)] public static extern int k4lz4_decode_frames_device(
 			IntPtr ctx, byte* src, ulong* frameOff, ulong* frameLen, long n, byte* dst, ulong* dstOff, ulong* dstCap, long* outLen,
 			IntPtr stream);
+		// legacy formats (K4os.Compression.LZ4.Legacy: LZ4Wrapper, LZ4Stream; DESIGN.md 4.12).  Per-item results < 0 are the
+		// LEGACY_* codes: the exception the reference throws.  unwrap: decoded[i] = what LZ4Codec.Decode returned (Unwrap ignores it).
+		public const int LEGACY_END_OF_STREAM = -1, LEGACY_OVERFLOW = -2, LEGACY_NOT_SUPPORTED = -3, LEGACY_INVALID_DATA = -4,
+			LEGACY_ARGUMENT = -5, LEGACY_CAPACITY = -6, LEGACY_NOT_ENCODED = -7;
+		[DllImport(Lib)] public static extern int k4lz4_wrap_bound(int srcLen);
+		[DllImport(Lib)] public static extern int k4lz4_wrap_batch(
+			IntPtr ctx, byte* src, ulong* srcOff, int* srcLen, byte* dst, ulong* dstOff, int* dstCap, int* outLen, long n, int high, int flags);
+		[DllImport(Lib)] public static extern int k4lz4_wrap_batch_device(
+			IntPtr ctx, byte* src, ulong* srcOff, int* srcLen, byte* dst, ulong* dstOff, int* dstCap, int* outLen, long n, int high, int flags,
+			IntPtr stream);
+		[DllImport(Lib)] public static extern int k4lz4_unwrap_size(byte* buf, long len);
+		[DllImport(Lib)] public static extern int k4lz4_unwrap_sizes_device(
+			IntPtr ctx, byte* src, ulong* srcOff, int* srcLen, int* outLen, long n, IntPtr stream);
+		[DllImport(Lib)] public static extern int k4lz4_unwrap_batch(
+			IntPtr ctx, byte* src, ulong* srcOff, int* srcLen, byte* dst, ulong* dstOff, int* dstCap, int* outLen, int* decoded, long n);
+		[DllImport(Lib)] public static extern int k4lz4_unwrap_batch_device(
+			IntPtr ctx, byte* src, ulong* srcOff, int* srcLen, byte* dst, ulong* dstOff, int* dstCap, int* outLen, int* decoded, long n,
+			IntPtr stream);
+		[DllImport(Lib)] public static extern long k4lz4_legacy_stream_bound(long srcLen, int blockSize);
+		[DllImport(Lib)] public static extern int k4lz4_encode_legacy_streams(
+			IntPtr ctx, byte* src, ulong* srcOff, ulong* srcLen, long n, int blockSize, int high, int flags, byte* dst, ulong* dstOff,
+			ulong* dstCap, long* outLen);
+		[DllImport(Lib)] public static extern int k4lz4_encode_legacy_streams_device(
+			IntPtr ctx, byte* src, ulong* srcOff, ulong* srcLen, long n, int blockSize, int high, int flags, byte* dst, ulong* dstOff,
+			ulong* dstCap, long* outLen, IntPtr stream);
+		[DllImport(Lib)] public static extern int k4lz4_legacy_stream_sizes(
+			IntPtr ctx, byte* src, ulong* streamOff, ulong* streamLen, long n, ulong* outSize, int* outStatus);
+		[DllImport(Lib)] public static extern int k4lz4_legacy_stream_sizes_device(
+			IntPtr ctx, byte* src, ulong* streamOff, ulong* streamLen, long n, ulong* outSize, int* outStatus, IntPtr stream);
+		[DllImport(Lib)] public static extern int k4lz4_decode_legacy_streams(
+			IntPtr ctx, byte* src, ulong* streamOff, ulong* streamLen, long n, byte* dst, ulong* dstOff, ulong* dstCap, long* outLen);
+		[DllImport(Lib)] public static extern int k4lz4_decode_legacy_streams_device(
+			IntPtr ctx, byte* src, ulong* streamOff, ulong* streamLen, long n, byte* dst, ulong* dstOff, ulong* dstCap, long* outLen,
+			IntPtr stream);
 		// chained HC streams: LZ4HighChainEncoder(level, blockSize, extraBlocks) over whole contents, every block of every stream in
 		// one launch sequence; dictLen (may be null): ring-buffer bytes in front of each content's first new block
 		[DllImport(Lib)] public static extern int k4lz4_encode_hc_chain_batch(

@@ -372,6 +372,77 @@ K4LZ4_API int k4lz4_frame_sizes(k4lz4_ctx *ctx, const uint8_t *src, const uint64
 K4LZ4_API int k4lz4_decode_frames(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
                                   uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen);
 
+/* ---- legacy formats: K4os.Compression.LZ4.Legacy (LZ4Wrapper.cs, LZ4Stream.cs) ------------------------------
+ * Per-item codes: the exception the reference throws, in the order it meets them. */
+#define K4LZ4_LEGACY_END_OF_STREAM (-1)   /* EndOfStreamException: truncated varint or payload, a varint where the stream ends, C > U */
+#define K4LZ4_LEGACY_OVERFLOW      (-2)   /* OverflowException: a negative length (after truncation to 32 bits) reaches new byte[] */
+#define K4LZ4_LEGACY_NOT_SUPPORTED (-3)   /* NotSupportedException: a compressed chunk with passes ((int)flags >> 2 != 0) */
+#define K4LZ4_LEGACY_INVALID_DATA  (-4)   /* InvalidDataException: a compressed chunk does not decode to exactly U bytes (also: U > 255 * C + 32) */
+#define K4LZ4_LEGACY_ARGUMENT      (-5)   /* ArgumentException (Unwrap): fewer than 8 bytes, a payload past the end, a negative source length */
+#define K4LZ4_LEGACY_CAPACITY      (-6)   /* not the reference's: the caller's target is too small */
+#define K4LZ4_LEGACY_NOT_ENCODED   (-7)   /* not the reference's: an HC chunk was not encoded for want of reserved scratch
+                                             (k4lz4_ctx_reserve_hc; the call's status says so too) */
+
+/* LZ4Wrapper.Wrap / WrapHC: outLen[i] = 8 + payload bytes written to dst + dstOff[i] ([u32 U][u32 C][block], or [u32 U][u32 U][the
+ * bytes] when the block is not shorter than U; 8 zero bytes for an empty message), -1 when dstCap[i] < k4lz4_wrap_bound(srcLen[i]).
+ * high = 0: L00_FAST, else L09_HC.  flags: K4LZ4_FLAG_X32, K4LZ4_FLAG_NO_REORDER.  The encoder writes straight into the slot
+ * (cap U - 1); fast batches take the pickles' two-step encoder and segments, HC the pickles' envelope path.  Scratch: the
+ * encoders' (d_pk_meta, 16 bytes per message; HC as k4lz4_pickle_batch). */
+K4LZ4_API int k4lz4_wrap_bound(int srcLen);
+K4LZ4_API int k4lz4_wrap_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                               const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int high, int flags);
+K4LZ4_API int k4lz4_wrap_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                                      const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int high, int flags,
+                                      void *stream);
+/* LZ4Wrapper.Unwrap on one buffer of len bytes (host arithmetic): the result's length, or K4LZ4_LEGACY_ARGUMENT / _OVERFLOW */
+K4LZ4_API int k4lz4_unwrap_size(const uint8_t *buf, int64_t len);
+/* the same for a batch on the device: outLen[i] = length or code */
+K4LZ4_API int k4lz4_unwrap_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                        int32_t *outLen, int64_t n, void *stream);
+/* Unwrap a batch: outLen[i] = the length Unwrap returns (bytes at dst + dstOff[i]), a K4LZ4_LEGACY_* code, or K4LZ4_LEGACY_CAPACITY
+ * when dstCap[i] is smaller.  decoded[i] = what LZ4Codec.Decode returned: the decoded length, -1 for a payload that does not decode,
+ * 0 for an empty payload; for a stored (raw) result its length.  Unwrap ignores that value and returns outLen bytes all the same:
+ * decoded[i] == outLen[i] says the bytes are the payload's.  Compressed payloads go through the batch decoder with cap = outLen.
+ * Scratch (device form): 20 bytes per buffer. */
+K4LZ4_API int k4lz4_unwrap_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                                 const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int32_t *decoded, int64_t n);
+K4LZ4_API int k4lz4_unwrap_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                        uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int32_t *decoded,
+                                        int64_t n, void *stream);
+
+/* LZ4Stream (LZ4Legacy.Encode) with the whole content written and the stream disposed: chunks of max(16, blockSize) bytes, each
+ * `varint(flags) varint(U) [varint(C)] payload`, compressed iff C < U, HighCompression (2) on every chunk of a high stream.
+ * The most a stream of srcLen bytes takes: */
+K4LZ4_API int64_t k4lz4_legacy_stream_bound(int64_t srcLen, int blockSize);
+/* Content i = src[srcOff[i] .. + srcLen[i]) -> stream i at dst + dstOff[i]; outLen[i] = its bytes, K4LZ4_LEGACY_CAPACITY when it
+ * does not fit dstCap[i] (nothing is written then), or K4LZ4_LEGACY_NOT_ENCODED.  high = 0: L00_FAST, else L09_HC; flags:
+ * K4LZ4_FLAG_X32.  Every chunk of every stream is encoded in one batch into an arena; record sizes, their scan and the assembly
+ * run on the device.  The device form reads the chunk count back once (it WAITS FOR `stream` after the first scan).  Grow-only
+ * scratch: 36 bytes per stream, 48 bytes per chunk, and an arena of the contents' bytes (each rounded up to 16). */
+K4LZ4_API int k4lz4_encode_legacy_streams(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, int64_t n,
+                                          int blockSize, int high, int flags, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                                          int64_t *outLen);
+K4LZ4_API int k4lz4_encode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen,
+                                                 int64_t n, int blockSize, int high, int flags, uint8_t *dst, const uint64_t *dstOff,
+                                                 const uint64_t *dstCap, int64_t *outLen, void *stream);
+/* Stream i = src[streamOff[i] .. + streamLen[i]), read as LZ4Stream (LZ4Legacy.Decode) reads it to its end; nothing outside that
+ * range is read.  outSize[i] = the bytes of the chunks before the first structural defect, each compressed chunk's U trusted only
+ * up to 255 * C + 32 (a chunk that claims more is an InvalidData defect there); outStatus[i] = 0 or that defect's code. */
+K4LZ4_API int k4lz4_legacy_stream_sizes(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen,
+                                        int64_t n, uint64_t *outSize, int32_t *outStatus);
+K4LZ4_API int k4lz4_legacy_stream_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen,
+                                               int64_t n, uint64_t *outSize, int32_t *outStatus, void *stream);
+/* Decodes stream i into dst + dstOff[i]; outLen[i] = the content's bytes, or the code of the first defect in stream order: a chunk
+ * that does not decode (compressed chunks before the walk's defect are decoded by the batch decoder, straight into place, cap U),
+ * a chunk that does not fit dstCap[i] (K4LZ4_LEGACY_CAPACITY at that chunk), or the walk's structural defect.  Bytes of a failing
+ * stream's slot may be written, nothing outside [dstOff[i], dstOff[i] + dstCap[i]).  The device form reads the chunk count back
+ * once (it WAITS FOR `stream` after the walk).  Grow-only scratch: 36 bytes per stream and 48 bytes per chunk. */
+K4LZ4_API int k4lz4_decode_legacy_streams(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen,
+                                          int64_t n, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen);
+K4LZ4_API int k4lz4_decode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen,
+                                                 int64_t n, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen,
+                                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ FLAG_SEGMENTS = 256
 
 _u8p = C.c_void_p
 _BATCH = [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+_LEGACY_ENC = [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 # every symbol include/k4lz4.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -83,6 +84,21 @@ SYMBOLS = {
                                                 C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
     "k4lz4_encode_fast_chain_batch_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                        C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "k4lz4_wrap_bound": (C.c_int, [C.c_int]),
+    "k4lz4_wrap_batch": (C.c_int, _BATCH + [C.c_int, C.c_int]),
+    "k4lz4_wrap_batch_device": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p]),
+    "k4lz4_unwrap_size": (C.c_int, [_u8p, C.c_int64]),
+    "k4lz4_unwrap_sizes_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "k4lz4_unwrap_batch": (C.c_int, _BATCH[:8] + [C.c_void_p, C.c_int64]),
+    "k4lz4_unwrap_batch_device": (C.c_int, _BATCH[:8] + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "k4lz4_legacy_stream_bound": (C.c_int64, [C.c_int64, C.c_int]),
+    "k4lz4_encode_legacy_streams": (C.c_int, _LEGACY_ENC),
+    "k4lz4_encode_legacy_streams_device": (C.c_int, _LEGACY_ENC + [C.c_void_p]),
+    "k4lz4_legacy_stream_sizes": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "k4lz4_legacy_stream_sizes_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_decode_legacy_streams": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_decode_legacy_streams_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]),
 }
 
 

@@ -36,6 +36,7 @@
 #include "k4lz4_fast_chain.hpp"
 #include "k4lz4_frame.hpp"
 #include "k4lz4_frame_read.hpp"
+#include "k4lz4_legacy.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 
@@ -137,6 +138,10 @@ struct k4lz4_ctx {
     /* frame reader (k4lz4_frame_read.hpp): per-frame words and the block table, both grow-only */
     uint8_t *d_fr = nullptr; size_t d_fr_cap = 0;
     uint8_t *d_fb = nullptr; size_t d_fb_cap = 0;
+    /* legacy streams (k4lz4_legacy.hpp): per-stream words, the chunk table and the writer's arena, all grow-only */
+    uint8_t *d_lg = nullptr; size_t d_lg_cap = 0;
+    uint8_t *d_lgr = nullptr; size_t d_lgr_cap = 0;
+    uint8_t *d_lga = nullptr; size_t d_lga_cap = 0;
 };
 
 /* a few helper threads for the staging copies of big host-pointer calls (memcpy between the caller's pageable memory and
@@ -218,7 +223,9 @@ int hip_fail(k4lz4_ctx *ctx, hipError_t e, const char *what)
         if (e_ != hipSuccess) return hip_fail(ctx, e_, #call);              \
     } while (0)
 
-enum Kind { KIND_ENCODE, KIND_DECODE, KIND_PICKLE, KIND_UNPICKLE };
+enum Kind { KIND_ENCODE, KIND_DECODE, KIND_PICKLE, KIND_UNPICKLE, KIND_WRAP };
+/* the envelope an encode is wrapped in (launch_hc): none, LZ4Pickler's, LZ4Wrapper's */
+enum Envelope { ENV_NONE, ENV_PICKLE, ENV_WRAP };
 constexpr int FLAG_SEGMENTS_OK = 1 << 20;   /* launch_inner, fast encode: big blocks may be cut into segments (k4lz4_segments.hpp); not part of the API */
 
 /* LL.Enforce32 (Engine/LL.tools.cs:19-27): a process-wide switch in the reference, so here too */
@@ -250,11 +257,11 @@ int take_device_status(k4lz4_ctx *ctx)
 }
 
 /* HC levels: layout -> (sync for the scratch size) -> hash-table clear -> chain kernel -> parse kernel.
- * `pickle`: the same around the LZ4Pickler envelope (encoder slot = envelope + 5, cap U - 1). */
+ * `env`: the same around the LZ4Pickler envelope (encoder slot = envelope + 5, cap U - 1) or LZ4Wrapper's (+ 8, cap U - 1). */
 /* hostLen: the blocks' lengths when the caller has them on the host (host-pointer calls), else nullptr */
 /* hist: chained HC streams (k4::HcArgs::hist, device pointer), else nullptr -- such a batch takes the memory paths: the LDS
  * kernels are built around blocks of at most 64 KiB that start at their position 0 */
-int launch_hc(k4lz4_ctx *ctx, bool pickle, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
               const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
               hipStream_t stream, const int32_t *hostLen, const int32_t *hist = nullptr)
 {
@@ -283,8 +290,9 @@ int launch_hc(k4lz4_ctx *ctx, bool pickle, const uint8_t *src, const uint64_t *s
         k4::BatchArgs a{};
         a.src = src; a.srcOff = h.srcOff; a.srcLen = h.srcLen; a.dst = dst; a.dstOff = h.dstOff; a.dstCap = h.dstCap;
         a.outLen = h.outLen; a.n = cnt; a.level = level; a.accel = 1; a.flags = flags;
-        if (pickle) {
-            hipLaunchKernelGGL(k4::k4_pickle_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
+        if (env == ENV_PICKLE || env == ENV_WRAP) {
+            if (env == ENV_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
+            else hipLaunchKernelGGL(k4::k4_wrap_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
             h.dstOff = d_encoff; h.dstCap = d_enccap; h.outLen = d_enclen; h.flags = K4LZ4_FLAG_RAW_RETURN;
         }
         /* How much work area, and how long the longest block is: from the host's copy of the lengths, from the
@@ -391,7 +399,8 @@ int launch_hc(k4lz4_ctx *ctx, bool pickle, const uint8_t *src, const uint64_t *s
             else if (h.recs) hipLaunchKernelGGL(k4::k4_hc_parse_rec_kernel, dim3((unsigned)((cnt + k4::HC_REC_WAVES_PER_WG - 1) / k4::HC_REC_WAVES_PER_WG)), dim3(64 * k4::HC_REC_WAVES_PER_WG), 0, pstream, h);
             else hipLaunchKernelGGL(k4::k4_hc_parse_kernel, dim3((unsigned)((cnt + k4::HC_PARSE_WAVES_PER_WG - 1) / k4::HC_PARSE_WAVES_PER_WG)), dim3(64 * k4::HC_PARSE_WAVES_PER_WG), 0, pstream, h);
         }
-        if (pickle) hipLaunchKernelGGL(k4::k4_pickle_finish_kernel, dim3((unsigned)((cnt + k4::PICKLE_FINISH_WAVES_PER_WG - 1) / k4::PICKLE_FINISH_WAVES_PER_WG)), dim3(64 * k4::PICKLE_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
+        if (env == ENV_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_finish_kernel, dim3((unsigned)((cnt + k4::PICKLE_FINISH_WAVES_PER_WG - 1) / k4::PICKLE_FINISH_WAVES_PER_WG)), dim3(64 * k4::PICKLE_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
+        if (env == ENV_WRAP) hipLaunchKernelGGL(k4::k4_wrap_finish_kernel, dim3((unsigned)((cnt + k4::WRAP_FINISH_WAVES_PER_WG - 1) / k4::WRAP_FINISH_WAVES_PER_WG)), dim3(64 * k4::WRAP_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
         K4_HIP(ctx, hipGetLastError());
     }
     return K4LZ4_OK;
@@ -445,7 +454,7 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
 #else
     const bool parse_prof_ok = false;
 #endif
-    const bool encode_like = kind == KIND_ENCODE || kind == KIND_PICKLE;
+    const bool encode_like = kind == KIND_ENCODE || kind == KIND_PICKLE || kind == KIND_WRAP;
     /* Fast-level LZ4Codec.Encode batches beyond what is resident at once (16 blocks per CU: the parse kernel's one workgroup per CU,
      * nine waves with their table in LDS and seven that move into a table as one becomes free): one persistent launch (round 6,
      * below); with K4LZ4_NO_PERSIST, or through the one-kernel encoders of rounds 1-4, equal parts of at most one residency each --
@@ -470,7 +479,7 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
     }
     if (parse_path && !parse_persistent) chunk_max = std::min<int64_t>(chunk_max, (int64_t)k4::PARSE_MAX_WAVES * (int64_t)ctx->cu_count);      /* (one residency) */
     if (encode_like && level >= K4LZ4_L03_HC) {
-        const int rc = launch_hc(ctx, kind == KIND_PICKLE, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, stream, hostLen);
+        const int rc = launch_hc(ctx, kind == KIND_PICKLE ? ENV_PICKLE : kind == KIND_WRAP ? ENV_WRAP : ENV_NONE, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, stream, hostLen);
         if (rc != K4LZ4_OK || kind != KIND_ENCODE || !(flags & K4LZ4_FLAG_ALLOW_COPY)) return rc;
         for (int64_t first = 0; first < n; first += chunk_max) {
             const int64_t cnt = std::min<int64_t>(chunk_max, n - first);
@@ -490,7 +499,7 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
         may_cut = false;
         for (int64_t i = 0; i < n && !may_cut; i++) may_cut = (uint32_t)hostLen[i] >= ctx->seg_min;
     }
-    if (kind == KIND_PICKLE && (n > (int64_t)ctx->pickle_split_min || may_cut) && !ctx->prof) {
+    if ((kind == KIND_PICKLE && (n > (int64_t)ctx->pickle_split_min || may_cut) && !ctx->prof) || kind == KIND_WRAP) {
         /* Fast-level pickles of a batch go the encoders' way: slots prepared (block = envelope + 5, cap U - 1, exactly what
          * k4_pickle_kernel hands its encoder), the batch encoded by the two encoder kernels side by side -- the expensive
          * messages with their tables in LDS, the others with tables in memory, which puts a ragged batch on all the
@@ -508,11 +517,15 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
             a.src = src; a.srcOff = srcOff + first; a.srcLen = srcLen + first; a.dst = dst; a.dstOff = dstOff + first;
             a.dstCap = dstCap + first; a.outLen = outLen + first; a.n = cnt; a.level = level; a.accel = 1;
             a.flags = flags | (g_enforce32.load(std::memory_order_relaxed) ? K4LZ4_FLAG_X32 : 0);
-            hipLaunchKernelGGL(k4::k4_pickle_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
+            /* (wraps take this way whatever the batch; without a message big enough to be cut, not into segments) */
+            const int seg_ok = kind == KIND_PICKLE || may_cut ? FLAG_SEGMENTS_OK : 0;
+            if (kind == KIND_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
+            else hipLaunchKernelGGL(k4::k4_wrap_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
             rc = launch_inner(ctx, KIND_ENCODE, src, srcOff + first, srcLen + first, dst, d_encoff, d_enccap, d_enclen, cnt, level,
-                              (flags & (K4LZ4_FLAG_NO_REORDER | K4LZ4_FLAG_X32)) | K4LZ4_FLAG_RAW_RETURN | FLAG_SEGMENTS_OK, stream, nullptr, hostLen ? hostLen + first : nullptr);
+                              (flags & (K4LZ4_FLAG_NO_REORDER | K4LZ4_FLAG_X32)) | K4LZ4_FLAG_RAW_RETURN | seg_ok, stream, nullptr, hostLen ? hostLen + first : nullptr);
             if (rc != K4LZ4_OK) return rc;
-            hipLaunchKernelGGL(k4::k4_pickle_finish_kernel, dim3((unsigned)((cnt + k4::PICKLE_FINISH_WAVES_PER_WG - 1) / k4::PICKLE_FINISH_WAVES_PER_WG)), dim3(64 * k4::PICKLE_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
+            if (kind == KIND_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_finish_kernel, dim3((unsigned)((cnt + k4::PICKLE_FINISH_WAVES_PER_WG - 1) / k4::PICKLE_FINISH_WAVES_PER_WG)), dim3(64 * k4::PICKLE_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
+            else hipLaunchKernelGGL(k4::k4_wrap_finish_kernel, dim3((unsigned)((cnt + k4::WRAP_FINISH_WAVES_PER_WG - 1) / k4::WRAP_FINISH_WAVES_PER_WG)), dim3(64 * k4::WRAP_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
             K4_HIP(ctx, hipGetLastError());
         }
         return K4LZ4_OK;
@@ -810,6 +823,7 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
                                    dim3(128 * k4::DECODE_PAIRS_PER_WG), 0, stream, a);
             }
             else hipLaunchKernelGGL(k4::k4_unpickle_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
+            break;        case KIND_WRAP:         /* (wraps are closed above, behind the encoder kernels) */
             break;
         }
         if (kind == KIND_ENCODE && (flags & K4LZ4_FLAG_ALLOW_COPY))
@@ -1075,7 +1089,7 @@ int run_host_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t
 {
     int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
     if (rc != K4LZ4_OK) return rc;
-    if (kind == KIND_ENCODE || kind == KIND_PICKLE) {
+    if (kind == KIND_ENCODE || kind == KIND_PICKLE || kind == KIND_WRAP) {
         rc = check_level(ctx, level);
         if (rc != K4LZ4_OK) return rc;
     }
@@ -1126,7 +1140,7 @@ int run_host_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t
     /* Two halves (of about equal source bytes) when the call is big: see k4lz4_ctx::copyq.  HC levels and dictionaries keep
      * to one part (their launches size scratch and synchronise on their own). */
     const uint64_t up_bytes = packed ? packed_bytes : (uint64_t)span;
-    const bool hc = (kind == KIND_ENCODE || kind == KIND_PICKLE) && level >= K4LZ4_L03_HC;
+    const bool hc = (kind == KIND_ENCODE || kind == KIND_PICKLE || kind == KIND_WRAP) && level >= K4LZ4_L03_HC;
     /* Encoders: two parts (a part's kernels last as long as their slowest block whatever their number, and the parts' kernels
      * run one after the other).  Decoders, whose kernels are short: four, so that more of the way up and of the way down
      * overlap. */
@@ -1330,7 +1344,7 @@ int run_host_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t
          * target (this part's range of it; a memset on the device, ~0.1 ms per 256 MB beside the milliseconds of PCIe), so that such
          * bytes are zeros and never what an earlier call of this context left there.  Not in the kernels: carrying the
          * case through decode_block cost the pair kernel five spilled VGPRs and the single-wave kernels a wave per SIMD. */
-        if (kind != KIND_ENCODE && kind != KIND_PICKLE) {
+        if (kind != KIND_ENCODE && kind != KIND_PICKLE && kind != KIND_WRAP) {
             const uint64_t lo_d = h_doff[(size_t)b0];
             const uint64_t hi_d = b1 < n ? h_doff[(size_t)b1] : dtotal;
             if (hi_d > lo_d) { const hipError_t me = hipMemsetAsync(ctx->d_dst + lo_d, 0, (size_t)(hi_d - lo_d), st); if (me != hipSuccess) return finish(hip_fail(ctx, me, "hipMemsetAsync")); }
@@ -1359,7 +1373,7 @@ int run_device(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *sr
 {
     int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
     if (rc != K4LZ4_OK) return rc;
-    if (kind == KIND_ENCODE || kind == KIND_PICKLE) {
+    if (kind == KIND_ENCODE || kind == KIND_PICKLE || kind == KIND_WRAP) {
         rc = check_level(ctx, level);
         if (rc != K4LZ4_OK) return rc;
     }
@@ -1499,7 +1513,7 @@ int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, con
     if (ctx->busy && ctx->last_stream != stream) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_busy, 0));
     K4_HIP(ctx, hipMemcpyAsync(ctx->d_chain, ctx->h_chain.data(), bytes, hipMemcpyHostToDevice, stream));
     K4_HIP(ctx, hipEventRecord(ctx->ev_chain, stream));
-    rc = launch_hc(ctx, false, src, d.woff, d.wlen, dst, d.doff, d.cap, outLen, nb, level, 0, stream, h.wlen, d.hist);
+    rc = launch_hc(ctx, ENV_NONE, src, d.woff, d.wlen, dst, d.doff, d.cap, outLen, nb, level, 0, stream, h.wlen, d.hist);
     if (rc == K4LZ4_OK && (flags & K4LZ4_FLAG_ALLOW_COPY)) {
         /* LZ4EncoderBase.Encode(allowCopy): a block that did not shrink is stored raw -- its bytes stay in the history all the same */
         for (int64_t first = 0; first < nb; first += (int64_t)1 << 24) {
@@ -1734,6 +1748,41 @@ int frame_stage(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, co
     return K4LZ4_OK;
 }
 
+
+/* ---- legacy formats (k4lz4_legacy.hpp): grow-only scratch; what has to grow waits for the context's earlier work first */
+int lg_grow(k4lz4_ctx *ctx, uint8_t **p, size_t *cap, size_t need)
+{
+    if (need > *cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
+    return grow(ctx, p, cap, need, false);
+}
+
+constexpr size_t LG_STREAM_BYTES = 4 * 8 + 4, LG_ROW_BYTES = 48;
+
+/* per-stream words behind 64 bytes of counters: four u64 arrays and one 32-bit array */
+int lg_streams(k4lz4_ctx *ctx, int64_t n, unsigned long long **cnt, uint64_t *w[4], int32_t **w32)
+{
+    int rc;
+    if ((rc = lg_grow(ctx, &ctx->d_lg, &ctx->d_lg_cap, 64 + (size_t)n * LG_STREAM_BYTES + 64)) != K4LZ4_OK) return rc;
+    uint8_t *m = ctx->d_lg;
+    *cnt = (unsigned long long *)m;
+    m += 64;
+    for (int i = 0; i < 4; i++, m += (size_t)n * 8) w[i] = (uint64_t *)m;
+    *w32 = (int32_t *)m;
+    return K4LZ4_OK;
+}
+
+/* host-pointer calls: copy the results back into the caller's slots (the device form wrote them packed at h_doff) */
+int lg_out_stage(k4lz4_ctx *ctx, int64_t n, const uint64_t *cap, std::vector<uint64_t> &h_doff, uint64_t *total)
+{
+    h_doff.resize((size_t)n);
+    uint64_t t = 0;
+    for (int64_t i = 0; i < n; i++) { h_doff[(size_t)i] = t; t += (cap[i] + 15u) & ~(uint64_t)15u; }
+    *total = t;
+    int rc;
+    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)t + 64, false)) != K4LZ4_OK) return rc;
+    return grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)t + 64, true);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1881,6 +1930,9 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_meta) (void)hipFree(ctx->d_meta);
     if (ctx->d_fr) (void)hipFree(ctx->d_fr);
     if (ctx->d_fb) (void)hipFree(ctx->d_fb);
+    if (ctx->d_lg) (void)hipFree(ctx->d_lg);
+    if (ctx->d_lgr) (void)hipFree(ctx->d_lgr);
+    if (ctx->d_lga) (void)hipFree(ctx->d_lga);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->d_sched) (void)hipFree(ctx->d_sched);
     if (ctx->d_hc_hash) (void)hipFree(ctx->d_hc_hash);
@@ -2590,6 +2642,342 @@ int k4lz4_decode_frames(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *fram
     if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
     for (int64_t i = 0; i < n; i++)
         if (outLen[i] > 0 && (uint64_t)outLen[i] <= dstCap[i]) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
+    return K4LZ4_OK;
+}
+
+/* ---- legacy formats: LZ4Wrapper, LZ4Stream (k4lz4_legacy.hpp) ------------------------------------------ */
+int k4lz4_wrap_bound(int srcLen) { return srcLen < 0 || srcLen > 0x7fffffff - 8 ? 0 : 8 + srcLen; }
+
+int k4lz4_wrap_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                     const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int high, int flags)
+{
+    return run_host(ctx, KIND_WRAP, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, high ? K4LZ4_L09_HC : K4LZ4_L00_FAST,
+                    flags & (K4LZ4_FLAG_X32 | K4LZ4_FLAG_NO_REORDER));
+}
+
+int k4lz4_wrap_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                            const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int high, int flags, void *stream)
+{
+    return run_device(ctx, KIND_WRAP, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, high ? K4LZ4_L09_HC : K4LZ4_L00_FAST,
+                      flags & (K4LZ4_FLAG_X32 | K4LZ4_FLAG_NO_REORDER), stream);
+}
+
+int k4lz4_unwrap_size(const uint8_t *buf, int64_t len)
+{
+    if (len < 0 || (len > 0 && !buf)) return K4LZ4_LEGACY_ARGUMENT;
+    if (len > 0x7fffffff) len = 0x7fffffff;           /* (a .NET array) */
+    bool dec;
+    int in;
+    return (int)k4::unwrap_plan(buf, len, &dec, &in);
+}
+
+int k4lz4_unwrap_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, int32_t *outLen,
+                              int64_t n, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !srcOff || !srcLen || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    k4::UnwrapArgs u{src, srcOff, srcLen, nullptr, n, outLen, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(k4::k4_unwrap_sizes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u);
+    K4_HIP(ctx, hipGetLastError());
+    return K4LZ4_OK;
+}
+
+int k4lz4_unwrap_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                              const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int32_t *decoded, int64_t n, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen || !decoded)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    int rc;
+    if ((rc = lg_grow(ctx, &ctx->d_lg, &ctx->d_lg_cap, (size_t)n * 20 + 64)) != K4LZ4_OK) return rc;
+    uint64_t *d_off = (uint64_t *)ctx->d_lg;
+    int32_t *d_len = (int32_t *)(d_off + n), *d_cap = d_len + n, *d_out = d_cap + n;
+    k4::UnwrapArgs u{src, srcOff, srcLen, dstCap, n, outLen, d_off, d_len, d_cap};
+    hipLaunchKernelGGL(k4::k4_unwrap_sizes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, u);
+    K4_HIP(ctx, hipGetLastError());
+    /* the payloads that LZ4Codec.Decode takes, by the ordinary batch decoder with cap = outLen (the others have length 0) */
+    if ((rc = launch(ctx, KIND_DECODE, src, d_off, d_len, dst, dstOff, d_cap, d_out, n, 0, 0, st)) != K4LZ4_OK) return rc;
+    hipLaunchKernelGGL(k4::k4_unwrap_finish_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, src, srcOff, dst, dstOff, u, d_out, decoded);
+    K4_HIP(ctx, hipGetLastError());
+    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
+    else (void)hipGetLastError();
+    return K4LZ4_OK;
+}
+
+int k4lz4_unwrap_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                       const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int32_t *decoded, int64_t n)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen || !decoded)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> len64((size_t)n), cap64((size_t)n), h_doff;
+    for (int64_t i = 0; i < n; i++) {
+        len64[(size_t)i] = srcLen[i] > 0 ? (uint64_t)srcLen[i] : 0;
+        cap64[(size_t)i] = dstCap[i] > 0 ? (uint64_t)dstCap[i] : 0;
+    }
+    uint64_t *d_off, *d_len, total;
+    uint8_t *m;
+    int rc;
+    if ((rc = frame_stage(ctx, src, srcOff, len64.data(), n, (size_t)n * 24, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
+    if ((rc = lg_out_stage(ctx, n, cap64.data(), h_doff, &total)) != K4LZ4_OK) return rc;
+    uint64_t *d_doff = (uint64_t *)m;
+    int32_t *d_slen = (int32_t *)(d_doff + n), *d_cap = d_slen + n, *d_out = d_cap + n, *d_dec = d_out + n;
+    hipStream_t st = ctx->stream;
+    std::vector<int32_t> slen((size_t)n);
+    for (int64_t i = 0; i < n; i++) slen[(size_t)i] = (int32_t)len64[(size_t)i];
+    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipMemcpyAsync(d_slen, slen.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipMemcpyAsync(d_cap, dstCap, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (total) K4_HIP(ctx, hipMemsetAsync(ctx->d_dst, 0, (size_t)total, st));      /* (as k4lz4_decode_frames) */
+    if ((rc = k4lz4_unwrap_batch_device(ctx, ctx->d_src, d_off, d_slen, ctx->d_dst, d_doff, d_cap, d_out, d_dec, n, st)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipMemcpyAsync(decoded, d_dec, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (total) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)total, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (outLen[i] > 0) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
+    return K4LZ4_OK;
+}
+
+int64_t k4lz4_legacy_stream_bound(int64_t srcLen, int blockSize)
+{
+    if (srcLen < 0) return 0;
+    const int64_t bs = std::max(16, blockSize);
+    return srcLen + 10 * ((srcLen + bs - 1) / bs);       /* a compressed record: 1 + 5 + 5 bytes of varints and at most U - 1 */
+}
+
+int k4lz4_encode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, int64_t n,
+                                       int blockSize, int high, int flags, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                                       int64_t *outLen, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    unsigned long long *cnt;
+    uint64_t *w[4];
+    int32_t *w32;
+    int rc;
+    if ((rc = lg_streams(ctx, n, &cnt, w, &w32)) != K4LZ4_OK) return rc;
+    k4::LegacyWriteArgs a{};
+    a.src = src; a.srcOff = srcOff; a.srcLen = srcLen; a.n = n; a.bs = (uint64_t)std::max(16, blockSize); a.high = high ? 1 : 0;
+    a.nch = w[0]; a.pad = w[1]; a.first = w[2]; a.arenaOff = w[3];
+    const unsigned sgrid = (unsigned)((n + 255) / 256);
+    K4_HIP(ctx, hipMemsetAsync(cnt, 0, 64, st));
+    hipLaunchKernelGGL(k4::k4_lw_count_kernel, dim3(sgrid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k4::k4_legacy_scan_kernel, dim3(1), dim3(k4::LEGACY_SCAN_THREADS), 0, st, (const uint64_t *)a.nch, a.first, (long long)n, cnt);
+    hipLaunchKernelGGL(k4::k4_legacy_scan_kernel, dim3(1), dim3(k4::LEGACY_SCAN_THREADS), 0, st, (const uint64_t *)a.pad, a.arenaOff, (long long)n, cnt + 1);
+    K4_HIP(ctx, hipGetLastError());
+    /* the one wait: chunks and arena bytes size the chunk table and the arena */
+    unsigned long long h[2];
+    K4_HIP(ctx, hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    const int64_t rows = (int64_t)h[0];
+    if (h[0] > 0xffffffffull) return fail(ctx, K4LZ4_E_ARG, "more than 2^32 chunks in one call");
+    if ((rc = lg_grow(ctx, &ctx->d_lgr, &ctx->d_lgr_cap, (size_t)std::max<int64_t>(rows, 1) * LG_ROW_BYTES + 64)) != K4LZ4_OK) return rc;
+    if ((rc = lg_grow(ctx, &ctx->d_lga, &ctx->d_lga_cap, (size_t)h[1] + 64)) != K4LZ4_OK) return rc;
+    {
+        uint8_t *m = ctx->d_lgr;
+        const size_t w8 = (size_t)std::max<int64_t>(rows, 1) * 8, w4 = w8 / 2;
+        a.cSrcOff = (uint64_t *)m;  m += w8;
+        a.cEncOff = (uint64_t *)m;  m += w8;
+        a.recLen = (uint64_t *)m;   m += w8;
+        a.recOff = (uint64_t *)m;   m += w8;
+        a.owner = (uint32_t *)m;    m += w4;
+        a.cSrcLen = (int32_t *)m;   m += w4;
+        a.cEncCap = (int32_t *)m;   m += w4;
+        a.cEncLen = (int32_t *)m;
+    }
+    a.rows = rows;
+    if (rows) {
+        const unsigned rgrid = (unsigned)((rows + 255) / 256);
+        hipLaunchKernelGGL(k4::k4_lw_fill_kernel, dim3(rgrid), dim3(256), 0, st, a);
+        K4_HIP(ctx, hipGetLastError());
+        /* every chunk of every stream in one batch, cap U - 1: compressed iff C < U (LZ4Stream.cs FlushCurrentChunk); few big chunks
+         * may be cut into segments */
+        const int seg_ok = (!high && a.bs >= ctx->seg_min && rows <= 2 * (int64_t)ctx->cu_count) ? FLAG_SEGMENTS_OK : 0;
+        if ((rc = launch(ctx, KIND_ENCODE, src, a.cSrcOff, a.cSrcLen, ctx->d_lga, a.cEncOff, a.cEncCap, a.cEncLen, rows,
+                         high ? K4LZ4_L09_HC : K4LZ4_L00_FAST, (flags & K4LZ4_FLAG_X32) | K4LZ4_FLAG_RAW_RETURN | seg_ok, st)) != K4LZ4_OK)
+            return rc;
+        hipLaunchKernelGGL(k4::k4_lw_header_kernel, dim3(rgrid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k4::k4_legacy_scan_kernel, dim3(1), dim3(k4::LEGACY_SCAN_THREADS), 0, st, (const uint64_t *)a.recLen, a.recOff, (long long)rows, cnt + 2);
+        hipLaunchKernelGGL(k4::k4_lw_assemble_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, dst, dstOff, dstCap, (const uint8_t *)ctx->d_lga);
+    }
+    hipLaunchKernelGGL(k4::k4_lw_finish_kernel, dim3(sgrid), dim3(256), 0, st, a, dstCap, outLen);
+    K4_HIP(ctx, hipGetLastError());
+    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
+    else (void)hipGetLastError();
+    return K4LZ4_OK;
+}
+
+int k4lz4_encode_legacy_streams(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, int64_t n,
+                                int blockSize, int high, int flags, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                                int64_t *outLen)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> h_doff;
+    uint64_t *d_off, *d_len, total;
+    uint8_t *m;
+    int rc;
+    if ((rc = frame_stage(ctx, src, srcOff, srcLen, n, (size_t)n * 24, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
+    if ((rc = lg_out_stage(ctx, n, dstCap, h_doff, &total)) != K4LZ4_OK) return rc;
+    uint64_t *d_doff = (uint64_t *)m, *d_dcap = d_doff + n;
+    int64_t *d_out = (int64_t *)(d_dcap + n);
+    hipStream_t st = ctx->stream;
+    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipMemcpyAsync(d_dcap, dstCap, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if ((rc = k4lz4_encode_legacy_streams_device(ctx, ctx->d_src, d_off, d_len, n, blockSize, high, flags, ctx->d_dst, d_doff, d_dcap,
+                                                 d_out, st)) != K4LZ4_OK)
+        return rc;
+    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (total) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)total, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (outLen[i] > 0) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
+    return K4LZ4_OK;
+}
+
+int k4lz4_legacy_stream_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen, int64_t n,
+                                     uint64_t *outSize, int32_t *outStatus, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !streamOff || !streamLen || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    unsigned long long *cnt;
+    uint64_t *w[4];
+    int32_t *w32;
+    int rc;
+    if ((rc = lg_streams(ctx, n, &cnt, w, &w32)) != K4LZ4_OK) return rc;
+    k4::LegacyReadArgs a{src, streamOff, streamLen, n, w[0], w[1], w32, w[2], (unsigned long long *)w[3], outSize, outStatus};
+    hipLaunchKernelGGL(k4::k4_lr_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    K4_HIP(ctx, hipGetLastError());
+    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
+    else (void)hipGetLastError();
+    return K4LZ4_OK;
+}
+
+int k4lz4_decode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen, int64_t n,
+                                       uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !streamOff || !streamLen || !dst || !dstOff || !dstCap || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    unsigned long long *cnt;
+    uint64_t *w[4];
+    int32_t *w32;
+    int rc;
+    if ((rc = lg_streams(ctx, n, &cnt, w, &w32)) != K4LZ4_OK) return rc;
+    k4::LegacyReadArgs a{src, streamOff, streamLen, n, w[0], w[1], w32, w[2], (unsigned long long *)w[3], nullptr, nullptr};
+    const unsigned sgrid = (unsigned)((n + 255) / 256);
+    K4_HIP(ctx, hipMemsetAsync(cnt, 0, 64, st));
+    hipLaunchKernelGGL(k4::k4_lr_walk_kernel, dim3(sgrid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k4::k4_legacy_scan_kernel, dim3(1), dim3(k4::LEGACY_SCAN_THREADS), 0, st, (const uint64_t *)a.nch, a.first, (long long)n, cnt);
+    K4_HIP(ctx, hipGetLastError());
+    /* the one wait: the chunk count sizes the table */
+    unsigned long long h = 0;
+    K4_HIP(ctx, hipMemcpyAsync(&h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    const int64_t rows = (int64_t)h;
+    if (h > 0xffffffffull) return fail(ctx, K4LZ4_E_ARG, "more than 2^32 chunks in one call");
+    if ((rc = lg_grow(ctx, &ctx->d_lgr, &ctx->d_lgr_cap, (size_t)std::max<int64_t>(rows, 1) * LG_ROW_BYTES + 64)) != K4LZ4_OK) return rc;
+    k4::LegacyRows rw;
+    {
+        uint8_t *m = ctx->d_lgr;
+        const size_t w8 = (size_t)std::max<int64_t>(rows, 1) * 8, w4 = w8 / 2;
+        rw.off = (uint64_t *)m;     m += w8;
+        rw.dstOff = (uint64_t *)m;  m += w8;
+        rw.owner = (uint32_t *)m;   m += w4;
+        rw.idx = (uint32_t *)m;     m += w4;
+        rw.srcLen = (int32_t *)m;   m += w4;
+        rw.dstCap = (int32_t *)m;   m += w4;
+        rw.len = (int32_t *)m;      m += w4;
+        rw.outLen = (int32_t *)m;   m += w4;
+        rw.kind = m;
+    }
+    hipLaunchKernelGGL(k4::k4_lr_fill_kernel, dim3(sgrid), dim3(256), 0, st, a, rw, dstOff, dstCap);
+    K4_HIP(ctx, hipGetLastError());
+    if (rows) {
+        /* compressed chunks straight into place, cap U; raw chunks (srcLen 0 there) copied behind them */
+        if ((rc = launch(ctx, KIND_DECODE, src, rw.off, rw.srcLen, dst, rw.dstOff, rw.dstCap, rw.outLen, rows, 0, 0, st)) != K4LZ4_OK) return rc;
+        hipLaunchKernelGGL(k4::k4_lr_copy_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, src, dst, a, rw, (long long)rows);
+    }
+    hipLaunchKernelGGL(k4::k4_lr_finish_kernel, dim3(sgrid), dim3(256), 0, st, a, outLen);
+    K4_HIP(ctx, hipGetLastError());
+    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
+    else (void)hipGetLastError();
+    return K4LZ4_OK;
+}
+
+int k4lz4_legacy_stream_sizes(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen, int64_t n,
+                              uint64_t *outSize, int32_t *outStatus)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !streamOff || !streamLen || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    uint64_t *d_off, *d_len;
+    uint8_t *m;
+    int rc;
+    if ((rc = frame_stage(ctx, src, streamOff, streamLen, n, (size_t)n * 12, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
+    uint64_t *d_size = (uint64_t *)m;
+    int32_t *d_status = (int32_t *)(d_size + n);
+    hipStream_t st = ctx->stream;
+    if ((rc = k4lz4_legacy_stream_sizes_device(ctx, ctx->d_src, d_off, d_len, n, d_size, d_status, st)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipMemcpyAsync(outSize, d_size, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipMemcpyAsync(outStatus, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    return take_device_status(ctx);
+}
+
+int k4lz4_decode_legacy_streams(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen, int64_t n,
+                                uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !streamOff || !streamLen || !dst || !dstOff || !dstCap || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> h_doff;
+    uint64_t *d_off, *d_len, total;
+    uint8_t *m;
+    int rc;
+    if ((rc = frame_stage(ctx, src, streamOff, streamLen, n, (size_t)n * 24, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
+    if ((rc = lg_out_stage(ctx, n, dstCap, h_doff, &total)) != K4LZ4_OK) return rc;
+    uint64_t *d_doff = (uint64_t *)m, *d_dcap = d_doff + n;
+    int64_t *d_out = (int64_t *)(d_dcap + n);
+    hipStream_t st = ctx->stream;
+    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipMemcpyAsync(d_dcap, dstCap, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (total) K4_HIP(ctx, hipMemsetAsync(ctx->d_dst, 0, (size_t)total, st));
+    if ((rc = k4lz4_decode_legacy_streams_device(ctx, ctx->d_src, d_off, d_len, n, ctx->d_dst, d_doff, d_dcap, d_out, st)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (total) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)total, hipMemcpyDeviceToHost, st));
+    K4_HIP(ctx, hipStreamSynchronize(st));
+    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (outLen[i] > 0) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
     return K4LZ4_OK;
 }
 
