@@ -18,7 +18,8 @@
  *   - Call-level return: K4LZ4_OK or a negative k4lz4_status; text via k4lz4_last_error().
  *     The library never throws, aborts or calls back.  No pointer is retained after return
  *     (the *_device calls return after enqueueing on the given stream; the buffers must stay
- *     valid until that stream work completes).
+ *     valid until that stream work completes).  A host-pointer call that fails part-way drains the work
+ *     it queued and clears the context's status word before it returns, so the next call starts clean.
  *   - There is NO CPU fallback: without a usable gfx950 device every compute entry point fails
  *     with K4LZ4_E_NO_DEVICE.
  *   - A k4lz4_ctx is bound to one GPU and may be used by one host thread at a time; different

@@ -430,17 +430,35 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
                  const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
                  hipStream_t stream, const DictArgs *dd, const int32_t *hostLen);
 
+/* A device form's prologue: the context's scratch (dispatch order, hash tables, HC work areas, the stream formats' tables)
+ * may still be in use by a call that was enqueued on another stream -- st waits for it. */
+hipError_t order_after_ctx(k4lz4_ctx *ctx, hipStream_t st)
+{
+    return ctx->busy && ctx->last_stream != st ? hipStreamWaitEvent(st, ctx->ev_busy, 0) : hipSuccess;
+}
+
+/* ... and its epilogue: the end of its work on st is what the next call on another stream waits for */
+void mark_busy(k4lz4_ctx *ctx, hipStream_t st)
+{
+    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
+    else (void)hipGetLastError();
+}
+
+/* grow-only scratch of the device forms: grow frees the old buffer, so one that has to grow waits for the context's earlier work */
+int grow_scratch(k4lz4_ctx *ctx, uint8_t **p, size_t *cap, size_t need)
+{
+    if (need > *cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
+    return grow(ctx, p, cap, need, false);
+}
+
 int launch(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
            const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
            hipStream_t stream, const DictArgs *dd = nullptr, const int32_t *hostLen = nullptr)
 {
     if (n == 0) return K4LZ4_OK;
-    /* the context's scratch (dispatch order, global hash tables, HC work areas) may still be in use by a call that was
-     * enqueued on another stream */
-    if (ctx->busy && ctx->last_stream != stream) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, stream));
     const int rc = launch_inner(ctx, kind, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, stream, dd, hostLen);
-    if (hipEventRecord(ctx->ev_busy, stream) == hipSuccess) { ctx->busy = true; ctx->last_stream = stream; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, stream);
     return rc;
 }
 
@@ -1060,26 +1078,27 @@ int run_host_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t
                    uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level,
                    int flags, const DictArgs *hd);
 
-/* host-pointer batch: stage, run, scatter.  A call that fails part-way has copies and kernels in flight on the context's
- * two queues that use its staging buffers and scratch: they are drained -- and a status bit they may have raised is taken
- * with them -- before the error is returned, so that the next call on the context starts from nothing. */
+/* A host-pointer call that fails part-way has copies and kernels in flight on the context's queues that use its staging
+ * buffers and scratch: they are drained -- and a status bit they may have raised is taken with them -- before the error is
+ * returned, so that the next call on the context starts from nothing.  The call's own error message stays. */
+void drain_after_failure(k4lz4_ctx *ctx)
+{
+    const std::string why = ctx->error;
+    for (hipStream_t q : {ctx->stream, ctx->copyq, ctx->dlq, ctx->aux, ctx->aux2})
+        if (q) (void)hipStreamSynchronize(q);
+    (void)hipGetLastError();
+    (void)take_device_status(ctx);
+    ctx->error = why;
+    tl_error = why;
+}
+
+/* host-pointer batch: stage, run, scatter */
 int run_host(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
              uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level,
              int flags, const DictArgs *hd = nullptr)
 {
     const int rc = run_host_inner(ctx, kind, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, hd);
-    if (rc != K4LZ4_OK && ctx) {
-        const std::string why = ctx->error;
-        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->copyq) (void)hipStreamSynchronize(ctx->copyq);
-        if (ctx->dlq) (void)hipStreamSynchronize(ctx->dlq);
-        if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
-        if (ctx->aux2) (void)hipStreamSynchronize(ctx->aux2);
-        (void)hipGetLastError();
-        (void)take_device_status(ctx);
-        ctx->error = why;
-        tl_error = why;
-    }
+    if (rc != K4LZ4_OK && ctx) drain_after_failure(ctx);
     return rc;
 }
 
@@ -1506,11 +1525,10 @@ int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, con
     h.place(ctx->h_chain.data(), nb);
     rc = hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, &h);
     if (rc != K4LZ4_OK) return rc;
-    if (bytes > ctx->d_chain_cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));     /* (grow frees the old table) */
-    if ((rc = grow(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes)) != K4LZ4_OK) return rc;
     HcChainPlan d;
     d.place(ctx->d_chain, nb);
-    if (ctx->busy && ctx->last_stream != stream) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, stream));
     K4_HIP(ctx, hipMemcpyAsync(ctx->d_chain, ctx->h_chain.data(), bytes, hipMemcpyHostToDevice, stream));
     K4_HIP(ctx, hipEventRecord(ctx->ev_chain, stream));
     rc = launch_hc(ctx, ENV_NONE, src, d.woff, d.wlen, dst, d.doff, d.cap, outLen, nb, level, 0, stream, h.wlen, d.hist);
@@ -1525,8 +1543,7 @@ int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, con
         }
         if (hipGetLastError() != hipSuccess) rc = fail(ctx, K4LZ4_E_HIP, "k4_allow_copy_kernel launch failed");
     }
-    if (hipEventRecord(ctx->ev_busy, stream) == hipSuccess) { ctx->busy = true; ctx->last_stream = stream; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, stream);
     return rc;
 }
 
@@ -1640,11 +1657,10 @@ int fast_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, c
         std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return srcLen[x] - (dictLen ? dictLen[x] : 0) > srcLen[y] - (dictLen ? dictLen[y] : 0); });
         memcpy(h.order, ord.data(), ord.size() * 4);
     }
-    if (bytes > ctx->d_chain_cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));     /* (grow frees the old table) */
-    if ((rc = grow(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes)) != K4LZ4_OK) return rc;
     FastChainPlan d;
     d.place(ctx->d_chain, nStreams, nb);
-    if (ctx->busy && ctx->last_stream != stream) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, stream));
     K4_HIP(ctx, hipMemcpyAsync(ctx->d_chain, ctx->h_chain.data(), bytes, hipMemcpyHostToDevice, stream));
     K4_HIP(ctx, hipEventRecord(ctx->ev_chain, stream));
     k4::FastChainArgs a{};
@@ -1655,8 +1671,7 @@ int fast_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, c
     const int64_t wgs = std::min<int64_t>((nStreams + k4::FAST_CHAIN_WAVES_PER_WG - 1) / k4::FAST_CHAIN_WAVES_PER_WG, ctx->cu_count);
     hipLaunchKernelGGL(k4::k4_fast_chain_kernel, dim3((unsigned)wgs), dim3(64 * k4::FAST_CHAIN_WAVES_PER_WG), 0, stream, a);
     if (hipGetLastError() != hipSuccess) rc = fail(ctx, K4LZ4_E_HIP, "k4_fast_chain_kernel launch failed");
-    if (hipEventRecord(ctx->ev_busy, stream) == hipSuccess) { ctx->busy = true; ctx->last_stream = stream; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, stream);
     return rc;
 }
 
@@ -1673,10 +1688,8 @@ constexpr size_t FRAME_BYTES = 8 * 8 + 10 * 4 + 1, BLOCK_BYTES = 3 * 8 + 8 * 4;
 
 int frame_scratch(k4lz4_ctx *ctx, int64_t n, k4::FrameTab *t, unsigned long long **counters)
 {
-    const size_t need = 64 + (size_t)n * FRAME_BYTES + 64;
     int rc;
-    if (need > ctx->d_fr_cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
-    if ((rc = grow(ctx, &ctx->d_fr, &ctx->d_fr_cap, need, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_fr, &ctx->d_fr_cap, 64 + (size_t)n * FRAME_BYTES + 64)) != K4LZ4_OK) return rc;
     uint8_t *m = ctx->d_fr;
     const size_t w8 = (size_t)n * 8, w4 = (size_t)n * 4;
     *counters = (unsigned long long *)m;         m += 64;
@@ -1704,10 +1717,8 @@ int frame_scratch(k4lz4_ctx *ctx, int64_t n, k4::FrameTab *t, unsigned long long
 
 int block_scratch(k4lz4_ctx *ctx, int64_t nb, k4::BlockTab *b)
 {
-    const size_t need = (size_t)std::max<int64_t>(nb, 1) * BLOCK_BYTES + 64;
     int rc;
-    if (need > ctx->d_fb_cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
-    if ((rc = grow(ctx, &ctx->d_fb, &ctx->d_fb_cap, need, false)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_fb, &ctx->d_fb_cap, (size_t)std::max<int64_t>(nb, 1) * BLOCK_BYTES + 64)) != K4LZ4_OK) return rc;
     uint8_t *m = ctx->d_fb;
     const size_t w8 = (size_t)std::max<int64_t>(nb, 1) * 8, w4 = w8 / 2;
     b->off = (uint64_t *)m;                      m += w8;
@@ -1724,45 +1735,14 @@ int block_scratch(k4lz4_ctx *ctx, int64_t nb, k4::BlockTab *b)
     return K4LZ4_OK;
 }
 
-/* host-pointer frame calls: the frames' span goes up to ctx->d_src, their rebased offsets and lengths to d_off / d_len */
-int frame_stage(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n, size_t extra_meta,
-                uint64_t **d_off, uint64_t **d_len, uint8_t **meta_rest)
-{
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (int64_t i = 0; i < n; i++)
-        if (frameLen[i]) { lo = std::min(lo, frameOff[i]); hi = std::max(hi, frameOff[i] + frameLen[i]); }
-    if (lo == UINT64_MAX) { lo = 0; hi = 0; }
-    std::vector<uint64_t> h_off((size_t)n);
-    for (int64_t i = 0; i < n; i++) h_off[(size_t)i] = frameLen[i] ? frameOff[i] - lo : 0;
-    const size_t span = (size_t)(hi - lo);
-    int rc;
-    if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, span + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, (size_t)n * 16 + extra_meta + 64, false)) != K4LZ4_OK) return rc;
-    *d_off = (uint64_t *)ctx->d_meta;
-    *d_len = *d_off + n;
-    *meta_rest = (uint8_t *)(*d_len + n);
-    hipStream_t st = ctx->stream;
-    if (span) K4_HIP(ctx, hipMemcpyAsync(ctx->d_src, src + lo, span, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(*d_off, h_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(*d_len, frameLen, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    return K4LZ4_OK;
-}
-
-
-/* ---- legacy formats (k4lz4_legacy.hpp): grow-only scratch; what has to grow waits for the context's earlier work first */
-int lg_grow(k4lz4_ctx *ctx, uint8_t **p, size_t *cap, size_t need)
-{
-    if (need > *cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
-    return grow(ctx, p, cap, need, false);
-}
-
+/* ---- legacy formats (k4lz4_legacy.hpp): grow-only scratch, grown by grow_scratch */
 constexpr size_t LG_STREAM_BYTES = 4 * 8 + 4, LG_ROW_BYTES = 48;
 
 /* per-stream words behind 64 bytes of counters: four u64 arrays and one 32-bit array */
 int lg_streams(k4lz4_ctx *ctx, int64_t n, unsigned long long **cnt, uint64_t *w[4], int32_t **w32)
 {
     int rc;
-    if ((rc = lg_grow(ctx, &ctx->d_lg, &ctx->d_lg_cap, 64 + (size_t)n * LG_STREAM_BYTES + 64)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_lg, &ctx->d_lg_cap, 64 + (size_t)n * LG_STREAM_BYTES + 64)) != K4LZ4_OK) return rc;
     uint8_t *m = ctx->d_lg;
     *cnt = (unsigned long long *)m;
     m += 64;
@@ -1771,16 +1751,175 @@ int lg_streams(k4lz4_ctx *ctx, int64_t n, unsigned long long **cnt, uint64_t *w[
     return K4LZ4_OK;
 }
 
-/* host-pointer calls: copy the results back into the caller's slots (the device form wrote them packed at h_doff) */
-int lg_out_stage(k4lz4_ctx *ctx, int64_t n, const uint64_t *cap, std::vector<uint64_t> &h_doff, uint64_t *total)
+/* ---- the host-pointer forms of the stream calls: one staging path.  A call lays out its inputs in ctx->d_src (span(): one
+ * span of the caller's buffer, offsets rebased; pack(): every stream's content at a 16-byte step), its output slots at 16-byte
+ * steps at the same offsets of ctx->d_dst and ctx->h_stage (slots()) and its per-item arrays at 16-byte steps of ctx->d_meta
+ * (meta(): uploaded from a host array, or left for the kernels).  upload() grows the buffers, then queues the copies; the call
+ * runs its device form on st; finish() queues the downloads, synchronises once, takes the status word and copies each item's
+ * bytes into the caller's slot.  A stage that has queued work and is left without a finished synchronisation -- any failure
+ * after the first enqueue -- drains the context on the way out. */
+struct HostStage {
+    struct Down { void *host; const void *dev; size_t bytes; };
+    struct Up { uint8_t **base; uint64_t at; const void *host; size_t bytes; };       /* base: &ctx->d_src or &ctx->d_meta */
+    k4lz4_ctx *const ctx;
+    const hipStream_t st;
+    std::vector<uint64_t> in_off, slot;     /* per item: its input's offset in d_src, its output slot's in d_dst / h_stage */
+    std::vector<Up> ups;
+    std::vector<std::function<void()>> places;
+    uint64_t in_bytes = 0, out_bytes = 0, meta_bytes = 0;
+    bool zero = false, queued = false, done = false;
+
+    explicit HostStage(k4lz4_ctx *c) : ctx(c), st(c->stream) {}
+    ~HostStage() { if (queued && !done) drain_after_failure(ctx); }
+    template <class Len> void span(const uint8_t *s, const uint64_t *off, int64_t n, Len len)
+    {
+        uint64_t lo = UINT64_MAX, hi = 0;
+        for (int64_t i = 0; i < n; i++)
+            if (len(i)) { lo = std::min(lo, off[i]); hi = std::max(hi, off[i] + len(i)); }
+        if (lo == UINT64_MAX) lo = hi = 0;
+        in_off.assign((size_t)n, 0);
+        for (int64_t i = 0; i < n; i++) if (len(i)) in_off[(size_t)i] = off[i] - lo;
+        in_bytes = hi - lo;
+        ups.push_back(Up{&ctx->d_src, 0, s + lo, (size_t)in_bytes});
+    }
+    void pack(const uint8_t *s, const uint64_t *off, const int64_t *len, int64_t n)
+    {
+        in_off.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            in_off[(size_t)i] = in_bytes;
+            ups.push_back(Up{&ctx->d_src, in_bytes, s + off[i], (size_t)std::max<int64_t>(len[i], 0)});
+            in_bytes += ((uint64_t)len[i] + 15u) & ~(uint64_t)15u;
+        }
+    }
+    /* clear: the slots start as zeros (a hostile stream's offset-0 matches leave zeros, not an earlier call's bytes: see run_host_inner) */
+    template <class Cap> void slots(int64_t n, Cap cap, bool clear)
+    {
+        slot.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) { slot[(size_t)i] = out_bytes; out_bytes += ((uint64_t)cap(i) + 15u) & ~(uint64_t)15u; }
+        zero = clear;
+    }
+    template <class T> void meta(T **p, int64_t count, const void *host = nullptr)
+    {
+        const uint64_t at = meta_bytes;
+        places.push_back([this, p, at] { *p = (T *)(ctx->d_meta + at); });
+        ups.push_back(Up{&ctx->d_meta, at, host, host ? (size_t)count * sizeof(T) : 0});
+        meta_bytes += ((uint64_t)count * sizeof(T) + 15u) & ~(uint64_t)15u;
+    }
+    int upload()
+    {
+        int rc;
+        if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, (size_t)in_bytes + 64, false)) != K4LZ4_OK ||
+            (rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, (size_t)meta_bytes + 64, false)) != K4LZ4_OK ||
+            (!slot.empty() && ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)out_bytes + 64, false)) != K4LZ4_OK ||
+                               (rc = grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)out_bytes + 64, true)) != K4LZ4_OK)))
+            return rc;
+        for (const auto &place : places) place();
+        queued = true;
+        for (const Up &u : ups)
+            if (u.bytes) K4_HIP(ctx, hipMemcpyAsync(*u.base + u.at, u.host, u.bytes, hipMemcpyHostToDevice, st));
+        if (zero && out_bytes) K4_HIP(ctx, hipMemsetAsync(ctx->d_dst, 0, (size_t)out_bytes, st));
+        return K4LZ4_OK;
+    }
+    /* bytes(i): how many bytes of item i's slot go to dst + dstOff[i] */
+    int finish(std::initializer_list<Down> results, uint8_t *dst = nullptr, const uint64_t *dstOff = nullptr,
+               const std::function<size_t(int64_t)> &bytes = nullptr)
+    {
+        for (const Down &d : results)
+            if (d.bytes) K4_HIP(ctx, hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, st));
+        if (out_bytes) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, st));
+        K4_HIP(ctx, hipStreamSynchronize(st));
+        done = true;
+        const int rc = take_device_status(ctx);
+        for (size_t i = 0; rc == K4LZ4_OK && bytes && i < slot.size(); i++)
+            if (const size_t b = bytes((int64_t)i)) memcpy(dst + dstOff[i], ctx->h_stage + slot[i], b);
+        return rc;
+    }
+};
+
+/* the chained encoders' host forms after their argument checks.  table(nb) counts the blocks (host arithmetic: before the
+ * context); the contents go up packed, every stream's block slots lie behind each other, the states in the tail of the
+ * metadata; run(s, nb, d_out, d_in, d_outst) is the device form; exactly |outLen| bytes of every block's slot go to the caller's */
+template <class Table, class Run>
+int chain_host(k4lz4_ctx *ctx, const char *what, Table table, Run run, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen,
+               const int32_t *blockSize, const int32_t *dictLen, int64_t nStreams, const k4lz4_fast_chain_state *stateIn,
+               k4lz4_fast_chain_state *stateOut, uint8_t *dst, const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks)
 {
-    h_doff.resize((size_t)n);
-    uint64_t t = 0;
-    for (int64_t i = 0; i < n; i++) { h_doff[(size_t)i] = t; t += (cap[i] + 15u) & ~(uint64_t)15u; }
-    *total = t;
+    int64_t nb = 0;
+    int rc = table(nb);
+    if (rc != K4LZ4_OK) return rc;
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, std::string(what) + ": outLen has fewer entries than the streams have blocks");
+    if (nStreams == 0 || (nb == 0 && !stateOut)) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    s.pack(src, srcOff, srcLen, nStreams);
+    auto fresh = [&](int64_t si) { return srcLen[si] - (dictLen ? dictLen[si] : 0); };     /* (validated by the block table) */
+    s.slots(nStreams, [&](int64_t si) {
+        const uint64_t B = (uint64_t)hc_chain_block_size(blockSize[si]);
+        return ((uint64_t)fresh(si) + B - 1u) / B * (B + B / 255 + 16);
+    }, false);
+    int32_t *d_out;
+    k4lz4_fast_chain_state *d_in = nullptr, *d_outst = nullptr;
+    s.meta(&d_out, nb);
+    if (stateIn) s.meta(&d_in, nStreams, stateIn);
+    if (stateOut) s.meta(&d_outst, nStreams);
+    if ((rc = s.upload()) != K4LZ4_OK || (rc = run(s, nb, d_out, d_in, d_outst)) != K4LZ4_OK ||
+        (rc = s.finish({{outLen, d_out, (size_t)nb * 4}, {stateOut, d_outst, stateOut ? (size_t)nStreams * sizeof(*stateOut) : 0}})) != K4LZ4_OK)
+        return rc;
+    int64_t k = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t B = hc_chain_block_size(blockSize[si]), slot = B + B / 255 + 16;
+        for (int64_t j = 0; j * B < fresh(si); j++, k++)
+            if (outLen[k]) memcpy(dst + dstOff[si] + (uint64_t)(j * slot), ctx->h_stage + s.slot[(size_t)si] + (uint64_t)(j * slot),
+                                  (size_t)std::abs((int64_t)outLen[k]));
+    }
+    return K4LZ4_OK;
+}
+
+/* the size calls (k4lz4_frame_sizes, k4lz4_legacy_stream_sizes): the streams' span up, their sizes and statuses down */
+template <class Device>
+int host_sizes(Device device, k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *off, const uint64_t *len, int64_t n,
+               uint64_t *outSize, int32_t *outStatus)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !off || !len || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    s.span(src, off, n, [&](int64_t i) { return len[i]; });
+    uint64_t *d_off, *d_len, *d_size;
+    int32_t *d_status;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, len); s.meta(&d_size, n); s.meta(&d_status, n);
     int rc;
-    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)t + 64, false)) != K4LZ4_OK) return rc;
-    return grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)t + 64, true);
+    if ((rc = s.upload()) != K4LZ4_OK || (rc = device(ctx, ctx->d_src, d_off, d_len, n, d_size, d_status, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outSize, d_size, (size_t)n * 8}, {outStatus, d_status, (size_t)n * 4}});
+}
+
+/* the slot-filling stream calls with u64 offsets, lengths and capacities (k4lz4_decode_frames, the legacy streams' encoder and
+ * decoder); device(ctx, src, off, len, n, dst, dstOff, dstCap, outLen, stream) is the device form.  zero: the slots start as
+ * zeros (the decoders); capped: an outLen beyond the slot's capacity copies nothing */
+template <class Device>
+int host_streams(Device device, k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *off, const uint64_t *len, int64_t n,
+                 uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, bool zero, bool capped)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!src || !off || !len || !dst || !dstOff || !dstCap || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    s.span(src, off, n, [&](int64_t i) { return len[i]; });
+    s.slots(n, [&](int64_t i) { return dstCap[i]; }, zero);
+    uint64_t *d_off, *d_len, *d_doff, *d_dcap;
+    int64_t *d_out;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, len); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_dcap, n, dstCap);
+    s.meta(&d_out, n);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK || (rc = device(ctx, ctx->d_src, d_off, d_len, n, ctx->d_dst, d_doff, d_dcap, d_out, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff, [&](int64_t i) {
+        return outLen[i] > 0 && (!capped || (uint64_t)outLen[i] <= dstCap[i]) ? (size_t)outLen[i] : 0;
+    });
 }
 
 }  // namespace
@@ -2209,27 +2348,15 @@ int k4lz4_xxh32_batch(k4lz4_ctx *ctx, const uint8_t *data, const uint64_t *off, 
     if (n < 0 || (n > 0 && (!data || !off || !len || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (int64_t i = 0; i < n; i++)
-        if (len[i]) { lo = std::min(lo, off[i]); hi = std::max(hi, off[i] + len[i]); }
-    if (lo == UINT64_MAX) { lo = 0; hi = 0; }
-    std::vector<uint64_t> h_off((size_t)n);
-    for (int64_t i = 0; i < n; i++) h_off[(size_t)i] = len[i] ? off[i] - lo : 0;
-    const size_t span = (size_t)(hi - lo);
+    HostStage s(ctx);
+    s.span(data, off, n, [&](int64_t i) { return len[i]; });
+    uint64_t *d_off, *d_len;
+    uint32_t *d_out;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, len); s.meta(&d_out, n);
     int rc;
-    if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, span + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, (size_t)n * 20 + 64, false)) != K4LZ4_OK) return rc;
-    uint64_t *d_off = (uint64_t *)ctx->d_meta, *d_len = d_off + n;
-    uint32_t *d_out = (uint32_t *)(d_len + n);
-    hipStream_t st = ctx->stream;
-    if (span) K4_HIP(ctx, hipMemcpyAsync(ctx->d_src, data + lo, span, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_off, h_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_len, len, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    rc = k4lz4_xxh32_batch_device(ctx, ctx->d_src, d_off, d_len, d_out, n, seed, st);
-    if (rc != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipStreamSynchronize(st));
-    return K4LZ4_OK;
+    if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_xxh32_batch_device(ctx, ctx->d_src, d_off, d_len, d_out, n, seed, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{out, d_out, (size_t)n * 4}});
 }
 
 int k4lz4_decode_chain_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *blkOff, const uint32_t *blkLen,
@@ -2266,60 +2393,26 @@ int k4lz4_decode_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t 
         return fail(ctx, K4LZ4_E_ARG, "bad argument");
     if (nStreams == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (int64_t i = 0; i < nBlocks; i++) {
-        const uint64_t l = blkLen[i] & 0x7fffffffu;
-        if (l) { lo = std::min(lo, blkOff[i]); hi = std::max(hi, blkOff[i] + l); }
-    }
-    if (lo == UINT64_MAX) { lo = 0; hi = 0; }
-    std::vector<uint64_t> h_boff((size_t)std::max<int64_t>(nBlocks, 1)), h_doff((size_t)nStreams);
-    for (int64_t i = 0; i < nBlocks; i++) h_boff[(size_t)i] = (blkLen[i] & 0x7fffffffu) ? blkOff[i] - lo : 0;
-    uint64_t dtotal = 0;
-    for (int64_t i = 0; i < nStreams; i++) {
-        if (firstBlk[i] + nBlk[i] > (uint64_t)nBlocks) return fail(ctx, K4LZ4_E_ARG, "stream refers to blocks outside the block table");
-        h_doff[(size_t)i] = dtotal;
-        dtotal += (dstCap[i] + 15u) & ~(uint64_t)15u;
-    }
-    const size_t span = (size_t)(hi - lo);
-    const size_t meta = (size_t)nBlocks * 12 + (size_t)nStreams * (8 + 4 + 4 + 1 + 8 + 8 + 8) + 256;
-    int rc;
-    if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, span + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)dtotal + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, meta, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)dtotal + 64, true)) != K4LZ4_OK) return rc;
-    uint8_t *m = ctx->d_meta;
-    uint64_t *d_boff = (uint64_t *)m;            m += (size_t)nBlocks * 8;
-    uint64_t *d_first = (uint64_t *)m;           m += (size_t)nStreams * 8;
-    uint64_t *d_doff = (uint64_t *)m;            m += (size_t)nStreams * 8;
-    uint64_t *d_dcap = (uint64_t *)m;            m += (size_t)nStreams * 8;
-    int64_t *d_out = (int64_t *)m;               m += (size_t)nStreams * 8;
-    uint32_t *d_blen = (uint32_t *)m;            m += (size_t)nBlocks * 4;
-    uint32_t *d_nblk = (uint32_t *)m;            m += (size_t)nStreams * 4;
-    int32_t *d_bsize = (int32_t *)m;             m += (size_t)nStreams * 4;
-    uint8_t *d_chained = m;
-    hipStream_t st = ctx->stream;
-    if (span) K4_HIP(ctx, hipMemcpyAsync(ctx->d_src, src + lo, span, hipMemcpyHostToDevice, st));
-    if (nBlocks) {
-        K4_HIP(ctx, hipMemcpyAsync(d_boff, h_boff.data(), (size_t)nBlocks * 8, hipMemcpyHostToDevice, st));
-        K4_HIP(ctx, hipMemcpyAsync(d_blen, blkLen, (size_t)nBlocks * 4, hipMemcpyHostToDevice, st));
-    }
-    K4_HIP(ctx, hipMemcpyAsync(d_first, firstBlk, (size_t)nStreams * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)nStreams * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_dcap, dstCap, (size_t)nStreams * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_nblk, nBlk, (size_t)nStreams * 4, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_bsize, blockSize, (size_t)nStreams * 4, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_chained, chained, (size_t)nStreams, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemsetAsync(ctx->d_dst, 0, (size_t)dtotal, st));       /* (offset-0 matches of a hostile stream leave zeros, not an earlier call's bytes: see run_host_inner) */
-    rc = k4lz4_decode_chain_batch_device(ctx, ctx->d_src, d_boff, d_blen, d_first, d_nblk, d_bsize, d_chained, ctx->d_dst, d_doff,
-                                         d_dcap, d_out, nStreams, st);
-    if (rc != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)nStreams * 8, hipMemcpyDeviceToHost, st));
-    if (dtotal) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)dtotal, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipStreamSynchronize(st));
-    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
     for (int64_t i = 0; i < nStreams; i++)
-        if (outLen[i] > 0 && (uint64_t)outLen[i] <= dstCap[i]) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
-    return K4LZ4_OK;
+        if (firstBlk[i] + nBlk[i] > (uint64_t)nBlocks) return fail(ctx, K4LZ4_E_ARG, "stream refers to blocks outside the block table");
+    HostStage s(ctx);
+    s.span(src, blkOff, nBlocks, [&](int64_t i) { return (uint64_t)(blkLen[i] & 0x7fffffffu); });
+    s.slots(nStreams, [&](int64_t i) { return dstCap[i]; }, true);
+    uint64_t *d_boff, *d_first, *d_doff, *d_dcap;
+    int64_t *d_out;
+    uint32_t *d_blen, *d_nblk;
+    int32_t *d_bsize;
+    uint8_t *d_chained;
+    s.meta(&d_boff, nBlocks, s.in_off.data()); s.meta(&d_blen, nBlocks, blkLen);
+    s.meta(&d_first, nStreams, firstBlk); s.meta(&d_doff, nStreams, s.slot.data()); s.meta(&d_dcap, nStreams, dstCap);
+    s.meta(&d_nblk, nStreams, nBlk); s.meta(&d_bsize, nStreams, blockSize); s.meta(&d_chained, nStreams, chained); s.meta(&d_out, nStreams);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_decode_chain_batch_device(ctx, ctx->d_src, d_boff, d_blen, d_first, d_nblk, d_bsize, d_chained, ctx->d_dst, d_doff,
+                                              d_dcap, d_out, nStreams, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)nStreams * 8}}, dst, dstOff,
+                    [&](int64_t i) { return outLen[i] > 0 && (uint64_t)outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
 }
 
 int k4lz4_frame_assemble_device(k4lz4_ctx *ctx, const uint8_t *arena, const uint64_t *slotOff, const int32_t *outLen,
@@ -2374,49 +2467,13 @@ int k4lz4_encode_hc_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64
 {
     if (nStreams < 0 || nBlocks < 0 || (nStreams > 0 && (!src || !srcOff || !srcLen || !blockSize || !dst || !dstOff || !outLen)))
         return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    int64_t nb = 0;
-    int rc = hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, nullptr);    /* (host arithmetic: before the context) */
-    if (rc != K4LZ4_OK) return rc;
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: outLen has fewer entries than the streams have blocks");
-    if (nb == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    /* the contents packed on the device, the slots of every stream's blocks behind each other */
-    std::vector<uint64_t> d_soff((size_t)nStreams), d_doff((size_t)nStreams);
-    uint64_t stotal = 0, dtotal = 0;
-    for (int64_t si = 0; si < nStreams; si++) {
-        const int64_t B = hc_chain_block_size(blockSize[si]);
-        d_soff[(size_t)si] = stotal; stotal += ((uint64_t)srcLen[si] + 15u) & ~(uint64_t)15u;
-        const uint64_t fresh = (uint64_t)(srcLen[si] - (dictLen ? dictLen[si] : 0));       /* (validated by hc_chain_table) */
-        d_doff[(size_t)si] = dtotal; dtotal += ((fresh + (uint64_t)B - 1u) / (uint64_t)B) * (uint64_t)(B + B / 255 + 16);
-    }
-    if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, (size_t)stotal + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)dtotal + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, (size_t)nb * 4 + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)dtotal + 64, true)) != K4LZ4_OK) return rc;
-    hipStream_t st = ctx->stream;
-    for (int64_t si = 0; si < nStreams; si++)
-        if (srcLen[si] > 0) K4_HIP(ctx, hipMemcpyAsync(ctx->d_src + d_soff[(size_t)si], src + srcOff[si], (size_t)srcLen[si], hipMemcpyHostToDevice, st));
-    int32_t *d_out = (int32_t *)ctx->d_meta;
-    rc = hc_chain_run(ctx, ctx->d_src, d_soff.data(), srcLen, blockSize, extraBlocks, dictLen, nStreams, ctx->d_dst, d_doff.data(), d_out, nb, level,
-                      flags, st);
-    if (rc == K4LZ4_OK) rc = hipMemcpyAsync(outLen, d_out, (size_t)nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "outLen download");
-    if (rc == K4LZ4_OK) rc = hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)dtotal, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "output download");
-    const hipError_t e = hipStreamSynchronize(st);
-    if (rc != K4LZ4_OK) { (void)take_device_status(ctx); return rc; }
-    K4_HIP(ctx, e);
-    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
-    /* exactly |outLen| bytes of every slot to the caller's */
-    int64_t k = 0;
-    for (int64_t si = 0; si < nStreams; si++) {
-        const int64_t B = hc_chain_block_size(blockSize[si]), slot = B + B / 255 + 16;
-        for (int64_t j = 0; j * B < srcLen[si] - (dictLen ? dictLen[si] : 0); j++, k++) {
-            const int32_t r = outLen[k];
-            const size_t nbytes = (size_t)(r < 0 ? -(int64_t)r : r);
-            if (nbytes) memcpy(dst + dstOff[si] + (uint64_t)(j * slot), ctx->h_stage + d_doff[(size_t)si] + (uint64_t)(j * slot), nbytes);
-        }
-    }
-    return K4LZ4_OK;
+    return chain_host(ctx, "k4lz4_encode_hc_chain_batch",
+        [&](int64_t &nb) { return hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, nullptr); },
+        [&](HostStage &s, int64_t nb, int32_t *d_out, k4lz4_fast_chain_state *, k4lz4_fast_chain_state *) {
+            return hc_chain_run(ctx, ctx->d_src, s.in_off.data(), srcLen, blockSize, extraBlocks, dictLen, nStreams, ctx->d_dst, s.slot.data(),
+                                d_out, nb, level, flags, s.st);
+        },
+        src, srcOff, srcLen, blockSize, dictLen, nStreams, nullptr, nullptr, dst, dstOff, outLen, nBlocks);
 }
 
 
@@ -2457,55 +2514,13 @@ int k4lz4_encode_fast_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint
     std::vector<uint32_t> cur0, sdict;
     if (stateIn) fast_chain_indices(stateIn, nStreams, cur0, sdict);
     const uint32_t *c0 = stateIn ? cur0.data() : nullptr, *sd = stateIn ? sdict.data() : nullptr;
-    int64_t nb = 0;
-    rc = fast_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, c0, sd, nStreams, dstOff, nb, nullptr);    /* (host arithmetic: before the context) */
-    if (rc != K4LZ4_OK) return rc;
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: outLen has fewer entries than the streams have blocks");
-    if (nStreams == 0 || (nb == 0 && !stateOut)) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    /* the contents packed on the device, the slots of every stream's blocks behind each other, the states behind the slots */
-    std::vector<uint64_t> d_soff((size_t)nStreams), d_doff((size_t)nStreams);
-    uint64_t stotal = 0, dtotal = 0;
-    for (int64_t si = 0; si < nStreams; si++) {
-        const int64_t B = hc_chain_block_size(blockSize[si]);
-        d_soff[(size_t)si] = stotal; stotal += ((uint64_t)srcLen[si] + 15u) & ~(uint64_t)15u;
-        const uint64_t fresh = (uint64_t)(srcLen[si] - (dictLen ? dictLen[si] : 0));       /* (validated by fast_chain_table) */
-        d_doff[(size_t)si] = dtotal; dtotal += ((fresh + (uint64_t)B - 1u) / (uint64_t)B) * (uint64_t)(B + B / 255 + 16);
-    }
-    dtotal = (dtotal + 15u) & ~(uint64_t)15u;
-    const size_t sbytes = (size_t)nStreams * sizeof(k4lz4_fast_chain_state);
-    const size_t nstate = (stateIn ? sbytes : 0) + (stateOut ? sbytes : 0);
-    if ((rc = grow(ctx, &ctx->d_src, &ctx->d_src_cap, (size_t)stotal + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)dtotal + nstate + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->d_meta, &ctx->d_meta_cap, (size_t)nb * 4 + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)dtotal + 64, true)) != K4LZ4_OK) return rc;
-    k4lz4_fast_chain_state *d_in = stateIn ? (k4lz4_fast_chain_state *)(ctx->d_dst + dtotal) : nullptr;
-    k4lz4_fast_chain_state *d_outst = stateOut ? (k4lz4_fast_chain_state *)(ctx->d_dst + dtotal + (stateIn ? sbytes : 0)) : nullptr;
-    hipStream_t st = ctx->stream;
-    for (int64_t si = 0; si < nStreams; si++)
-        if (srcLen[si] > 0) K4_HIP(ctx, hipMemcpyAsync(ctx->d_src + d_soff[(size_t)si], src + srcOff[si], (size_t)srcLen[si], hipMemcpyHostToDevice, st));
-    if (stateIn) K4_HIP(ctx, hipMemcpyAsync(d_in, stateIn, sbytes, hipMemcpyHostToDevice, st));
-    int32_t *d_out = (int32_t *)ctx->d_meta;
-    rc = fast_chain_run(ctx, ctx->d_src, d_soff.data(), srcLen, blockSize, extraBlocks, dictLen, c0, sd, nStreams, d_in, d_outst, ctx->d_dst,
-                        d_doff.data(), d_out, nb, flags, st);
-    if (rc == K4LZ4_OK && nb) rc = hipMemcpyAsync(outLen, d_out, (size_t)nb * 4, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "outLen download");
-    if (rc == K4LZ4_OK && dtotal) rc = hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)dtotal, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "output download");
-    if (rc == K4LZ4_OK && stateOut) rc = hipMemcpyAsync(stateOut, d_outst, sbytes, hipMemcpyDeviceToHost, st) == hipSuccess ? K4LZ4_OK : hip_fail(ctx, hipErrorUnknown, "state download");
-    const hipError_t e = hipStreamSynchronize(st);
-    if (rc != K4LZ4_OK) return rc;
-    K4_HIP(ctx, e);
-    /* exactly |outLen| bytes of every slot to the caller's */
-    int64_t k = 0;
-    for (int64_t si = 0; si < nStreams; si++) {
-        const int64_t B = hc_chain_block_size(blockSize[si]), slot = B + B / 255 + 16;
-        for (int64_t j = 0; j * B < srcLen[si] - (dictLen ? dictLen[si] : 0); j++, k++) {
-            const int32_t r = outLen[k];
-            const size_t nbytes = (size_t)(r < 0 ? -(int64_t)r : r);
-            if (nbytes) memcpy(dst + dstOff[si] + (uint64_t)(j * slot), ctx->h_stage + d_doff[(size_t)si] + (uint64_t)(j * slot), nbytes);
-        }
-    }
-    return K4LZ4_OK;
+    return chain_host(ctx, "k4lz4_encode_fast_chain_batch",
+        [&](int64_t &nb) { return fast_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, c0, sd, nStreams, dstOff, nb, nullptr); },
+        [&](HostStage &s, int64_t nb, int32_t *d_out, k4lz4_fast_chain_state *d_in, k4lz4_fast_chain_state *d_outst) {
+            return fast_chain_run(ctx, ctx->d_src, s.in_off.data(), srcLen, blockSize, extraBlocks, dictLen, c0, sd, nStreams, d_in, d_outst,
+                                  ctx->d_dst, s.slot.data(), d_out, nb, flags, s.st);
+        },
+        src, srcOff, srcLen, blockSize, dictLen, nStreams, stateIn, stateOut, dst, dstOff, outLen, nBlocks);
 }
 
 
@@ -2518,7 +2533,7 @@ int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t 
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, st));
     k4::FrameTab t;
     unsigned long long *cnt;
     int rc;
@@ -2526,8 +2541,7 @@ int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t 
     k4::FrameWalkArgs w{src, frameOff, frameLen, n, t, nullptr, outSize, outStatus};
     hipLaunchKernelGGL(k4::k4_frame_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w);
     K4_HIP(ctx, hipGetLastError());
-    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, st);
     return K4LZ4_OK;
 }
 
@@ -2540,7 +2554,7 @@ int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, st));
     k4::FrameTab t;
     k4::BlockTab b;
     unsigned long long *cnt;
@@ -2583,66 +2597,21 @@ int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_
     hipLaunchKernelGGL(k4::k4_frame_finish_kernel, dim3(fgrid), dim3(256), 0, st, t, outLen, (long long)n,
                        h[k4::FRC_CSUM_FRAMES] ? 1 : 0);
     K4_HIP(ctx, hipGetLastError());
-    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, st);
     return K4LZ4_OK;
 }
 
 int k4lz4_frame_sizes(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
                       uint64_t *outSize, int32_t *outStatus)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t *d_off, *d_len;
-    uint8_t *m;
-    int rc;
-    if ((rc = frame_stage(ctx, src, frameOff, frameLen, n, (size_t)n * 12, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
-    uint64_t *d_size = (uint64_t *)m;
-    int32_t *d_status = (int32_t *)(d_size + n);
-    hipStream_t st = ctx->stream;
-    if ((rc = k4lz4_frame_sizes_device(ctx, ctx->d_src, d_off, d_len, n, d_size, d_status, st)) != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipMemcpyAsync(outSize, d_size, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipMemcpyAsync(outStatus, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipStreamSynchronize(st));
-    return take_device_status(ctx);
+    return host_sizes(k4lz4_frame_sizes_device, ctx, src, frameOff, frameLen, n, outSize, outStatus);
 }
 
 int k4lz4_decode_frames(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
                         uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !dst || !dstOff || !dstCap || !outLen)))
-        return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> h_doff((size_t)n);
-    uint64_t dtotal = 0;
-    for (int64_t i = 0; i < n; i++) {
-        h_doff[(size_t)i] = dtotal;
-        dtotal += (dstCap[i] + 15u) & ~(uint64_t)15u;
-    }
-    uint64_t *d_off, *d_len;
-    uint8_t *m;
-    int rc;
-    if ((rc = frame_stage(ctx, src, frameOff, frameLen, n, (size_t)n * 24, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
-    uint64_t *d_doff = (uint64_t *)m, *d_dcap = d_doff + n;
-    int64_t *d_out = (int64_t *)(d_dcap + n);
-    if ((rc = grow(ctx, &ctx->d_dst, &ctx->d_dst_cap, (size_t)dtotal + 64, false)) != K4LZ4_OK) return rc;
-    if ((rc = grow(ctx, &ctx->h_stage, &ctx->h_stage_cap, (size_t)dtotal + 64, true)) != K4LZ4_OK) return rc;
-    hipStream_t st = ctx->stream;
-    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_dcap, dstCap, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemsetAsync(ctx->d_dst, 0, (size_t)dtotal, st));      /* (as k4lz4_decode_chain_batch: no earlier call's bytes) */
-    if ((rc = k4lz4_decode_frames_device(ctx, ctx->d_src, d_off, d_len, n, ctx->d_dst, d_doff, d_dcap, d_out, st)) != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    if (dtotal) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)dtotal, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipStreamSynchronize(st));
-    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
-    for (int64_t i = 0; i < n; i++)
-        if (outLen[i] > 0 && (uint64_t)outLen[i] <= dstCap[i]) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
-    return K4LZ4_OK;
+    return host_streams(k4lz4_decode_frames_device, ctx, src, frameOff, frameLen, n, dst, dstOff, dstCap, outLen, /* zero */ true,
+                        /* capped */ true);
 }
 
 /* ---- legacy formats: LZ4Wrapper, LZ4Stream (k4lz4_legacy.hpp) ------------------------------------------ */
@@ -2693,9 +2662,9 @@ int k4lz4_unwrap_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, st));
     int rc;
-    if ((rc = lg_grow(ctx, &ctx->d_lg, &ctx->d_lg_cap, (size_t)n * 20 + 64)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_lg, &ctx->d_lg_cap, (size_t)n * 20 + 64)) != K4LZ4_OK) return rc;
     uint64_t *d_off = (uint64_t *)ctx->d_lg;
     int32_t *d_len = (int32_t *)(d_off + n), *d_cap = d_len + n, *d_out = d_cap + n;
     k4::UnwrapArgs u{src, srcOff, srcLen, dstCap, n, outLen, d_off, d_len, d_cap};
@@ -2705,8 +2674,7 @@ int k4lz4_unwrap_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t
     if ((rc = launch(ctx, KIND_DECODE, src, d_off, d_len, dst, dstOff, d_cap, d_out, n, 0, 0, st)) != K4LZ4_OK) return rc;
     hipLaunchKernelGGL(k4::k4_unwrap_finish_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, src, srcOff, dst, dstOff, u, d_out, decoded);
     K4_HIP(ctx, hipGetLastError());
-    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, st);
     return K4LZ4_OK;
 }
 
@@ -2718,34 +2686,21 @@ int k4lz4_unwrap_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOf
         return fail(ctx, K4LZ4_E_ARG, "bad argument");
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> len64((size_t)n), cap64((size_t)n), h_doff;
-    for (int64_t i = 0; i < n; i++) {
-        len64[(size_t)i] = srcLen[i] > 0 ? (uint64_t)srcLen[i] : 0;
-        cap64[(size_t)i] = dstCap[i] > 0 ? (uint64_t)dstCap[i] : 0;
-    }
-    uint64_t *d_off, *d_len, total;
-    uint8_t *m;
-    int rc;
-    if ((rc = frame_stage(ctx, src, srcOff, len64.data(), n, (size_t)n * 24, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
-    if ((rc = lg_out_stage(ctx, n, cap64.data(), h_doff, &total)) != K4LZ4_OK) return rc;
-    uint64_t *d_doff = (uint64_t *)m;
-    int32_t *d_slen = (int32_t *)(d_doff + n), *d_cap = d_slen + n, *d_out = d_cap + n, *d_dec = d_out + n;
-    hipStream_t st = ctx->stream;
     std::vector<int32_t> slen((size_t)n);
-    for (int64_t i = 0; i < n; i++) slen[(size_t)i] = (int32_t)len64[(size_t)i];
-    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_slen, slen.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_cap, dstCap, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (total) K4_HIP(ctx, hipMemsetAsync(ctx->d_dst, 0, (size_t)total, st));      /* (as k4lz4_decode_frames) */
-    if ((rc = k4lz4_unwrap_batch_device(ctx, ctx->d_src, d_off, d_slen, ctx->d_dst, d_doff, d_cap, d_out, d_dec, n, st)) != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipMemcpyAsync(decoded, d_dec, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (total) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)total, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipStreamSynchronize(st));
-    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
-    for (int64_t i = 0; i < n; i++)
-        if (outLen[i] > 0) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
-    return K4LZ4_OK;
+    for (int64_t i = 0; i < n; i++) slen[(size_t)i] = std::max(srcLen[i], 0);
+    HostStage s(ctx);
+    s.span(src, srcOff, n, [&](int64_t i) { return (uint64_t)slen[(size_t)i]; });
+    s.slots(n, [&](int64_t i) { return (uint64_t)std::max(dstCap[i], 0); }, true);
+    uint64_t *d_off, *d_doff;
+    int32_t *d_slen, *d_cap, *d_out, *d_dec;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_slen, n, slen.data()); s.meta(&d_cap, n, dstCap);
+    s.meta(&d_out, n); s.meta(&d_dec, n);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_unwrap_batch_device(ctx, ctx->d_src, d_off, d_slen, ctx->d_dst, d_doff, d_cap, d_out, d_dec, n, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 4}, {decoded, d_dec, (size_t)n * 4}}, dst, dstOff,
+                    [&](int64_t i) { return outLen[i] > 0 ? (size_t)outLen[i] : 0; });
 }
 
 int64_t k4lz4_legacy_stream_bound(int64_t srcLen, int blockSize)
@@ -2764,7 +2719,7 @@ int k4lz4_encode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, st));
     unsigned long long *cnt;
     uint64_t *w[4];
     int32_t *w32;
@@ -2785,8 +2740,8 @@ int k4lz4_encode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const
     K4_HIP(ctx, hipStreamSynchronize(st));
     const int64_t rows = (int64_t)h[0];
     if (h[0] > 0xffffffffull) return fail(ctx, K4LZ4_E_ARG, "more than 2^32 chunks in one call");
-    if ((rc = lg_grow(ctx, &ctx->d_lgr, &ctx->d_lgr_cap, (size_t)std::max<int64_t>(rows, 1) * LG_ROW_BYTES + 64)) != K4LZ4_OK) return rc;
-    if ((rc = lg_grow(ctx, &ctx->d_lga, &ctx->d_lga_cap, (size_t)h[1] + 64)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_lgr, &ctx->d_lgr_cap, (size_t)std::max<int64_t>(rows, 1) * LG_ROW_BYTES + 64)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_lga, &ctx->d_lga_cap, (size_t)h[1] + 64)) != K4LZ4_OK) return rc;
     {
         uint8_t *m = ctx->d_lgr;
         const size_t w8 = (size_t)std::max<int64_t>(rows, 1) * 8, w4 = w8 / 2;
@@ -2816,8 +2771,7 @@ int k4lz4_encode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const
     }
     hipLaunchKernelGGL(k4::k4_lw_finish_kernel, dim3(sgrid), dim3(256), 0, st, a, dstCap, outLen);
     K4_HIP(ctx, hipGetLastError());
-    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, st);
     return K4LZ4_OK;
 }
 
@@ -2825,31 +2779,11 @@ int k4lz4_encode_legacy_streams(k4lz4_ctx *ctx, const uint8_t *src, const uint64
                                 int blockSize, int high, int flags, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
                                 int64_t *outLen)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!src || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> h_doff;
-    uint64_t *d_off, *d_len, total;
-    uint8_t *m;
-    int rc;
-    if ((rc = frame_stage(ctx, src, srcOff, srcLen, n, (size_t)n * 24, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
-    if ((rc = lg_out_stage(ctx, n, dstCap, h_doff, &total)) != K4LZ4_OK) return rc;
-    uint64_t *d_doff = (uint64_t *)m, *d_dcap = d_doff + n;
-    int64_t *d_out = (int64_t *)(d_dcap + n);
-    hipStream_t st = ctx->stream;
-    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_dcap, dstCap, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    if ((rc = k4lz4_encode_legacy_streams_device(ctx, ctx->d_src, d_off, d_len, n, blockSize, high, flags, ctx->d_dst, d_doff, d_dcap,
-                                                 d_out, st)) != K4LZ4_OK)
-        return rc;
-    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    if (total) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)total, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipStreamSynchronize(st));
-    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
-    for (int64_t i = 0; i < n; i++)
-        if (outLen[i] > 0) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
-    return K4LZ4_OK;
+    auto device = [=](k4lz4_ctx *c, const uint8_t *s, const uint64_t *off, const uint64_t *len, int64_t m, uint8_t *d,
+                      const uint64_t *dOff, const uint64_t *dCap, int64_t *out, void *st) {
+        return k4lz4_encode_legacy_streams_device(c, s, off, len, m, blockSize, high, flags, d, dOff, dCap, out, st);
+    };
+    return host_streams(device, ctx, src, srcOff, srcLen, n, dst, dstOff, dstCap, outLen, /* zero */ false, /* capped */ false);
 }
 
 int k4lz4_legacy_stream_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen, int64_t n,
@@ -2860,7 +2794,7 @@ int k4lz4_legacy_stream_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const u
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, st));
     unsigned long long *cnt;
     uint64_t *w[4];
     int32_t *w32;
@@ -2869,8 +2803,7 @@ int k4lz4_legacy_stream_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const u
     k4::LegacyReadArgs a{src, streamOff, streamLen, n, w[0], w[1], w32, w[2], (unsigned long long *)w[3], outSize, outStatus};
     hipLaunchKernelGGL(k4::k4_lr_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     K4_HIP(ctx, hipGetLastError());
-    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, st);
     return K4LZ4_OK;
 }
 
@@ -2883,7 +2816,7 @@ int k4lz4_decode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    if (ctx->busy && ctx->last_stream != st) K4_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_busy, 0));
+    K4_HIP(ctx, order_after_ctx(ctx, st));
     unsigned long long *cnt;
     uint64_t *w[4];
     int32_t *w32;
@@ -2901,7 +2834,7 @@ int k4lz4_decode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const
     K4_HIP(ctx, hipStreamSynchronize(st));
     const int64_t rows = (int64_t)h;
     if (h > 0xffffffffull) return fail(ctx, K4LZ4_E_ARG, "more than 2^32 chunks in one call");
-    if ((rc = lg_grow(ctx, &ctx->d_lgr, &ctx->d_lgr_cap, (size_t)std::max<int64_t>(rows, 1) * LG_ROW_BYTES + 64)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_lgr, &ctx->d_lgr_cap, (size_t)std::max<int64_t>(rows, 1) * LG_ROW_BYTES + 64)) != K4LZ4_OK) return rc;
     k4::LegacyRows rw;
     {
         uint8_t *m = ctx->d_lgr;
@@ -2925,60 +2858,21 @@ int k4lz4_decode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *src, const
     }
     hipLaunchKernelGGL(k4::k4_lr_finish_kernel, dim3(sgrid), dim3(256), 0, st, a, outLen);
     K4_HIP(ctx, hipGetLastError());
-    if (hipEventRecord(ctx->ev_busy, st) == hipSuccess) { ctx->busy = true; ctx->last_stream = st; }
-    else (void)hipGetLastError();
+    mark_busy(ctx, st);
     return K4LZ4_OK;
 }
 
 int k4lz4_legacy_stream_sizes(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen, int64_t n,
                               uint64_t *outSize, int32_t *outStatus)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!src || !streamOff || !streamLen || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t *d_off, *d_len;
-    uint8_t *m;
-    int rc;
-    if ((rc = frame_stage(ctx, src, streamOff, streamLen, n, (size_t)n * 12, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
-    uint64_t *d_size = (uint64_t *)m;
-    int32_t *d_status = (int32_t *)(d_size + n);
-    hipStream_t st = ctx->stream;
-    if ((rc = k4lz4_legacy_stream_sizes_device(ctx, ctx->d_src, d_off, d_len, n, d_size, d_status, st)) != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipMemcpyAsync(outSize, d_size, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipMemcpyAsync(outStatus, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipStreamSynchronize(st));
-    return take_device_status(ctx);
+    return host_sizes(k4lz4_legacy_stream_sizes_device, ctx, src, streamOff, streamLen, n, outSize, outStatus);
 }
 
 int k4lz4_decode_legacy_streams(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *streamOff, const uint64_t *streamLen, int64_t n,
                                 uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!src || !streamOff || !streamLen || !dst || !dstOff || !dstCap || !outLen)))
-        return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> h_doff;
-    uint64_t *d_off, *d_len, total;
-    uint8_t *m;
-    int rc;
-    if ((rc = frame_stage(ctx, src, streamOff, streamLen, n, (size_t)n * 24, &d_off, &d_len, &m)) != K4LZ4_OK) return rc;
-    if ((rc = lg_out_stage(ctx, n, dstCap, h_doff, &total)) != K4LZ4_OK) return rc;
-    uint64_t *d_doff = (uint64_t *)m, *d_dcap = d_doff + n;
-    int64_t *d_out = (int64_t *)(d_dcap + n);
-    hipStream_t st = ctx->stream;
-    K4_HIP(ctx, hipMemcpyAsync(d_doff, h_doff.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipMemcpyAsync(d_dcap, dstCap, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    if (total) K4_HIP(ctx, hipMemsetAsync(ctx->d_dst, 0, (size_t)total, st));
-    if ((rc = k4lz4_decode_legacy_streams_device(ctx, ctx->d_src, d_off, d_len, n, ctx->d_dst, d_doff, d_dcap, d_out, st)) != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipMemcpyAsync(outLen, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    if (total) K4_HIP(ctx, hipMemcpyAsync(ctx->h_stage, ctx->d_dst, (size_t)total, hipMemcpyDeviceToHost, st));
-    K4_HIP(ctx, hipStreamSynchronize(st));
-    if ((rc = take_device_status(ctx)) != K4LZ4_OK) return rc;
-    for (int64_t i = 0; i < n; i++)
-        if (outLen[i] > 0) memcpy(dst + dstOff[i], ctx->h_stage + h_doff[(size_t)i], (size_t)outLen[i]);
-    return K4LZ4_OK;
+    return host_streams(k4lz4_decode_legacy_streams_device, ctx, src, streamOff, streamLen, n, dst, dstOff, dstCap, outLen,
+                        /* zero */ true, /* capped */ false);
 }
 
 }  // extern "C"
