@@ -139,6 +139,36 @@ namespace K4os.Compression.LZ4.Engine
 			IntPtr ctx, IntPtr src, ulong* srcOff, long* srcLen, int* blockSize, int* extraBlocks, int* dictLen, long nStreams,
 			IntPtr stateIn, IntPtr stateOut, IntPtr dst, ulong* dstOff, IntPtr outLen, long nBlocks, int flags, IntPtr stream);
 
+		// incremental frame writer (DESIGN.md 4.13): many LZ4FrameWriters, one Write / OpenFrame / CloseFrame each per call; the records
+		// in host memory, the stores (rings, XXH32 states, fast-chain states) in device memory
+		[StructLayout(LayoutKind.Sequential)]
+		public struct k4lz4_frame_writer_settings
+		{
+			public long contentLength;            // < 0: no content size in the header
+			public int blockSize, level, chainBlocks, blockChecksum, contentChecksum, extraMemory;
+		}
+		[StructLayout(LayoutKind.Sequential)]
+		public struct k4lz4_frame_writer
+		{
+			public k4lz4_frame_writer_settings settings;
+			public int kind, encBlock, extraBlocks, ringBytes;
+			public long written;
+			public int index, pointer;
+			public uint currentOffset, dictSize;
+			public int phase, reserved;
+		}
+		public const int FWRITE_OP_WRITE = 0, FWRITE_OP_OPEN = 1, FWRITE_OP_CLOSE = 2;
+		public const int FWRITE_TARGET = -1, FWRITE_CLOSED = -2, FWRITE_LENGTH = -3;
+		[DllImport(Lib)] public static extern int k4lz4_frame_writer_init(k4lz4_frame_writer* w, k4lz4_frame_writer_settings* settings);
+		[DllImport(Lib)] public static extern long k4lz4_frame_writer_store_bytes(k4lz4_frame_writer* w);
+		[DllImport(Lib)] public static extern long k4lz4_frame_write_bound(k4lz4_frame_writer* w, long srcLen, int closing);
+		[DllImport(Lib)] public static extern int k4lz4_frame_write_batch(
+			IntPtr ctx, k4lz4_frame_writer* w, IntPtr store, ulong* storeOff, byte* src, ulong* srcOff, long* srcLen, byte* dst, ulong* dstOff,
+			ulong* dstCap, long* outLen, long n, int op, int flags);
+		[DllImport(Lib)] public static extern int k4lz4_frame_write_batch_device(
+			IntPtr ctx, k4lz4_frame_writer* w, IntPtr store, ulong* storeOff, IntPtr src, ulong* srcOff, long* srcLen, IntPtr dst, ulong* dstOff,
+			ulong* dstCap, IntPtr outLen, long n, int op, int flags, IntPtr stream);
+
 		// ---- device-resident variants: every pointer is a device pointer of the context's GPU, stream = hipStream_t
 		[DllImport(Lib)] public static extern int k4lz4_encode_batch_device(
 			IntPtr ctx, IntPtr src, IntPtr srcOff, IntPtr srcLen, IntPtr dst, IntPtr dstOff, IntPtr dstCap, IntPtr outLen, long n, int level, int flags, IntPtr stream);

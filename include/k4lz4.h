@@ -444,6 +444,71 @@ K4LZ4_API int k4lz4_decode_legacy_streams_device(k4lz4_ctx *ctx, const uint8_t *
                                                  int64_t n, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen,
                                                  void *stream);
 
+/* ---- incremental frame writer: many LZ4FrameWriters (Frames/LZ4FrameWriter*.cs, Streams/LZ4EncoderStream.cs:44-66) advanced by one
+ * Write, OpenFrame or CloseFrame each per call.  For every stream a call returns exactly the bytes the reference's
+ * writer pushes to its inner stream during that call: the header at the first Write (even an empty one) or at an explicit open,
+ * a block record for every block that fills up (TopupAndEncode(forceEncode: false, allowCopy: true)), and at close the last partial
+ * block, the EndMark and the content checksum.  Block and content checksums and ContentLength follow LZ4Frame.EncodeBatch (the
+ * content size is written when asked for; a close whose byte count differs is refused).  Levels: every LZ4Level for independent
+ * and chained-HC frames; chained frames below L03_HC take LZ4FastChainEncoder's blocks (not under K4LZ4_FLAG_X32 / Enforce32:
+ * K4LZ4_E_ARG).  Chained streams longer than 2 GB - 64 KiB are refused with K4LZ4_E_ARG.
+ *
+ * k4lz4_frame_writer is the per-stream record, in HOST memory, owned by the caller: the settings and the counters.  The counters depend
+ * on lengths only, so a call updates them without waiting for the device.  The bytes a stream holds between calls (the encoder's
+ * ring buffer: the saved dictionary and the pending bytes), its XXH32 state and, for chained fast streams, its
+ * k4lz4_fast_chain_state live in a DEVICE store of k4lz4_frame_writer_store_bytes(w) bytes at store + storeOff[s], also the caller's;
+ * it needs no initialisation. */
+typedef struct k4lz4_frame_writer_settings {
+    int64_t contentLength;       /* < 0: no content size in the header */
+    int32_t blockSize;           /* the descriptor's BlockSize, 1 .. 4 MiB (LZ4FrameWriter.cs:184-189) */
+    int32_t level;               /* k4lz4_level */
+    int32_t chainBlocks, blockChecksum, contentChecksum;
+    int32_t extraMemory;         /* LZ4EncoderSettings.ExtraMemory (Streams/Extensions.cs:18-19) */
+} k4lz4_frame_writer_settings;
+
+typedef struct k4lz4_frame_writer {
+    k4lz4_frame_writer_settings settings;
+    int32_t kind;                /* 0 independent blocks, 1 chained HC, 2 chained fast */
+    int32_t encBlock;            /* the encoder's block: BlockSize, or for chained frames the ring's whole-KiB block */
+    int32_t extraBlocks;
+    int32_t ringBytes;           /* the ring buffer: 64 KiB + (1 + extraBlocks) * encBlock + 32, or encBlock for independent blocks */
+    int64_t written;             /* content bytes taken so far */
+    int32_t index, pointer;      /* the ring: its encoded prefix (the dictionary) and the bytes it holds */
+    uint32_t currentOffset, dictSize; /* chained fast: LZ4_stream_t's two indices */
+    int32_t phase;               /* 0 not opened, 1 open, 2 closed */
+    int32_t reserved;
+} k4lz4_frame_writer;
+
+enum k4lz4_frame_write_op { K4LZ4_FWRITE_WRITE = 0, K4LZ4_FWRITE_OPEN = 1, K4LZ4_FWRITE_CLOSE = 2 };
+
+/* per-stream codes in outLen (decided on the host before anything is enqueued; such a stream keeps its record and store unchanged) */
+#define K4LZ4_FWRITE_TARGET        (-1)   /* dstCap[s] is below k4lz4_frame_write_bound */
+#define K4LZ4_FWRITE_CLOSED        (-2)   /* the stream was closed by an earlier call */
+#define K4LZ4_FWRITE_LENGTH        (-3)   /* close: the bytes written differ from the settings' contentLength */
+
+/* K4LZ4_OK or K4LZ4_E_ARG (a block size outside 1 .. 4 MiB) */
+K4LZ4_API int k4lz4_frame_writer_init(k4lz4_frame_writer *w, const k4lz4_frame_writer_settings *settings);
+K4LZ4_API int64_t k4lz4_frame_writer_store_bytes(const k4lz4_frame_writer *w);
+/* the most a call can emit for the stream: srcLen new bytes, closing (CLOSE) or not */
+K4LZ4_API int64_t k4lz4_frame_write_bound(const k4lz4_frame_writer *w, int64_t srcLen, int closing);
+/* op: k4lz4_frame_write_op for every stream; srcLen[s] < 0 leaves stream s untouched (outLen 0).  WRITE: srcLen[s] bytes at
+ * src + srcOff[s]; OPEN: srcLen[s] must be 0; CLOSE: srcLen[s] bytes are written first, then the frame is closed.  flags:
+ * K4LZ4_FLAG_X32 (LZ4Codec.Enforce32 is read as well).  outLen[s]: the bytes written at dst + dstOff[s], or a K4LZ4_FWRITE_* code.
+ * A call-level failure (K4LZ4_E_ARG is decided before anything is enqueued) leaves every record as it was; after K4LZ4_E_HIP or
+ * K4LZ4_E_NOMEM the stores of the streams the call ran are undefined and those streams cannot be continued.
+ * _device: src, store, dst and outLen (int64_t) are device pointers, the other arrays host arrays.  It enqueues this call's work on `stream`
+ * and returns without waiting for it.  Before it rewrites its host-side plan it waits until the previous writer call's plan has been
+ * copied up (the context's own event), and each chained group waits the same way for the previous chained block table, as
+ * k4lz4_encode_hc_chain_batch_device does: a call whose batch holds two or more chained groups (two HC levels, HC and fast, with and
+ * without block checksums) therefore waits, part-way, until the device has reached the previous group's table upload. */
+K4LZ4_API int k4lz4_frame_write_batch(k4lz4_ctx *ctx, k4lz4_frame_writer *w, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                                      const uint64_t *srcOff, const int64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                                      int64_t *outLen, int64_t n, int op, int flags);
+K4LZ4_API int k4lz4_frame_write_batch_device(k4lz4_ctx *ctx, k4lz4_frame_writer *w, uint8_t *store, const uint64_t *storeOff,
+                                             const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen, uint8_t *dst,
+                                             const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, int64_t n, int op, int flags,
+                                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@ FLAG_SEGMENTS = 256
 
 _u8p = C.c_void_p
 _BATCH = [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+# k4lz4_frame_write_batch*: ctx, w, store, storeOff, src, srcOff, srcLen, dst, dstOff, dstCap, outLen
+_FWRITE = [C.c_void_p, C.c_void_p, _u8p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]
 _LEGACY_ENC = [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 # every symbol include/k4lz4.h declares: name -> (restype, argtypes)
@@ -99,6 +101,11 @@ SYMBOLS = {
     "k4lz4_decode_legacy_streams": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "k4lz4_decode_legacy_streams_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]),
+    "k4lz4_frame_writer_init": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "k4lz4_frame_writer_store_bytes": (C.c_int64, [C.c_void_p]),
+    "k4lz4_frame_write_bound": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int]),
+    "k4lz4_frame_write_batch": (C.c_int, _FWRITE + [C.c_int64, C.c_int, C.c_int]),
+    "k4lz4_frame_write_batch_device": (C.c_int, _FWRITE + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
 }
 
 

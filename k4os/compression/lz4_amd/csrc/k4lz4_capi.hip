@@ -37,6 +37,7 @@
 #include "k4lz4_frame.hpp"
 #include "k4lz4_frame_read.hpp"
 #include "k4lz4_legacy.hpp"
+#include "k4lz4_frame_write.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 
@@ -142,6 +143,11 @@ struct k4lz4_ctx {
     uint8_t *d_lg = nullptr; size_t d_lg_cap = 0;
     uint8_t *d_lgr = nullptr; size_t d_lgr_cap = 0;
     uint8_t *d_lga = nullptr; size_t d_lga_cap = 0;
+    /* incremental frame writer (k4lz4_frame_write.hpp): the call's plan, built on the host (rewritten only after ev_fw says the
+     * previous upload is over), and the device scratch it is laid out in with the windows, the arena and the fast-chain states */
+    std::vector<uint8_t> h_fw;
+    uint8_t *d_fw = nullptr; size_t d_fw_cap = 0;
+    hipEvent_t ev_fw = nullptr;
 };
 
 /* a few helper threads for the staging copies of big host-pointer calls (memcpy between the caller's pageable memory and
@@ -1922,6 +1928,13 @@ int host_streams(Device device, k4lz4_ctx *ctx, const uint8_t *src, const uint64
     });
 }
 
+/* ---- incremental frame writer: the host half of k4lz4_frame_write.hpp (the store's layout, the header, the ring model, the bound) */
+using k4::FW_XXH_BYTES; using k4::FW_CHAIN_LIMIT; using k4::FwAfter;
+using k4::fw_ring_at; using k4::fw_slot; using k4::fw_header; using k4::fw_opens; using k4::fw_model; using k4::fw_bound; using k4::fw_code;
+using k4::fw_advance;
+
+size_t fw_take(size_t &at, size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
+
 }  // namespace
 
 extern "C" {
@@ -2078,6 +2091,8 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_hc_work) (void)hipFree(ctx->d_hc_work);
     if (ctx->d_hc_meta) (void)hipFree(ctx->d_hc_meta);
     if (ctx->d_chain) (void)hipFree(ctx->d_chain);
+    if (ctx->d_fw) (void)hipFree(ctx->d_fw);
+    if (ctx->ev_fw) (void)hipEventDestroy(ctx->ev_fw);
     if (ctx->ev_chain) (void)hipEventDestroy(ctx->ev_chain);
     if (ctx->d_pk_meta) (void)hipFree(ctx->d_pk_meta);
     delete ctx;
@@ -2873,6 +2888,310 @@ int k4lz4_decode_legacy_streams(k4lz4_ctx *ctx, const uint8_t *src, const uint64
 {
     return host_streams(k4lz4_decode_legacy_streams_device, ctx, src, streamOff, streamLen, n, dst, dstOff, dstCap, outLen,
                         /* zero */ true, /* capped */ false);
+}
+
+/* ---- incremental frame writer (k4lz4_frame_write.hpp) ------------------------------------------------------- */
+int k4lz4_frame_writer_init(k4lz4_frame_writer *w, const k4lz4_frame_writer_settings *settings)
+{
+    if (!w || !settings) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_frame_writer_init: NULL argument");
+    const k4lz4_frame_writer_settings &s = *settings;
+    if (s.blockSize <= 0 || s.blockSize > (4 << 20)) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_frame_writer_init: block size outside 1 .. 4 MiB");
+    memset(w, 0, sizeof *w);
+    w->settings = s;
+    w->settings.chainBlocks = s.chainBlocks ? 1 : 0; w->settings.blockChecksum = s.blockChecksum ? 1 : 0;
+    w->settings.contentChecksum = s.contentChecksum ? 1 : 0;
+    if (w->settings.contentLength < 0) w->settings.contentLength = -1;
+    const int64_t bs = s.blockSize;
+    w->kind = !s.chainBlocks ? 0 : s.level >= K4LZ4_L03_HC ? 1 : 2;
+    w->extraBlocks = (int32_t)(std::max<int64_t>(s.extraMemory > 0 ? bs : 0, s.extraMemory) / bs);     /* Streams/Extensions.cs:18-19 */
+    w->encBlock = w->kind == 0 ? (int32_t)bs : (int32_t)hc_chain_block_size(s.blockSize);
+    w->ringBytes = w->kind == 0 ? w->encBlock : (int32_t)(65536 + (1 + (int64_t)w->extraBlocks) * w->encBlock + 32);   /* LZ4EncoderBase.cs:25 */
+    return K4LZ4_OK;
+}
+
+int64_t k4lz4_frame_writer_store_bytes(const k4lz4_frame_writer *w)
+{
+    return w ? (fw_ring_at(*w) + w->ringBytes + 8 + 63) / 64 * 64 : 0;
+}
+
+int64_t k4lz4_frame_write_bound(const k4lz4_frame_writer *w, int64_t srcLen, int closing)
+{
+    return w ? fw_bound(*w, srcLen, closing != 0) : 0;
+}
+
+int k4lz4_frame_write_batch_device(k4lz4_ctx *ctx, k4lz4_frame_writer *w, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                                   const uint64_t *srcOff, const int64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                                   int64_t *outLen, int64_t n, int op, int flags, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!w || !store || !storeOff || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (op < K4LZ4_FWRITE_WRITE || op > K4LZ4_FWRITE_CLOSE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_write_batch: unknown op");
+    if (flags & ~(int)K4LZ4_FLAG_X32) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_write_batch: the only flag it takes is K4LZ4_FLAG_X32");
+    if (n == 0) return K4LZ4_OK;
+    const bool x32 = (flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed);
+    const bool closing = op == K4LZ4_FWRITE_CLOSE;
+    hipStream_t st = (hipStream_t)stream;
+
+    /* ---- the plan: per-stream codes, the model's blocks, the groups -- host index arithmetic, nothing enqueued yet */
+    std::vector<int32_t> code((size_t)n, 1);
+    std::vector<FwAfter> after((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const k4lz4_frame_writer &r = w[i];
+        const int64_t len = srcLen[i];
+        if (len < 0) continue;
+        if (op == K4LZ4_FWRITE_OPEN && len != 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_write_batch: an open takes no bytes");
+        if (r.kind == 2 && x32)
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_write_batch: the 32-bit engine's chained encoder (LZ4Codec.Enforce32) is not supported");
+        if ((code[(size_t)i] = fw_code(r, len, closing, dstCap[i])) != 0) continue;
+        if (r.kind == 1 && r.written + len > FW_CHAIN_LIMIT)
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_write_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
+        after[(size_t)i] = fw_model(r, len, closing, [](int64_t, int64_t) {});
+        if (after[(size_t)i].too_long)
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_write_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
+        code[(size_t)i] = 0;
+    }
+    /* groups of streams whose blocks go to one encoder call: (block checksum, kind, level), those without checksums first */
+    auto key = [&](int64_t i) { const k4lz4_frame_writer &r = w[i]; return r.settings.blockChecksum * 1000 + r.kind * 100 + (r.kind == 2 ? 0 : r.settings.level); };
+    std::vector<int> keys;
+    for (int64_t i = 0; i < n; i++) if (code[(size_t)i] == 0 && after[(size_t)i].nblk) keys.push_back(key(i));
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    struct Group { int key; std::vector<int64_t> streams; int64_t first = 0, nb = 0; };
+    std::vector<Group> groups(keys.size());
+    for (size_t g = 0; g < keys.size(); g++) groups[g].key = keys[g];
+    for (int64_t i = 0; i < n; i++)
+        if (code[(size_t)i] == 0 && after[(size_t)i].nblk)
+            groups[(size_t)(std::lower_bound(keys.begin(), keys.end(), key(i)) - keys.begin())].streams.push_back(i);
+    int64_t nb = 0, firstSum = -1, nind = 0, nfast = 0, nhash = 0, nstage = 0, nback = 0;
+    for (Group &g : groups) {
+        g.first = nb;
+        for (int64_t i : g.streams) g.nb += after[(size_t)i].nblk;
+        nb += g.nb;
+        if (g.key >= 1000 && firstSum < 0) firstSum = g.first;
+        if (g.key % 1000 < 100) nind += g.nb;
+        if (g.key % 1000 / 100 == 2) nfast += (int64_t)g.streams.size();
+    }
+    if (firstSum < 0) firstSum = nb;
+    if (nb > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_write_batch: more than 2^32 blocks in one call");
+    for (int64_t i = 0; i < n; i++) {
+        if (code[(size_t)i] != 0) continue;
+        const k4lz4_frame_writer &r = w[i];
+        if (r.settings.contentChecksum && (srcLen[i] > 0 || fw_opens(r, srcLen[i], closing))) nhash++;
+        if (after[(size_t)i].nblk) { nstage += 2; nback += 1; }
+        else if (srcLen[i] > 0) nstage += 1;
+    }
+    nstage += nfast; nback += nfast;
+
+    /* ---- scratch layout: the uploaded plan first, then what the kernels fill, then windows, arena and states */
+    size_t at = 0;
+    const size_t o_streams = fw_take(at, (size_t)n * sizeof(k4::FwStream)), o_hash = fw_take(at, (size_t)nhash * sizeof(k4::FwHashItem)),
+                 o_stage = fw_take(at, (size_t)nstage * sizeof(k4::FwPiece)), o_back = fw_take(at, (size_t)nback * sizeof(k4::FwPiece)),
+                 o_owner = fw_take(at, (size_t)nb * 4), o_slot = fw_take(at, (size_t)nb * 8),
+                 o_isrc = fw_take(at, (size_t)nind * 8), o_ilen = fw_take(at, (size_t)nind * 4), o_icap = fw_take(at, (size_t)nind * 4);
+    const size_t plan_bytes = at;
+    const size_t o_out = fw_take(at, (size_t)nb * 4), o_stored = fw_take(at, (size_t)nb * 8), o_rec = fw_take(at, (size_t)nb * 8),
+                 o_excl = fw_take(at, (size_t)nb * 8), o_roff = fw_take(at, (size_t)nb * 8), o_sum = fw_take(at, (size_t)nb * 4),
+                 o_cnt = fw_take(at, 64);
+    std::vector<uint64_t> win((size_t)n, 0), aoff((size_t)n, 0);
+    for (const Group &g : groups)
+        for (int64_t i : g.streams) { win[(size_t)i] = at; fw_take(at, (size_t)(w[i].pointer + srcLen[i]) + 16); }
+    for (const Group &g : groups)
+        for (int64_t i : g.streams) { aoff[(size_t)i] = at; fw_take(at, (size_t)(after[(size_t)i].nblk * fw_slot(w[i]))); }
+    const size_t o_stin = fw_take(at, (size_t)nfast * sizeof(k4lz4_fast_chain_state)),
+                 o_stout = fw_take(at, (size_t)nfast * sizeof(k4lz4_fast_chain_state));
+    const size_t total_bytes = at + 64;
+
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->ev_fw) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fw, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fw));        /* the previous upload of the host plan is over */
+    try { ctx->h_fw.assign(plan_bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    int rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, total_bytes)) != K4LZ4_OK) return rc;
+    uint8_t *h = ctx->h_fw.data(), *d = ctx->d_fw;
+    k4::FwStream *hs = (k4::FwStream *)(h + o_streams);
+    k4::FwHashItem *hh = (k4::FwHashItem *)(h + o_hash);
+    k4::FwPiece *hstage = (k4::FwPiece *)(h + o_stage), *hback = (k4::FwPiece *)(h + o_back);
+    uint32_t *howner = (uint32_t *)(h + o_owner);
+    uint64_t *hslot = (uint64_t *)(h + o_slot), *hisrc = (uint64_t *)(h + o_isrc);
+    int32_t *hilen = (int32_t *)(h + o_ilen), *hicap = (int32_t *)(h + o_icap);
+    k4lz4_fast_chain_state *d_stin = (k4lz4_fast_chain_state *)(d + o_stin), *d_stout = (k4lz4_fast_chain_state *)(d + o_stout);
+
+    /* per stream: the table row, the hash item, the pieces; per block: owner, arena slot, the independent blocks' arrays */
+    int64_t kh = 0, ks = 0, kb = 0, kfast = 0;
+    std::vector<int64_t> first((size_t)n, 0), fast_index((size_t)n, -1);
+    for (const Group &g : groups) {
+        int64_t b = g.first, ind = 0;
+        for (const Group &g2 : groups) if (&g2 == &g) break; else if (g2.key % 1000 < 100) ind += g2.nb;
+        for (int64_t i : g.streams) {
+            first[(size_t)i] = b;
+            const int64_t slot = fw_slot(w[i]);
+            int64_t j = 0;
+            fw_model(w[i], srcLen[i], closing, [&](int64_t start, int64_t len) {
+                howner[b] = (uint32_t)i;
+                hslot[b] = aoff[(size_t)i] + (uint64_t)(j * slot);
+                if (g.key % 1000 < 100) {
+                    hisrc[ind] = win[(size_t)i] + (uint64_t)start; hilen[ind] = (int32_t)len; hicap[ind] = (int32_t)slot; ind++;
+                }
+                b++; j++;
+            });
+            if (w[i].kind == 2) fast_index[(size_t)i] = kfast++;
+        }
+    }
+    for (int64_t i = 0; i < n; i++) {
+        k4::FwStream &row = hs[i];
+        row.code = code[(size_t)i];
+        if (row.code != 0) continue;
+        const k4lz4_frame_writer &r = w[i];
+        const FwAfter &a = after[(size_t)i];
+        uint8_t *sto = store + storeOff[i];
+        const int64_t len = srcLen[i];
+        row.out = dstOff[i]; row.first = (unsigned long long)first[(size_t)i]; row.nblk = (uint32_t)a.nblk;
+        const bool opens = fw_opens(r, len, closing);
+        row.hdrLen = opens ? fw_header(r, row.hdr) : 0;
+        row.close = closing && !(r.phase == 0 && len == 0) ? (r.settings.contentChecksum ? 2u : 1u) : 0u;
+        row.xxh = (const k4::FwXxhState *)sto;
+        if (r.settings.contentChecksum && (len > 0 || opens)) {
+            hh[kh].data = src + srcOff[i]; hh[kh].len = (unsigned long long)len; hh[kh].state = (k4::FwXxhState *)sto;
+            hh[kh].fresh = opens ? 1u : 0u; kh++;
+        }
+        uint8_t *ring = sto + fw_ring_at(r);
+        if (a.nblk) {
+            uint8_t *wp = d + win[(size_t)i];
+            hstage[ks++] = k4::FwPiece{wp, ring, (unsigned long long)r.pointer, 0};
+            hstage[ks++] = k4::FwPiece{wp + r.pointer, src + srcOff[i], (unsigned long long)len, 0};
+            const int64_t r0 = a.ws == 0 ? r.pointer : 0;                 /* bytes of the ring that stay where they are */
+            hback[kb++] = k4::FwPiece{ring + r0, wp + a.ws + r0, (unsigned long long)(a.pointer - r0), 0};
+            if (r.kind == 2) {
+                const int64_t f = fast_index[(size_t)i];
+                k4lz4_fast_chain_state *sst = (k4lz4_fast_chain_state *)(sto + FW_XXH_BYTES);
+                /* a stream that has encoded nothing yet starts from a zeroed LZ4_stream_t (LZ4FastChainEncoder.cs) */
+                hstage[ks++] = k4::FwPiece{(uint8_t *)(d_stin + f), r.currentOffset ? (const uint8_t *)sst : nullptr, sizeof(k4lz4_fast_chain_state), 0};
+                hback[kb++] = k4::FwPiece{(uint8_t *)sst, (const uint8_t *)(d_stout + f), sizeof(k4lz4_fast_chain_state), 0};
+            }
+        } else if (len > 0) {
+            hstage[ks++] = k4::FwPiece{ring + r.pointer, src + srcOff[i], (unsigned long long)len, 0};
+        }
+    }
+    auto chunks = [](k4::FwPiece *p, int64_t cnt) {
+        unsigned long long c = 0;
+        for (int64_t k = 0; k < cnt; k++) { p[k].chunk0 = c; c += std::max<unsigned long long>(1, (p[k].len + k4::FW_CHUNK - 1) / k4::FW_CHUNK); }
+        return c;
+    };
+    const unsigned long long stage_chunks = chunks(hstage, ks), back_chunks = chunks(hback, kb);
+
+    /* ---- enqueue: plan up, hash, stage, encode, write back, records, edges */
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    K4_HIP(ctx, hipMemcpyAsync(d, h, plan_bytes, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
+    const k4::FwStream *d_streams = (const k4::FwStream *)(d + o_streams);
+    int32_t *d_out = (int32_t *)(d + o_out);
+    unsigned long long *d_stored = (unsigned long long *)(d + o_stored), *d_rec = (unsigned long long *)(d + o_rec),
+                       *d_excl = (unsigned long long *)(d + o_excl), *d_roff = (unsigned long long *)(d + o_roff);
+    uint32_t *d_sum = (uint32_t *)(d + o_sum);
+    if (kh) hipLaunchKernelGGL(k4::k4_fw_xxh32_kernel, dim3((unsigned)((kh * 4 + k4::FW_THREADS - 1) / k4::FW_THREADS)), dim3(k4::FW_THREADS), 0, st,
+                               (const k4::FwHashItem *)(d + o_hash), (long long)kh);
+    if (ks) hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)stage_chunks), dim3(k4::FW_THREADS), 0, st, (const k4::FwPiece *)(d + o_stage), (long long)ks);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    int64_t ind = 0;
+    for (const Group &g : groups) {
+        const int kind = g.key % 1000 / 100, level = g.key % 100;
+        const int64_t ns = (int64_t)g.streams.size();
+        if (kind == 0) {
+            rc = launch(ctx, KIND_ENCODE, d, (const uint64_t *)(d + o_isrc) + ind, (const int32_t *)(d + o_ilen) + ind, d,
+                        (const uint64_t *)(d + o_slot) + g.first, (const int32_t *)(d + o_icap) + ind, d_out + g.first, g.nb, level,
+                        K4LZ4_FLAG_ALLOW_COPY | (x32 ? K4LZ4_FLAG_X32 : 0), st, nullptr, hilen + ind);
+            ind += g.nb;
+        } else {
+            std::vector<uint64_t> soff((size_t)ns), doff((size_t)ns);
+            std::vector<int64_t> slen((size_t)ns);
+            std::vector<int32_t> bsz((size_t)ns), ext((size_t)ns), dlen((size_t)ns);
+            std::vector<uint32_t> cur0((size_t)ns), sdict((size_t)ns);
+            int64_t f0 = -1;
+            for (int64_t k = 0; k < ns; k++) {
+                const int64_t i = g.streams[(size_t)k];
+                soff[(size_t)k] = win[(size_t)i]; doff[(size_t)k] = aoff[(size_t)i];
+                /* the window up to the end of the last block this call encodes */
+                int64_t end = w[i].index;
+                fw_model(w[i], srcLen[i], closing, [&](int64_t s0, int64_t l0) { end = s0 + l0; });
+                slen[(size_t)k] = end;
+                bsz[(size_t)k] = w[i].settings.blockSize; ext[(size_t)k] = w[i].extraBlocks; dlen[(size_t)k] = w[i].index;
+                cur0[(size_t)k] = w[i].currentOffset; sdict[(size_t)k] = w[i].dictSize;
+                if (f0 < 0) f0 = fast_index[(size_t)i];
+            }
+            if (kind == 1)
+                rc = hc_chain_run(ctx, d, soff.data(), slen.data(), bsz.data(), ext.data(), dlen.data(), ns, d, doff.data(), d_out + g.first, g.nb,
+                                  level, K4LZ4_FLAG_ALLOW_COPY, st);
+            else      /* the states' two indices from the records (k4lz4_encode_fast_chain_batch_device reads them back instead) */
+                rc = fast_chain_run(ctx, d, soff.data(), slen.data(), bsz.data(), ext.data(), dlen.data(), cur0.data(), sdict.data(), ns,
+                                    d_stin + f0, d_stout + f0, d, doff.data(), d_out + g.first, g.nb, K4LZ4_FLAG_ALLOW_COPY, st);
+        }
+        if (rc != K4LZ4_OK) return rc;
+    }
+    if (kb) hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)back_chunks), dim3(k4::FW_THREADS), 0, st, (const k4::FwPiece *)(d + o_back), (long long)kb);
+    if (nb) {
+        const unsigned bgrid = (unsigned)((nb + k4::FW_THREADS - 1) / k4::FW_THREADS);
+        hipLaunchKernelGGL(k4::k4_fw_reclen_kernel, dim3(bgrid), dim3(k4::FW_THREADS), 0, st, (const int32_t *)d_out, d_stored, d_rec, (long long)nb, (long long)firstSum);
+        if (firstSum < nb) {
+            k4::HashArgs ha{d, (const uint64_t *)(d + o_slot) + firstSum, (const uint64_t *)d_stored + firstSum, d_sum + firstSum, nb - firstSum, 0u};
+            hipLaunchKernelGGL(k4::k4_xxh32_kernel, dim3((unsigned)(((nb - firstSum) * 4 + k4::XXH_THREADS - 1) / k4::XXH_THREADS)), dim3(k4::XXH_THREADS), 0, st, ha);
+        }
+        hipLaunchKernelGGL(k4::k4_legacy_scan_kernel, dim3(1), dim3(k4::LEGACY_SCAN_THREADS), 0, st, (const uint64_t *)d_rec, (uint64_t *)d_excl,
+                           (long long)nb, (unsigned long long *)(d + o_cnt));
+        hipLaunchKernelGGL(k4::k4_fw_place_kernel, dim3(bgrid), dim3(k4::FW_THREADS), 0, st, d_streams, (const uint32_t *)(d + o_owner),
+                           (const unsigned long long *)d_excl, d_roff, (long long)nb);
+        if (firstSum > 0) {
+            k4::FrameBlocksArgs fa{d, (const uint64_t *)(d + o_slot), d_out, nullptr, (const uint64_t *)d_roff, dst, firstSum};
+            hipLaunchKernelGGL(k4::k4_frame_blocks_kernel, dim3((unsigned)((firstSum + 3) / 4)), dim3(256), 0, st, fa);
+        }
+        if (firstSum < nb) {
+            k4::FrameBlocksArgs fa{d, (const uint64_t *)(d + o_slot) + firstSum, d_out + firstSum, d_sum + firstSum, (const uint64_t *)d_roff + firstSum,
+                                   dst, nb - firstSum};
+            hipLaunchKernelGGL(k4::k4_frame_blocks_kernel, dim3((unsigned)((nb - firstSum + 3) / 4)), dim3(256), 0, st, fa);
+        }
+    }
+    hipLaunchKernelGGL(k4::k4_fw_edges_kernel, dim3((unsigned)((n + k4::FW_THREADS - 1) / k4::FW_THREADS)), dim3(k4::FW_THREADS), 0, st, d_streams,
+                       (const unsigned long long *)d_excl, (const unsigned long long *)d_rec, dst, (long long *)outLen, (long long)n);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+
+    /* ---- the records: what the calls enqueued leaves them in */
+    for (int64_t i = 0; i < n; i++) {
+        if (code[(size_t)i] != 0) continue;
+        fw_advance(w[i], srcLen[i], closing, after[(size_t)i]);
+    }
+    return K4LZ4_OK;
+}
+
+int k4lz4_frame_write_batch(k4lz4_ctx *ctx, k4lz4_frame_writer *w, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                            const uint64_t *srcOff, const int64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                            int64_t *outLen, int64_t n, int op, int flags)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!w || !store || !storeOff || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    for (int64_t i = 0; i < n; i++)
+        if (srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* the output slots: what the call can emit, not the caller's capacities (the codes are decided on dstCap all the same) */
+    std::vector<uint64_t> cap((size_t)n);
+    for (int64_t i = 0; i < n; i++) cap[(size_t)i] = std::min<uint64_t>(dstCap[i], (uint64_t)fw_bound(w[i], srcLen[i], op == K4LZ4_FWRITE_CLOSE));
+    std::vector<int64_t> len0((size_t)n);
+    for (int64_t i = 0; i < n; i++) len0[(size_t)i] = std::max<int64_t>(srcLen[i], 0);
+    HostStage s(ctx);
+    s.pack(src, srcOff, len0.data(), n);
+    s.slots(n, [&](int64_t i) { return cap[(size_t)i]; }, false);
+    int64_t *d_out;
+    s.meta(&d_out, n);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_frame_write_batch_device(ctx, w, store, storeOff, ctx->d_src, s.in_off.data(), srcLen, ctx->d_dst, s.slot.data(), cap.data(),
+                                             d_out, n, op, flags, s.st)) != K4LZ4_OK)
+        return rc;
+    /* codes from dstCap: the device form saw the clipped capacities, which pass the same bound */
+    return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff, [&](int64_t i) { return outLen[i] > 0 ? (size_t)outLen[i] : 0; });
 }
 
 }  // extern "C"

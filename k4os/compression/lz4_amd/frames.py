@@ -619,3 +619,135 @@ def encode_fast_chain_frames(sources: Sequence, settings: Optional[LZ4EncoderSet
     else:
         out, arena, aoff, owner = np.zeros(0, np.int32), None, None, []
     return _assemble_frames(s, contents, out, arena, aoff, owner, ctx)
+
+
+# ---- incremental frame writer: many LZ4FrameWriters, one Write / OpenFrame / CloseFrame each per call (k4lz4_frame_write_batch*,
+# DESIGN.md 4.13) ------------------------------------------------------------------------------------------------------------
+import ctypes as _C
+
+FWRITE_WRITE, FWRITE_OPEN, FWRITE_CLOSE = 0, 1, 2
+FWRITE_TARGET, FWRITE_CLOSED, FWRITE_LENGTH = -1, -2, -3          # per-stream codes (include/k4lz4.h K4LZ4_FWRITE_*)
+
+
+class _WriterSettings(_C.Structure):          # k4lz4_frame_writer_settings
+    _fields_ = [("contentLength", _C.c_int64), ("blockSize", _C.c_int32), ("level", _C.c_int32), ("chainBlocks", _C.c_int32),
+                ("blockChecksum", _C.c_int32), ("contentChecksum", _C.c_int32), ("extraMemory", _C.c_int32)]
+
+
+class FrameWriterRecord(_C.Structure):        # k4lz4_frame_writer: settings and counters, host memory
+    _fields_ = [("settings", _WriterSettings), ("kind", _C.c_int32), ("encBlock", _C.c_int32), ("extraBlocks", _C.c_int32),
+                ("ringBytes", _C.c_int32), ("written", _C.c_int64), ("index", _C.c_int32), ("pointer", _C.c_int32),
+                ("currentOffset", _C.c_uint32), ("dictSize", _C.c_uint32), ("phase", _C.c_int32), ("reserved", _C.c_int32)]
+
+
+def _writer_records(n: int, settings, lib):
+    """n k4lz4_frame_writer records from one LZ4EncoderSettings or a list of n; their stores' offsets and total size"""
+    lst = list(settings) if isinstance(settings, (list, tuple)) else [settings or LZ4EncoderSettings()] * n
+    if len(lst) != n:
+        raise ValueError("one settings object, or one per stream")
+    recs = (FrameWriterRecord * max(n, 1))()
+    store_off = np.zeros(n, np.uint64)
+    at = 0
+    for i, s in enumerate(lst):
+        max_block_size_code(int(s.BlockSize))
+        ws = _WriterSettings(-1 if s.ContentLength is None else int(s.ContentLength), int(s.BlockSize), int(s.CompressionLevel),
+                             int(bool(s.ChainBlocks)), int(bool(s.BlockChecksum)), int(bool(s.ContentChecksum)), int(s.ExtraMemory))
+        if lib.k4lz4_frame_writer_init(_C.byref(recs[i]), _C.byref(ws)) != 0:
+            raise ValueError(f"Invalid block size ${s.BlockSize} for this operation")
+        store_off[i] = at
+        at += int(lib.k4lz4_frame_writer_store_bytes(_C.byref(recs[i])))
+    return recs, store_off, at
+
+
+class LZ4FrameWriterBatch:
+    """n LZ4FrameWriters (Frames/LZ4FrameWriter*.cs) advanced together: Write(chunks) is one WriteManyBytes per stream, Open() one
+    OpenFrame, Close() one CloseFrame; each returns, per stream, the bytes the reference's writer pushes to its inner stream during
+    that call (None where a chunk is None).  The streams' encoder state lives in device memory; the data goes up and the bytes come
+    back in one host-pointer call (k4lz4_frame_write_batch).  A stream the call refuses reports None and its K4LZ4_FWRITE_* code in
+    LastCodes."""
+
+    def __init__(self, n: int, settings=None, ctx: Optional[_native.Context] = None):
+        import torch
+        self.ctx = ctx or _native.default_context()
+        self.n = int(n)
+        self.records, self.store_off, size = _writer_records(self.n, settings, self.ctx.lib)
+        dev = int(self.ctx.lib.k4lz4_ctx_device(self.ctx.handle))
+        self.store = torch.empty(max(size, 1) + 64, dtype=torch.uint8, device=f"cuda:{dev}")
+        self.LastCodes = np.zeros(self.n, np.int64)
+
+    def _call(self, chunks, op: int, dst_cap=None) -> List[Optional[bytes]]:
+        if len(chunks) != self.n:
+            raise ValueError("one chunk (or None) per stream")
+        views = [None if c is None else _ro_view(c, "source") for c in chunks]
+        lens = np.array([-1 if v is None else v.size for v in views], np.int64)
+        src, soff, _ = pack_blocks([v if v is not None else np.zeros(0, np.uint8) for v in views])
+        caps = np.array([self.ctx.lib.k4lz4_frame_write_bound(_C.byref(self.records[i]), int(lens[i]), int(op == FWRITE_CLOSE))
+                         for i in range(self.n)], np.uint64) if dst_cap is None else np.asarray(dst_cap, np.uint64)
+        doff = np.zeros(self.n, np.uint64)
+        if self.n > 1:
+            doff[1:] = np.cumsum(caps[:-1])
+        dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
+        out = np.zeros(self.n, np.int64)
+        self.ctx.check(self.ctx.lib.k4lz4_frame_write_batch(self.ctx.handle, self.records, self.store.data_ptr(), self.store_off.ctypes.data,
+                                                            src.ctypes.data, soff.ctypes.data, lens.ctypes.data, dst.ctypes.data,
+                                                            doff.ctypes.data, caps.ctypes.data, out.ctypes.data, self.n, op, 0))
+        self.LastCodes = np.minimum(out, 0)
+        return [None if (lens[i] < 0 or out[i] < 0) else dst[int(doff[i]):int(doff[i]) + int(out[i])].tobytes() for i in range(self.n)]
+
+    def Write(self, chunks) -> List[Optional[bytes]]:
+        return self._call(chunks, FWRITE_WRITE)
+
+    def Open(self, streams=None) -> List[Optional[bytes]]:
+        return self._call([b"" if streams is None or i in streams else None for i in range(self.n)], FWRITE_OPEN)
+
+    def Close(self, streams=None) -> List[Optional[bytes]]:
+        return self._call([b"" if streams is None or i in streams else None for i in range(self.n)], FWRITE_CLOSE)
+
+    def Bound(self, stream: int, length: int, closing: bool = False) -> int:
+        return int(self.ctx.lib.k4lz4_frame_write_bound(_C.byref(self.records[stream]), int(length), int(closing)))
+
+
+class FrameWriterDevice:
+    """n LZ4FrameWriters over HBM-resident data (k4lz4_frame_write_batch_device): write(data, off, length) takes stream s's bytes
+    from data[off[s] : off[s] + length[s]] (data a uint8 torch tensor, off / length host arrays, length < 0: untouched) and returns
+    (out, out_off, out_len) like encode_frames_device: stream s's bytes of this call are out[out_off[s] : out_off[s] + out_len[s]],
+    out_off a host array, out_len an int64 device tensor (negative: a K4LZ4_FWRITE_* code).  Asynchronous on the current torch
+    stream; `dc` is a device.DeviceCodec."""
+
+    def __init__(self, dc, n: int, settings=None):
+        import torch
+        self.dc = dc
+        self.n = int(n)
+        self.records, self.store_off, size = _writer_records(self.n, settings, dc.lib)
+        self.store = torch.empty(max(size, 1) + 64, dtype=torch.uint8, device=dc.device)
+
+    def bound(self, length, closing: bool = False) -> np.ndarray:
+        length = np.broadcast_to(np.asarray(length, np.int64), (self.n,))
+        return np.array([self.dc.lib.k4lz4_frame_write_bound(_C.byref(self.records[i]), int(length[i]), int(closing)) for i in range(self.n)],
+                        np.uint64)
+
+    def _call(self, data, off, length, op: int, dst_cap=None):
+        import torch
+        from .device import _dp
+        length = np.ascontiguousarray(np.broadcast_to(np.asarray(length, np.int64), (self.n,)))
+        off = np.ascontiguousarray(np.broadcast_to(np.asarray(off, np.int64), (self.n,))).astype(np.uint64)
+        caps = self.bound(length, op == FWRITE_CLOSE) if dst_cap is None else np.ascontiguousarray(dst_cap, np.uint64)
+        out_off = np.zeros(self.n, np.uint64)
+        if self.n > 1:
+            out_off[1:] = np.cumsum((caps[:-1] + 15) // 16 * 16)
+        out = torch.empty(int(((caps + 15) // 16 * 16).sum()) + 64, dtype=torch.uint8, device=self.dc.device)
+        out_len = torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.dc.device)
+        self.dc.ctx.check(self.dc.lib.k4lz4_frame_write_batch_device(
+            self.dc.ctx.handle, self.records, _dp(self.store), self.store_off.ctypes.data, _dp(data), off.ctypes.data, length.ctypes.data,
+            _dp(out), out_off.ctypes.data, caps.ctypes.data, _dp(out_len), self.n, op, 0, _C.c_void_p(self.dc._stream())))
+        return out, out_off.astype(np.int64), out_len[:self.n]
+
+    def write(self, data, off, length, dst_cap=None):
+        return self._call(data, off, length, FWRITE_WRITE, dst_cap)
+
+    def open(self, streams=None):
+        return self._call(None, 0, [0 if streams is None or i in streams else -1 for i in range(self.n)], FWRITE_OPEN)
+
+    def close(self, data=None, off=0, length=None, dst_cap=None):
+        """CloseFrame; with data, the bytes are written first (Write then CloseFrame in one call)"""
+        return self._call(data, off, 0 if length is None else length, FWRITE_CLOSE, dst_cap)
