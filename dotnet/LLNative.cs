@@ -169,6 +169,26 @@ namespace K4os.Compression.LZ4.Engine
 			IntPtr ctx, k4lz4_frame_writer* w, IntPtr store, ulong* storeOff, IntPtr src, ulong* srcOff, long* srcLen, IntPtr dst, ulong* dstOff,
 			ulong* dstCap, IntPtr outLen, long n, int op, int flags, IntPtr stream);
 
+		// incremental frame reader (DESIGN.md 4.14): many LZ4FrameReaders, one ReadManyBytes / OpenFrame each per call; the record holds
+		// the settings and the per-stream store size, everything a reader keeps between calls is in the device store
+		[StructLayout(LayoutKind.Sequential)]
+		public struct k4lz4_frame_reader_settings { public int maxBlockSize, reserved; }
+		[StructLayout(LayoutKind.Sequential)]
+		public struct k4lz4_frame_reader { public k4lz4_frame_reader_settings settings; public long storeBytes; }
+		public const int FREAD_OP_READ = 0, FREAD_OP_OPEN = 1, FREAD_OP_RESET = 2, FREAD_INTERACTIVE = 1;
+		public const int FRAME_BLOCK_SIZE = -11, FRQ_BYTES_READ = 0, FRQ_FRAME_LENGTH = 1, FRQ_PHASE = 2, FRQ_CODE = 3, FRQ_BLOCKS = 4, FRQ_DIRECT = 5, FRQ_FAST = 6, FRQ_HANDED_BACK = 7, FRQ_WORDS = 8;
+		[DllImport(Lib)] public static extern int k4lz4_frame_reader_init(k4lz4_frame_reader* r, k4lz4_frame_reader_settings* settings);
+		[DllImport(Lib)] public static extern long k4lz4_frame_reader_store_bytes(k4lz4_frame_reader* r);
+		[DllImport(Lib)] public static extern int k4lz4_frame_read_batch(
+			IntPtr ctx, k4lz4_frame_reader* r, IntPtr store, ulong* storeOff, byte* src, ulong* srcOff, ulong* srcLen, byte* dst, ulong* dstOff,
+			long* count, long* outLen, long n, int op, int flags);
+		[DllImport(Lib)] public static extern int k4lz4_frame_read_batch_device(
+			IntPtr ctx, k4lz4_frame_reader* r, IntPtr store, IntPtr storeOff, IntPtr src, IntPtr srcOff, IntPtr srcLen, IntPtr dst, IntPtr dstOff,
+			IntPtr count, IntPtr outLen, long n, int op, int flags, long maxCount, IntPtr stream);
+		[DllImport(Lib)] public static extern long k4lz4_frame_read_table_rows(long maxCount);
+		[DllImport(Lib)] public static extern int k4lz4_frame_reader_query(IntPtr ctx, IntPtr store, ulong* storeOff, long n, long* @out);
+		[DllImport(Lib)] public static extern int k4lz4_frame_reader_query_device(IntPtr ctx, IntPtr store, IntPtr storeOff, long n, IntPtr @out, IntPtr stream);
+
 		// ---- device-resident variants: every pointer is a device pointer of the context's GPU, stream = hipStream_t
 		[DllImport(Lib)] public static extern int k4lz4_encode_batch_device(
 			IntPtr ctx, IntPtr src, IntPtr srcOff, IntPtr srcLen, IntPtr dst, IntPtr dstOff, IntPtr dstCap, IntPtr outLen, long n, int level, int flags, IntPtr stream);

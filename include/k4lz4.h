@@ -509,6 +509,85 @@ K4LZ4_API int k4lz4_frame_write_batch_device(k4lz4_ctx *ctx, k4lz4_frame_writer 
                                              const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, int64_t n, int op, int flags,
                                              void *stream);
 
+/* ---- incremental frame reader: many LZ4FrameReaders (Frames/LZ4FrameReader*.cs, Streams/LZ4DecoderStream.cs) advanced by one
+ * ReadManyBytes(count[s]) or one OpenFrame each per call.  Stream s is src[srcOff[s] .. srcOff[s] + srcLen[s]): zero
+ * or more frames one after another, all of it present at every call (the same bytes at every call: the reader keeps its position,
+ * not the data); nothing outside that range is read.  A READ delivers what the reference's reader delivers for the same sequence of
+ * reads: it opens a frame if none is open (no bytes left: 0; one to three bytes left: K4LZ4_FRAME_EOF), then reads blocks and drains
+ * them until count[s] bytes are delivered, the EndMark is read (the frame is closed and the read ends with what it has, possibly 0;
+ * the next read opens the next frame), or a block yields nothing (a raw block of stored length 0; under chained frames a compressed
+ * block that decodes to nothing).  A read satisfied exactly at a block's end does not look at the next length word.  Independent
+ * frames are decoded as LZ4BlockDecoder does (capacity blockSize + 8, a block of nothing is a defect), chained ones as
+ * LZ4ChainDecoder does (capacity blockSize, the last 64 KiB of the frame's output as prefix).  The output is not compared with a
+ * declared ContentLength (the reference's reader does not; k4lz4_decode_frames does).  interactive != 0: return after the first
+ * drain.  OPEN is OpenFrame().
+ *
+ * outLen[s]: READ: the bytes written at dst + dstOff[s] (0 .. count[s]); OPEN: 1 a frame is open, 0 the source is at its end; or the
+ * code of the exception the reference throws during that call, in the order it meets them: K4LZ4_FRAME_EOF .. _CONTENT_SUM with
+ * their meanings above (-9 and -10 do not occur), or K4LZ4_FRAME_BLOCK_SIZE.  A stored block length above the frame's block size is
+ * K4LZ4_FRAME_BLOCK (in the reference it overruns a pooled buffer whose length depends on the pool).  A stream that has reported a
+ * code is failed: every later call reports the same code and touches nothing.  The bytes of a failing call's slot are unspecified;
+ * nothing outside [dstOff[s], dstOff[s] + count[s]) is ever written.  count[s] < 0 leaves stream s untouched (outLen 0).
+ *
+ * Everything a reader keeps between calls lives in a caller-owned DEVICE store of k4lz4_frame_reader_store_bytes(r) bytes at
+ * store + storeOff[s] (256-byte aligned): position, phase, descriptor, the content checksum's state, the undrained rest of one block
+ * and, for chained frames, the 64 KiB of history.  It must be reset once (K4LZ4_FREAD_RESET) before its first use.  The host record
+ * holds the settings and the store size and is never changed by a call. */
+#define K4LZ4_FRAME_BLOCK_SIZE     (-11)  /* the frame's block size is above the reader's maxBlockSize (not the reference's) */
+
+typedef struct k4lz4_frame_reader_settings {
+    int32_t maxBlockSize;        /* the largest block size the store holds: rounded up to 64 KiB, 256 KiB, 1 MiB or 4 MiB; <= 0: 4 MiB */
+    int32_t reserved;
+} k4lz4_frame_reader_settings;
+
+typedef struct k4lz4_frame_reader {
+    k4lz4_frame_reader_settings settings;      /* maxBlockSize as rounded */
+    int64_t storeBytes;                        /* per stream */
+} k4lz4_frame_reader;
+
+enum k4lz4_frame_read_op { K4LZ4_FREAD_READ = 0, K4LZ4_FREAD_OPEN = 1, K4LZ4_FREAD_RESET = 2 };
+#define K4LZ4_FREAD_INTERACTIVE 1          /* flags: ReadManyBytes(buffer, interactive: true) */
+
+/* k4lz4_frame_reader_query: int64 words per stream */
+enum { K4LZ4_FRQ_BYTES_READ = 0,       /* GetBytesRead: over all the frames read so far */
+       K4LZ4_FRQ_FRAME_LENGTH = 1,     /* the open frame's ContentLength; -1: no frame is open or it declares none */
+       K4LZ4_FRQ_PHASE = 2,            /* 0 no frame open, 1 a frame is open, 2 failed */
+       K4LZ4_FRQ_CODE = 3,             /* the failed stream's code */
+       K4LZ4_FRQ_BLOCKS = 4,           /* blocks read so far */
+       K4LZ4_FRQ_DIRECT = 5,           /* of those, decoded straight into dst */
+       K4LZ4_FRQ_FAST = 6,             /* of those, decoded by the batch decoder on the fast path */
+       K4LZ4_FRQ_HANDED_BACK = 7,      /* calls in which the fast path's hypothesis failed for the stream and the general reader replayed it */
+       K4LZ4_FRQ_WORDS = 8 };
+
+/* K4LZ4_OK or K4LZ4_E_ARG (a maxBlockSize above 4 MiB) */
+K4LZ4_API int k4lz4_frame_reader_init(k4lz4_frame_reader *r, const k4lz4_frame_reader_settings *settings);
+K4LZ4_API int64_t k4lz4_frame_reader_store_bytes(const k4lz4_frame_reader *r);
+/* op: k4lz4_frame_read_op for every stream of the call (RESET: count[s] >= 0 resets stream s's store; src, dst may be NULL for RESET
+ * and OPEN where nothing is written).  flags: K4LZ4_FREAD_INTERACTIVE.
+ * k4lz4_frame_read_batch: store is a device pointer, every other pointer a host pointer; the sources and the per-stream arrays are
+ * staged through the context's staging buffers, the bytes come back into dst + dstOff[s].  Synchronous.
+ * _device: every pointer is a device pointer (the per-stream arrays too).  maxCount: no count[s] of the call is above it (the host
+ * form takes the largest count).  It bounds the fast path's block table -- maxCount / 64 KiB + 2 rows per stream in the context's
+ * grow-only scratch (about 48 bytes a row) -- so the call enqueues on `stream` and returns without waiting for its own work (a scratch
+ * that has to grow waits for the context's earlier work).  maxCount <= 0: the general reader alone, one kernel.
+ * Two ways through a READ: streams that read with nothing pending from an independent-block frame are planned under
+ * the hypothesis that the blocks the read covers are full: those blocks go through the batch decoder straight into dst, the one that
+ * straddles the read's end into the store, and a kernel verifies the hypothesis and commits the state.  Every other stream, and every
+ * stream whose hypothesis fails, is read by the general reader (one wavefront per stream) from its unchanged state, in the same call. */
+K4LZ4_API int k4lz4_frame_read_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                     const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                     const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags);
+K4LZ4_API int k4lz4_frame_read_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                            const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                            const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags,
+                                            int64_t maxCount, void *stream);
+/* rows of the fast path's block table per stream for a call whose counts do not pass maxCount */
+K4LZ4_API int64_t k4lz4_frame_read_table_rows(int64_t maxCount);
+/* out[s * K4LZ4_FRQ_WORDS + k]: host form (storeOff, out host arrays; synchronous) and device form (device arrays; asynchronous) */
+K4LZ4_API int k4lz4_frame_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out);
+K4LZ4_API int k4lz4_frame_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out,
+                                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ _u8p = C.c_void_p
 _BATCH = [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
 # k4lz4_frame_write_batch*: ctx, w, store, storeOff, src, srcOff, srcLen, dst, dstOff, dstCap, outLen
 _FWRITE = [C.c_void_p, C.c_void_p, _u8p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]
+_FREAD = [C.c_void_p] * 11
 _LEGACY_ENC = [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 # every symbol include/k4lz4.h declares: name -> (restype, argtypes)
@@ -106,6 +107,13 @@ SYMBOLS = {
     "k4lz4_frame_write_bound": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int]),
     "k4lz4_frame_write_batch": (C.c_int, _FWRITE + [C.c_int64, C.c_int, C.c_int]),
     "k4lz4_frame_write_batch_device": (C.c_int, _FWRITE + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "k4lz4_frame_reader_init": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "k4lz4_frame_reader_store_bytes": (C.c_int64, [C.c_void_p]),
+    "k4lz4_frame_read_batch": (C.c_int, _FREAD + [C.c_int64, C.c_int, C.c_int]),
+    "k4lz4_frame_read_batch_device": (C.c_int, _FREAD + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "k4lz4_frame_read_table_rows": (C.c_int64, [C.c_int64]),
+    "k4lz4_frame_reader_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "k4lz4_frame_reader_query_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -38,6 +38,7 @@
 #include "k4lz4_frame_read.hpp"
 #include "k4lz4_legacy.hpp"
 #include "k4lz4_frame_write.hpp"
+#include "k4lz4_frame_reader.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 
@@ -141,6 +142,7 @@ struct k4lz4_ctx {
     uint8_t *d_fb = nullptr; size_t d_fb_cap = 0;
     /* legacy streams (k4lz4_legacy.hpp): per-stream words, the chunk table and the writer's arena, all grow-only */
     uint8_t *d_lg = nullptr; size_t d_lg_cap = 0;
+    uint8_t *d_frd = nullptr; size_t d_frd_cap = 0;      /* the incremental reader's fast path: plans and block table */
     uint8_t *d_lgr = nullptr; size_t d_lgr_cap = 0;
     uint8_t *d_lga = nullptr; size_t d_lga_cap = 0;
     /* incremental frame writer (k4lz4_frame_write.hpp): the call's plan, built on the host (rewritten only after ev_fw says the
@@ -2083,6 +2085,7 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_fr) (void)hipFree(ctx->d_fr);
     if (ctx->d_fb) (void)hipFree(ctx->d_fb);
     if (ctx->d_lg) (void)hipFree(ctx->d_lg);
+    if (ctx->d_frd) (void)hipFree(ctx->d_frd);
     if (ctx->d_lgr) (void)hipFree(ctx->d_lgr);
     if (ctx->d_lga) (void)hipFree(ctx->d_lga);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -3192,6 +3195,145 @@ int k4lz4_frame_write_batch(k4lz4_ctx *ctx, k4lz4_frame_writer *w, uint8_t *stor
         return rc;
     /* codes from dstCap: the device form saw the clipped capacities, which pass the same bound */
     return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff, [&](int64_t i) { return outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+}
+
+/* ---- incremental frame reader (k4lz4_frame_reader.hpp) --------------------------------------------------- */
+int k4lz4_frame_reader_init(k4lz4_frame_reader *r, const k4lz4_frame_reader_settings *settings)
+{
+    if (!r) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_frame_reader_init: NULL argument");
+    const int32_t asked = settings ? settings->maxBlockSize : 0;
+    if (asked > (4 << 20)) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_frame_reader_init: maxBlockSize above 4 MiB");
+    r->settings.maxBlockSize = k4::fr_max_block(asked);
+    r->settings.reserved = 0;
+    r->storeBytes = k4::fr_store_bytes(r->settings.maxBlockSize);
+    return K4LZ4_OK;
+}
+
+int64_t k4lz4_frame_reader_store_bytes(const k4lz4_frame_reader *r) { return r ? r->storeBytes : 0; }
+int64_t k4lz4_frame_read_table_rows(int64_t maxCount) { return k4::fr_table_rows(maxCount); }
+
+int k4lz4_frame_read_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                  const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                  const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags,
+                                  int64_t maxCount, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (op < K4LZ4_FREAD_READ || op > K4LZ4_FREAD_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: unknown op");
+    if (flags & ~(int)K4LZ4_FREAD_INTERACTIVE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: the only flag it takes is K4LZ4_FREAD_INTERACTIVE");
+    if (n < 0 || (n > 0 && (!r || !store || !storeOff || !count || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && op != K4LZ4_FREAD_RESET && (!src || !srcOff || !srcLen)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && op == K4LZ4_FREAD_READ && (!dst || !dstOff)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && (r->storeBytes != k4::fr_store_bytes(r->settings.maxBlockSize) || r->settings.maxBlockSize != k4::fr_max_block(r->settings.maxBlockSize)))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: the record was not made by k4lz4_frame_reader_init");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    k4::FrReadArgs a{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op,
+                     (flags & K4LZ4_FREAD_INTERACTIVE) ? 1 : 0, r->settings.maxBlockSize, nullptr};
+    const long long rows = k4::fr_table_rows(maxCount);
+    if (op == K4LZ4_FREAD_READ && !a.interactive && rows > 0) {
+        /* the fast path: plan, block checksums, the batch decoder into dst and into the stores, verify and commit; the table is
+         * bounded by maxCount, so nothing is read back */
+        if (n * rows > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows");
+        int rc;
+        if ((rc = grow_scratch(ctx, &ctx->d_frd, &ctx->d_frd_cap, k4::fr_fast_scratch(n, rows))) != K4LZ4_OK) return rc;
+        const size_t nr = (size_t)n * (size_t)rows;
+        uint8_t *m = ctx->d_frd;
+        auto take = [&](size_t bytes) { uint8_t *q = m; m += (bytes + 63) & ~(size_t)63; return q; };
+        k4::FrFastArgs f{};
+        f.r = a; f.rows = rows;
+        f.plan = (k4::FrPlan *)take((size_t)n * sizeof(k4::FrPlan));
+        f.done = (uint32_t *)take((size_t)n * 4);
+        f.sSrcOff = (uint64_t *)take((size_t)n * 8); f.sDstOff = (uint64_t *)take((size_t)n * 8);
+        f.sSrcLen = (int32_t *)take((size_t)n * 4); f.sDstCap = (int32_t *)take((size_t)n * 4); f.sOutLen = (int32_t *)take((size_t)n * 4);
+        f.srcOff = (uint64_t *)take(nr * 8); f.dstOff = (uint64_t *)take(nr * 8); f.hlen = (uint64_t *)take(nr * 8);
+        f.srcLen = (int32_t *)take(nr * 4); f.dstCap = (int32_t *)take(nr * 4); f.outLen = (int32_t *)take(nr * 4);
+        f.sum = (uint32_t *)take(nr * 4); f.got = (uint32_t *)take(nr * 4); f.lc = (uint32_t *)take(nr * 4);
+        hipLaunchKernelGGL(k4::k4_fr_plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f);
+        K4_HIP(ctx, hipGetLastError());
+        if ((rc = k4lz4_xxh32_batch_device(ctx, src, f.srcOff, f.hlen, f.got, (int64_t)nr, 0, st)) != K4LZ4_OK ||
+            (rc = launch(ctx, KIND_DECODE, src, f.srcOff, f.srcLen, dst, f.dstOff, f.dstCap, f.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
+            (rc = launch(ctx, KIND_DECODE, src, f.sSrcOff, f.sSrcLen, store, f.sDstOff, f.sDstCap, f.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
+            return rc;
+        hipLaunchKernelGGL(k4::k4_fr_commit_kernel, dim3((unsigned)((n + k4::FR_WAVES_PER_WG - 1) / k4::FR_WAVES_PER_WG)),
+                           dim3(64 * k4::FR_WAVES_PER_WG), 0, st, f);
+        a.done = f.done;
+    }
+    hipLaunchKernelGGL(k4::k4_fr_read_kernel, dim3((unsigned)((n + k4::FR_WAVES_PER_WG - 1) / k4::FR_WAVES_PER_WG)), dim3(64 * k4::FR_WAVES_PER_WG),
+                       0, st, a);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_frame_read_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                           const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const int64_t *count,
+                           int64_t *outLen, int64_t n, int op, int flags)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (op < K4LZ4_FREAD_READ || op > K4LZ4_FREAD_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: unknown op");
+    if (n < 0 || (n > 0 && (!r || !store || !storeOff || !count || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && op != K4LZ4_FREAD_RESET && (!srcOff || !srcLen)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && op == K4LZ4_FREAD_READ && (!dst || !dstOff)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (flags & ~(int)K4LZ4_FREAD_INTERACTIVE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: the only flag it takes is K4LZ4_FREAD_INTERACTIVE");
+    if (n > 0 && (r->storeBytes != k4::fr_store_bytes(r->settings.maxBlockSize) || r->settings.maxBlockSize != k4::fr_max_block(r->settings.maxBlockSize)))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: the record was not made by k4lz4_frame_reader_init");
+    if (n == 0) return K4LZ4_OK;
+    const bool reads = op != K4LZ4_FREAD_RESET;
+    int64_t maxCount = 0;
+    for (int64_t i = 0; op == K4LZ4_FREAD_READ && i < n; i++) maxCount = std::max(maxCount, count[i]);
+    for (int64_t i = 0; reads && i < n; i++)
+        if (count[i] >= 0 && srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* streams that sit the call out send nothing up */
+    std::vector<int64_t> len0((size_t)n, 0);
+    std::vector<uint64_t> off0((size_t)n, 0);
+    for (int64_t i = 0; reads && i < n; i++)
+        if (count[i] >= 0) { len0[(size_t)i] = (int64_t)srcLen[i]; off0[(size_t)i] = srcOff[i]; }
+    HostStage s(ctx);
+    s.pack(src, off0.data(), len0.data(), n);
+    s.slots(n, [&](int64_t i) { return op == K4LZ4_FREAD_READ && count[i] > 0 ? (uint64_t)count[i] : 0u; }, false);
+    uint64_t *d_soff, *d_slen, *d_store, *d_doff;
+    int64_t *d_count, *d_out;
+    s.meta(&d_soff, n, s.in_off.data()); s.meta(&d_slen, n, len0.data()); s.meta(&d_store, n, storeOff); s.meta(&d_doff, n, s.slot.data());
+    s.meta(&d_count, n, count); s.meta(&d_out, n);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_frame_read_batch_device(ctx, r, store, d_store, ctx->d_src, d_soff, d_slen, ctx->d_dst, d_doff, d_count, d_out, n, op, flags,
+                                            maxCount, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff,
+                    [&](int64_t i) { return op == K4LZ4_FREAD_READ && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+}
+
+int k4lz4_frame_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    hipLaunchKernelGGL(k4::k4_fr_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, store, storeOff, out, (long long)n);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_frame_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    uint64_t *d_store;
+    int64_t *d_out;
+    s.meta(&d_store, n, storeOff); s.meta(&d_out, n * K4LZ4_FRQ_WORDS);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_frame_reader_query_device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
+    return s.finish({{out, d_out, (size_t)n * K4LZ4_FRQ_WORDS * 8}});
 }
 
 }  // extern "C"

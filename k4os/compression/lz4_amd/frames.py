@@ -514,6 +514,7 @@ def encode_frames_device(dc, data, off: np.ndarray, length: np.ndarray, settings
 # per-frame codes of the device reader (include/k4lz4.h K4LZ4_FRAME_*) and what the reference's reader raises for each
 FRAME_EOF, FRAME_MAGIC, FRAME_VERSION, FRAME_HEADER_SUM, FRAME_DICTIONARY = -1, -2, -3, -4, -5
 FRAME_BLOCK, FRAME_BLOCK_SUM, FRAME_CONTENT_SUM, FRAME_CAPACITY, FRAME_LENGTH = -6, -7, -8, -9, -10
+FRAME_BLOCK_SIZE = -11          # the incremental reader's: a block size above its maxBlockSize
 
 
 def frame_exception(code: int) -> Exception:
@@ -528,6 +529,7 @@ def frame_exception(code: int) -> Exception:
             FRAME_CONTENT_SUM: lambda: InvalidDataException("Invalid content checksum"),
             FRAME_CAPACITY: lambda: InvalidDataException("Decoded frame does not fit its target"),
             FRAME_LENGTH: lambda: InvalidDataException("Content length does not match the frame header"),
+            FRAME_BLOCK_SIZE: lambda: InvalidDataException("LZ4 frame block size is above the reader's maxBlockSize"),
             }.get(int(code), lambda: RuntimeError(f"unknown frame result {int(code)}"))()
 
 
@@ -751,3 +753,172 @@ class FrameWriterDevice:
     def close(self, data=None, off=0, length=None, dst_cap=None):
         """CloseFrame; with data, the bytes are written first (Write then CloseFrame in one call)"""
         return self._call(data, off, 0 if length is None else length, FWRITE_CLOSE, dst_cap)
+
+
+# ---- incremental frame reader: many LZ4FrameReaders, one ReadManyBytes / OpenFrame each per call (k4lz4_frame_read_batch*,
+# DESIGN.md 4.14) ------------------------------------------------------------------------------------------------------------
+FREAD_READ, FREAD_OPEN, FREAD_RESET = 0, 1, 2
+FREAD_INTERACTIVE = 1
+FRQ_BYTES_READ, FRQ_FRAME_LENGTH, FRQ_PHASE, FRQ_CODE, FRQ_BLOCKS, FRQ_DIRECT, FRQ_FAST, FRQ_HANDED_BACK, FRQ_WORDS = 0, 1, 2, 3, 4, 5, 6, 7, 8
+
+
+class FrameReaderRecord(_C.Structure):        # k4lz4_frame_reader: the settings and the per-stream store size, host memory
+    _fields_ = [("maxBlockSize", _C.c_int32), ("reserved", _C.c_int32), ("storeBytes", _C.c_int64)]
+
+
+def frame_reader_record(max_block_size: int, lib) -> FrameReaderRecord:
+    rec = FrameReaderRecord()
+    settings = (_C.c_int32 * 2)(int(max_block_size), 0)
+    if lib.k4lz4_frame_reader_init(_C.byref(rec), settings) != 0:
+        raise ValueError(f"maxBlockSize {max_block_size} is above 4 MiB")
+    return rec
+
+
+def _store_offsets(n: int, rec: FrameReaderRecord):
+    return (np.arange(n, dtype=np.uint64) * np.uint64(rec.storeBytes)).astype(np.uint64)
+
+
+class LZ4FrameReaderBatch:
+    """n LZ4FrameReaders (Frames/LZ4FrameReader*.cs, what LZ4DecoderStream.Read drives) advanced together over sources held in host
+    memory: Read(counts) is one ReadManyBytes(count) per stream and returns, per stream, the bytes it delivers (b"" at the end of a
+    frame and at the end of the source, None where the count is None or negative); Open() is one OpenFrame.  The readers' state lives
+    in device memory; every call sends the sources up and brings the bytes back (k4lz4_frame_read_batch).  A stream that fails raises
+    the reader's exception (the lowest-index one) when raise_errors, else reports None and its K4LZ4_FRAME_* code in LastCodes; it
+    stays failed.  maxBlockSize: the largest block size a frame may declare (the stores are sized by it)."""
+
+    def __init__(self, sources, maxBlockSize: int = 4 << 20, ctx: Optional[_native.Context] = None, raise_errors: bool = True):
+        import torch
+        self.ctx = ctx or _native.default_context()
+        self.views = [_ro_view(s, "source") for s in sources]
+        self.n = len(self.views)
+        self.raise_errors = raise_errors
+        self.record = frame_reader_record(maxBlockSize, self.ctx.lib)
+        self.store_off = _store_offsets(self.n, self.record)
+        dev = int(self.ctx.lib.k4lz4_ctx_device(self.ctx.handle))
+        self.store = torch.empty(max(self.n, 1) * int(self.record.storeBytes) + 64, dtype=torch.uint8, device=f"cuda:{dev}")
+        self.src, soff, _ = pack_blocks(self.views) if self.n else (np.zeros(16, np.uint8), np.zeros(0, np.uint64), None)
+        self.src_off = np.ascontiguousarray(soff, np.uint64)
+        self.src_len = np.array([v.size for v in self.views], np.uint64)
+        self.LastCodes = np.zeros(self.n, np.int64)
+        self._call(FREAD_RESET, np.zeros(self.n, np.int64), False)
+
+    def _call(self, op: int, counts: np.ndarray, interactive: bool):
+        caps = np.maximum(counts, 0).astype(np.uint64) if op == FREAD_READ else np.zeros(self.n, np.uint64)
+        doff = np.zeros(self.n, np.uint64)
+        if self.n > 1:
+            doff[1:] = np.cumsum(caps[:-1])
+        dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
+        out = np.zeros(max(self.n, 1), np.int64)
+        self.ctx.check(self.ctx.lib.k4lz4_frame_read_batch(
+            self.ctx.handle, _C.byref(self.record), self.store.data_ptr(), self.store_off.ctypes.data, self.src.ctypes.data,
+            self.src_off.ctypes.data, self.src_len.ctypes.data, dst.ctypes.data, doff.ctypes.data, counts.ctypes.data, out.ctypes.data,
+            self.n, op, FREAD_INTERACTIVE if interactive else 0))
+        out = out[:self.n]
+        self.LastCodes = np.where(counts >= 0, np.minimum(out, 0), 0)
+        bad = np.flatnonzero(self.LastCodes < 0)
+        if self.raise_errors and bad.size:
+            raise frame_exception(int(self.LastCodes[bad[0]]))
+        return out, dst, doff
+
+    @staticmethod
+    def _counts(counts, n):
+        if len(counts) != n:
+            raise ValueError("one count (or None) per stream")
+        return np.array([-1 if c is None else int(c) for c in counts], np.int64)
+
+    def Read(self, counts, interactive: bool = False) -> List[Optional[bytes]]:
+        counts = self._counts(counts, self.n)
+        out, dst, doff = self._call(FREAD_READ, counts, interactive)
+        return [None if (counts[i] < 0 or out[i] < 0) else dst[int(doff[i]):int(doff[i]) + int(out[i])].tobytes() for i in range(self.n)]
+
+    def Open(self, streams=None) -> List[Optional[bool]]:
+        """OpenFrame per stream: True a frame is open, False the source is at its end, None untouched or failed"""
+        counts = np.array([0 if streams is None or i in streams else -1 for i in range(self.n)], np.int64)
+        out, _, _ = self._call(FREAD_OPEN, counts, False)
+        return [None if (counts[i] < 0 or out[i] < 0) else bool(out[i]) for i in range(self.n)]
+
+    def Query(self) -> np.ndarray:
+        """(n, FRQ_WORDS) int64: bytes read, the open frame's ContentLength or -1, phase, code, blocks read, blocks decoded in place"""
+        q = np.zeros(max(self.n, 1) * FRQ_WORDS, np.int64)
+        self.ctx.check(self.ctx.lib.k4lz4_frame_reader_query(self.ctx.handle, self.store.data_ptr(), self.store_off.ctypes.data, self.n,
+                                                             q.ctypes.data))
+        return q[:self.n * FRQ_WORDS].reshape(self.n, FRQ_WORDS)
+
+    @property
+    def BytesRead(self) -> List[int]:
+        return [int(v) for v in self.Query()[:, FRQ_BYTES_READ]]
+
+    @property
+    def FrameLength(self) -> List[Optional[int]]:
+        """GetFrameLength per stream: opens a frame where none is open, then its ContentLength or None"""
+        self.Open()
+        return [None if v < 0 else int(v) for v in self.Query()[:, FRQ_FRAME_LENGTH]]
+
+
+class FrameReaderDevice:
+    """n LZ4FrameReaders over HBM-resident sources (k4lz4_frame_read_batch_device): stream s is data[off[s] : off[s] + length[s]]
+    (data a uint8 torch tensor; off / length host arrays or device tensors).  read(counts) delivers up to counts[s] bytes per stream
+    (host array or device tensor; negative: the stream sits the call out) and returns (out, out_off, out_len): stream s's bytes of
+    this call are out[out_off[s] : out_off[s] + out_len[s]], out_len an int64 device tensor (negative: a K4LZ4_FRAME_* code).  With
+    out=(buffer, out_off) the bytes go to buffer[out_off[s] : out_off[s] + counts[s]] (host array or device tensor), and with
+    device tensors throughout the call touches no host memory.  Asynchronous on the current torch stream: one kernel, no
+    synchronisation; `dc` is a device.DeviceCodec."""
+
+    def __init__(self, dc, data, off, length, maxBlockSize: int = 4 << 20):
+        import torch
+        self.dc = dc
+        self.data = data
+        self.off, self.length = _dev_i64(off, dc.device), _dev_i64(length, dc.device)
+        self.n = int(self.off.numel())
+        self.record = frame_reader_record(maxBlockSize, dc.lib)
+        self.store_off = torch.from_numpy(_store_offsets(self.n, self.record).astype(np.int64)).to(dc.device)
+        self.store = torch.empty(max(self.n, 1) * int(self.record.storeBytes) + 64, dtype=torch.uint8, device=dc.device)
+        self._zero = torch.zeros(max(self.n, 1), dtype=torch.int64, device=dc.device)
+        self._call(FREAD_RESET, self._zero, None, None, False)
+
+    def _call(self, op, counts, buf, out_off, interactive, max_count=0):
+        import torch
+        from .device import _dp
+        out_len = torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.dc.device)
+        if self.n:
+            self.dc.ctx.check(self.dc.lib.k4lz4_frame_read_batch_device(
+                self.dc.ctx.handle, _C.byref(self.record), _dp(self.store), _dp(self.store_off), _dp(self.data), _dp(self.off),
+                _dp(self.length), _dp(buf), _dp(out_off), _dp(counts), _dp(out_len), self.n, op, FREAD_INTERACTIVE if interactive else 0,
+                int(max_count),
+                _C.c_void_p(self.dc._stream())))
+        return out_len[:self.n]
+
+    def read(self, counts, out=None, interactive: bool = False, max_count: Optional[int] = None):
+        """max_count: an upper bound of the counts (it sizes the fast path's block table); None: taken from host counts, and for
+        device counts 0, which leaves every stream to the general reader"""
+        import torch
+        if max_count is None and not isinstance(counts, torch.Tensor):
+            max_count = int(np.max(np.asarray(counts, np.int64), initial=0))
+        if out is None:
+            c = np.ascontiguousarray(np.broadcast_to(np.asarray(counts.cpu().numpy() if isinstance(counts, torch.Tensor) else counts,
+                                                                np.int64), (self.n,)))
+            caps = (np.maximum(c, 0) + 15) // 16 * 16
+            out_off = np.zeros(self.n, np.int64)
+            if self.n > 1:
+                out_off[1:] = np.cumsum(caps[:-1])
+            buf = torch.empty(int(caps.sum()) + 64, dtype=torch.uint8, device=self.dc.device)
+            counts_d, off_d = _dev_i64(c, self.dc.device), _dev_i64(out_off, self.dc.device)
+        else:
+            buf, out_off = out
+            counts_d, off_d = _dev_i64(counts, self.dc.device), _dev_i64(out_off, self.dc.device)
+        return buf, out_off, self._call(FREAD_READ, counts_d, buf, off_d, interactive, max_count or 0)
+
+    def open(self, streams=None):
+        """OpenFrame per stream: an int64 device tensor of 1 / 0 / K4LZ4_FRAME_* codes"""
+        counts = self._zero if streams is None else _dev_i64([0 if i in streams else -1 for i in range(self.n)], self.dc.device)
+        return self._call(FREAD_OPEN, counts, None, None, False)
+
+    def query(self):
+        """(n, FRQ_WORDS) int64 device tensor, see LZ4FrameReaderBatch.Query"""
+        import torch
+        from .device import _dp
+        q = torch.zeros(max(self.n, 1) * FRQ_WORDS, dtype=torch.int64, device=self.dc.device)
+        if self.n:
+            self.dc.ctx.check(self.dc.lib.k4lz4_frame_reader_query_device(self.dc.ctx.handle, _dp(self.store), _dp(self.store_off), self.n,
+                                                                          _dp(q), _C.c_void_p(self.dc._stream())))
+        return q[:self.n * FRQ_WORDS].reshape(self.n, FRQ_WORDS)
