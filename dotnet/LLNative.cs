@@ -172,7 +172,7 @@ namespace K4os.Compression.LZ4.Engine
 		// incremental frame reader (DESIGN.md 4.14): many LZ4FrameReaders, one ReadManyBytes / OpenFrame each per call; the record holds
 		// the settings and the per-stream store size, everything a reader keeps between calls is in the device store
 		[StructLayout(LayoutKind.Sequential)]
-		public struct k4lz4_frame_reader_settings { public int maxBlockSize, reserved; }
+		public struct k4lz4_frame_reader_settings { public int maxBlockSize, flags; }
 		[StructLayout(LayoutKind.Sequential)]
 		public struct k4lz4_frame_reader { public k4lz4_frame_reader_settings settings; public long storeBytes; }
 		public const int FREAD_OP_READ = 0, FREAD_OP_OPEN = 1, FREAD_OP_RESET = 2, FREAD_INTERACTIVE = 1;
@@ -186,6 +186,15 @@ namespace K4os.Compression.LZ4.Engine
 			IntPtr ctx, k4lz4_frame_reader* r, IntPtr store, IntPtr storeOff, IntPtr src, IntPtr srcOff, IntPtr srcLen, IntPtr dst, IntPtr dstOff,
 			IntPtr count, IntPtr outLen, long n, int op, int flags, long maxCount, IntPtr stream);
 		[DllImport(Lib)] public static extern long k4lz4_frame_read_table_rows(long maxCount);
+		// the same readers fed their sources in pieces (DESIGN.md 4.15): a record made with FREADER_FED, per call the unconsumed part of
+		// each source and whether it is final; consumed and need come back beside outLen
+		public const int FREADER_FED = 1;
+		[DllImport(Lib)] public static extern int k4lz4_frame_read_fed_batch(
+			IntPtr ctx, k4lz4_frame_reader* r, IntPtr store, ulong* storeOff, byte* src, ulong* srcOff, ulong* srcLen, long* final, byte* dst,
+			ulong* dstOff, long* count, long* outLen, long* consumed, long* need, long n, int op, int flags);
+		[DllImport(Lib)] public static extern int k4lz4_frame_read_fed_batch_device(
+			IntPtr ctx, k4lz4_frame_reader* r, IntPtr store, IntPtr storeOff, IntPtr src, IntPtr srcOff, IntPtr srcLen, IntPtr final, IntPtr dst,
+			IntPtr dstOff, IntPtr count, IntPtr outLen, IntPtr consumed, IntPtr need, long n, int op, int flags, long maxCount, IntPtr stream);
 		[DllImport(Lib)] public static extern int k4lz4_frame_reader_query(IntPtr ctx, IntPtr store, ulong* storeOff, long n, long* @out);
 		[DllImport(Lib)] public static extern int k4lz4_frame_reader_query_device(IntPtr ctx, IntPtr store, IntPtr storeOff, long n, IntPtr @out, IntPtr stream);
 

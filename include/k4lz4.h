@@ -537,7 +537,7 @@ K4LZ4_API int k4lz4_frame_write_batch_device(k4lz4_ctx *ctx, k4lz4_frame_writer 
 
 typedef struct k4lz4_frame_reader_settings {
     int32_t maxBlockSize;        /* the largest block size the store holds: rounded up to 64 KiB, 256 KiB, 1 MiB or 4 MiB; <= 0: 4 MiB */
-    int32_t reserved;
+    int32_t flags;               /* 0, or K4LZ4_FREADER_FED: a record for k4lz4_frame_read_fed_batch (below) */
 } k4lz4_frame_reader_settings;
 
 typedef struct k4lz4_frame_reader {
@@ -559,7 +559,7 @@ enum { K4LZ4_FRQ_BYTES_READ = 0,       /* GetBytesRead: over all the frames read
        K4LZ4_FRQ_HANDED_BACK = 7,      /* calls in which the fast path's hypothesis failed for the stream and the general reader replayed it */
        K4LZ4_FRQ_WORDS = 8 };
 
-/* K4LZ4_OK or K4LZ4_E_ARG (a maxBlockSize above 4 MiB) */
+/* K4LZ4_OK or K4LZ4_E_ARG (a maxBlockSize above 4 MiB, unknown flags) */
 K4LZ4_API int k4lz4_frame_reader_init(k4lz4_frame_reader *r, const k4lz4_frame_reader_settings *settings);
 K4LZ4_API int64_t k4lz4_frame_reader_store_bytes(const k4lz4_frame_reader *r);
 /* op: k4lz4_frame_read_op for every stream of the call (RESET: count[s] >= 0 resets stream s's store; src, dst may be NULL for RESET
@@ -587,6 +587,47 @@ K4LZ4_API int64_t k4lz4_frame_read_table_rows(int64_t maxCount);
 K4LZ4_API int k4lz4_frame_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out);
 K4LZ4_API int k4lz4_frame_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out,
                                               void *stream);
+
+/* ---- The incremental frame reader fed its source in pieces ------------------------------------------------
+ * What LZ4DecoderStream does over a socket, a pipe or a file that hands bytes over as they arrive: the reference loops over short
+ * reads of its inner stream until the field it wants is complete (Streams/Internal/ReaderExtensions.cs:10-28), so how a source is
+ * cut into pieces is invisible in what is delivered.  Here stream s's source is the concatenation of the pieces given so far.  For
+ * a call, src[srcOff[s] .. + srcLen[s]) is the part of it the reader has not consumed yet (any length, 0 included) and
+ * final[s] != 0 says that no byte will follow it (final == NULL: none is final).  One READ or OPEN per stream and call.
+ *
+ * A record made with K4LZ4_FREADER_FED has a larger store -- today's, followed by a stash of 4 + maxBlockSize + 4 bytes (rounded to
+ * 256) that holds at most one incomplete field -- and is taken by the _fed calls only; they refuse any other record, and the calls
+ * above refuse a fed record (K4LZ4_E_ARG).  k4lz4_frame_reader_query[_device] read either kind of store.
+ *
+ * starved      the field the reader needs next (the 4 bytes of the magic; FLG / BD; the rest of the header once FLG is known; a
+ *              length word; a payload plus its block checksum; the content checksum behind an EndMark) is not wholly there and
+ *              final[s] == 0: the call ends for that stream with outLen[s] what was delivered so far (0 .. count[s]; OPEN: 0),
+ *              consumed[s] == srcLen[s] (the incomplete field's bytes are kept in the store) and need[s] > 0, the number of further
+ *              bytes with which that field is complete.  Issue the read again with the count reduced by outLen[s] and with further
+ *              source; with fewer than need[s] bytes it delivers nothing and reports what is still missing.  The bytes, the total
+ *              and the code of such a sequence are those of ONE ReadManyBytes(count) over the concatenated source, however it was
+ *              cut.  With final[s] != 0 running out is what it is above: nothing left before a frame is a clean end (0), anything
+ *              else K4LZ4_FRAME_EOF.
+ * not starved  need[s] == 0 and consumed[s] <= srcLen[s]: present the unconsumed rest first in the next call.  Nothing is kept in
+ *              the store then.  A read satisfied exactly at a block's end does not consume the next length word.
+ * defects      are reported in the call in which their bytes are present: a wrong magic after 4 bytes, a bad version after 6, a
+ *              stored length above the block size after the length word.  consumed[s] of a failing call is unspecified.
+ * count[s] < 0 leaves the stream untouched (outLen, consumed, need 0).
+ *
+ * k4lz4_frame_read_fed_batch: store is a device pointer, every other pointer a host pointer; only the pieces go up, through the
+ * context's staging buffers; dst, outLen, consumed and need come back.  Synchronous.  _device: every pointer a device pointer,
+ * maxCount as above; enqueues on `stream` and returns, nothing is read back.  The fast path takes streams with nothing kept and
+ * nothing pending in an independent-block frame, over the records that are wholly in the piece. */
+#define K4LZ4_FREADER_FED 1                /* k4lz4_frame_reader_settings.flags */
+K4LZ4_API int k4lz4_frame_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                         const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final,
+                                         uint8_t *dst, const uint64_t *dstOff, const int64_t *count, int64_t *outLen,
+                                         int64_t *consumed, int64_t *need, int64_t n, int op, int flags);
+K4LZ4_API int k4lz4_frame_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                                const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen,
+                                                const int64_t *final, uint8_t *dst, const uint64_t *dstOff, const int64_t *count,
+                                                int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags,
+                                                int64_t maxCount, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ from .encoders import (LZ4BlockEncoder, LZ4HighChainEncoder, LZ4FastChainEncoder
                        FAST_CHAIN_STATE)
 from .frames import (LZ4Frame, LZ4EncoderSettings, LZ4Descriptor, parse_frame, xxh32_many, encode_fast_chain_frames,
                      frame_sizes_device, decode_frames_device, frame_exception, LZ4FrameWriterBatch, FrameWriterDevice,
-                     LZ4FrameReaderBatch, FrameReaderDevice)
+                     LZ4FrameReaderBatch, FrameReaderDevice, LZ4FrameFedReaderBatch, FrameFedReaderDevice)
 from .legacy import (LZ4Legacy, EndOfStreamException, OverflowException, NotSupportedException, ArgumentException, legacy_exception,
                      wrap_device, unwrap_device, encode_legacy_streams_device, legacy_stream_sizes_device, decode_legacy_streams_device)
 from ._native import NativeLibraryError, Context, load_library, default_context, host_register, host_unregister
@@ -20,5 +20,6 @@ __all__ = ["LZ4Codec", "LZ4Level", "LZ4Pickler", "InvalidDataException", "Native
            "LZ4EncoderSettings", "LZ4Descriptor", "parse_frame", "xxh32_many", "encode_fast_chain_packed", "encode_fast_chain_device",
            "fast_chain_blocks", "FAST_CHAIN_STATE", "encode_fast_chain_frames",
            "frame_sizes_device", "decode_frames_device", "frame_exception", "LZ4FrameWriterBatch", "FrameWriterDevice", "LZ4FrameReaderBatch", "FrameReaderDevice",
+           "LZ4FrameFedReaderBatch", "FrameFedReaderDevice",
            "LZ4Legacy", "EndOfStreamException", "OverflowException", "NotSupportedException", "ArgumentException", "legacy_exception",
            "wrap_device", "unwrap_device", "encode_legacy_streams_device", "legacy_stream_sizes_device", "decode_legacy_streams_device"]

@@ -59,6 +59,8 @@ struct FrState {
     unsigned long long handedBack;   /* calls in which the fast path's hypothesis failed and the general reader replayed the stream */
     FwXxhState content;              /* XXH32.State of the content checksum */
     FwXxhState scratch;              /* a block checksum in the making */
+    uint32_t stashFill;              /* fed records (k4lz4_frame_feed.hpp): bytes of an incomplete field kept behind the buffer */
+    uint32_t stashWant;              /* ... and the length with which that field is complete (0: nothing is awaited) */
 };
 static_assert(sizeof(FrState) <= (size_t)FR_STATE_BYTES, "FrState outgrew its slot");
 

@@ -763,12 +763,16 @@ FRQ_BYTES_READ, FRQ_FRAME_LENGTH, FRQ_PHASE, FRQ_CODE, FRQ_BLOCKS, FRQ_DIRECT, F
 
 
 class FrameReaderRecord(_C.Structure):        # k4lz4_frame_reader: the settings and the per-stream store size, host memory
-    _fields_ = [("maxBlockSize", _C.c_int32), ("reserved", _C.c_int32), ("storeBytes", _C.c_int64)]
+    _fields_ = [("maxBlockSize", _C.c_int32), ("flags", _C.c_int32), ("storeBytes", _C.c_int64)]
 
 
-def frame_reader_record(max_block_size: int, lib) -> FrameReaderRecord:
+FREADER_FED = 1
+
+
+def frame_reader_record(max_block_size: int, lib, fed: bool = False) -> FrameReaderRecord:
+    """fed: a record for the fed calls (k4lz4_frame_read_fed_batch[_device]); its store has a stash behind the buffer"""
     rec = FrameReaderRecord()
-    settings = (_C.c_int32 * 2)(int(max_block_size), 0)
+    settings = (_C.c_int32 * 2)(int(max_block_size), FREADER_FED if fed else 0)
     if lib.k4lz4_frame_reader_init(_C.byref(rec), settings) != 0:
         raise ValueError(f"maxBlockSize {max_block_size} is above 4 MiB")
     return rec
@@ -915,6 +919,182 @@ class FrameReaderDevice:
 
     def query(self):
         """(n, FRQ_WORDS) int64 device tensor, see LZ4FrameReaderBatch.Query"""
+        import torch
+        from .device import _dp
+        q = torch.zeros(max(self.n, 1) * FRQ_WORDS, dtype=torch.int64, device=self.dc.device)
+        if self.n:
+            self.dc.ctx.check(self.dc.lib.k4lz4_frame_reader_query_device(self.dc.ctx.handle, _dp(self.store), _dp(self.store_off), self.n,
+                                                                          _dp(q), _C.c_void_p(self.dc._stream())))
+        return q[:self.n * FRQ_WORDS].reshape(self.n, FRQ_WORDS)
+
+
+class LZ4FrameFedReaderBatch:
+    """n LZ4FrameReaders whose sources arrive in pieces (k4lz4_frame_read_fed_batch): what LZ4DecoderStream does
+    over a socket or a pipe.  Feed(pieces, final) appends to a per-stream host queue; Read(counts) presents each stream's unconsumed
+    bytes to one ReadManyBytes per stream, drops what was consumed and returns the bytes delivered; Need[s] > 0 then says that the
+    read is starved: the field it stands at wants that many further bytes, and the same read is to be issued again with the count
+    reduced by what it delivered once more has been fed.  ReadAll(counts) does that over what is queued.  Every source byte goes up
+    once.  Errors as LZ4FrameReaderBatch."""
+
+    def __init__(self, n: int, maxBlockSize: int = 4 << 20, ctx: Optional[_native.Context] = None, raise_errors: bool = True):
+        import torch
+        self.ctx = ctx or _native.default_context()
+        self.n = int(n)
+        self.raise_errors = raise_errors
+        self.record = frame_reader_record(maxBlockSize, self.ctx.lib, fed=True)
+        self.store_off = _store_offsets(self.n, self.record)
+        dev = int(self.ctx.lib.k4lz4_ctx_device(self.ctx.handle))
+        self.store = torch.empty(max(self.n, 1) * int(self.record.storeBytes) + 64, dtype=torch.uint8, device=f"cuda:{dev}")
+        self.queue = [bytearray() for _ in range(self.n)]
+        self.final = np.zeros(self.n, np.int64)
+        self.LastCodes = np.zeros(self.n, np.int64)
+        self.Need = np.zeros(self.n, np.int64)
+        self.Consumed = np.zeros(self.n, np.int64)
+        self.call(FREAD_RESET, [b""] * self.n, self.final, np.zeros(self.n, np.int64), False)
+
+    def call(self, op: int, pieces, final, counts, interactive: bool):
+        """the raw call: pieces[s] is the part of stream s's source that has not been consumed yet -> (outLen, [bytes], consumed, need)"""
+        n = self.n
+        counts = np.ascontiguousarray(counts, np.int64)
+        final = np.ascontiguousarray(final, np.int64)
+        views = [_ro_view(p, "piece") for p in pieces]
+        src, soff, _ = pack_blocks(views) if n else (np.zeros(16, np.uint8), np.zeros(0, np.uint64), None)
+        src_off = np.ascontiguousarray(soff, np.uint64)
+        src_len = np.array([v.size for v in views], np.uint64)
+        caps = np.maximum(counts, 0).astype(np.uint64) if op == FREAD_READ else np.zeros(n, np.uint64)
+        doff = np.zeros(n, np.uint64)
+        if n > 1:
+            doff[1:] = np.cumsum(caps[:-1])
+        dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
+        out, consumed, need = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+        self.ctx.check(self.ctx.lib.k4lz4_frame_read_fed_batch(
+            self.ctx.handle, _C.byref(self.record), self.store.data_ptr(), self.store_off.ctypes.data, src.ctypes.data,
+            src_off.ctypes.data, src_len.ctypes.data, final.ctypes.data, dst.ctypes.data, doff.ctypes.data, counts.ctypes.data,
+            out.ctypes.data, consumed.ctypes.data, need.ctypes.data, n, op, FREAD_INTERACTIVE if interactive else 0))
+        out = out[:n]
+        data = [dst[int(doff[i]):int(doff[i]) + max(int(out[i]), 0)].tobytes() if op == FREAD_READ else b"" for i in range(n)]
+        return out, data, consumed[:n], need[:n]
+
+    def Feed(self, pieces, final=None) -> None:
+        """pieces[s]: the next bytes of stream s's source (None: none now); final[s]: no byte follows them"""
+        if len(pieces) != self.n or (final is not None and len(final) != self.n):
+            raise ValueError("one piece (or None) per stream")
+        for i, p in enumerate(pieces):
+            if p is not None and len(p):
+                if self.final[i]:
+                    raise ValueError(f"stream {i} was fed its final piece already")
+                self.queue[i] += bytes(p)
+            if final is not None and final[i]:
+                self.final[i] = 1
+
+    def _queued(self, op, counts, interactive):
+        out, data, consumed, need = self.call(op, [bytes(q) for q in self.queue], self.final, counts, interactive)
+        for i in range(self.n):
+            if counts[i] >= 0 and out[i] >= 0:
+                del self.queue[i][:int(consumed[i])]
+        self.Consumed, self.Need = consumed.copy(), np.where(out >= 0, need, 0)
+        self.LastCodes = np.where(counts >= 0, np.minimum(out, 0), 0)
+        bad = np.flatnonzero(self.LastCodes < 0)
+        if self.raise_errors and bad.size:
+            raise frame_exception(int(self.LastCodes[bad[0]]))
+        return out, data
+
+    def Read(self, counts, interactive: bool = False) -> List[Optional[bytes]]:
+        counts = LZ4FrameReaderBatch._counts(counts, self.n)
+        out, data = self._queued(FREAD_READ, counts, interactive)
+        return [None if (counts[i] < 0 or out[i] < 0) else data[i] for i in range(self.n)]
+
+    def ReadAll(self, counts, interactive: bool = False) -> List[Optional[bytes]]:
+        """a logical read over what is queued: a starved stream is read again while its queue holds the bytes it needs"""
+        left = LZ4FrameReaderBatch._counts(counts, self.n)
+        acc: List[Optional[bytearray]] = [None if c < 0 else bytearray() for c in left]
+        while (left >= 0).any():
+            got = self.Read([None if c < 0 else int(c) for c in left], interactive)
+            for i in range(self.n):
+                if left[i] < 0:
+                    continue
+                if got[i] is None:
+                    acc[i], left[i] = None, -1
+                    continue
+                acc[i] += got[i]
+                again = self.Need[i] > 0 and len(self.queue[i]) > 0
+                left[i] = left[i] - len(got[i]) if again else -1
+        return [None if a is None else bytes(a) for a in acc]
+
+    def Open(self, streams=None) -> List[Optional[bool]]:
+        """OpenFrame per stream: True a frame is open, False the source is at its end or (Need[s] > 0) the header is not all there"""
+        counts = np.array([0 if streams is None or i in streams else -1 for i in range(self.n)], np.int64)
+        out, _ = self._queued(FREAD_OPEN, counts, False)
+        return [None if (counts[i] < 0 or out[i] < 0) else bool(out[i]) for i in range(self.n)]
+
+    def Query(self) -> np.ndarray:
+        q = np.zeros(max(self.n, 1) * FRQ_WORDS, np.int64)
+        self.ctx.check(self.ctx.lib.k4lz4_frame_reader_query(self.ctx.handle, self.store.data_ptr(), self.store_off.ctypes.data, self.n,
+                                                             q.ctypes.data))
+        return q[:self.n * FRQ_WORDS].reshape(self.n, FRQ_WORDS)
+
+    @property
+    def BytesRead(self) -> List[int]:
+        return [int(v) for v in self.Query()[:, FRQ_BYTES_READ]]
+
+
+class FrameFedReaderDevice:
+    """n fed LZ4FrameReaders over pieces in HBM (k4lz4_frame_read_fed_batch_device).  Per call stream s is given
+    data[off[s] : off[s] + length[s]], the part of its source it has not consumed yet, and final[s] (None: none is final); read()
+    returns (out, out_off, out_len, consumed, need), the last three int64 device tensors.  Arguments as FrameReaderDevice.read;
+    asynchronous on the current torch stream, nothing is read back."""
+
+    def __init__(self, dc, n: int, maxBlockSize: int = 4 << 20):
+        import torch
+        self.dc = dc
+        self.n = int(n)
+        self.record = frame_reader_record(maxBlockSize, dc.lib, fed=True)
+        self.store_off = torch.from_numpy(_store_offsets(self.n, self.record).astype(np.int64)).to(dc.device)
+        self.store = torch.empty(max(self.n, 1) * int(self.record.storeBytes) + 64, dtype=torch.uint8, device=dc.device)
+        self._zero = torch.zeros(max(self.n, 1), dtype=torch.int64, device=dc.device)
+        self._call(FREAD_RESET, None, self._zero, self._zero, None, self._zero, None, None, False)
+
+    def _call(self, op, data, off, length, final, counts, buf, out_off, interactive, max_count=0):
+        import torch
+        from .device import _dp
+        out_len, consumed, need = (torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.dc.device) for _ in range(3))
+        if self.n:
+            self.dc.ctx.check(self.dc.lib.k4lz4_frame_read_fed_batch_device(
+                self.dc.ctx.handle, _C.byref(self.record), _dp(self.store), _dp(self.store_off), _dp(data), _dp(off), _dp(length),
+                _dp(final), _dp(buf), _dp(out_off), _dp(counts), _dp(out_len), _dp(consumed), _dp(need), self.n, op,
+                FREAD_INTERACTIVE if interactive else 0, int(max_count), _C.c_void_p(self.dc._stream())))
+        return out_len[:self.n], consumed[:self.n], need[:self.n]
+
+    def _pieces(self, off, length, final):
+        dev = self.dc.device
+        return _dev_i64(off, dev), _dev_i64(length, dev), None if final is None else _dev_i64(final, dev)
+
+    def read(self, data, off, length, final, counts, out=None, interactive: bool = False, max_count: Optional[int] = None):
+        import torch
+        off_d, len_d, fin_d = self._pieces(off, length, final)
+        if max_count is None and not isinstance(counts, torch.Tensor):
+            max_count = int(np.max(np.asarray(counts, np.int64), initial=0))
+        if out is None:
+            c = np.ascontiguousarray(np.broadcast_to(np.asarray(counts.cpu().numpy() if isinstance(counts, torch.Tensor) else counts,
+                                                                np.int64), (self.n,)))
+            caps = (np.maximum(c, 0) + 15) // 16 * 16
+            out_off = np.zeros(self.n, np.int64)
+            if self.n > 1:
+                out_off[1:] = np.cumsum(caps[:-1])
+            buf = torch.empty(int(caps.sum()) + 64, dtype=torch.uint8, device=self.dc.device)
+            counts_d, ooff_d = _dev_i64(c, self.dc.device), _dev_i64(out_off, self.dc.device)
+        else:
+            buf, out_off = out
+            counts_d, ooff_d = _dev_i64(counts, self.dc.device), _dev_i64(out_off, self.dc.device)
+        return (buf, out_off) + self._call(FREAD_READ, data, off_d, len_d, fin_d, counts_d, buf, ooff_d, interactive, max_count or 0)
+
+    def open(self, data, off, length, final, streams=None):
+        """-> (out_len, consumed, need): out_len 1 / 0 / a K4LZ4_FRAME_* code"""
+        off_d, len_d, fin_d = self._pieces(off, length, final)
+        counts = self._zero if streams is None else _dev_i64([0 if i in streams else -1 for i in range(self.n)], self.dc.device)
+        return self._call(FREAD_OPEN, data, off_d, len_d, fin_d, counts, None, None, False)
+
+    def query(self):
         import torch
         from .device import _dp
         q = torch.zeros(max(self.n, 1) * FRQ_WORDS, dtype=torch.int64, device=self.dc.device)
