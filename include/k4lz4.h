@@ -629,6 +629,113 @@ K4LZ4_API int k4lz4_frame_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_fram
                                                 int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags,
                                                 int64_t maxCount, void *stream);
 
+/* ---- LZ4Stream written and read piece by piece: many open K4os.Compression.LZ4.Legacy.LZ4Streams advanced by one Write, Flush,
+ * Dispose or Read each per call ---------------------------------------------------------------------------------
+ * Writer.  For every stream a call returns exactly the bytes the reference's stream pushes to its inner stream during that call.
+ * The reference flushes lazily (LZ4Stream.cs:425-439): a buffer that a Write fills exactly is not emitted by that call -- it goes
+ * out when the next byte arrives, or at Flush / Dispose.  With p pending bytes and L > 0 new ones a WRITE emits
+ * max(0, ceil((p + L) / B) - 1) chunks of B = max(16, blockSize) bytes and leaves p + L - B * emitted pending; L == 0 emits
+ * nothing.  FLUSH emits the pending bytes as one chunk if there are any.  CLOSE writes its bytes first, then flushes, and the
+ * stream is closed.
+ *
+ * k4lz4_legacy_writer is the per-stream record, in HOST memory, owned by the caller.  Everything in it follows from lengths, so a
+ * call advances it without waiting for the device.  The pending bytes (the stream's _buffer) live in a DEVICE store of
+ * k4lz4_legacy_writer_store_bytes(w) bytes at store + storeOff[s], also the caller's; it needs no initialisation. */
+#define K4LZ4_LEGACY_BLOCK_SIZE    (-8)   /* not the reference's: a chunk's U is above the reader's maxBlockSize */
+#define K4LZ4_LEGACY_CLOSED        (-9)   /* not the reference's: the stream was closed by an earlier call */
+
+typedef struct k4lz4_legacy_writer {
+    int32_t blockSize;           /* as applied: max(16, blockSize) */
+    int32_t high;                /* 0: L00_FAST; else L09_HC, HighCompression on every chunk */
+    int32_t pending;             /* _bufferOffset: bytes in the store */
+    int32_t closed;
+} k4lz4_legacy_writer;
+
+enum k4lz4_legacy_write_op { K4LZ4_LWRITE_WRITE = 0, K4LZ4_LWRITE_FLUSH = 1, K4LZ4_LWRITE_CLOSE = 2 };
+
+/* K4LZ4_OK or K4LZ4_E_ARG (a block size above 0x7E000000, the block encoder's longest input) */
+K4LZ4_API int k4lz4_legacy_writer_init(k4lz4_legacy_writer *w, int blockSize, int high);
+K4LZ4_API int64_t k4lz4_legacy_writer_store_bytes(const k4lz4_legacy_writer *w);
+/* the most a call with op can emit for the stream given srcLen new bytes (FLUSH takes none) */
+K4LZ4_API int64_t k4lz4_legacy_write_bound(const k4lz4_legacy_writer *w, int64_t srcLen, int op);
+/* op: k4lz4_legacy_write_op for every stream of the call; srcLen[s] < 0 leaves stream s untouched (outLen 0).  WRITE and CLOSE take
+ * srcLen[s] bytes at src + srcOff[s]; for FLUSH srcLen[s] must be 0.  flags: K4LZ4_FLAG_X32 (LZ4Codec.Enforce32 is read as well).
+ * outLen[s]: the bytes written at dst + dstOff[s]; K4LZ4_LEGACY_CAPACITY (dstCap[s] is below k4lz4_legacy_write_bound) or
+ * K4LZ4_LEGACY_CLOSED, both decided on the host before anything is enqueued -- such a stream keeps its record and store as they
+ * were and the call may be issued again; or K4LZ4_LEGACY_NOT_ENCODED.  A call-level K4LZ4_E_ARG leaves every record as it was.
+ * Only the first chunk of a call can straddle the store and the call's bytes: it is staged into a window; every other chunk is
+ * encoded from src in place.  All chunks of all streams go through the batch encoder in one batch per level (cap U - 1); record
+ * sizes, their scan and the assembly run on the device, then the tail is appended to the store.
+ * _device: src, store, dst and outLen (int64_t) are device pointers, the other arrays host arrays.  It enqueues on `stream` and
+ * returns: nothing is read back.  Before it rewrites its host-side plan it waits until the previous writer call's plan (this
+ * writer's or the frame writer's) has been copied up. */
+K4LZ4_API int k4lz4_legacy_write_batch(k4lz4_ctx *ctx, k4lz4_legacy_writer *w, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                                       const uint64_t *srcOff, const int64_t *srcLen, uint8_t *dst, const uint64_t *dstOff,
+                                       const uint64_t *dstCap, int64_t *outLen, int64_t n, int op, int flags);
+K4LZ4_API int k4lz4_legacy_write_batch_device(k4lz4_ctx *ctx, k4lz4_legacy_writer *w, uint8_t *store, const uint64_t *storeOff,
+                                              const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen, uint8_t *dst,
+                                              const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, int64_t n, int op, int flags,
+                                              void *stream);
+
+/* Reader.  Stream s is src[srcOff[s] .. + srcLen[s]), all of it present at every call (the reader keeps its position, not the
+ * data); nothing outside that range is read.  A READ delivers, byte for byte and exception for exception, what LZ4Stream.Read
+ * (LZ4Stream.cs:349-377) returns for the same sequence of counts: it drains the buffered chunk and acquires chunks
+ * (AcquireNextChunk, :248-294; chunks that produce no bytes are skipped) until count[s] bytes are delivered or the source ends
+ * cleanly; with K4LZ4_LREAD_INTERACTIVE it returns after the first copy.  count 0 acquires nothing; ReadByte is a read of 1.
+ * outLen[s]: the bytes written at dst + dstOff[s] (0 .. count[s]), or the code of the exception the reference throws during that
+ * call -- K4LZ4_LEGACY_END_OF_STREAM, _OVERFLOW, _NOT_SUPPORTED, _INVALID_DATA in AcquireNextChunk's order, as
+ * k4lz4_decode_legacy_streams reports them -- or K4LZ4_LEGACY_BLOCK_SIZE.  A stream that has reported a code is failed: every
+ * later call reports the same code and touches nothing.  The bytes of a failing call's slot are unspecified; nothing outside
+ * [dstOff[s], dstOff[s] + count[s]) is ever written.  count[s] < 0 leaves stream s untouched (outLen 0).
+ *
+ * The state (source position, _bufferOffset, _bufferLength, the code) and one decoded chunk live in a caller-owned DEVICE store of
+ * k4lz4_legacy_reader_store_bytes(r) bytes at store + storeOff[s] (256-byte aligned), reset once (K4LZ4_LREAD_RESET) before its
+ * first use.  The host record holds settings only.  Sources fed in pieces (4.15's contract) are not offered for this format. */
+typedef struct k4lz4_legacy_reader {
+    int32_t maxBlockSize;        /* the largest chunk (U) the store holds; as applied: max(16, asked), asked <= 0: 1 MiB */
+    int32_t reserved;
+    int64_t storeBytes;          /* per stream */
+} k4lz4_legacy_reader;
+
+enum k4lz4_legacy_read_op { K4LZ4_LREAD_READ = 0, K4LZ4_LREAD_RESET = 1 };
+#define K4LZ4_LREAD_INTERACTIVE 1          /* flags: LZ4StreamFlags.InteractiveRead */
+
+/* k4lz4_legacy_reader_query: int64 words per stream */
+enum { K4LZ4_LSQ_POSITION = 0,         /* bytes of the source consumed */
+       K4LZ4_LSQ_BYTES_READ = 1,       /* bytes delivered */
+       K4LZ4_LSQ_PENDING = 2,          /* _bufferLength - _bufferOffset */
+       K4LZ4_LSQ_CODE = 3,             /* the failed stream's code, else 0 */
+       K4LZ4_LSQ_CHUNKS = 4,           /* chunks acquired (those that produce bytes) */
+       K4LZ4_LSQ_DIRECT = 5,           /* of those, made straight in dst by the general kernel */
+       K4LZ4_LSQ_BATCHED = 6,          /* of those, decoded by the batch decoder on the direct path */
+       K4LZ4_LSQ_HANDED_BACK = 7,      /* calls in which the direct path handed the stream back to the general kernel */
+       K4LZ4_LSQ_WORDS = 8 };
+
+/* K4LZ4_OK or K4LZ4_E_ARG (a maxBlockSize above 0x7E000000) */
+K4LZ4_API int k4lz4_legacy_reader_init(k4lz4_legacy_reader *r, int maxBlockSize);
+K4LZ4_API int64_t k4lz4_legacy_reader_store_bytes(const k4lz4_legacy_reader *r);
+/* rows of the direct path's chunk table per stream: min(maxCount / maxBlockSize + 2, 1024) */
+K4LZ4_API int64_t k4lz4_legacy_read_table_rows(const k4lz4_legacy_reader *r, int64_t maxCount);
+/* k4lz4_legacy_read_batch: store is a device pointer, every other pointer a host pointer; synchronous.
+ * _device: every pointer is a device pointer (the per-stream arrays too); enqueues on `stream` and returns.  maxCount: no count[s]
+ * is above it; it bounds the direct path's chunk table (<= 0: the general kernel alone).
+ * Two ways through a READ, decided on the device: streams that read (not interactive) with nothing pending are planned by a walk
+ * over their chunk headers; whole chunks go through the batch decoder straight into dst (stored ones are copied), the chunk that
+ * straddles the read's end into the store.  Interactive streams, streams with bytes pending, streams with more whole chunks than
+ * table rows and streams with a defect in the planned range are read by the general kernel (one wavefront per stream) from their
+ * unchanged state, in the same call. */
+K4LZ4_API int k4lz4_legacy_read_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                      const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                      const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags);
+K4LZ4_API int k4lz4_legacy_read_batch_device(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                             const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                             const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags,
+                                             int64_t maxCount, void *stream);
+/* out[s * K4LZ4_LSQ_WORDS + k]: host form (storeOff, out host arrays; synchronous) and device form (device arrays; asynchronous) */
+K4LZ4_API int k4lz4_legacy_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out);
+K4LZ4_API int k4lz4_legacy_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out,
+                                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

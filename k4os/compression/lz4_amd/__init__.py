@@ -11,7 +11,8 @@ from .frames import (LZ4Frame, LZ4EncoderSettings, LZ4Descriptor, parse_frame, x
                      frame_sizes_device, decode_frames_device, frame_exception, LZ4FrameWriterBatch, FrameWriterDevice,
                      LZ4FrameReaderBatch, FrameReaderDevice, LZ4FrameFedReaderBatch, FrameFedReaderDevice)
 from .legacy import (LZ4Legacy, EndOfStreamException, OverflowException, NotSupportedException, ArgumentException, legacy_exception,
-                     wrap_device, unwrap_device, encode_legacy_streams_device, legacy_stream_sizes_device, decode_legacy_streams_device)
+                     wrap_device, unwrap_device, encode_legacy_streams_device, legacy_stream_sizes_device, decode_legacy_streams_device,
+                     LZ4StreamWriterBatch, LegacyWriterDevice, LZ4StreamReaderBatch, LegacyReaderDevice)
 from ._native import NativeLibraryError, Context, load_library, default_context, host_register, host_unregister
 
 __all__ = ["LZ4Codec", "LZ4Level", "LZ4Pickler", "InvalidDataException", "NativeLibraryError", "Context",
@@ -22,4 +23,5 @@ __all__ = ["LZ4Codec", "LZ4Level", "LZ4Pickler", "InvalidDataException", "Native
            "frame_sizes_device", "decode_frames_device", "frame_exception", "LZ4FrameWriterBatch", "FrameWriterDevice", "LZ4FrameReaderBatch", "FrameReaderDevice",
            "LZ4FrameFedReaderBatch", "FrameFedReaderDevice",
            "LZ4Legacy", "EndOfStreamException", "OverflowException", "NotSupportedException", "ArgumentException", "legacy_exception",
-           "wrap_device", "unwrap_device", "encode_legacy_streams_device", "legacy_stream_sizes_device", "decode_legacy_streams_device"]
+           "wrap_device", "unwrap_device", "encode_legacy_streams_device", "legacy_stream_sizes_device", "decode_legacy_streams_device",
+           "LZ4StreamWriterBatch", "LegacyWriterDevice", "LZ4StreamReaderBatch", "LegacyReaderDevice"]

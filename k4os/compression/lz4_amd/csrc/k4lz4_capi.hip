@@ -40,6 +40,7 @@
 #include "k4lz4_frame_write.hpp"
 #include "k4lz4_frame_reader.hpp"
 #include "k4lz4_frame_feed.hpp"
+#include "k4lz4_legacy_stream.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 
@@ -3438,6 +3439,260 @@ int k4lz4_frame_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint
         return rc;
     return s.finish({{outLen, d_out, (size_t)n * 8}, {consumed, d_cons, (size_t)n * 8}, {need, d_need, (size_t)n * 8}}, dst, dstOff,
                     [&](int64_t i) { return op == K4LZ4_FREAD_READ && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+}
+
+/* ---- LZ4Stream written and read piece by piece (k4lz4_legacy_stream.hpp) ---------------------------------- */
+int k4lz4_legacy_writer_init(k4lz4_legacy_writer *w, int blockSize, int high)
+{
+    if (!w) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_legacy_writer_init: NULL argument");
+    if (blockSize > 0x7E000000) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_legacy_writer_init: block size above 0x7E000000");
+    w->blockSize = std::max(16, blockSize);              /* LZ4Stream.cs:89 */
+    w->high = high ? 1 : 0;
+    w->pending = 0; w->closed = 0;
+    return K4LZ4_OK;
+}
+
+int64_t k4lz4_legacy_writer_store_bytes(const k4lz4_legacy_writer *w) { return w ? k4::ls_w_store_bytes(*w) : 0; }
+
+int64_t k4lz4_legacy_write_bound(const k4lz4_legacy_writer *w, int64_t srcLen, int op)
+{
+    return w && op >= K4LZ4_LWRITE_WRITE && op <= K4LZ4_LWRITE_CLOSE ? k4::ls_w_bound(*w, srcLen, op) : 0;
+}
+
+int k4lz4_legacy_write_batch_device(k4lz4_ctx *ctx, k4lz4_legacy_writer *w, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                                    const uint64_t *srcOff, const int64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                                    int64_t *outLen, int64_t n, int op, int flags, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!w || !store || !storeOff || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (op < K4LZ4_LWRITE_WRITE || op > K4LZ4_LWRITE_CLOSE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_write_batch: unknown op");
+    if (flags & ~(int)K4LZ4_FLAG_X32) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_write_batch: the only flag it takes is K4LZ4_FLAG_X32");
+    if (n == 0) return K4LZ4_OK;
+    for (int64_t i = 0; i < n; i++) {
+        if (op == K4LZ4_LWRITE_FLUSH && srcLen[i] > 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_write_batch: a flush takes no bytes");
+        if (srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+        if (srcLen[i] >= 0 && (w[i].blockSize < 16 || w[i].pending < 0 || w[i].pending > w[i].blockSize))
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_write_batch: the record was not made by k4lz4_legacy_writer_init");
+    }
+    hipStream_t st = (hipStream_t)stream;
+
+    /* ---- the plan: per-stream codes and the chunk table -- host arithmetic over lengths, nothing enqueued yet */
+    std::vector<int32_t> code;
+    k4::LsWLayout L;
+    try { k4::ls_w_layout(w, srcLen, dstCap, n, op, code, L); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    if (L.rows > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_write_batch: more than 2^32 chunks in one call");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* the writers share the plan buffers: the previous upload of a host plan is over before this one is written */
+    if (!ctx->ev_fw) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fw, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fw));
+    try { ctx->h_fw.assign(L.plan_bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    int rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, L.total)) != K4LZ4_OK) return rc;
+    uint8_t *h = ctx->h_fw.data(), *d = ctx->d_fw;
+    k4::ls_w_fill(w, store, storeOff, src, srcOff, srcLen, dstOff, n, op, code, L, h, d);
+
+    /* ---- enqueue: plan up, stage, encode (a batch per level), records, assembly, tails, lengths */
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    K4_HIP(ctx, hipMemcpyAsync(d, h, L.plan_bytes, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
+    k4::LsWriteArgs a{};
+    a.streams = (const k4::LsWStream *)(d + L.o_streams); a.n = n; a.rows = L.rows;
+    a.cSrc = (const uint64_t *)(d + L.o_src); a.cEnc = (const uint64_t *)(d + L.o_enc); a.cLen = (const int32_t *)(d + L.o_len);
+    a.owner = (const uint32_t *)(d + L.o_owner);
+    a.cEncLen = (int32_t *)(d + L.o_elen); a.recLen = (uint64_t *)(d + L.o_rlen); a.recOff = (uint64_t *)(d + L.o_roff);
+    if (L.nstage) hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)L.stage_chunks), dim3(k4::FW_THREADS), 0, st,
+                                     (const k4::FwPiece *)(d + L.o_stage), (long long)L.nstage);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    /* sources and arena slots are addresses (window, store, the caller's bytes): the encoder's bases are null.  The lengths are
+     * on the host, so HC sizes its work area without asking the device. */
+    const int32_t *hlen = (const int32_t *)(h + L.o_len), *dcap = (const int32_t *)(d + L.o_cap);
+    const int xf = flags & K4LZ4_FLAG_X32;
+    if (L.nfast && (rc = launch(ctx, KIND_ENCODE, nullptr, a.cSrc, a.cLen, nullptr, a.cEnc, dcap, a.cEncLen, L.nfast, K4LZ4_L00_FAST,
+                                xf | K4LZ4_FLAG_RAW_RETURN, st, nullptr, hlen)) != K4LZ4_OK)
+        return rc;
+    if (L.rows > L.nfast && (rc = launch(ctx, KIND_ENCODE, nullptr, a.cSrc + L.nfast, a.cLen + L.nfast, nullptr, a.cEnc + L.nfast, dcap + L.nfast,
+                                         a.cEncLen + L.nfast, L.rows - L.nfast, K4LZ4_L09_HC, xf | K4LZ4_FLAG_RAW_RETURN, st, nullptr,
+                                         hlen + L.nfast)) != K4LZ4_OK)
+        return rc;
+    if (L.rows) {
+        hipLaunchKernelGGL(k4::k4_ls_reclen_kernel, dim3((unsigned)((L.rows + 255) / 256)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k4::k4_legacy_scan_kernel, dim3(1), dim3(k4::LEGACY_SCAN_THREADS), 0, st, (const uint64_t *)a.recLen, a.recOff,
+                           (long long)L.rows, (unsigned long long *)(d + L.o_cnt));
+        hipLaunchKernelGGL(k4::k4_ls_assemble_kernel, dim3((unsigned)((L.rows + 3) / 4)), dim3(256), 0, st, a, dst);
+    }
+    if (L.ntail) hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)L.tail_chunks), dim3(k4::FW_THREADS), 0, st,
+                                    (const k4::FwPiece *)(d + L.o_tail), (long long)L.ntail);
+    hipLaunchKernelGGL(k4::k4_ls_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, outLen);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+
+    /* ---- the records: what the calls enqueued leaves them in */
+    for (int64_t i = 0; i < n; i++)
+        if (code[(size_t)i] == 0) k4::ls_w_advance(w[i], srcLen[i], op);
+    return K4LZ4_OK;
+}
+
+int k4lz4_legacy_write_batch(k4lz4_ctx *ctx, k4lz4_legacy_writer *w, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                             const uint64_t *srcOff, const int64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                             int64_t *outLen, int64_t n, int op, int flags)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!w || !store || !storeOff || !srcOff || !srcLen || !dst || !dstOff || !dstCap || !outLen)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (op < K4LZ4_LWRITE_WRITE || op > K4LZ4_LWRITE_CLOSE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_write_batch: unknown op");
+    if (n == 0) return K4LZ4_OK;
+    for (int64_t i = 0; i < n; i++)
+        if (srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* the output slots: what the call can emit, not the caller's capacities (the codes are decided on dstCap all the same) */
+    std::vector<uint64_t> cap((size_t)n);
+    std::vector<int64_t> len0((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        cap[(size_t)i] = std::min<uint64_t>(dstCap[i], (uint64_t)k4::ls_w_bound(w[i], srcLen[i], op));
+        len0[(size_t)i] = op == K4LZ4_LWRITE_FLUSH ? 0 : std::max<int64_t>(srcLen[i], 0);
+    }
+    HostStage s(ctx);
+    s.pack(src, srcOff, len0.data(), n);
+    s.slots(n, [&](int64_t i) { return cap[(size_t)i]; }, false);
+    int64_t *d_out;
+    s.meta(&d_out, n);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_legacy_write_batch_device(ctx, w, store, storeOff, ctx->d_src, s.in_off.data(), srcLen, ctx->d_dst, s.slot.data(), dstCap,
+                                              d_out, n, op, flags, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff, [&](int64_t i) { return outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+}
+
+int k4lz4_legacy_reader_init(k4lz4_legacy_reader *r, int maxBlockSize)
+{
+    if (!r) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_legacy_reader_init: NULL argument");
+    if (maxBlockSize > 0x7E000000) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_legacy_reader_init: maxBlockSize above 0x7E000000");
+    r->maxBlockSize = maxBlockSize <= 0 ? 1 << 20 : std::max(16, maxBlockSize);
+    r->reserved = 0;
+    r->storeBytes = k4::ls_rd_store_bytes(r->maxBlockSize);
+    return K4LZ4_OK;
+}
+
+int64_t k4lz4_legacy_reader_store_bytes(const k4lz4_legacy_reader *r) { return r ? r->storeBytes : 0; }
+int64_t k4lz4_legacy_read_table_rows(const k4lz4_legacy_reader *r, int64_t maxCount) { return r ? k4::ls_table_rows(maxCount, r->maxBlockSize) : 0; }
+
+int k4lz4_legacy_read_batch_device(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                   const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                   const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags,
+                                   int64_t maxCount, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (op < K4LZ4_LREAD_READ || op > K4LZ4_LREAD_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_batch: unknown op");
+    if (flags & ~(int)K4LZ4_LREAD_INTERACTIVE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_batch: the only flag it takes is K4LZ4_LREAD_INTERACTIVE");
+    if (n < 0 || (n > 0 && (!r || !store || !storeOff || !count || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && op == K4LZ4_LREAD_READ && (!src || !srcOff || !srcLen || !dst || !dstOff)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && (r->maxBlockSize < 16 || r->storeBytes != k4::ls_rd_store_bytes(r->maxBlockSize)))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_batch: the record was not made by k4lz4_legacy_reader_init");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    k4::LsReadArgs a{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op,
+                     (flags & K4LZ4_LREAD_INTERACTIVE) ? 1 : 0, r->maxBlockSize, nullptr};
+    const long long rows = k4::ls_table_rows(maxCount, r->maxBlockSize);
+    const unsigned wgrid = (unsigned)((n + k4::LS_WAVES_PER_WG - 1) / k4::LS_WAVES_PER_WG);
+    if (op == K4LZ4_LREAD_READ && !a.interactive && rows > 0) {
+        /* the direct path: plan, the batch decoder into dst and into the stores, check and commit; the table is bounded by
+         * maxCount, so nothing is read back */
+        if (n * rows > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_batch: the chunk table passes 2^31 rows");
+        int rc;
+        if ((rc = grow_scratch(ctx, &ctx->d_frd, &ctx->d_frd_cap, k4::ls_direct_scratch(n, rows))) != K4LZ4_OK) return rc;
+        const size_t nr = (size_t)n * (size_t)rows;
+        uint8_t *m = ctx->d_frd;
+        auto take = [&](size_t bytes) { uint8_t *q = m; m += (bytes + 63) & ~(size_t)63; return q; };
+        k4::LsDirectArgs f{};
+        f.r = a; f.rows = rows;
+        f.plan = (k4::LsPlan *)take((size_t)n * sizeof(k4::LsPlan));
+        f.done = (uint32_t *)take((size_t)n * 4);
+        f.sSrcOff = (uint64_t *)take((size_t)n * 8); f.sDstOff = (uint64_t *)take((size_t)n * 8);
+        f.sSrcLen = (int32_t *)take((size_t)n * 4); f.sDstCap = (int32_t *)take((size_t)n * 4); f.sOutLen = (int32_t *)take((size_t)n * 4);
+        f.srcOff = (uint64_t *)take(nr * 8); f.dstOff = (uint64_t *)take(nr * 8);
+        f.srcLen = (int32_t *)take(nr * 4); f.dstCap = (int32_t *)take(nr * 4); f.outLen = (int32_t *)take(nr * 4);
+        f.rawLen = (uint32_t *)take(nr * 4);
+        hipLaunchKernelGGL(k4::k4_ls_plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f);
+        K4_HIP(ctx, hipGetLastError());
+        if ((rc = launch(ctx, KIND_DECODE, src, f.srcOff, f.srcLen, dst, f.dstOff, f.dstCap, f.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
+            (rc = launch(ctx, KIND_DECODE, src, f.sSrcOff, f.sSrcLen, store, f.sDstOff, f.sDstCap, f.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
+            return rc;
+        hipLaunchKernelGGL(k4::k4_ls_commit_kernel, dim3(wgrid), dim3(64 * k4::LS_WAVES_PER_WG), 0, st, f);
+        a.done = f.done;
+    }
+    hipLaunchKernelGGL(k4::k4_ls_read_kernel, dim3(wgrid), dim3(64 * k4::LS_WAVES_PER_WG), 0, st, a);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_legacy_read_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                            const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const int64_t *count,
+                            int64_t *outLen, int64_t n, int op, int flags)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (op < K4LZ4_LREAD_READ || op > K4LZ4_LREAD_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_batch: unknown op");
+    if (n < 0 || (n > 0 && (!r || !store || !storeOff || !count || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && op == K4LZ4_LREAD_READ && (!srcOff || !srcLen || !dst || !dstOff)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    const bool reads = op == K4LZ4_LREAD_READ;
+    int64_t maxCount = 0;
+    for (int64_t i = 0; reads && i < n; i++) maxCount = std::max(maxCount, count[i]);
+    for (int64_t i = 0; reads && i < n; i++)
+        if (count[i] >= 0 && srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* streams that sit the call out send nothing up */
+    std::vector<int64_t> len0((size_t)n, 0);
+    std::vector<uint64_t> off0((size_t)n, 0);
+    for (int64_t i = 0; reads && i < n; i++)
+        if (count[i] >= 0) { len0[(size_t)i] = (int64_t)srcLen[i]; off0[(size_t)i] = srcOff[i]; }
+    HostStage s(ctx);
+    s.pack(src, off0.data(), len0.data(), n);
+    s.slots(n, [&](int64_t i) { return reads && count[i] > 0 ? (uint64_t)count[i] : 0u; }, false);
+    uint64_t *d_soff, *d_slen, *d_store, *d_doff;
+    int64_t *d_count, *d_out;
+    s.meta(&d_soff, n, s.in_off.data()); s.meta(&d_slen, n, len0.data()); s.meta(&d_store, n, storeOff); s.meta(&d_doff, n, s.slot.data());
+    s.meta(&d_count, n, count); s.meta(&d_out, n);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_legacy_read_batch_device(ctx, r, store, d_store, ctx->d_src, d_soff, d_slen, ctx->d_dst, d_doff, d_count, d_out, n, op, flags,
+                                             maxCount, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff, [&](int64_t i) { return reads && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+}
+
+int k4lz4_legacy_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    hipLaunchKernelGGL(k4::k4_ls_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, store, storeOff, out, (long long)n);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_legacy_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    uint64_t *d_store;
+    int64_t *d_out;
+    s.meta(&d_store, n, storeOff); s.meta(&d_out, n * K4LZ4_LSQ_WORDS);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_legacy_reader_query_device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
+    return s.finish({{out, d_out, (size_t)n * K4LZ4_LSQ_WORDS * 8}});
 }
 
 }  // extern "C"
