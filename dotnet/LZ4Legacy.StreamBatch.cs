@@ -18,7 +18,7 @@ namespace K4os.Compression.LZ4.Legacy
 		public struct Writer { public int blockSize, high, pending, closed; }
 
 		[StructLayout(LayoutKind.Sequential)]
-		public struct Reader { public int maxBlockSize, reserved; public long storeBytes; }
+		public struct Reader { public int maxBlockSize, flags; public long storeBytes; }
 
 		public const int WRITE = 0, FLUSH = 1, CLOSE = 2;
 		public const int READ = 0, RESET = 1, INTERACTIVE = 1, QUERY_WORDS = 8;

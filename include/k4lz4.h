@@ -690,10 +690,11 @@ K4LZ4_API int k4lz4_legacy_write_batch_device(k4lz4_ctx *ctx, k4lz4_legacy_write
  *
  * The state (source position, _bufferOffset, _bufferLength, the code) and one decoded chunk live in a caller-owned DEVICE store of
  * k4lz4_legacy_reader_store_bytes(r) bytes at store + storeOff[s] (256-byte aligned), reset once (K4LZ4_LREAD_RESET) before its
- * first use.  The host record holds settings only.  Sources fed in pieces (4.15's contract) are not offered for this format. */
+ * first use.  The host record holds settings only.  Sources that arrive in pieces (4.15's contract) are read by
+ * k4lz4_legacy_read_fed_batch, below, through a record of its own kind. */
 typedef struct k4lz4_legacy_reader {
     int32_t maxBlockSize;        /* the largest chunk (U) the store holds; as applied: max(16, asked), asked <= 0: 1 MiB */
-    int32_t reserved;
+    int32_t flags;               /* 0, or K4LZ4_LREADER_FED: a record for k4lz4_legacy_read_fed_batch (below) */
     int64_t storeBytes;          /* per stream */
 } k4lz4_legacy_reader;
 
@@ -735,6 +736,57 @@ K4LZ4_API int k4lz4_legacy_read_batch_device(k4lz4_ctx *ctx, const k4lz4_legacy_
 K4LZ4_API int k4lz4_legacy_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out);
 K4LZ4_API int k4lz4_legacy_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out,
                                                void *stream);
+
+/* ---- The incremental LZ4Stream reader fed its source in pieces ---------------------------------------------
+ * What LZ4Stream does in Decompress mode over a socket, a pipe or a file that hands bytes over as they arrive: the reference reads
+ * a chunk's varints one byte at a time (TryReadVarInt, LZ4Stream.cs:133-155) and loops until a payload is complete (ReadBlock,
+ * :176-191), so how a source is cut into pieces is invisible in what Read returns.  Here stream s's source is the concatenation of
+ * the pieces given so far.  For a call, src[srcOff[s] .. + srcLen[s]) is the part of it the reader has not consumed yet (any
+ * length, 0 included) and final[s] != 0 says that no byte will follow it (final == NULL: none is final).  op and flags are
+ * k4lz4_legacy_read_op and K4LZ4_LREAD_INTERACTIVE.
+ *
+ * A record made by k4lz4_legacy_reader_init_fed (flags == K4LZ4_LREADER_FED) has a larger store -- today's, followed by a stash of
+ * 30 + maxBlockSize bytes (rounded to 256: one chunk header, one payload) that holds at most one incomplete field -- and is taken
+ * by the _fed calls only; they refuse any other record, and the calls above refuse a fed record (K4LZ4_E_ARG).
+ * k4lz4_legacy_reader_query[_device] read either kind of store; for a fed stream K4LZ4_LSQ_POSITION is the sum of consumed.
+ *
+ * starved      the field the reader needs next -- the next byte of a chunk header (the flags varint, the U varint, the C varint of a
+ *              compressed chunk: need 1), or a chunk's payload of C bytes (need: the bytes still missing) -- is not wholly there and
+ *              final[s] == 0: the call ends for that stream with outLen[s] what was delivered so far (0 .. count[s]),
+ *              consumed[s] == srcLen[s] (the incomplete field's bytes are kept in the store) and need[s] > 0.  Issue the read again
+ *              with the count reduced by outLen[s] and with further source; with fewer than need[s] bytes it delivers nothing and
+ *              reports what is still missing.  The bytes, the total and the code of such a sequence are those of ONE
+ *              LZ4Stream.Read(count) over the concatenated source, however it was cut.  An interactive read that starves has
+ *              delivered nothing.  With final[s] != 0, no byte left at a chunk boundary is the clean end (the read ends with what it
+ *              has) and running out inside a header or a payload is K4LZ4_LEGACY_END_OF_STREAM -- which, from running out, occurs
+ *              only with final.
+ * not starved  need[s] == 0 and consumed[s] <= srcLen[s]: present the unconsumed rest first in the next call.  Nothing of an
+ *              incomplete field is kept then.  A read satisfied exactly at a chunk's end does not consume the next header byte;
+ *              count 0 consumes nothing.
+ * defects      come when their bytes do, with the codes of the calls above in their order: C > U (END_OF_STREAM) and C < 0
+ *              (OVERFLOW) in the call that completes the header; everything else (passes != 0, U > 255 C + 32, U > maxBlockSize, a
+ *              payload that does not decode to U) in the call that hands over the payload's last byte.  The payload of a chunk that
+ *              is refused whatever its bytes are (U > maxBlockSize, passes != 0) is counted, not kept.  consumed[s] of a failing
+ *              call is unspecified; a failed stream stays failed and touches nothing.
+ * count[s] < 0 leaves the stream untouched (outLen, consumed, need 0).
+ *
+ * k4lz4_legacy_read_fed_batch: store is a device pointer, every other pointer a host pointer; only the pieces go up, through the
+ * context's staging buffers; dst, outLen, consumed and need come back.  Synchronous.  _device: every pointer a device pointer,
+ * maxCount as above (<= 0: the general reader alone); enqueues on `stream` and returns, nothing is read back.  The direct path
+ * takes streams that read (not interactive) with nothing pending and a stash that is empty or that the piece completes: the kept
+ * chunk is completed from the head of the piece and goes through the batch decoder as the first row, the chunks wholly in the piece
+ * follow; where those do not satisfy the count the piece's tail is kept and the read is left starved. */
+#define K4LZ4_LREADER_FED 1                /* k4lz4_legacy_reader.flags */
+K4LZ4_API int k4lz4_legacy_reader_init_fed(k4lz4_legacy_reader *r, int maxBlockSize);
+K4LZ4_API int k4lz4_legacy_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                          const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final,
+                                          uint8_t *dst, const uint64_t *dstOff, const int64_t *count, int64_t *outLen,
+                                          int64_t *consumed, int64_t *need, int64_t n, int op, int flags);
+K4LZ4_API int k4lz4_legacy_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                                 const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen,
+                                                 const int64_t *final, uint8_t *dst, const uint64_t *dstOff, const int64_t *count,
+                                                 int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags,
+                                                 int64_t maxCount, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,8 @@ from .frames import (LZ4Frame, LZ4EncoderSettings, LZ4Descriptor, parse_frame, x
                      LZ4FrameReaderBatch, FrameReaderDevice, LZ4FrameFedReaderBatch, FrameFedReaderDevice)
 from .legacy import (LZ4Legacy, EndOfStreamException, OverflowException, NotSupportedException, ArgumentException, legacy_exception,
                      wrap_device, unwrap_device, encode_legacy_streams_device, legacy_stream_sizes_device, decode_legacy_streams_device,
-                     LZ4StreamWriterBatch, LegacyWriterDevice, LZ4StreamReaderBatch, LegacyReaderDevice)
+                     LZ4StreamWriterBatch, LegacyWriterDevice, LZ4StreamReaderBatch, LegacyReaderDevice,
+                     LZ4StreamFedReaderBatch, LegacyFedReaderDevice)
 from ._native import NativeLibraryError, Context, load_library, default_context, host_register, host_unregister
 
 __all__ = ["LZ4Codec", "LZ4Level", "LZ4Pickler", "InvalidDataException", "NativeLibraryError", "Context",
@@ -24,4 +25,5 @@ __all__ = ["LZ4Codec", "LZ4Level", "LZ4Pickler", "InvalidDataException", "Native
            "LZ4FrameFedReaderBatch", "FrameFedReaderDevice",
            "LZ4Legacy", "EndOfStreamException", "OverflowException", "NotSupportedException", "ArgumentException", "legacy_exception",
            "wrap_device", "unwrap_device", "encode_legacy_streams_device", "legacy_stream_sizes_device", "decode_legacy_streams_device",
-           "LZ4StreamWriterBatch", "LegacyWriterDevice", "LZ4StreamReaderBatch", "LegacyReaderDevice"]
+           "LZ4StreamWriterBatch", "LegacyWriterDevice", "LZ4StreamReaderBatch", "LegacyReaderDevice",
+           "LZ4StreamFedReaderBatch", "LegacyFedReaderDevice"]

@@ -128,6 +128,9 @@ SYMBOLS = {
     "k4lz4_legacy_read_batch_device": (C.c_int, _FREAD + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "k4lz4_legacy_reader_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "k4lz4_legacy_reader_query_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "k4lz4_legacy_reader_init_fed": (C.c_int, [C.c_void_p, C.c_int]),
+    "k4lz4_legacy_read_fed_batch": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int]),
+    "k4lz4_legacy_read_fed_batch_device": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
 }
 
 

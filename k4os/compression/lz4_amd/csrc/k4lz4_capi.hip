@@ -41,6 +41,7 @@
 #include "k4lz4_frame_reader.hpp"
 #include "k4lz4_frame_feed.hpp"
 #include "k4lz4_legacy_stream.hpp"
+#include "k4lz4_legacy_feed.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 
@@ -3571,7 +3572,7 @@ int k4lz4_legacy_reader_init(k4lz4_legacy_reader *r, int maxBlockSize)
     if (!r) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_legacy_reader_init: NULL argument");
     if (maxBlockSize > 0x7E000000) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_legacy_reader_init: maxBlockSize above 0x7E000000");
     r->maxBlockSize = maxBlockSize <= 0 ? 1 << 20 : std::max(16, maxBlockSize);
-    r->reserved = 0;
+    r->flags = 0;
     r->storeBytes = k4::ls_rd_store_bytes(r->maxBlockSize);
     return K4LZ4_OK;
 }
@@ -3693,6 +3694,113 @@ int k4lz4_legacy_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64
     int rc;
     if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_legacy_reader_query_device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
     return s.finish({{out, d_out, (size_t)n * K4LZ4_LSQ_WORDS * 8}});
+}
+
+/* ---- the incremental LZ4Stream reader fed its source in pieces (k4lz4_legacy_feed.hpp) --------------------- */
+int k4lz4_legacy_reader_init_fed(k4lz4_legacy_reader *r, int maxBlockSize)
+{
+    const int rc = k4lz4_legacy_reader_init(r, maxBlockSize);
+    if (rc != K4LZ4_OK) return rc;
+    r->flags = K4LZ4_LREADER_FED;
+    r->storeBytes = k4::ls_fed_store_bytes(r->maxBlockSize);
+    return K4LZ4_OK;
+}
+
+/* the record's kind is checked first: a record of the other family is refused whatever else the call holds */
+static int lfed_args(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, const void *store, const void *storeOff, const void *srcOff, const void *srcLen,
+                     const void *dst, const void *dstOff, const void *count, const void *outLen, const void *consumed, const void *need,
+                     int64_t n, int op, int flags)
+{
+    if (n > 0 && r && (r->flags != K4LZ4_LREADER_FED || r->maxBlockSize < 16 || r->storeBytes != k4::ls_fed_store_bytes(r->maxBlockSize)))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_fed_batch: the record was not made by k4lz4_legacy_reader_init_fed");
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (op < K4LZ4_LREAD_READ || op > K4LZ4_LREAD_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_fed_batch: unknown op");
+    if (flags & ~(int)K4LZ4_LREAD_INTERACTIVE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_fed_batch: the only flag it takes is K4LZ4_LREAD_INTERACTIVE");
+    if (n < 0 || (n > 0 && (!r || !store || !storeOff || !count || !outLen || !consumed || !need))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && op == K4LZ4_LREAD_READ && (!srcOff || !srcLen || !dst || !dstOff)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    return K4LZ4_OK;
+}
+
+int k4lz4_legacy_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                       const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final,
+                                       uint8_t *dst, const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t *consumed,
+                                       int64_t *need, int64_t n, int op, int flags, int64_t maxCount, void *stream)
+{
+    int rc;
+    if ((rc = lfed_args(ctx, r, store, storeOff, srcOff, srcLen, dst, dstOff, count, outLen, consumed, need, n, op, flags)) != K4LZ4_OK) return rc;
+    if (n > 0 && op == K4LZ4_LREAD_READ && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    k4::LsFeedArgs a{{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op,
+                      (flags & K4LZ4_LREAD_INTERACTIVE) ? 1 : 0, r->maxBlockSize, nullptr},
+                     final, consumed, need, nullptr};
+    const long long rows = k4::ls_table_rows(maxCount, r->maxBlockSize);
+    const dim3 waves((unsigned)((n + k4::LS_WAVES_PER_WG - 1) / k4::LS_WAVES_PER_WG)), wg(64 * k4::LS_WAVES_PER_WG);
+    if (op == K4LZ4_LREAD_READ && !a.r.interactive && rows > 0) {
+        /* the direct path: the kept chunks are completed, then 4.16's launches with the fed plan and commit kernels.  The rows hold
+         * addresses (a row's source may be a stash), so the decoder's bases are null. */
+        if (n * rows > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_fed_batch: the chunk table passes 2^31 rows");
+        if ((rc = grow_scratch(ctx, &ctx->d_frd, &ctx->d_frd_cap, k4::ls_feed_direct_scratch(n, rows))) != K4LZ4_OK) return rc;
+        const size_t nr = (size_t)n * (size_t)rows;
+        uint8_t *m = ctx->d_frd;
+        auto take = [&](size_t bytes) { uint8_t *q = m; m += (bytes + 63) & ~(size_t)63; return q; };
+        k4::LsFeedDirectArgs f{};
+        f.f = a; f.rows = rows;
+        f.plan = (k4::LsFeedPlan *)take((size_t)n * sizeof(k4::LsFeedPlan));
+        f.done = (uint32_t *)take((size_t)n * 4); f.head = (uint32_t *)take((size_t)n * 4);
+        f.sSrcAddr = (uint64_t *)take((size_t)n * 8); f.sDstAddr = (uint64_t *)take((size_t)n * 8);
+        f.sSrcLen = (int32_t *)take((size_t)n * 4); f.sDstCap = (int32_t *)take((size_t)n * 4); f.sOutLen = (int32_t *)take((size_t)n * 4);
+        f.srcAddr = (uint64_t *)take(nr * 8); f.dstAddr = (uint64_t *)take(nr * 8);
+        f.srcLen = (int32_t *)take(nr * 4); f.dstCap = (int32_t *)take(nr * 4); f.outLen = (int32_t *)take(nr * 4);
+        f.rawLen = (uint32_t *)take(nr * 4);
+        hipLaunchKernelGGL(k4::k4_ls_feed_topup_kernel, waves, wg, 0, st, f);
+        hipLaunchKernelGGL(k4::k4_ls_feed_plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f);
+        K4_HIP(ctx, hipGetLastError());
+        if ((rc = launch(ctx, KIND_DECODE, nullptr, f.srcAddr, f.srcLen, nullptr, f.dstAddr, f.dstCap, f.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
+            (rc = launch(ctx, KIND_DECODE, nullptr, f.sSrcAddr, f.sSrcLen, nullptr, f.sDstAddr, f.sDstCap, f.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
+            return rc;
+        hipLaunchKernelGGL(k4::k4_ls_feed_commit_kernel, waves, wg, 0, st, f);
+        a.r.done = f.done; a.head = f.head;
+    }
+    hipLaunchKernelGGL(k4::k4_ls_feed_kernel, waves, wg, 0, st, a);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_legacy_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                                const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final, uint8_t *dst, const uint64_t *dstOff,
+                                const int64_t *count, int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags)
+{
+    int rc;
+    if ((rc = lfed_args(ctx, r, store, storeOff, srcOff, srcLen, dst, dstOff, count, outLen, consumed, need, n, op, flags)) != K4LZ4_OK) return rc;
+    if (n == 0) return K4LZ4_OK;
+    const bool reads = op == K4LZ4_LREAD_READ;
+    int64_t maxCount = 0;
+    for (int64_t i = 0; reads && i < n; i++) maxCount = std::max(maxCount, count[i]);
+    for (int64_t i = 0; reads && i < n; i++)
+        if (count[i] >= 0 && srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* only the pieces go up; streams that sit the call out send nothing */
+    std::vector<int64_t> len0((size_t)n, 0), fin0((size_t)n, 0);
+    std::vector<uint64_t> off0((size_t)n, 0);
+    for (int64_t i = 0; reads && i < n; i++)
+        if (count[i] >= 0) { len0[(size_t)i] = (int64_t)srcLen[i]; off0[(size_t)i] = srcOff[i]; fin0[(size_t)i] = final ? final[i] : 0; }
+    HostStage s(ctx);
+    s.pack(src, off0.data(), len0.data(), n);
+    s.slots(n, [&](int64_t i) { return reads && count[i] > 0 ? (uint64_t)count[i] : 0u; }, false);
+    uint64_t *d_soff, *d_slen, *d_store, *d_doff;
+    int64_t *d_count, *d_out, *d_fin, *d_cons, *d_need;
+    s.meta(&d_soff, n, s.in_off.data()); s.meta(&d_slen, n, len0.data()); s.meta(&d_store, n, storeOff); s.meta(&d_doff, n, s.slot.data());
+    s.meta(&d_count, n, count); s.meta(&d_fin, n, fin0.data()); s.meta(&d_out, n); s.meta(&d_cons, n); s.meta(&d_need, n);
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_legacy_read_fed_batch_device(ctx, r, store, d_store, ctx->d_src, d_soff, d_slen, d_fin, ctx->d_dst, d_doff, d_count, d_out,
+                                                 d_cons, d_need, n, op, flags, maxCount, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 8}, {consumed, d_cons, (size_t)n * 8}, {need, d_need, (size_t)n * 8}}, dst, dstOff,
+                    [&](int64_t i) { return reads && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
 }
 
 }  // extern "C"

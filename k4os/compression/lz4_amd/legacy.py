@@ -360,6 +360,7 @@ def decode_legacy_streams_device(dc, streams, off, length, out=None, raise_error
 LWRITE_WRITE, LWRITE_FLUSH, LWRITE_CLOSE = 0, 1, 2
 LREAD_READ, LREAD_RESET = 0, 1
 LREAD_INTERACTIVE = 1
+LREADER_FED = 1
 LSQ_POSITION, LSQ_BYTES_READ, LSQ_PENDING, LSQ_CODE, LSQ_CHUNKS, LSQ_DIRECT, LSQ_BATCHED, LSQ_HANDED_BACK, LSQ_WORDS = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 
@@ -368,7 +369,7 @@ class LegacyWriterRecord(C.Structure):        # k4lz4_legacy_writer: settings an
 
 
 class LegacyReaderRecord(C.Structure):        # k4lz4_legacy_reader
-    _fields_ = [("maxBlockSize", C.c_int32), ("reserved", C.c_int32), ("storeBytes", C.c_int64)]
+    _fields_ = [("maxBlockSize", C.c_int32), ("flags", C.c_int32), ("storeBytes", C.c_int64)]
 
 
 def _per_stream(value, n):
@@ -493,9 +494,10 @@ class LegacyWriterDevice:
         return self._call(data, off, 0 if length is None else length, LWRITE_CLOSE, dst_cap, out)
 
 
-def legacy_reader_record(max_block_size: int, lib) -> LegacyReaderRecord:
+def legacy_reader_record(max_block_size: int, lib, fed: bool = False) -> LegacyReaderRecord:
+    """fed: a record for the _fed calls (k4lz4_legacy_reader_init_fed: the store has a stash behind it)"""
     rec = LegacyReaderRecord()
-    if lib.k4lz4_legacy_reader_init(C.byref(rec), int(max_block_size)) != 0:
+    if (lib.k4lz4_legacy_reader_init_fed if fed else lib.k4lz4_legacy_reader_init)(C.byref(rec), int(max_block_size)) != 0:
         raise ArgumentException(f"maxBlockSize {max_block_size} is too large")
     return rec
 
@@ -613,6 +615,149 @@ class LegacyReaderDevice:
             buf, out_off = out
             counts_d, off_d = _dev_i64(counts, self.dc.device), _dev_i64(out_off, self.dc.device)
         return buf, out_off, self._call(LREAD_READ, counts_d, buf, off_d, interactive, max_count or 0)
+
+    def query(self):
+        """(n, LSQ_WORDS) int64 device tensor, see LZ4StreamReaderBatch.Query"""
+        import torch
+        from .device import _dp
+        q = torch.zeros(max(self.n, 1) * LSQ_WORDS, dtype=torch.int64, device=self.dc.device)
+        if self.n:
+            self.dc.ctx.check(self.dc.lib.k4lz4_legacy_reader_query_device(self.dc.ctx.handle, _dp(self.store), _dp(self.store_off), self.n,
+                                                                           _dp(q), C.c_void_p(self.dc._stream())))
+        return q[:self.n * LSQ_WORDS].reshape(self.n, LSQ_WORDS)
+
+
+# ---- the incremental LZ4Stream reader fed its source in pieces (k4lz4_legacy_read_fed_batch*, DESIGN.md 4.17) ---------------
+class LZ4StreamFedReaderBatch:
+    """n LZ4Streams in Decompress mode whose sources arrive in pieces (sockets, pipes, files read as they grow).  Feed(pieces,
+    final) hands stream s its next bytes (appended behind what it has not consumed yet; final[s]: nothing follows); Read(counts)
+    is one k4lz4_legacy_read_fed_batch over what is held and returns (bytes, consumed, need) per stream: the bytes delivered (None
+    where the count is None or negative, or the stream failed), the source bytes the call consumed, and need > 0 where the read is
+    starved -- it wants that many further bytes before it can go on; issue it again with the count reduced by what it delivered
+    once they are fed.  The bytes, total and code of such a sequence are those of one LZ4Stream.Read(count) over the whole source.
+    Only the pieces travel to the device; the readers' state and stash live there.  Errors as LZ4StreamReaderBatch."""
+
+    def __init__(self, n: int, maxBlockSize: int = 1 << 20, ctx: Optional[_native.Context] = None, raise_errors: bool = True):
+        import torch
+        self.ctx = ctx or _native.default_context()
+        self.n = int(n)
+        self.raise_errors = raise_errors
+        self.record = legacy_reader_record(maxBlockSize, self.ctx.lib, fed=True)
+        self.store_off = (np.arange(self.n, dtype=np.uint64) * np.uint64(self.record.storeBytes)).astype(np.uint64)
+        dev = int(self.ctx.lib.k4lz4_ctx_device(self.ctx.handle))
+        self.store = torch.empty(max(self.n, 1) * int(self.record.storeBytes) + 64, dtype=torch.uint8, device=f"cuda:{dev}")
+        self.held = [bytearray() for _ in range(self.n)]
+        self.final = np.zeros(self.n, np.int64)
+        self.LastCodes = np.zeros(self.n, np.int64)
+        self._call(LREAD_RESET, np.zeros(self.n, np.int64), False)
+
+    def Feed(self, pieces, final=None) -> None:
+        if len(pieces) != self.n:
+            raise ValueError("one piece (or None) per stream")
+        for i, p in enumerate(pieces):
+            if p is not None and len(p):
+                if self.final[i]:
+                    raise ArgumentException(f"stream {i} was fed its final piece already")
+                self.held[i] += bytes(p)
+        if final is not None:
+            self.final |= np.asarray([1 if f else 0 for f in final], np.int64)
+
+    def _call(self, op: int, counts: np.ndarray, interactive: bool):
+        n = self.n
+        lens = np.array([len(h) for h in self.held], np.uint64)
+        soff = np.zeros(n, np.uint64)
+        if n > 1:
+            soff[1:] = np.cumsum(lens[:-1])
+        src = np.frombuffer(b"".join(bytes(h) for h in self.held) + bytes(16), np.uint8)
+        caps = np.maximum(counts, 0).astype(np.uint64) if op == LREAD_READ else np.zeros(n, np.uint64)
+        doff = np.zeros(n, np.uint64)
+        if n > 1:
+            doff[1:] = np.cumsum(caps[:-1])
+        dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
+        out, consumed, need = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+        self.ctx.check(self.ctx.lib.k4lz4_legacy_read_fed_batch(
+            self.ctx.handle, C.byref(self.record), self.store.data_ptr(), self.store_off.ctypes.data, src.ctypes.data, soff.ctypes.data,
+            lens.ctypes.data, self.final.ctypes.data, dst.ctypes.data, doff.ctypes.data, counts.ctypes.data, out.ctypes.data,
+            consumed.ctypes.data, need.ctypes.data, n, op, LREAD_INTERACTIVE if interactive else 0))
+        out, consumed, need = out[:n], consumed[:n], need[:n]
+        for i in range(n):
+            if out[i] >= 0 and consumed[i] > 0:
+                del self.held[i][:int(consumed[i])]
+        self.LastCodes = np.where(counts >= 0, np.minimum(out, 0), 0)
+        if self.raise_errors:
+            _first_error(self.LastCodes)
+        return out, dst, doff, consumed, need
+
+    def Read(self, counts, interactive: bool = False):
+        """-> ([bytes or None], consumed, need)"""
+        if len(counts) != self.n:
+            raise ValueError("one count (or None) per stream")
+        counts = np.array([-1 if c is None else int(c) for c in counts], np.int64)
+        out, dst, doff, consumed, need = self._call(LREAD_READ, counts, interactive)
+        got = [None if (counts[i] < 0 or out[i] < 0) else dst[int(doff[i]):int(doff[i]) + int(out[i])].tobytes() for i in range(self.n)]
+        return got, consumed, need
+
+    def Query(self) -> np.ndarray:
+        """(n, LSQ_WORDS) int64, see LZ4StreamReaderBatch.Query; the position is the sum of consumed"""
+        q = np.zeros(max(self.n, 1) * LSQ_WORDS, np.int64)
+        self.ctx.check(self.ctx.lib.k4lz4_legacy_reader_query(self.ctx.handle, self.store.data_ptr(), self.store_off.ctypes.data, self.n,
+                                                              q.ctypes.data))
+        return q[:self.n * LSQ_WORDS].reshape(self.n, LSQ_WORDS)
+
+
+class LegacyFedReaderDevice:
+    """n LZ4Streams in Decompress mode fed HBM-resident pieces (k4lz4_legacy_read_fed_batch_device).  read(data, off, length, final,
+    counts) takes stream s's unconsumed source from data[off[s] : off[s] + length[s]] (data a uint8 torch tensor; off / length /
+    final / counts host arrays or device tensors; final may be None) and returns (out, out_off, out_len, consumed, need): stream s's
+    bytes of this call are out[out_off[s] : out_off[s] + out_len[s]]; out_len (negative: a K4LZ4_LEGACY_* code), consumed and need
+    are int64 device tensors.  With out=(buffer, out_off) and device tensors throughout the call touches no host memory.
+    Asynchronous on the current torch stream, no synchronisation; `dc` is a device.DeviceCodec."""
+
+    def __init__(self, dc, n: int, maxBlockSize: int = 1 << 20):
+        import torch
+        self.dc = dc
+        self.n = int(n)
+        self.record = legacy_reader_record(maxBlockSize, dc.lib, fed=True)
+        so = np.arange(self.n, dtype=np.int64) * int(self.record.storeBytes)
+        self.store_off = torch.from_numpy(so).to(dc.device)
+        self.store = torch.empty(max(self.n, 1) * int(self.record.storeBytes) + 64, dtype=torch.uint8, device=dc.device)
+        self._zero = torch.zeros(max(self.n, 1), dtype=torch.int64, device=dc.device)
+        self._call(LREAD_RESET, None, self._zero, self._zero, None, self._zero, None, None, False, 0)
+
+    def _call(self, op, data, off, length, final, counts, buf, out_off, interactive, max_count):
+        import torch
+        from .device import _dp
+        out_len, consumed, need = (torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.dc.device) for _ in range(3))
+        if self.n:
+            self.dc.ctx.check(self.dc.lib.k4lz4_legacy_read_fed_batch_device(
+                self.dc.ctx.handle, C.byref(self.record), _dp(self.store), _dp(self.store_off), _dp(data), _dp(off), _dp(length),
+                _dp(final), _dp(buf), _dp(out_off), _dp(counts), _dp(out_len), _dp(consumed), _dp(need), self.n, op,
+                LREAD_INTERACTIVE if interactive else 0, int(max_count), C.c_void_p(self.dc._stream())))
+        return out_len[:self.n], consumed[:self.n], need[:self.n]
+
+    def read(self, data, off, length, final, counts, out=None, interactive: bool = False, max_count: Optional[int] = None):
+        """max_count: an upper bound of the counts (it sizes the direct path's chunk table); None: taken from host counts, and for
+        device counts 0, which leaves every stream to the general reader"""
+        import torch
+        dev = self.dc.device
+        if max_count is None and not isinstance(counts, torch.Tensor):
+            max_count = int(np.max(np.asarray(counts, np.int64), initial=0))
+        off_d, len_d = _dev_i64(off, dev), _dev_i64(length, dev)
+        fin_d = None if final is None else _dev_i64(final, dev)
+        if out is None:
+            c = np.ascontiguousarray(np.broadcast_to(np.asarray(counts.cpu().numpy() if isinstance(counts, torch.Tensor) else counts,
+                                                                np.int64), (self.n,)))
+            caps = (np.maximum(c, 0) + 15) // 16 * 16
+            out_off = np.zeros(self.n, np.int64)
+            if self.n > 1:
+                out_off[1:] = np.cumsum(caps[:-1])
+            buf = torch.empty(int(caps.sum()) + 64, dtype=torch.uint8, device=dev)
+            counts_d, oo_d = _dev_i64(c, dev), _dev_i64(out_off, dev)
+        else:
+            buf, out_off = out
+            counts_d, oo_d = _dev_i64(counts, dev), _dev_i64(out_off, dev)
+        res = self._call(LREAD_READ, data, off_d, len_d, fin_d, counts_d, buf, oo_d, interactive, max_count or 0)
+        return (buf, out_off) + res
 
     def query(self):
         """(n, LSQ_WORDS) int64 device tensor, see LZ4StreamReaderBatch.Query"""
