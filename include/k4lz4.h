@@ -788,6 +788,114 @@ K4LZ4_API int k4lz4_legacy_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_leg
                                                  int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags,
                                                  int64_t maxCount, void *stream);
 
+/* ---- Many open ILZ4Decoders advanced per call -------------------------------------------------------------
+ * Stream s is one decoder as LZ4Decoder.Create(chaining, blockSize, extraBlocks) makes it (Encoders/LZ4Decoder.cs): an
+ * LZ4ChainDecoder (Encoders/LZ4ChainDecoder.cs), or without chaining an LZ4BlockDecoder (Encoders/LZ4BlockDecoder.cs).  Its state
+ * and its ring buffer live in a caller-owned DEVICE store of k4lz4_chain_decoder_store_bytes(d) bytes at store + storeOff[s]
+ * (256-byte aligned), made a fresh decoder by K4LZ4_CDEC_RESET before its first use.  Results are byte for byte and defect for
+ * defect the reference's decoder's for the same sequence of calls.
+ *
+ * The ring is the reference's: 65536 + (1 + extraBlocks) * B + 32 bytes for a chained decoder, B + 8 for an independent one, with
+ * B = blockSize rounded up to a whole KiB, at least 1 KiB.  Prepare(blockSize) moves the last min(index, 64 KiB) bytes to the
+ * front when index + blockSize would pass the end; Inject appends, or (64 KiB and longer) goes to the front, or moves the tail of
+ * the history down first.  The block that follows sees as prefix the ring's bytes before the index, the last 64 KiB of them.  An
+ * independent decoder holds one block: every Decode or Inject replaces what was there, Inject of nothing empties it.
+ *
+ * RUN.  Stream s owns records firstRec[s] .. firstRec[s] + nRec[s] - 1 of the record table, applied in order; nRec[s] == 0 leaves
+ * the stream untouched (outLen 0).  Record r is src[recOff[r] .. + (recLen[r] & 0x7fffffff)): Decode(source, length,
+ * recBlockSize[r]), or with bit 31 of recLen[r] set Inject(source, length).  recBlockSize may be NULL (every record 0).  Chained:
+ * a blockSize <= 0 means B; otherwise it is what Prepare makes room for and the decode's capacity, and a value above
+ * (1 + extraBlocks) * B + 32 is refused with K4LZ4_CDEC_BLOCK_SIZE (this library's own: the reference would write past its buffer
+ * after CopyDict).  Independent: the capacity is B + 8 whatever the value, and a value above B is K4LZ4_CDEC_BLOCK_SIZE (the
+ * reference's InvalidOperationException).  With K4LZ4_CDEC_DRAIN every record's bytes -- Inject's too -- are appended to
+ * dst + dstOff[s] the way DecodeAndDrain calls Drain(target, -decoded, decoded) (Encoders/LZ4EncoderExtensions.cs:305-323; a
+ * Decode record of length 0 then decodes nothing and leaves the decoder as it is, as there); without it nothing is copied and
+ * BytesReady grows.
+ *   recOut[r]   the bytes the record produced (0 is legal for a chained Decode), or its code; K4LZ4_CDEC_NOT_RUN for the records
+ *               behind a failing one
+ *   outLen[s]   the run's total, or the failing record's code
+ * Codes, in the order the reference meets them: K4LZ4_CDEC_BLOCK_SIZE; K4LZ4_CDEC_DECODE (Decode threw: the block does not decode
+ * within its capacity); K4LZ4_CDEC_INJECT (longer than max(B, 64 KiB), than B + 8 for an independent decoder);
+ * K4LZ4_CDEC_TARGET (dstCap[s] has less room left than the record produced -- DecodeAndDrain returning false: the block IS decoded
+ * and stays in the decoder, where a later drain fetches it; the records behind it are not run).  A decoder that reported a code is
+ * not failed: it holds what the reference's object holds after the exception -- Prepare's move applied, the failing block not
+ * counted, the earlier records of the run applied -- and the next call continues from there.  A store that was never reset
+ * answers K4LZ4_CDEC_NO_DECODER.  Nothing outside [dstOff[s], dstOff[s] + dstCap[s]) and the stream's own store is written.
+ *
+ * RESET takes the records (dec[s]) and writes nothing but the stores (outLen 0); a RUN takes no records, the store remembers.
+ * DRAIN is Drain(target, offset, length): offset[s] is relative to BytesReady (<= 0); outLen[s] is length[s], or K4LZ4_CDEC_RANGE
+ * where the reference's range check throws.  It does not change the store.  Peek(offset) is a drain of -offset bytes.
+ *
+ * k4lz4_chain_decode_batch / k4lz4_chain_drain_batch / k4lz4_chain_decoder_query: store is a device pointer, every other pointer
+ * a host pointer; sources and per-stream arrays go through the context's staging buffers; synchronous.  _device: every pointer
+ * is a device pointer (dec and the per-stream arrays too); enqueues on `stream` -- one launch for a RUN, one for a RESET -- and
+ * returns; nothing is read back.  K4LZ4_E_ARG (a store that is not 256-byte aligned, an unknown op or flag, a negative count, in
+ * the host forms a record that k4lz4_chain_decoder_init did not make or a stream whose records lie outside the table) is decided
+ * before anything is enqueued. */
+typedef struct k4lz4_chain_decoder_settings {
+    int32_t blockSize;
+    int32_t extraBlocks;
+    int32_t chaining;            /* 0: LZ4BlockDecoder (extraBlocks is ignored) */
+} k4lz4_chain_decoder_settings;
+
+typedef struct k4lz4_chain_decoder {
+    int32_t blockSize;           /* as rounded: Mem.RoundUp(Math.Max(blockSize, 1 KiB), 1 KiB) */
+    int32_t extraBlocks;         /* as applied: max(extraBlocks, 0); 0 without chaining */
+    int32_t chaining;            /* 0 or 1 */
+    int32_t reserved;
+    int64_t storeBytes;          /* per stream */
+} k4lz4_chain_decoder;
+
+enum k4lz4_chain_decode_op { K4LZ4_CDEC_RUN = 0, K4LZ4_CDEC_RESET = 1 };
+#define K4LZ4_CDEC_DRAIN 1                 /* flags */
+
+#define K4LZ4_CDEC_DECODE       (-1)   /* Decode threw: the block does not decode within its capacity */
+#define K4LZ4_CDEC_INJECT       (-2)   /* Inject threw: longer than the decoder takes */
+#define K4LZ4_CDEC_BLOCK_SIZE   (-3)   /* the per-record blockSize was refused */
+#define K4LZ4_CDEC_TARGET       (-4)   /* DecodeAndDrain returned false: the drain target is too small, the block stays */
+#define K4LZ4_CDEC_NOT_RUN      (-5)   /* a record behind a failing one */
+#define K4LZ4_CDEC_RANGE        (-6)   /* Drain threw: the range is not inside what is ready */
+#define K4LZ4_CDEC_NO_DECODER   (-7)   /* the store was never reset */
+
+/* k4lz4_chain_decoder_query: int64 words per stream */
+enum { K4LZ4_CDQ_BYTES_READY = 0,      /* BytesReady */
+       K4LZ4_CDQ_BLOCK_SIZE = 1,       /* BlockSize */
+       K4LZ4_CDQ_RECORDS = 2,          /* records applied */
+       K4LZ4_CDQ_BYTES = 3,            /* the bytes they produced */
+       K4LZ4_CDQ_CODE = 4,             /* the last run's code, 0 when it reported none */
+       K4LZ4_CDQ_CHAINING = 5,
+       K4LZ4_CDQ_EXTRA_BLOCKS = 6,
+       K4LZ4_CDQ_MOVES = 7,            /* moves inside the ring (a statistic) */
+       K4LZ4_CDQ_WORDS = 8 };
+
+/* host arithmetic, no device needed.  K4LZ4_OK, or K4LZ4_E_ARG (NULL, or a ring above 0x7E000000 bytes) */
+K4LZ4_API int k4lz4_chain_decoder_init(k4lz4_chain_decoder *d, const k4lz4_chain_decoder_settings *settings);
+K4LZ4_API int64_t k4lz4_chain_decoder_store_bytes(const k4lz4_chain_decoder *d);
+/* dec: n records (RESET; ignored by RUN, may be NULL).  nRecords: the record table's rows.  dst, dstOff, dstCap: with
+ * K4LZ4_CDEC_DRAIN.  recOut: nRecords words, of which the rows owned by a stream with nRec[s] > 0 are written and no others;
+ * outLen: n.  k4lz4_chain_drain_batch's host form stages per stream what the decoder holds at most, so a length out of range costs
+ * no room.  src, recOff and recLen may be NULL when the record table is empty (every
+ * nRec[s] is 0): the host form checks that against nRecords, the device form reads them only for a stream that has records. */
+K4LZ4_API int k4lz4_chain_decode_batch(k4lz4_ctx *ctx, const k4lz4_chain_decoder *dec, uint8_t *store, const uint64_t *storeOff,
+                                       const uint8_t *src, const uint64_t *recOff, const uint32_t *recLen, const int32_t *recBlockSize,
+                                       int64_t nRecords, const uint64_t *firstRec, const uint32_t *nRec, uint8_t *dst,
+                                       const uint64_t *dstOff, const uint64_t *dstCap, int32_t *recOut, int64_t *outLen, int64_t n,
+                                       int op, int flags);
+K4LZ4_API int k4lz4_chain_decode_batch_device(k4lz4_ctx *ctx, const k4lz4_chain_decoder *dec, uint8_t *store, const uint64_t *storeOff,
+                                              const uint8_t *src, const uint64_t *recOff, const uint32_t *recLen,
+                                              const int32_t *recBlockSize, const uint64_t *firstRec, const uint32_t *nRec, uint8_t *dst,
+                                              const uint64_t *dstOff, const uint64_t *dstCap, int32_t *recOut, int64_t *outLen, int64_t n,
+                                              int op, int flags, void *stream);
+K4LZ4_API int k4lz4_chain_drain_batch(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, const int64_t *offset,
+                                      const int64_t *length, uint8_t *dst, const uint64_t *dstOff, int64_t *outLen, int64_t n);
+K4LZ4_API int k4lz4_chain_drain_batch_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, const int64_t *offset,
+                                             const int64_t *length, uint8_t *dst, const uint64_t *dstOff, int64_t *outLen, int64_t n,
+                                             void *stream);
+/* out[s * K4LZ4_CDQ_WORDS + k] */
+K4LZ4_API int k4lz4_chain_decoder_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out);
+K4LZ4_API int k4lz4_chain_decoder_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out,
+                                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,15 @@ SYMBOLS = {
     "k4lz4_legacy_reader_init_fed": (C.c_int, [C.c_void_p, C.c_int]),
     "k4lz4_legacy_read_fed_batch": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int]),
     "k4lz4_legacy_read_fed_batch_device": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "k4lz4_chain_decoder_init": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "k4lz4_chain_decoder_store_bytes": (C.c_int64, [C.c_void_p]),
+    # ctx, dec, store, storeOff, src, recOff, recLen, recBlockSize, [nRecords,] firstRec, nRec, dst, dstOff, dstCap, recOut, outLen
+    "k4lz4_chain_decode_batch": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 7 + [C.c_int64, C.c_int, C.c_int]),
+    "k4lz4_chain_decode_batch_device": (C.c_int, [C.c_void_p] * 15 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "k4lz4_chain_drain_batch": (C.c_int, [C.c_void_p] * 8 + [C.c_int64]),
+    "k4lz4_chain_drain_batch_device": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_void_p]),
+    "k4lz4_chain_decoder_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "k4lz4_chain_decoder_query_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 

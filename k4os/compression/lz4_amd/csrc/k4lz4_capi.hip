@@ -42,6 +42,7 @@
 #include "k4lz4_frame_feed.hpp"
 #include "k4lz4_legacy_stream.hpp"
 #include "k4lz4_legacy_feed.hpp"
+#include "k4lz4_chain_decoder.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 
@@ -3801,6 +3802,210 @@ int k4lz4_legacy_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, ui
         return rc;
     return s.finish({{outLen, d_out, (size_t)n * 8}, {consumed, d_cons, (size_t)n * 8}, {need, d_need, (size_t)n * 8}}, dst, dstOff,
                     [&](int64_t i) { return reads && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+}
+
+/* ---- many open ILZ4Decoders advanced per call (k4lz4_chain_decoder.hpp) ------------------------------------ */
+static_assert(sizeof(k4lz4_chain_decoder) == sizeof(k4::CdRecord), "k4lz4_chain_decoder and the kernels' CdRecord are one layout");
+
+int k4lz4_chain_decoder_init(k4lz4_chain_decoder *d, const k4lz4_chain_decoder_settings *settings)
+{
+    if (!d) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_decoder_init: NULL argument");
+    const int64_t B = k4::cd_block_size(settings ? settings->blockSize : 0);
+    const bool chaining = settings && settings->chaining != 0;
+    const int64_t extra = chaining ? std::max<int64_t>(settings->extraBlocks, 0) : 0;
+    if (B > k4::CD_MAX_RING || extra > k4::CD_MAX_RING || k4::cd_ring_length(B, extra, chaining) > k4::CD_MAX_RING)
+        return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_decoder_init: the ring buffer passes 0x7E000000 bytes");
+    d->blockSize = (int32_t)B; d->extraBlocks = (int32_t)extra; d->chaining = chaining ? 1 : 0; d->reserved = 0;
+    d->storeBytes = k4::cd_store_bytes(B, extra, chaining);
+    return K4LZ4_OK;
+}
+
+int64_t k4lz4_chain_decoder_store_bytes(const k4lz4_chain_decoder *d) { return d ? d->storeBytes : 0; }
+
+static int cdec_args(k4lz4_ctx *ctx, const void *dec, const void *store, const void *storeOff, const void *src, const void *recOff,
+                     const void *recLen, const void *firstRec, const void *nRec, const void *dst, const void *dstOff, const void *dstCap,
+                     const void *recOut, const void *outLen, int64_t n, int op, int flags)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (op < K4LZ4_CDEC_RUN || op > K4LZ4_CDEC_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decode_batch: unknown op");
+    if (flags & ~(int)K4LZ4_CDEC_DRAIN) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decode_batch: the only flag it takes is K4LZ4_CDEC_DRAIN");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && ((uintptr_t)store & 255u)) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decode_batch: the store is not 256-byte aligned");
+    if (n > 0 && op == K4LZ4_CDEC_RESET && !dec) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decode_batch: RESET takes the decoders' records");
+    /* src, recOff and recLen belong to the record table, which is empty when every nRec is 0: only the host form, which is told
+       nRecords, can refuse them; the kernel reads none of them for a stream without records */
+    if (n > 0 && op == K4LZ4_CDEC_RUN && (!firstRec || !nRec || !recOut)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && op == K4LZ4_CDEC_RUN && (flags & K4LZ4_CDEC_DRAIN) && (!dst || !dstOff || !dstCap)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_decode_batch_device(k4lz4_ctx *ctx, const k4lz4_chain_decoder *dec, uint8_t *store, const uint64_t *storeOff,
+                                    const uint8_t *src, const uint64_t *recOff, const uint32_t *recLen, const int32_t *recBlockSize,
+                                    const uint64_t *firstRec, const uint32_t *nRec, uint8_t *dst, const uint64_t *dstOff,
+                                    const uint64_t *dstCap, int32_t *recOut, int64_t *outLen, int64_t n, int op, int flags, void *stream)
+{
+    int rc;
+    if ((rc = cdec_args(ctx, dec, store, storeOff, src, recOff, recLen, firstRec, nRec, dst, dstOff, dstCap, recOut, outLen, n, op, flags)) !=
+        K4LZ4_OK)
+        return rc;
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    if (op == K4LZ4_CDEC_RESET) {
+        hipLaunchKernelGGL(k4::k4_cdec_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const k4::CdRecord *)dec, store,
+                           storeOff, outLen, (long long)n);
+    } else {
+        k4::CdRunArgs a{src, recOff, recLen, recBlockSize, firstRec, nRec, store, storeOff, dst, dstOff, dstCap, recOut, outLen, (long long)n,
+                        flags, ctx->d_status};
+        hipLaunchKernelGGL(k4::k4_cdec_run_kernel, dim3((unsigned)((n + k4::DECODE_PAIRS_PER_WG - 1) / k4::DECODE_PAIRS_PER_WG)),
+                           dim3(128 * k4::DECODE_PAIRS_PER_WG), 0, st, a);
+    }
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_decode_batch(k4lz4_ctx *ctx, const k4lz4_chain_decoder *dec, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                             const uint64_t *recOff, const uint32_t *recLen, const int32_t *recBlockSize, int64_t nRecords,
+                             const uint64_t *firstRec, const uint32_t *nRec, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                             int32_t *recOut, int64_t *outLen, int64_t n, int op, int flags)
+{
+    int rc;
+    if ((rc = cdec_args(ctx, dec, store, storeOff, src, recOff, recLen, firstRec, nRec, dst, dstOff, dstCap, recOut, outLen, n, op, flags)) !=
+        K4LZ4_OK)
+        return rc;
+    if (n == 0) return K4LZ4_OK;
+    const bool runs = op == K4LZ4_CDEC_RUN, drains = runs && (flags & K4LZ4_CDEC_DRAIN);
+    if (nRecords < 0 || (runs && nRecords > 0 && (!recOff || !recLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    for (int64_t i = 0; i < n; i++) {
+        if (storeOff[i] & 255u) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decode_batch: a stream's store is not 256-byte aligned");
+        if (runs && firstRec[i] + nRec[i] > (uint64_t)nRecords && nRec[i])
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decode_batch: a stream refers to records outside the record table");
+        if (!runs && (dec[i].blockSize != k4::cd_block_size(dec[i].blockSize) || dec[i].extraBlocks < 0 || (dec[i].chaining & ~1) ||
+                      dec[i].storeBytes != k4::cd_store_bytes(dec[i].blockSize, dec[i].extraBlocks, dec[i].chaining != 0)))
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decode_batch: a record was not made by k4lz4_chain_decoder_init");
+    }
+    /* only the records of streams that run send their bytes up */
+    std::vector<uint8_t> used((size_t)(runs ? nRecords : 0), 0);
+    for (int64_t i = 0; runs && i < n; i++)
+        for (uint32_t k = 0; k < nRec[i]; k++) used[(size_t)(firstRec[i] + k)] = 1;
+    for (int64_t r = 0; runs && r < nRecords; r++)
+        if (used[(size_t)r] && (recLen[r] & 0x7fffffffu) && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    const int64_t nr = runs ? nRecords : 0;
+    s.span(src, recOff, nr, [&](int64_t r) { return used[(size_t)r] ? (uint64_t)(recLen[r] & 0x7fffffffu) : (uint64_t)0; });
+    if (drains) s.slots(n, [&](int64_t i) { return nRec[i] ? dstCap[i] : (uint64_t)0; }, false);
+    uint64_t *d_store, *d_roff = nullptr, *d_first = nullptr, *d_doff = nullptr, *d_dcap = nullptr;
+    uint32_t *d_rlen = nullptr, *d_nrec = nullptr;
+    int32_t *d_rbs = nullptr, *d_rout = nullptr;
+    int64_t *d_out;
+    k4lz4_chain_decoder *d_dec = nullptr;
+    s.meta(&d_store, n, storeOff); s.meta(&d_out, n);
+    if (runs) {
+        s.meta(&d_roff, nr, s.in_off.data()); s.meta(&d_rlen, nr, recLen);
+        if (recBlockSize) s.meta(&d_rbs, nr, recBlockSize);
+        s.meta(&d_first, n, firstRec); s.meta(&d_nrec, n, nRec); s.meta(&d_rout, nr);
+        if (drains) { s.meta(&d_doff, n, s.slot.data()); s.meta(&d_dcap, n, dstCap); }
+    } else {
+        s.meta(&d_dec, n, dec);
+    }
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_chain_decode_batch_device(ctx, d_dec, store, d_store, ctx->d_src, d_roff, d_rlen, d_rbs, d_first, d_nrec, ctx->d_dst, d_doff,
+                                              d_dcap, d_rout, d_out, n, op, flags, s.st)) != K4LZ4_OK)
+        return rc;
+    /* the kernel writes the rows of streams that run and no others: only those reach the caller's recOut */
+    std::vector<int32_t> rout((size_t)nr, 0);
+    /* a stream's slot holds what its records produced before the one that failed, if one did */
+    auto drained = [&](int64_t i) {
+        size_t b = 0;
+        for (uint32_t k = 0; drains && k < nRec[i]; k++) {
+            const int32_t got = rout[(size_t)(firstRec[i] + k)];
+            if (got < 0) break;
+            b += (size_t)got;
+        }
+        return b;
+    };
+    if ((rc = s.finish({{outLen, d_out, (size_t)n * 8}, {rout.data(), d_rout, (size_t)nr * 4}}, dst, dstOff, drained)) != K4LZ4_OK) return rc;
+    for (int64_t r = 0; r < nr; r++)
+        if (used[(size_t)r]) recOut[r] = rout[(size_t)r];
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_drain_batch_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, const int64_t *offset, const int64_t *length,
+                                   uint8_t *dst, const uint64_t *dstOff, int64_t *outLen, int64_t n, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !offset || !length || !dst || !dstOff || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && ((uintptr_t)store & 255u)) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_drain_batch: the store is not 256-byte aligned");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    k4::CdDrainArgs a{store, storeOff, dst, dstOff, offset, length, outLen, (long long)n};
+    hipLaunchKernelGGL(k4::k4_cdec_drain_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, a);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_drain_batch(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, const int64_t *offset, const int64_t *length,
+                            uint8_t *dst, const uint64_t *dstOff, int64_t *outLen, int64_t n)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !offset || !length || !dstOff || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    if ((uintptr_t)store & 255u) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_drain_batch: the store is not 256-byte aligned");
+    for (int64_t i = 0; i < n; i++) {
+        if (storeOff[i] & 255u) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_drain_batch: a stream's store is not 256-byte aligned");
+        if (length[i] > 0 && !dst) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    }
+    /* a range the device will refuse takes no room: the slots are sized by what each decoder holds now */
+    std::vector<int64_t> q((size_t)n * K4LZ4_CDQ_WORDS);
+    int rc;
+    if ((rc = k4lz4_chain_decoder_query(ctx, store, storeOff, n, q.data())) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    s.slots(n, [&](int64_t i) {
+        return length[i] > 0 && length[i] <= q[(size_t)i * K4LZ4_CDQ_WORDS + K4LZ4_CDQ_BYTES_READY] ? (uint64_t)length[i] : (uint64_t)0;
+    }, false);
+    uint64_t *d_store, *d_doff;
+    int64_t *d_offset, *d_length, *d_out;
+    s.meta(&d_store, n, storeOff); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_offset, n, offset); s.meta(&d_length, n, length); s.meta(&d_out, n);
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_chain_drain_batch_device(ctx, store, d_store, d_offset, d_length, ctx->d_dst, d_doff, d_out, n, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff, [&](int64_t i) { return outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+}
+
+int k4lz4_chain_decoder_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    hipLaunchKernelGGL(k4::k4_cdec_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, store, storeOff, out, (long long)n);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_decoder_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    uint64_t *d_store;
+    int64_t *d_out;
+    s.meta(&d_store, n, storeOff); s.meta(&d_out, n * K4LZ4_CDQ_WORDS);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_chain_decoder_query_device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
+    return s.finish({{out, d_out, (size_t)n * K4LZ4_CDQ_WORDS * 8}});
 }
 
 }  // extern "C"

@@ -193,3 +193,57 @@ class DevicePickleBackend:
                         ok = False
                         break
         return plen, t_p, t_u, ok
+
+
+class ChainDecoderDevice:
+    """Many open ILZ4Decoders over device tensors (k4lz4_chain_decode_batch_device / k4lz4_chain_drain_batch_device /
+    k4lz4_chain_decoder_query_device): settings is one (chaining, blockSize, extraBlocks) per decoder, as
+    LZ4Decoder.Create takes them.  Every array of a call is a device tensor, every call is enqueued on the current torch stream and
+    returns; nothing is read back."""
+
+    def __init__(self, settings, dc: Optional[DeviceCodec] = None):
+        from .encoders import chain_decoder_record, ChainDecoderRecord
+        self.dc = dc or DeviceCodec()
+        self.n = len(settings)
+        recs = (ChainDecoderRecord * max(self.n, 1))(*[chain_decoder_record(c, b, e, self.dc.lib) for c, b, e in settings])
+        self.block_size = [int(r.blockSize) for r in recs[:self.n]]
+        self.store_bytes = np.array([r.storeBytes for r in recs[:self.n]], np.int64)
+        off = np.concatenate(([0], np.cumsum(self.store_bytes[:-1]))).astype(np.int64) if self.n else np.zeros(0, np.int64)
+        dev = self.dc.device
+        self.store = torch.empty(int(self.store_bytes.sum()) + 256, dtype=torch.uint8, device=dev)
+        self.store_off = torch.from_numpy(off + (-self.store.data_ptr()) % 256).to(dev)
+        self.records = torch.from_numpy(np.frombuffer(bytes(recs), np.uint8)[:self.n * C.sizeof(ChainDecoderRecord)].copy()).to(dev)
+        self.reset()
+
+    def reset(self, out_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """every store becomes a fresh decoder"""
+        out_len = torch.empty(self.n, dtype=torch.int64, device=self.dc.device) if out_len is None else out_len
+        self.dc.ctx.check(self.dc.lib.k4lz4_chain_decode_batch_device(
+            self.dc.ctx.handle, _dp(self.records), _dp(self.store), _dp(self.store_off), None, None, None, None, None, None, None, None, None, None,
+            _dp(out_len), self.n, 1, 0, C.c_void_p(self.dc._stream())))
+        return out_len
+
+    def run(self, src, rec_off, rec_len, rec_block_size, first_rec, n_rec, rec_out, out_len, dst=None, dst_off=None, dst_cap=None):
+        """one run per decoder: decoder s owns records first_rec[s] .. + n_rec[s] of the table (rec_off uint64, rec_len uint32 with
+        bit 31 = Inject, rec_block_size int32 or None).  With dst / dst_off / dst_cap (uint64) the records' bytes are drained.
+        rec_out (int32 per record) and out_len (int64 per decoder) are written on the device."""
+        drain = dst is not None
+        self.dc.ctx.check(self.dc.lib.k4lz4_chain_decode_batch_device(
+            self.dc.ctx.handle, None, _dp(self.store), _dp(self.store_off), _dp(src), _dp(rec_off), _dp(rec_len), _dp(rec_block_size),
+            _dp(first_rec), _dp(n_rec), _dp(dst), _dp(dst_off), _dp(dst_cap), _dp(rec_out), _dp(out_len), self.n, 0, 1 if drain else 0,
+            C.c_void_p(self.dc._stream())))
+        return out_len
+
+    def drain(self, offset, length, dst, dst_off, out_len):
+        """Drain(target, offset, length) per decoder (offset, length int64; offset relative to BytesReady)"""
+        self.dc.ctx.check(self.dc.lib.k4lz4_chain_drain_batch_device(
+            self.dc.ctx.handle, _dp(self.store), _dp(self.store_off), _dp(offset), _dp(length), _dp(dst), _dp(dst_off), _dp(out_len), self.n,
+            C.c_void_p(self.dc._stream())))
+        return out_len
+
+    def query(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(n, 8) int64 on the device: BytesReady, BlockSize, records applied, bytes decoded, the last code, ..."""
+        out = torch.empty((self.n, 8), dtype=torch.int64, device=self.dc.device) if out is None else out
+        self.dc.ctx.check(self.dc.lib.k4lz4_chain_decoder_query_device(self.dc.ctx.handle, _dp(self.store), _dp(self.store_off), self.n, _dp(out),
+                                                                       C.c_void_p(self.dc._stream())))
+        return out

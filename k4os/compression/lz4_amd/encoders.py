@@ -9,6 +9,8 @@ Mirrors:
                                                               LZ4_saveDictHC over LZ4EncoderBase's ring buffer)
   ILZ4Decoder  (Decode / Inject / Drain / Peek / BytesReady)  Encoders/ILZ4Decoder.cs
   LZ4BlockDecoder(blockSize)                                  Encoders/LZ4BlockDecoder.cs:11-106
+  LZ4ChainDecoder(blockSize, extraBlocks)                     Encoders/LZ4ChainDecoder.cs
+  LZ4Decoder.Create(chaining, blockSize, extraBlocks)         Encoders/LZ4Decoder.cs
   LZ4EncoderExtensions.TopupAndEncode / FlushAndEncode /
       DecodeAndDrain, EncoderAction                           Encoders/LZ4EncoderExtensions.cs:8-205, EncoderAction.cs
   LZ4FastChainEncoder(blockSize, extraBlocks)                 Encoders/LZ4FastChainEncoder.cs (-> LZ4_compress_fast_continue,
@@ -19,7 +21,10 @@ block needs the bytes before it (at most 64 KiB of them), not the parse of the b
 positions its parse visited, so every block depends on the parse of the one before it: one wavefront
 encodes a stream's blocks in order with the table in LDS, many streams side by side
 (k4lz4_encode_fast_chain_batch); the table and indices travel between calls as a state blob
-(k4lz4_fast_chain_state).  Chained *decoding* is frames.py's (k4lz4_decode_chain_batch).
+(k4lz4_fast_chain_state).  Chained *decoding* of a stream that is all there is frames.py's (k4lz4_decode_chain_batch); of
+blocks that arrive over time it is LZ4ChainDecoder's here: the decoder's state and ring buffer live in a device store and every call
+applies a run of Decode / Inject records (k4lz4_chain_decode_batch) -- `LZ4ChainDecoderBatch` for many open
+decoders, `LZ4ChainDecoder` the single ILZ4Decoder over a batch of one, `LZ4Decoder.Create` the reference's factory.
 
 `LZ4BlockEncoder.EncodeBlocks` is the batching front-end the frame writer uses: K blocks, one launch,
 with the reference's allowCopy rule applied on the device; `encode_hc_chain_packed` / `encode_fast_chain_packed`
@@ -28,6 +33,7 @@ for the blocks of one.
 """
 from __future__ import annotations
 
+import ctypes as _C
 import enum
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -593,7 +599,7 @@ def FlushAndEncode(encoder: Union[LZ4BlockEncoder, LZ4HighChainEncoder, LZ4FastC
     return EncoderAction.Copied, -encoded
 
 
-def DecodeAndDrain(decoder: LZ4BlockDecoder, source, target):
+def DecodeAndDrain(decoder: Union[LZ4BlockDecoder, "LZ4ChainDecoder"], source, target):
     """-> (ok, decoded): decodes one block and copies it to the start of target
     (LZ4EncoderExtensions.cs:288-305: false for an empty source, a failed decode or a target too small)"""
     src = _ro_view(source, "source")
@@ -605,3 +611,174 @@ def DecodeAndDrain(decoder: LZ4BlockDecoder, source, target):
         return False, decoded
     decoder.Drain(dst, -decoded, decoded)
     return True, decoded
+
+
+# ---- many open ILZ4Decoders advanced per call (k4lz4_chain_decode_batch) ---------------------------------
+CDEC_RUN, CDEC_RESET = 0, 1
+CDEC_DRAIN = 1
+CDEC_DECODE, CDEC_INJECT, CDEC_BLOCK_SIZE, CDEC_TARGET, CDEC_NOT_RUN, CDEC_RANGE, CDEC_NO_DECODER = -1, -2, -3, -4, -5, -6, -7
+CDQ_BYTES_READY, CDQ_BLOCK_SIZE, CDQ_RECORDS, CDQ_BYTES, CDQ_CODE, CDQ_CHAINING, CDQ_EXTRA_BLOCKS, CDQ_MOVES, CDQ_WORDS = range(9)
+CDEC_INJECT_BIT = 0x80000000
+
+
+class ChainDecoderSettings(_C.Structure):
+    """k4lz4_chain_decoder_settings"""
+    _fields_ = [("blockSize", _C.c_int32), ("extraBlocks", _C.c_int32), ("chaining", _C.c_int32)]
+
+
+class ChainDecoderRecord(_C.Structure):
+    """k4lz4_chain_decoder"""
+    _fields_ = [("blockSize", _C.c_int32), ("extraBlocks", _C.c_int32), ("chaining", _C.c_int32), ("reserved", _C.c_int32),
+                ("storeBytes", _C.c_int64)]
+
+
+def chain_decoder_record(chaining, blockSize: int, extraBlocks: int = 0, lib=None) -> ChainDecoderRecord:
+    """k4lz4_chain_decoder_init: host arithmetic, no device"""
+    lib = lib or _native.load_library()
+    rec = ChainDecoderRecord()
+    _native._check_plain(lib, lib.k4lz4_chain_decoder_init(_C.byref(rec), _C.byref(ChainDecoderSettings(int(blockSize), int(extraBlocks),
+                                                                                                     1 if chaining else 0))))
+    return rec
+
+
+def chain_record_table(records):
+    """per-stream lists of (inject, bytes, blockSize) -> (src, recOff, recLen, recBlockSize, firstRec, nRec), the record table of
+    k4lz4_chain_decode_batch"""
+    flat = [r for rs in records for r in rs]
+    n_rec = np.array([len(rs) for rs in records], np.uint32)
+    first = np.zeros(len(records), np.uint64)
+    if len(records) > 1:
+        first[1:] = np.cumsum(n_rec[:-1].astype(np.uint64))
+    views = [_ro_view(r[1], "source") for r in flat]
+    src, off, _ = pack_blocks(views) if views else (np.zeros(1, np.uint8), np.zeros(0, np.uint64), None)
+    rec_len = np.array([v.size | (CDEC_INJECT_BIT if r[0] else 0) for v, r in zip(views, flat)], np.uint32)
+    rec_bs = np.array([int(r[2]) if len(r) > 2 else 0 for r in flat], np.int32)
+    return src, np.ascontiguousarray(off, np.uint64), rec_len, rec_bs, first, n_rec
+
+
+class LZ4ChainDecoderBatch:
+    """Many open ILZ4Decoders over host arrays (k4lz4_chain_decode_batch / k4lz4_chain_drain_batch / k4lz4_chain_decoder_query):
+    settings is one (chaining, blockSize, extraBlocks) per decoder, as LZ4Decoder.Create takes them.  The stores live in device
+    memory (a torch tensor); every call is synchronous."""
+
+    def __init__(self, settings, ctx: Optional[_native.Context] = None):
+        import torch
+        self.ctx = ctx or _native.default_context()
+        self.lib = self.ctx.lib
+        self.settings = [(1 if c else 0, int(b), int(e)) for c, b, e in settings]
+        self.n = len(self.settings)
+        self.records = (ChainDecoderRecord * max(self.n, 1))(*[chain_decoder_record(c, b, e, self.lib) for c, b, e in self.settings])
+        sizes = np.array([r.storeBytes for r in self.records[:self.n]], np.int64)
+        self.store_off = np.concatenate(([0], np.cumsum(sizes[:-1]))).astype(np.uint64) if self.n else np.zeros(0, np.uint64)
+        self.store = torch.empty(int(sizes.sum()) + 256, dtype=torch.uint8, device=torch.device("cuda", self.ctx.device))
+        self._base = (self.store.data_ptr() + 255) // 256 * 256
+        self.Reset()
+
+    def _subset(self, which):
+        idx = np.arange(self.n) if which is None else np.asarray(list(which), np.int64)
+        return idx, np.ascontiguousarray(self.store_off[idx])
+
+    def Reset(self, which=None) -> None:
+        """the stores of `which` (default: all) become fresh decoders"""
+        idx, off = self._subset(which)
+        if idx.size == 0:
+            return
+        recs = (ChainDecoderRecord * idx.size)(*[self.records[int(i)] for i in idx])
+        out = np.zeros(idx.size, np.int64)
+        self.ctx.check(self.lib.k4lz4_chain_decode_batch(self.ctx.handle, recs, _C.c_void_p(self._base), off.ctypes.data, None, None, None, None, 0,
+                                                         None, None, None, None, None, None, out.ctypes.data, idx.size, CDEC_RESET, 0))
+
+    def Run(self, records, drain: bool = False, caps=None):
+        """records[s]: the run of decoder s, a list of (inject, bytes, blockSize) -- Decode(source, length, blockSize), or Inject where
+        the first word is true; an empty list leaves the decoder untouched.  With drain the bytes of every record are appended to a
+        target of caps[s] bytes, as DecodeAndDrain does.  -> (recOut per decoder, outLen, the drained bytes per decoder)"""
+        n = self.n
+        assert len(records) == n
+        src, roff, rlen, rbs, first, nrec = chain_record_table(records)
+        nr = int(rlen.size)
+        caps = np.zeros(n, np.uint64) if caps is None else np.ascontiguousarray(caps, np.uint64)
+        doff = np.concatenate(([0], np.cumsum(caps[:-1]))).astype(np.uint64) if n else np.zeros(0, np.uint64)
+        dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
+        rec_out = np.zeros(max(nr, 1), np.int32)
+        out = np.zeros(max(n, 1), np.int64)
+        p = lambda a: a.ctypes.data  # noqa: E731
+        self.ctx.check(self.lib.k4lz4_chain_decode_batch(self.ctx.handle, None, _C.c_void_p(self._base), p(self.store_off), p(src), p(roff), p(rlen),
+                                                         p(rbs), nr, p(first), p(nrec), p(dst) if drain else None, p(doff) if drain else None,
+                                                         p(caps) if drain else None, p(rec_out), p(out), n, CDEC_RUN, CDEC_DRAIN if drain else 0))
+        ro = [rec_out[int(f):int(f) + int(k)].tolist() for f, k in zip(first, nrec)]
+        given = [sum(r[:next((j for j, g in enumerate(r) if g < 0), len(r))]) if drain else 0 for r in ro]
+        return ro, out[:n].tolist(), [dst[int(doff[i]):int(doff[i]) + given[i]].tobytes() for i in range(n)]
+
+    def Drain(self, offsets, lengths):
+        """Drain(target, offset, length) per decoder: offset relative to BytesReady (<= 0).  -> per decoder the bytes, or CDEC_RANGE"""
+        n = self.n
+        offsets, lengths = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(lengths, np.int64)
+        # a decoder holds less than its store: a longer range takes no room, the device answers it with CDEC_RANGE
+        held = np.array([r.storeBytes for r in self.records[:n]], np.int64)
+        caps = np.where((lengths > 0) & (lengths <= held), lengths, 0).astype(np.uint64)
+        doff = np.concatenate(([0], np.cumsum(caps[:-1]))).astype(np.uint64) if n else np.zeros(0, np.uint64)
+        dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
+        out = np.zeros(max(n, 1), np.int64)
+        self.ctx.check(self.lib.k4lz4_chain_drain_batch(self.ctx.handle, _C.c_void_p(self._base), self.store_off.ctypes.data, offsets.ctypes.data,
+                                                        lengths.ctypes.data, dst.ctypes.data, doff.ctypes.data, out.ctypes.data, n))
+        return [int(out[i]) if out[i] < 0 else dst[int(doff[i]):int(doff[i]) + int(out[i])].tobytes() for i in range(n)]
+
+    def Query(self) -> np.ndarray:
+        """(n, CDQ_WORDS) int64: BytesReady, BlockSize, records applied, bytes decoded, the last code, ..."""
+        q = np.zeros(max(self.n, 1) * CDQ_WORDS, np.int64)
+        self.ctx.check(self.lib.k4lz4_chain_decoder_query(self.ctx.handle, _C.c_void_p(self._base), self.store_off.ctypes.data, self.n, q.ctypes.data))
+        return q[:self.n * CDQ_WORDS].reshape(self.n, CDQ_WORDS)
+
+
+class LZ4ChainDecoder:
+    """Decoder for dependent blocks (LZ4ChainDecoder.cs): the ILZ4Decoder of one stream, a batch of one underneath.  With
+    chaining=False the same store is an LZ4BlockDecoder on the device (LZ4Decoder.Create uses the host class for that)."""
+
+    def __init__(self, blockSize: int = 65536, extraBlocks: int = 0, ctx: Optional[_native.Context] = None, chaining: bool = True):
+        self._batch = LZ4ChainDecoderBatch([(chaining, blockSize, extraBlocks)], ctx)
+        self._block_size = int(self._batch.records[0].blockSize)
+
+    @property
+    def BlockSize(self) -> int:
+        return self._block_size
+
+    @property
+    def BytesReady(self) -> int:
+        return int(self._batch.Query()[0, CDQ_BYTES_READY])
+
+    def _one(self, inject, source, offset, length, blockSize=0) -> int:
+        src = _ro_view(source, "source")
+        length = src.size - offset if length is None else int(length)
+        rec_out, _, _ = self._batch.Run([[(inject, src[offset:offset + max(length, 0)], blockSize)]])
+        if rec_out[0][0] < 0:
+            raise InvalidOperationException(f"code {rec_out[0][0]}")
+        return rec_out[0][0]
+
+    def Decode(self, source, offset: int = 0, length: Optional[int] = None, blockSize: int = 0) -> int:
+        return self._one(False, source, offset, length, blockSize)
+
+    def Inject(self, source, offset: int = 0, length: Optional[int] = None) -> int:
+        return self._one(True, source, offset, length)
+
+    def Drain(self, target, offset: int, length: int, targetOffset: int = 0) -> None:
+        """offset is relative to the end of the decoded data (negative), LZ4ChainDecoder.cs:96-103"""
+        dst = _rw_view(target, "target")
+        got = self._batch.Drain([int(offset)], [int(length)])[0]
+        if isinstance(got, int):
+            raise InvalidOperationException()
+        dst[targetOffset:targetOffset + length] = np.frombuffer(got, np.uint8)
+
+    def Peek(self, offset: int) -> np.ndarray:
+        """the bytes from BytesReady + offset to BytesReady (LZ4ChainDecoder.cs:106-115): a drain without a length"""
+        ready, offset = self.BytesReady, int(offset)
+        if ready + offset < 0 or offset > 0:
+            raise InvalidOperationException()
+        return np.frombuffer(self._batch.Drain([offset], [-offset])[0], np.uint8)
+
+
+class LZ4Decoder:
+    """Encoders/LZ4Decoder.cs"""
+
+    @staticmethod
+    def Create(chaining: bool, blockSize: int, extraBlocks: int = 0):
+        return LZ4ChainDecoder(blockSize, extraBlocks) if chaining else LZ4BlockDecoder(blockSize)
