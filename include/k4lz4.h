@@ -896,6 +896,110 @@ K4LZ4_API int k4lz4_chain_decoder_query(k4lz4_ctx *ctx, const uint8_t *store, co
 K4LZ4_API int k4lz4_chain_decoder_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out,
                                                void *stream);
 
+/* ---- Many open ILZ4Encoders advanced per call -------------------------------------------------------------
+ * Stream s is one encoder as LZ4Encoder.Create(chaining, level, blockSize, extraBlocks) makes it (Encoders/LZ4Encoder.cs): without
+ * chaining an LZ4BlockEncoder(level, blockSize), with chaining below L03_HC an LZ4FastChainEncoder(blockSize, extraBlocks), from
+ * L03_HC on an LZ4HighChainEncoder(level, blockSize, extraBlocks).  B is blockSize rounded up to a whole KiB, at least 1 KiB, and
+ * extraBlocks at least 0 (LZ4EncoderBase's constructor); the HC level is clamped to L03_HC .. L12_MAX (LZ4HighChainEncoder.cs).
+ * Every block is byte for byte what the reference's encoder object writes for the same sequence of calls.
+ *
+ * k4lz4_chain_encoder is the per-stream record, in HOST memory, owned by the caller: the settings as rounded and the counters
+ * that follow from lengths alone (_inputIndex, _inputPointer, the bytes taken, the fast chain's currentOffset / dictSize, the
+ * blocks emitted).  A call advances them without waiting for the device.  The bytes live in a caller-owned DEVICE store of
+ * k4lz4_chain_encoder_store_bytes(e) bytes at store + storeOff[s] (256-byte aligned): for a chained fast stream its
+ * k4lz4_fast_chain_state, then the ring -- 65536 + (1 + extraBlocks) * B + 32 bytes chained, B + 32 independent, and 8 more as the
+ * reference allocates.  It needs no initialisation.  After a run the ring holds what the reference's InputBuffer holds, from 0 to
+ * _inputPointer.
+ *
+ * RUN.  Stream s owns records firstRec[s] .. firstRec[s] + nRec[s] - 1 of the record table, applied in order; nRec[s] == 0 leaves
+ * the stream untouched (outLen 0).  Record r is one TopupAndEncode(src[recOff[r] .. + recLen[r]), forceEncode, allowCopy)
+ * (Encoders/LZ4EncoderExtensions.cs:117-210), its two switches the bits K4LZ4_CENC_FORCE and K4LZ4_CENC_ALLOW_COPY of recFlags[r];
+ * recLen[r] == 0 with K4LZ4_CENC_FORCE is FlushAndEncode.  Without FORCE the record encodes only when BytesReady == B, with it
+ * from 1 byte: a block shorter than B may stand in the middle of a chained stream.
+ *   recLoaded[r]  what Topup took; less than recLen[r] when the block fills -- the caller offers the rest in a later record
+ *   recOut[r]     the reference's `encoded` before the sign is dropped: > 0 an encoded block, < 0 the block stored raw under
+ *                 allowCopy (its length negated), 0 nothing encoded.  The action: 0 -> None (recLoaded 0) or Loaded; > 0 -> Encoded;
+ *                 < 0 -> Copied
+ *   outLen[s]     the run's total, or a code
+ * The run's blocks are appended to dst + dstOff[s] in record order, each right behind the one before it (the reference's caller
+ * advancing its target by |encoded|).  Nothing outside [dstOff[s], dstOff[s] + dstCap[s]) and the stream's own store is written.
+ *
+ * K4LZ4_CENC_TARGET: dstCap[s] is below k4lz4_chain_encode_bound(e, the run) -- the sum, over the blocks the run will encode (which
+ * follow from lengths alone), of k4lz4_compress_bound(len), or of len where the record allows copying.  The stream keeps its
+ * record and store and none of the run's Topups is applied (recLoaded and recOut 0).  This rule is this library's own and stricter
+ * than the reference, which throws only when a block really does not fit its target.  It is decided on the host before anything is
+ * enqueued, and so is K4LZ4_E_ARG at call level: a chained fast stream under K4LZ4_FLAG_X32 / Enforce32 (independent encoders
+ * honour it, as k4lz4_encode_batch does), a chained stream past 2 GB (the encoders' renormalisation), a store that is not 256-byte
+ * aligned, unknown flags or record flags, a record longer than INT32_MAX, records outside the table.  A call-level failure leaves
+ * every record as it was.
+ *
+ * RESET makes fresh encoders: it zeroes the records' counters (and a chained fast stream's state in the store).  What an
+ * ILZ4Encoder answers -- BytesReady = pointer - index, BlockSize -- is host arithmetic on the record and needs no call.
+ *
+ * k4lz4_chain_encode_batch: store is a device pointer, every other pointer a host pointer; sources and the target go through the
+ * context's staging buffers; synchronous.  _device: src, store, dst, recLoaded, recOut and outLen are device pointers, the plan
+ * arrays (enc, storeOff, recOff, recLen, recFlags, firstRec, nRec, dstOff, dstCap) host arrays; it enqueues on `stream` and returns
+ * without waiting for its own work.  It waits for the upload of the previous call's plan (the context's own event) before it
+ * rewrites it, and each chained group for the previous chained block table, as k4lz4_frame_write_batch_device does.  The launch
+ * count depends on the (kind, level) groups in the call, not on the number of streams. */
+typedef struct k4lz4_chain_encoder_settings {
+    int32_t chaining;
+    int32_t level;               /* k4lz4_level */
+    int32_t blockSize;
+    int32_t extraBlocks;
+} k4lz4_chain_encoder_settings;
+
+typedef struct k4lz4_chain_encoder {
+    int32_t kind;                /* 0 LZ4BlockEncoder, 1 LZ4HighChainEncoder, 2 LZ4FastChainEncoder */
+    int32_t level;               /* as clamped (HC); 0 for the fast chain */
+    int32_t blockSize;           /* as rounded */
+    int32_t extraBlocks;         /* as applied; 0 without chaining */
+    int32_t ringBytes;           /* _inputLength */
+    int32_t index, pointer;      /* _inputIndex, _inputPointer */
+    uint32_t currentOffset, dictSize; /* chained fast: LZ4_stream_t's two indices */
+    int32_t reserved;
+    int64_t taken;               /* bytes Topup took so far */
+    int64_t blocks;              /* blocks emitted so far */
+    int64_t storeBytes;          /* per stream */
+} k4lz4_chain_encoder;
+
+enum k4lz4_chain_encode_op { K4LZ4_CENC_RUN = 0, K4LZ4_CENC_RESET = 1 };
+#define K4LZ4_CENC_FORCE       1          /* recFlags */
+#define K4LZ4_CENC_ALLOW_COPY  2
+#define K4LZ4_CENC_TARGET      (-1)       /* dstCap[s] is below k4lz4_chain_encode_bound */
+
+/* host arithmetic, no device needed.  K4LZ4_OK, or K4LZ4_E_ARG (NULL, a block size above the input size limit) */
+K4LZ4_API int k4lz4_chain_encoder_init(k4lz4_chain_encoder *e, const k4lz4_chain_encoder_settings *settings);
+K4LZ4_API int64_t k4lz4_chain_encoder_store_bytes(const k4lz4_chain_encoder *e);
+/* the most a run of nRec records can emit for the stream */
+K4LZ4_API int64_t k4lz4_chain_encode_bound(const k4lz4_chain_encoder *e, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRec);
+/* the record as the run would leave it, and what each record loads and whether it encodes (blockLen[r]: the block's length, 0 none):
+ * the host's model alone, nothing runs.  `after`, recLoaded and blockLen may be NULL */
+K4LZ4_API int k4lz4_chain_encode_plan(const k4lz4_chain_encoder *e, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRec,
+                                      k4lz4_chain_encoder *after, int32_t *recLoaded, int32_t *blockLen);
+/* the two pieces of host arithmetic the call is laid out with, for checking them against each other (no device needed); a row
+ * is four int64 words: start, length, the HC context's dictLimit or the fast chain's dictSize in front of the block, dictSmall.
+ * k4lz4_chain_encode_blocks: the blocks the run would encode, as the record model yields them, in the coordinates of the window [the
+ * ring | the bytes the run loads] (dictLimit: the window position of the ring's first byte) -> the number of blocks (at most maxRows
+ * rows are written), or -1.  k4lz4_chain_table_rows: the chained encoders' block table for explicit block lengths -- kind 1 HC,
+ * 2 fast; the content's first dictLen bytes are what the ring holds. */
+K4LZ4_API int64_t k4lz4_chain_encode_blocks(const k4lz4_chain_encoder *e, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRec,
+                                            int64_t *rows, int64_t maxRows);
+K4LZ4_API int k4lz4_chain_table_rows(int kind, int64_t dictLen, int64_t currentOffset, const int32_t *len, int64_t n, int32_t blockSize,
+                                     int32_t extraBlocks, int64_t *rows);
+/* flags: K4LZ4_FLAG_X32.  nRecords: the record table's rows.  recLoaded, recOut: nRecords words, of which the rows owned by a
+ * stream with nRec[s] > 0 are written and no others */
+K4LZ4_API int k4lz4_chain_encode_batch(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff,
+                                       const uint8_t *src, const uint64_t *recOff, const uint32_t *recLen, const uint32_t *recFlags,
+                                       int64_t nRecords, const uint64_t *firstRec, const uint32_t *nRec, uint8_t *dst,
+                                       const uint64_t *dstOff, const uint64_t *dstCap, int32_t *recLoaded, int32_t *recOut,
+                                       int64_t *outLen, int64_t n, int op, int flags);
+K4LZ4_API int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff,
+                                              const uint8_t *src, const uint64_t *recOff, const uint32_t *recLen,
+                                              const uint32_t *recFlags, int64_t nRecords, const uint64_t *firstRec, const uint32_t *nRec,
+                                              uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int32_t *recLoaded,
+                                              int32_t *recOut, int64_t *outLen, int64_t n, int op, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

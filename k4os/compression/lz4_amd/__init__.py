@@ -6,7 +6,7 @@ from .codec import LZ4Codec, LZ4Level, pack_blocks, make_arena
 from .pickler import LZ4Pickler, InvalidDataException
 from .encoders import (LZ4BlockEncoder, LZ4HighChainEncoder, LZ4FastChainEncoder, LZ4BlockDecoder, EncoderAction, InvalidOperationException, TopupAndEncode,
                        FlushAndEncode, DecodeAndDrain, encode_fast_chain_packed, encode_fast_chain_device, fast_chain_blocks,
-                       FAST_CHAIN_STATE, LZ4ChainDecoder, LZ4Decoder, LZ4ChainDecoderBatch)
+                       FAST_CHAIN_STATE, LZ4ChainDecoder, LZ4Decoder, LZ4ChainDecoderBatch, LZ4EncoderBatch, LZ4ChainEncoder, LZ4Encoder)
 from .frames import (LZ4Frame, LZ4EncoderSettings, LZ4Descriptor, parse_frame, xxh32_many, encode_fast_chain_frames,
                      frame_sizes_device, decode_frames_device, frame_exception, LZ4FrameWriterBatch, FrameWriterDevice,
                      LZ4FrameReaderBatch, FrameReaderDevice, LZ4FrameFedReaderBatch, FrameFedReaderDevice)
@@ -26,4 +26,5 @@ __all__ = ["LZ4Codec", "LZ4Level", "LZ4Pickler", "InvalidDataException", "Native
            "LZ4Legacy", "EndOfStreamException", "OverflowException", "NotSupportedException", "ArgumentException", "legacy_exception",
            "wrap_device", "unwrap_device", "encode_legacy_streams_device", "legacy_stream_sizes_device", "decode_legacy_streams_device",
            "LZ4StreamWriterBatch", "LegacyWriterDevice", "LZ4StreamReaderBatch", "LegacyReaderDevice",
-           "LZ4StreamFedReaderBatch", "LegacyFedReaderDevice", "LZ4ChainDecoder", "LZ4Decoder", "LZ4ChainDecoderBatch"]
+           "LZ4StreamFedReaderBatch", "LegacyFedReaderDevice", "LZ4ChainDecoder", "LZ4Decoder", "LZ4ChainDecoderBatch",
+           "LZ4EncoderBatch", "LZ4ChainEncoder", "LZ4Encoder"]

@@ -140,6 +140,14 @@ SYMBOLS = {
     "k4lz4_chain_drain_batch_device": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_void_p]),
     "k4lz4_chain_decoder_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "k4lz4_chain_decoder_query_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "k4lz4_chain_encoder_init": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "k4lz4_chain_encoder_store_bytes": (C.c_int64, [C.c_void_p]),
+    "k4lz4_chain_encode_bound": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "k4lz4_chain_encode_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_chain_encode_blocks": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "k4lz4_chain_table_rows": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "k4lz4_chain_encode_batch": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int]),
+    "k4lz4_chain_encode_batch_device": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
 }
 
 

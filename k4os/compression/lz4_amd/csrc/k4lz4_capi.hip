@@ -43,6 +43,7 @@
 #include "k4lz4_legacy_stream.hpp"
 #include "k4lz4_legacy_feed.hpp"
 #include "k4lz4_chain_decoder.hpp"
+#include "k4lz4_chain_encoder.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 
@@ -1513,10 +1514,42 @@ int hc_chain_table(k4lz4_ctx *ctx, const uint64_t *srcOff, const int64_t *srcLen
     return K4LZ4_OK;
 }
 
+/* the same table with explicit block lengths (k4lz4_chain_encoder.hpp: ce_hc_rows): stream s has blocks lens.len[lens.first[s] ..
+ * + lens.count[s]), which may be shorter than B in mid-stream; its content is dictLen[s] bytes and the blocks behind them */
+struct ChainLens { const int64_t *first; const int32_t *count; const int32_t *len; };
+
+int hc_chain_table_lens(k4lz4_ctx *ctx, const uint64_t *srcOff, const ChainLens &lens, const int32_t *blockSize, const int32_t *extraBlocks,
+                        const int32_t *dictLen, int64_t nStreams, const uint64_t *dstOff, int64_t &nb, HcChainPlan *fill)
+{
+    int64_t k = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t B = hc_chain_block_size(blockSize[si]);
+        const int64_t extra = extraBlocks ? std::max<int32_t>(extraBlocks[si], 0) : 0;
+        const int64_t D = dictLen ? dictLen[si] : 0;
+        const int32_t *len = lens.len + lens.first[si];
+        if (D < 0 || lens.count[si] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: bad block table");
+        if (B > k4::MAX_INPUT_SIZE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: block size above the input size limit");
+        for (int64_t j = 0; j < lens.count[si]; j++)
+            if (len[j] <= 0 || len[j] > B) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a block length outside 1 .. BlockSize");
+        const int64_t slot = B + B / 255 + 16;
+        if (fill)
+            k4::ce_hc_rows(D, len, lens.count[si], B, extra, [&](int64_t j, int64_t ws, int64_t pos, int64_t n, int64_t) {
+                const int64_t r = k + j;
+                fill->woff[r] = srcOff[si] + (uint64_t)ws; fill->boff[r] = srcOff[si] + (uint64_t)pos;
+                fill->doff[r] = dstOff[si] + (uint64_t)(j * slot);
+                fill->wlen[r] = (int32_t)(pos - ws + n); fill->hist[r] = (int32_t)(pos - ws);
+                fill->blen[r] = (int32_t)n; fill->cap[r] = (int32_t)slot;
+            });
+        k += lens.count[si];
+    }
+    nb = k;
+    return K4LZ4_OK;
+}
+
 /* k4lz4_encode_hc_chain_batch_device: src / dst / outLen device pointers, the per-stream arrays host pointers */
 int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen, const int32_t *blockSize,
                  const int32_t *extraBlocks, const int32_t *dictLen, int64_t nStreams, uint8_t *dst, const uint64_t *dstOff, int32_t *outLen, int64_t nBlocks,
-                 int level, int flags, hipStream_t stream)
+                 int level, int flags, hipStream_t stream, const ChainLens *lens = nullptr)
 {
     if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
     if (nStreams < 0 || nBlocks < 0 || (nStreams > 0 && (!src || !srcOff || !srcLen || !blockSize || !dst || !dstOff || !outLen)))
@@ -1524,7 +1557,11 @@ int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, con
     if (flags & ~(int)K4LZ4_FLAG_ALLOW_COPY) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: the only flag it takes is K4LZ4_FLAG_ALLOW_COPY");
     level = std::max<int>(K4LZ4_L03_HC, std::min<int>(K4LZ4_L12_MAX, level));       /* LZ4HighChainEncoder's constructor */
     int64_t nb = 0;
-    int rc = hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, nullptr);
+    auto table = [&](HcChainPlan *fill) {
+        return lens ? hc_chain_table_lens(ctx, srcOff, *lens, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, fill)
+                    : hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, fill);
+    };
+    int rc = table(nullptr);
     if (rc != K4LZ4_OK) return rc;
     if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: outLen has fewer entries than the streams have blocks");
     if (nb == 0) return K4LZ4_OK;
@@ -1535,7 +1572,7 @@ int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, con
     try { ctx->h_chain.resize(bytes); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
     HcChainPlan h;
     h.place(ctx->h_chain.data(), nb);
-    rc = hc_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, nStreams, dstOff, nb, &h);
+    rc = table(&h);
     if (rc != K4LZ4_OK) return rc;
     if ((rc = grow_scratch(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes)) != K4LZ4_OK) return rc;
     HcChainPlan d;
@@ -1635,6 +1672,43 @@ int fast_chain_table(k4lz4_ctx *ctx, const uint64_t *srcOff, const int64_t *srcL
     return K4LZ4_OK;
 }
 
+/* the same table with explicit block lengths (ce_fast_rows), as hc_chain_table_lens */
+int fast_chain_table_lens(k4lz4_ctx *ctx, const uint64_t *srcOff, const ChainLens &lens, const int32_t *blockSize, const int32_t *extraBlocks,
+                          const int32_t *dictLen, const uint32_t *cur0, const uint32_t *sdict, int64_t nStreams, const uint64_t *dstOff,
+                          int64_t &nb, FastChainPlan *fill)
+{
+    int64_t k = 0;
+    for (int64_t si = 0; si < nStreams; si++) {
+        const int64_t B = hc_chain_block_size(blockSize[si]);
+        const int64_t extra = extraBlocks ? std::max<int32_t>(extraBlocks[si], 0) : 0;
+        const int64_t D = dictLen ? dictLen[si] : 0;
+        const int32_t *len = lens.len + lens.first[si];
+        if (D < 0 || lens.count[si] < 0 || !cur0 || !sdict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: bad block table");
+        if ((int64_t)sdict[si] != D || sdict[si] > cur0[si]) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a state that does not fit its ring");
+        if (B > k4::MAX_INPUT_SIZE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: block size above the input size limit");
+        int64_t total = 0;
+        for (int64_t j = 0; j < lens.count[si]; j++) {
+            if (len[j] <= 0 || len[j] > B) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a block length outside 1 .. BlockSize");
+            total += len[j];
+        }
+        if ((int64_t)cur0[si] + total > ((int64_t)1 << 31))
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
+        const int64_t slot = B + B / 255 + 16;
+        if (fill) {
+            const int64_t dict = k4::ce_fast_rows(D, (int64_t)cur0[si], len, lens.count[si], B, extra, [&](int64_t j, int64_t pos, int64_t n, int64_t d, bool) {
+                const int64_t r = k + j;
+                fill->bpos[r] = (uint32_t)pos; fill->blen[r] = (int32_t)n; fill->bdict[r] = (uint32_t)d;
+                fill->doff[r] = dstOff[si] + (uint64_t)(j * slot); fill->cap[r] = (int32_t)slot;
+            });
+            fill->soff[si] = srcOff[si]; fill->slen[si] = (uint64_t)(D + total); fill->first[si] = k; fill->nblk[si] = (uint32_t)lens.count[si];
+            fill->idx0[si] = (uint32_t)((int64_t)cur0[si] - D); fill->dict_end[si] = (uint32_t)dict;
+        }
+        k += lens.count[si];
+    }
+    nb = k;
+    return K4LZ4_OK;
+}
+
 int fast_chain_flags(k4lz4_ctx *ctx, int flags)
 {
     if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
@@ -1647,10 +1721,14 @@ int fast_chain_flags(k4lz4_ctx *ctx, int flags)
 int fast_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int64_t *srcLen, const int32_t *blockSize,
                    const int32_t *extraBlocks, const int32_t *dictLen, const uint32_t *cur0, const uint32_t *sdict, int64_t nStreams,
                    const k4lz4_fast_chain_state *stateIn, k4lz4_fast_chain_state *stateOut, uint8_t *dst, const uint64_t *dstOff,
-                   int32_t *outLen, int64_t nBlocks, int flags, hipStream_t stream)
+                   int32_t *outLen, int64_t nBlocks, int flags, hipStream_t stream, const ChainLens *lens = nullptr)
 {
     int64_t nb = 0;
-    int rc = fast_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, cur0, sdict, nStreams, dstOff, nb, nullptr);
+    auto table = [&](FastChainPlan *fill) {
+        return lens ? fast_chain_table_lens(ctx, srcOff, *lens, blockSize, extraBlocks, dictLen, cur0, sdict, nStreams, dstOff, nb, fill)
+                    : fast_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, cur0, sdict, nStreams, dstOff, nb, fill);
+    };
+    int rc = table(nullptr);
     if (rc != K4LZ4_OK) return rc;
     if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: outLen has fewer entries than the streams have blocks");
     if (nStreams == 0 || (nb == 0 && !stateOut)) return K4LZ4_OK;
@@ -1661,7 +1739,7 @@ int fast_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, c
     try { ctx->h_chain.assign(bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
     FastChainPlan h;
     h.place(ctx->h_chain.data(), nStreams, nb);
-    rc = fast_chain_table(ctx, srcOff, srcLen, blockSize, extraBlocks, dictLen, cur0, sdict, nStreams, dstOff, nb, &h);
+    rc = table(&h);
     if (rc != K4LZ4_OK) return rc;
     {   /* longest first: a wave that is done takes the next stream (the ticket) */
         std::vector<uint32_t> ord((size_t)nStreams);
@@ -4006,6 +4084,361 @@ int k4lz4_chain_decoder_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64
     int rc;
     if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_chain_decoder_query_device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
     return s.finish({{out, d_out, (size_t)n * K4LZ4_CDQ_WORDS * 8}});
+}
+
+/* ---- many open ILZ4Encoders advanced per call (k4lz4_chain_encoder.hpp) ------------------------------------ */
+int k4lz4_chain_encoder_init(k4lz4_chain_encoder *e, const k4lz4_chain_encoder_settings *settings)
+{
+    if (!e || !settings) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_encoder_init: NULL argument");
+    if (settings->blockSize > k4::MAX_INPUT_SIZE - 1023)
+        return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_encoder_init: block size above the input size limit");
+    k4::ce_init(*e, *settings);
+    if ((int64_t)65536 + (1 + (int64_t)e->extraBlocks) * e->blockSize + 32 > 0x7E000000ll)
+        return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_encoder_init: the ring buffer passes 0x7E000000 bytes");
+    return K4LZ4_OK;
+}
+
+int64_t k4lz4_chain_encoder_store_bytes(const k4lz4_chain_encoder *e) { return e ? e->storeBytes : 0; }
+
+int64_t k4lz4_chain_encode_bound(const k4lz4_chain_encoder *e, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRec)
+{
+    if (!e || nRec <= 0 || !recLen || !recFlags) return 0;
+    return k4::ce_after(*e, recLen, recFlags, nRec).bound;
+}
+
+int k4lz4_chain_encode_plan(const k4lz4_chain_encoder *e, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRec,
+                            k4lz4_chain_encoder *after, int32_t *recLoaded, int32_t *blockLen)
+{
+    if (!e || nRec < 0 || (nRec > 0 && (!recLen || !recFlags))) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_encode_plan: bad argument");
+    for (int64_t r = 0; r < nRec; r++) if (blockLen) blockLen[r] = 0;
+    const k4::CeAfter a = k4::ce_model(*e, recLen, recFlags, nRec,
+                                       [&](int64_t r, int64_t loaded, int64_t) { if (recLoaded) recLoaded[r] = (int32_t)loaded; },
+                                       [&](int64_t r, int64_t, int64_t len, int64_t, int64_t, bool) { if (blockLen) blockLen[r] = (int32_t)len; });
+    if (after) { *after = *e; k4::ce_advance(*after, a); }
+    return K4LZ4_OK;
+}
+
+int64_t k4lz4_chain_encode_blocks(const k4lz4_chain_encoder *e, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRec, int64_t *rows,
+                                  int64_t maxRows)
+{
+    if (!e || nRec < 0 || (nRec > 0 && (!recLen || !recFlags)) || maxRows < 0 || (maxRows > 0 && !rows)) return -1;
+    int64_t k = 0;
+    k4::ce_model(*e, recLen, recFlags, nRec, [](int64_t, int64_t, int64_t) {},
+                 [&](int64_t, int64_t start, int64_t len, int64_t dict, int64_t ws, bool small) {
+                     if (k < maxRows) { int64_t *r = rows + 4 * k; r[0] = start; r[1] = len; r[2] = e->kind == 2 ? dict : ws; r[3] = small ? 1 : 0; }
+                     k++;
+                 });
+    return k;
+}
+
+int k4lz4_chain_table_rows(int kind, int64_t dictLen, int64_t currentOffset, const int32_t *len, int64_t n, int32_t blockSize,
+                           int32_t extraBlocks, int64_t *rows)
+{
+    if ((kind != 1 && kind != 2) || dictLen < 0 || n < 0 || (n > 0 && (!len || !rows))) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_table_rows: bad argument");
+    const int64_t B = hc_chain_block_size(blockSize), extra = std::max<int32_t>(extraBlocks, 0);
+    if (kind == 1)
+        k4::ce_hc_rows(dictLen, len, n, B, extra, [&](int64_t j, int64_t, int64_t pos, int64_t l, int64_t dl) {
+            int64_t *r = rows + 4 * j; r[0] = pos; r[1] = l; r[2] = dl; r[3] = 0;
+        });
+    else
+        k4::ce_fast_rows(dictLen, currentOffset, len, n, B, extra, [&](int64_t j, int64_t pos, int64_t l, int64_t d, bool small) {
+            int64_t *r = rows + 4 * j; r[0] = pos; r[1] = l; r[2] = d; r[3] = small ? 1 : 0;
+        });
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                                    const uint64_t *recOff, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRecords,
+                                    const uint64_t *firstRec, const uint32_t *nRec, uint8_t *dst, const uint64_t *dstOff,
+                                    const uint64_t *dstCap, int32_t *recLoaded, int32_t *recOut, int64_t *outLen, int64_t n, int op, int flags,
+                                    void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (op < K4LZ4_CENC_RUN || op > K4LZ4_CENC_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: unknown op");
+    if (flags & ~(int)K4LZ4_FLAG_X32) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: the only flag it takes is K4LZ4_FLAG_X32");
+    if (n < 0 || nRecords < 0 || (n > 0 && (!enc || !store || !storeOff))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    if ((uintptr_t)store & 255u) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: the store is not 256-byte aligned");
+    for (int64_t i = 0; i < n; i++) {
+        if (storeOff[i] & 255u) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a stream's store is not 256-byte aligned");
+        k4lz4_chain_encoder probe;
+        const k4lz4_chain_encoder_settings back{enc[i].kind != 0, enc[i].kind == 2 ? 0 : enc[i].kind == 1 ? std::max<int32_t>(enc[i].level, K4LZ4_L03_HC) : enc[i].level,
+                                                enc[i].blockSize, enc[i].extraBlocks};
+        k4::ce_init(probe, back);
+        if (enc[i].kind < 0 || enc[i].kind > 2 || probe.kind != enc[i].kind || probe.blockSize != enc[i].blockSize || probe.ringBytes != enc[i].ringBytes ||
+            probe.storeBytes != enc[i].storeBytes || enc[i].index < 0 || enc[i].index > enc[i].pointer || enc[i].pointer > enc[i].ringBytes)
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a record was not made by k4lz4_chain_encoder_init");
+    }
+    const bool x32 = (flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<k4::FwPiece> stage, back;
+    auto chunks = [](std::vector<k4::FwPiece> &p) {
+        unsigned long long c = 0;
+        for (k4::FwPiece &x : p) { x.chunk0 = c; c += std::max<unsigned long long>(1, (x.len + k4::FW_CHUNK - 1) / k4::FW_CHUNK); }
+        return c;
+    };
+    auto sync_plan = [&]() -> int {
+        K4_HIP(ctx, hipSetDevice(ctx->device));
+        if (!ctx->ev_fw) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fw, hipEventDisableTiming));
+        else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fw));        /* the previous upload of the host plan is over */
+        return K4LZ4_OK;
+    };
+    int rc;
+
+    if (op == K4LZ4_CENC_RESET) {
+        for (int64_t i = 0; i < n; i++)
+            if (enc[i].kind == 2)
+                stage.push_back(k4::FwPiece{store + storeOff[i], nullptr, sizeof(k4lz4_fast_chain_state), 0});
+        if (!stage.empty()) {
+            const unsigned long long c = chunks(stage);
+            const size_t bytes = stage.size() * sizeof(k4::FwPiece);
+            if ((rc = sync_plan()) != K4LZ4_OK) return rc;
+            try { ctx->h_fw.assign(bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+            if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, bytes + 64)) != K4LZ4_OK) return rc;
+            memcpy(ctx->h_fw.data(), stage.data(), bytes);
+            K4_HIP(ctx, order_after_ctx(ctx, st));
+            K4_HIP(ctx, hipMemcpyAsync(ctx->d_fw, ctx->h_fw.data(), bytes, hipMemcpyHostToDevice, st));
+            K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
+            hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)c), dim3(k4::FW_THREADS), 0, st, (const k4::FwPiece *)ctx->d_fw, (long long)stage.size());
+            K4_HIP(ctx, hipGetLastError());
+            mark_busy(ctx, st);
+        }
+        for (int64_t i = 0; i < n; i++) {
+            k4lz4_chain_encoder &e = enc[i];
+            e.index = e.pointer = 0; e.currentOffset = e.dictSize = 0; e.taken = e.blocks = 0;
+        }
+        return K4LZ4_OK;
+    }
+
+    if (!firstRec || !nRec || !dstOff || !dstCap || !outLen || !dst) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    /* ---- the plan: per-stream codes and the model's blocks -- host index arithmetic, nothing enqueued yet */
+    std::vector<int32_t> code((size_t)n, 1);
+    std::vector<k4::CeAfter> after((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        if (nRec[i] == 0) continue;
+        if (firstRec[i] > (uint64_t)nRecords || (uint64_t)nRec[i] > (uint64_t)nRecords - firstRec[i])
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a stream refers to records outside the record table");
+        if (!recOff || !recLen || !recFlags || !recLoaded || !recOut) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+        const uint32_t *rl = recLen + firstRec[i], *rf = recFlags + firstRec[i];
+        for (uint32_t r = 0; r < nRec[i]; r++) {
+            if (rf[r] & ~(uint32_t)(K4LZ4_CENC_FORCE | K4LZ4_CENC_ALLOW_COPY)) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: unknown record flags");
+            if (rl[r] > 0x7fffffffu) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a record longer than INT32_MAX");
+            if (rl[r] && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+        }
+        if (enc[i].kind == 2 && x32)
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: the 32-bit engine's chained encoder (LZ4Codec.Enforce32) is not supported");
+        after[(size_t)i] = k4::ce_after(enc[i], rl, rf, nRec[i]);
+        if (after[(size_t)i].too_long)
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
+        code[(size_t)i] = (int64_t)std::min<uint64_t>(dstCap[i], (uint64_t)INT64_MAX) < after[(size_t)i].bound ? K4LZ4_CENC_TARGET : 0;
+    }
+    /* groups of streams whose blocks go to one encoder call: (kind, level) */
+    auto key = [&](int64_t i) { return enc[i].kind * 100 + (enc[i].kind == 2 ? 0 : enc[i].level); };
+    std::vector<int> keys;
+    for (int64_t i = 0; i < n; i++) if (code[(size_t)i] == 0 && after[(size_t)i].nblk) keys.push_back(key(i));
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    struct Group { int key; std::vector<int64_t> streams; int64_t first = 0, nb = 0; };
+    std::vector<Group> groups(keys.size());
+    for (size_t g = 0; g < keys.size(); g++) groups[g].key = keys[g];
+    for (int64_t i = 0; i < n; i++)
+        if (code[(size_t)i] == 0 && after[(size_t)i].nblk)
+            groups[(size_t)(std::lower_bound(keys.begin(), keys.end(), key(i)) - keys.begin())].streams.push_back(i);
+    int64_t nb = 0, nfast = 0;
+    for (Group &g : groups) {
+        g.first = nb;
+        for (int64_t i : g.streams) g.nb += after[(size_t)i].nblk;
+        nb += g.nb;
+        if (g.key / 100 == 2) nfast += (int64_t)g.streams.size();
+    }
+    if (nb > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: more than 2^31 blocks in one call");
+
+    /* ---- scratch layout: the uploaded plan first, then what the kernels fill, then windows, arena and states */
+    size_t at = 0;
+    const size_t o_streams = fw_take(at, (size_t)n * sizeof(k4::CeStream)), o_recs = fw_take(at, (size_t)nRecords * sizeof(k4::CeRec)),
+                 o_blocks = fw_take(at, (size_t)nb * sizeof(k4::CeBlock)), o_slot = fw_take(at, (size_t)nb * 8),
+                 o_isrc = fw_take(at, (size_t)nb * 8), o_ilen = fw_take(at, (size_t)nb * 4), o_icap = fw_take(at, (size_t)nb * 4);
+    std::vector<uint64_t> win((size_t)n, 0), aoff((size_t)n, 0);
+    /* (the pieces' tables follow the fixed part: their count is known once the streams are walked, their room is bounded now) */
+    size_t npiece_max = 0;
+    for (int64_t i = 0; i < n; i++) if (code[(size_t)i] == 0) npiece_max += (size_t)nRec[i] + 4;
+    const size_t o_stage = fw_take(at, npiece_max * sizeof(k4::FwPiece)), o_back = fw_take(at, (2 * (size_t)n + 1) * sizeof(k4::FwPiece));
+    const size_t plan_bytes = at;
+    const size_t o_out = fw_take(at, (size_t)nb * 4);
+    for (const Group &g : groups)
+        for (int64_t i : g.streams) { win[(size_t)i] = at; fw_take(at, (size_t)(enc[i].pointer + after[(size_t)i].loaded) + 16); }
+    for (const Group &g : groups)
+        for (int64_t i : g.streams) { aoff[(size_t)i] = at; fw_take(at, (size_t)(after[(size_t)i].nblk * k4::ce_slot(enc[i]))); }
+    const size_t o_stin = fw_take(at, (size_t)nfast * sizeof(k4lz4_fast_chain_state)),
+                 o_stout = fw_take(at, (size_t)nfast * sizeof(k4lz4_fast_chain_state));
+    const size_t total_bytes = at + 64;
+
+    if ((rc = sync_plan()) != K4LZ4_OK) return rc;
+    try { ctx->h_fw.assign(plan_bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, total_bytes)) != K4LZ4_OK) return rc;
+    uint8_t *h = ctx->h_fw.data(), *d = ctx->d_fw;
+    k4::CeStream *hs = (k4::CeStream *)(h + o_streams);
+    k4::CeRec *hr = (k4::CeRec *)(h + o_recs);
+    k4::CeBlock *hb = (k4::CeBlock *)(h + o_blocks);
+    uint64_t *hslot = (uint64_t *)(h + o_slot), *hisrc = (uint64_t *)(h + o_isrc);
+    int32_t *hilen = (int32_t *)(h + o_ilen), *hicap = (int32_t *)(h + o_icap);
+    k4lz4_fast_chain_state *d_stin = (k4lz4_fast_chain_state *)(d + o_stin), *d_stout = (k4lz4_fast_chain_state *)(d + o_stout);
+
+    std::vector<int64_t> first((size_t)n, 0), fast_index((size_t)n, -1);
+    int64_t kfast = 0;
+    for (const Group &g : groups) {
+        int64_t b = g.first;
+        for (int64_t i : g.streams) { first[(size_t)i] = b; b += after[(size_t)i].nblk; if (enc[i].kind == 2) fast_index[(size_t)i] = kfast++; }
+    }
+    for (int64_t i = 0; i < n; i++) {
+        k4::CeStream &row = hs[i];
+        row.code = code[(size_t)i]; row.nRec = nRec[i]; row.firstRec = nRec[i] ? firstRec[i] : 0;
+        if (row.code != 0) continue;
+        const k4lz4_chain_encoder &e = enc[i];
+        const k4::CeAfter &a = after[(size_t)i];
+        row.out = dstOff[i]; row.cap = dstCap[i]; row.firstBlk = (unsigned long long)first[(size_t)i];
+        uint8_t *sto = store + storeOff[i], *ring = sto + k4::ce_ring_at(e);
+        const bool runs = a.nblk > 0;
+        uint8_t *wp = d + win[(size_t)i];
+        const int64_t slot = k4::ce_slot(e);
+        const uint64_t *ro = recOff + firstRec[i];
+        k4::CeRec *rr = hr + firstRec[i];
+        int64_t j = 0;
+        if (runs) stage.push_back(k4::FwPiece{wp, ring, (unsigned long long)e.pointer, 0});
+        k4::ce_model(e, recLen + firstRec[i], recFlags + firstRec[i], nRec[i],
+            [&](int64_t r, int64_t loaded, int64_t where) {
+                rr[r].loaded = (int32_t)loaded; rr[r].blk = -1; rr[r].allow = (recFlags[firstRec[i] + r] & K4LZ4_CENC_ALLOW_COPY) ? 1u : 0u;
+                /* a stream that encodes nothing this run appends straight to its ring (ws stays 0: `where` is the ring's position) */
+                if (loaded) stage.push_back(k4::FwPiece{(runs ? wp : ring) + where, src + ro[r], (unsigned long long)loaded, 0});
+            },
+            [&](int64_t r, int64_t start, int64_t len, int64_t, int64_t, bool) {
+                const int64_t b = first[(size_t)i] + j;
+                rr[r].blk = (int32_t)j;
+                hb[b].slot = aoff[(size_t)i] + (uint64_t)(j * slot); hb[b].raw = win[(size_t)i] + (uint64_t)start; hb[b].len = (int32_t)len;
+                hslot[b] = hb[b].slot; hisrc[b] = hb[b].raw; hilen[b] = (int32_t)len; hicap[b] = (int32_t)slot;
+                j++;
+            });
+        if (!runs) continue;
+        const int64_t r0 = a.ws == 0 ? e.pointer : 0;                    /* bytes of the ring that stay where they are */
+        back.push_back(k4::FwPiece{ring + r0, wp + a.ws + r0, (unsigned long long)(a.pointer - r0), 0});
+        if (e.kind == 2) {
+            const int64_t f = fast_index[(size_t)i];
+            /* a stream that has encoded nothing yet starts from a zeroed LZ4_stream_t (LZ4FastChainEncoder.cs) */
+            stage.push_back(k4::FwPiece{(uint8_t *)(d_stin + f), e.currentOffset ? (const uint8_t *)sto : nullptr, sizeof(k4lz4_fast_chain_state), 0});
+            back.push_back(k4::FwPiece{sto, (const uint8_t *)(d_stout + f), sizeof(k4lz4_fast_chain_state), 0});
+        }
+    }
+    if (stage.size() > npiece_max || back.size() > 2 * (size_t)n) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: internal: piece table overflow");
+    const unsigned long long stage_chunks = chunks(stage), back_chunks = chunks(back);
+    if (!stage.empty()) memcpy(h + o_stage, stage.data(), stage.size() * sizeof(k4::FwPiece));
+    if (!back.empty()) memcpy(h + o_back, back.data(), back.size() * sizeof(k4::FwPiece));
+
+    /* ---- enqueue: plan up, stage, encode, write back, place */
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    K4_HIP(ctx, hipMemcpyAsync(d, h, plan_bytes, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
+    int32_t *d_out = (int32_t *)(d + o_out);
+    if (!stage.empty())
+        hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)stage_chunks), dim3(k4::FW_THREADS), 0, st, (const k4::FwPiece *)(d + o_stage), (long long)stage.size());
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    for (const Group &g : groups) {
+        const int kind = g.key / 100, level = g.key % 100;
+        const int64_t ns = (int64_t)g.streams.size();
+        if (kind == 0) {
+            rc = launch(ctx, KIND_ENCODE, d, (const uint64_t *)(d + o_isrc) + g.first, (const int32_t *)(d + o_ilen) + g.first, d,
+                        (const uint64_t *)(d + o_slot) + g.first, (const int32_t *)(d + o_icap) + g.first, d_out + g.first, g.nb, level,
+                        x32 ? K4LZ4_FLAG_X32 : 0, st, nullptr, hilen + g.first);
+        } else {
+            std::vector<uint64_t> soff((size_t)ns), doff((size_t)ns);
+            std::vector<int64_t> slen((size_t)ns), lfirst((size_t)ns);
+            std::vector<int32_t> bsz((size_t)ns), ext((size_t)ns), dlen((size_t)ns), lcount((size_t)ns);
+            std::vector<uint32_t> cur0((size_t)ns), sdict((size_t)ns);
+            int64_t f0 = -1;
+            for (int64_t k = 0; k < ns; k++) {
+                const int64_t i = g.streams[(size_t)k];
+                soff[(size_t)k] = win[(size_t)i]; doff[(size_t)k] = aoff[(size_t)i];
+                lfirst[(size_t)k] = first[(size_t)i] - g.first; lcount[(size_t)k] = (int32_t)after[(size_t)i].nblk;
+                int64_t total = enc[i].index;
+                for (int64_t j = 0; j < after[(size_t)i].nblk; j++) total += hilen[first[(size_t)i] + j];
+                slen[(size_t)k] = total;
+                bsz[(size_t)k] = enc[i].blockSize; ext[(size_t)k] = enc[i].extraBlocks; dlen[(size_t)k] = enc[i].index;
+                cur0[(size_t)k] = enc[i].currentOffset; sdict[(size_t)k] = enc[i].dictSize;
+                if (f0 < 0) f0 = fast_index[(size_t)i];
+            }
+            const ChainLens lens{lfirst.data(), lcount.data(), hilen + g.first};
+            /* allowCopy is a record's switch here: the encoders keep every block encoded and k4_ce_place_kernel applies the rule */
+            if (kind == 1)
+                rc = hc_chain_run(ctx, d, soff.data(), slen.data(), bsz.data(), ext.data(), dlen.data(), ns, d, doff.data(), d_out + g.first, g.nb,
+                                  level, 0, st, &lens);
+            else
+                rc = fast_chain_run(ctx, d, soff.data(), slen.data(), bsz.data(), ext.data(), dlen.data(), cur0.data(), sdict.data(), ns,
+                                    d_stin + f0, d_stout + f0, d, doff.data(), d_out + g.first, g.nb, 0, st, &lens);
+        }
+        if (rc != K4LZ4_OK) return rc;
+    }
+    if (!back.empty())
+        hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)back_chunks), dim3(k4::FW_THREADS), 0, st, (const k4::FwPiece *)(d + o_back), (long long)back.size());
+    hipLaunchKernelGGL(k4::k4_ce_place_kernel, dim3((unsigned)n), dim3(k4::CE_WAVE), 0, st, (const k4::CeStream *)(d + o_streams),
+                       (const k4::CeRec *)(d + o_recs), (const k4::CeBlock *)(d + o_blocks), (const int32_t *)d_out, (const uint8_t *)d, dst,
+                       recLoaded, recOut, (long long *)outLen, (long long)n);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+
+    /* ---- the records: what the calls enqueued leaves them in */
+    for (int64_t i = 0; i < n; i++)
+        if (code[(size_t)i] == 0) k4::ce_advance(enc[i], after[(size_t)i]);
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_encode_batch(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                             const uint64_t *recOff, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRecords,
+                             const uint64_t *firstRec, const uint32_t *nRec, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap,
+                             int32_t *recLoaded, int32_t *recOut, int64_t *outLen, int64_t n, int op, int flags)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (op == K4LZ4_CENC_RESET || n <= 0) {
+        const int rc0 = k4lz4_chain_encode_batch_device(ctx, enc, store, storeOff, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                                                        nullptr, nullptr, nullptr, nullptr, nullptr, n, op, flags, ctx->stream);
+        if (rc0 == K4LZ4_OK && n > 0) K4_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return rc0;
+    }
+    if (nRecords < 0 || !enc || !firstRec || !nRec || !dstOff || !dstCap || !outLen || !dst ||
+        (nRecords > 0 && (!recOff || !recLen || !recFlags || !recLoaded || !recOut)))
+        return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    std::vector<int64_t> len64((size_t)nRecords);
+    for (int64_t r = 0; r < nRecords; r++) {
+        if (recLen[r] > 0x7fffffffu) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a record longer than INT32_MAX");
+        if (recLen[r] && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+        len64[(size_t)r] = recLen[r];
+    }
+    /* the output slots: what the run can emit, not the caller's capacities (the codes are decided on dstCap all the same) */
+    std::vector<uint64_t> cap((size_t)n, 0);
+    for (int64_t i = 0; i < n; i++) {
+        if (nRec[i] == 0) continue;
+        if (firstRec[i] > (uint64_t)nRecords || (uint64_t)nRec[i] > (uint64_t)nRecords - firstRec[i])
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a stream refers to records outside the record table");
+        cap[(size_t)i] = std::min<uint64_t>(dstCap[i], (uint64_t)k4lz4_chain_encode_bound(enc + i, recLen + firstRec[i], recFlags + firstRec[i], nRec[i]));
+    }
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    s.pack(src, recOff, len64.data(), nRecords);
+    s.slots(n, [&](int64_t i) { return cap[(size_t)i]; }, false);
+    int64_t *d_out;
+    int32_t *d_loaded, *d_rout;
+    s.meta(&d_out, n); s.meta(&d_loaded, std::max<int64_t>(nRecords, 1)); s.meta(&d_rout, std::max<int64_t>(nRecords, 1));
+    std::vector<int32_t> h_loaded((size_t)std::max<int64_t>(nRecords, 1)), h_rout((size_t)std::max<int64_t>(nRecords, 1));
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_chain_encode_batch_device(ctx, enc, store, storeOff, ctx->d_src, s.in_off.data(), recLen, recFlags, nRecords, firstRec, nRec,
+                                              ctx->d_dst, s.slot.data(), cap.data(), d_loaded, d_rout, d_out, n, op, flags, s.st)) != K4LZ4_OK)
+        return rc;
+    rc = s.finish({{outLen, d_out, (size_t)n * 8}, {h_loaded.data(), d_loaded, (size_t)nRecords * 4}, {h_rout.data(), d_rout, (size_t)nRecords * 4}},
+                  dst, dstOff, [&](int64_t i) { return outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+    if (rc != K4LZ4_OK) return rc;
+    for (int64_t i = 0; i < n; i++)
+        for (uint32_t r = 0; r < nRec[i]; r++) { recLoaded[firstRec[i] + r] = h_loaded[(size_t)(firstRec[i] + r)]; recOut[firstRec[i] + r] = h_rout[(size_t)(firstRec[i] + r)]; }
+    return K4LZ4_OK;
 }
 
 }  // extern "C"

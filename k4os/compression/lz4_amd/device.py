@@ -247,3 +247,47 @@ class ChainDecoderDevice:
         self.dc.ctx.check(self.dc.lib.k4lz4_chain_decoder_query_device(self.dc.ctx.handle, _dp(self.store), _dp(self.store_off), self.n, _dp(out),
                                                                        C.c_void_p(self.dc._stream())))
         return out
+
+
+class ChainEncoderDevice:
+    """Many open ILZ4Encoders over device tensors (k4lz4_chain_encode_batch_device): settings is one (chaining, level,
+    blockSize, extraBlocks) per encoder, as LZ4Encoder.Create takes them.  The sources, the target and the result arrays of a call
+    are device tensors, the plan arrays (record offsets, lengths and flags, the streams' first records and counts, the target's
+    offsets and capacities) host arrays; the counters live in the host records.  Every call is enqueued on the current torch stream
+    and returns; nothing is read back."""
+
+    def __init__(self, settings, dc: Optional[DeviceCodec] = None):
+        from .encoders import chain_encoder_record, ChainEncoderRecord
+        self.dc = dc or DeviceCodec()
+        self.n = len(settings)
+        self.records = (ChainEncoderRecord * max(self.n, 1))(*[chain_encoder_record(c, int(l), b, e, self.dc.lib) for c, l, b, e in settings])
+        self.store_bytes = np.array([r.storeBytes for r in self.records[:self.n]], np.int64)
+        off = np.concatenate(([0], np.cumsum(self.store_bytes[:-1]))).astype(np.int64) if self.n else np.zeros(0, np.int64)
+        self.store = torch.empty(int(self.store_bytes.sum()) + 256, dtype=torch.uint8, device=self.dc.device)
+        self._base = (self.store.data_ptr() + 255) // 256 * 256
+        self.store_off = np.ascontiguousarray(off, np.uint64)
+
+    def bytes_ready(self, i: int) -> int:
+        return int(self.records[i].pointer - self.records[i].index)
+
+    def bound(self, i: int, rec_len, rec_flags) -> int:
+        rec_len, rec_flags = np.ascontiguousarray(rec_len, np.uint32), np.ascontiguousarray(rec_flags, np.uint32)
+        return int(self.dc.lib.k4lz4_chain_encode_bound(C.byref(self.records[i]), rec_len.ctypes.data, rec_flags.ctypes.data, rec_len.size))
+
+    def reset(self) -> None:
+        """every encoder becomes a fresh one"""
+        self.dc.ctx.check(self.dc.lib.k4lz4_chain_encode_batch_device(
+            self.dc.ctx.handle, self.records, C.c_void_p(self._base), self.store_off.ctypes.data, None, None, None, None, 0, None, None, None, None,
+            None, None, None, None, self.n, 1, 0, C.c_void_p(self.dc._stream())))
+
+    def run(self, src, rec_off, rec_len, rec_flags, first_rec, n_rec, dst, dst_off, dst_cap, rec_loaded, rec_out, out_len, flags: int = 0):
+        """one run per encoder: encoder s owns records first_rec[s] .. + n_rec[s] of the table (rec_off uint64, rec_len and rec_flags
+        uint32, first_rec uint64, n_rec uint32, dst_off and dst_cap uint64: host arrays).  src, dst (uint8), rec_loaded, rec_out (int32 per
+        record) and out_len (int64 per encoder) are device tensors."""
+        h = [np.ascontiguousarray(a, t) for a, t in ((rec_off, np.uint64), (rec_len, np.uint32), (rec_flags, np.uint32), (first_rec, np.uint64),
+                                                     (n_rec, np.uint32), (dst_off, np.uint64), (dst_cap, np.uint64))]
+        self.dc.ctx.check(self.dc.lib.k4lz4_chain_encode_batch_device(
+            self.dc.ctx.handle, self.records, C.c_void_p(self._base), self.store_off.ctypes.data, _dp(src), h[0].ctypes.data, h[1].ctypes.data,
+            h[2].ctypes.data, int(h[1].size), h[3].ctypes.data, h[4].ctypes.data, _dp(dst), h[5].ctypes.data, h[6].ctypes.data, _dp(rec_loaded),
+            _dp(rec_out), _dp(out_len), self.n, 0, flags, C.c_void_p(self.dc._stream())))
+        return out_len

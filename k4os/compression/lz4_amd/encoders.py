@@ -782,3 +782,219 @@ class LZ4Decoder:
     @staticmethod
     def Create(chaining: bool, blockSize: int, extraBlocks: int = 0):
         return LZ4ChainDecoder(blockSize, extraBlocks) if chaining else LZ4BlockDecoder(blockSize)
+
+
+# ---- many open ILZ4Encoders advanced per call (k4lz4_chain_encode_batch) ---------------------------------
+CENC_RUN, CENC_RESET = 0, 1
+CENC_FORCE, CENC_ALLOW_COPY = 1, 2
+CENC_TARGET = -1
+
+
+class ChainEncoderSettings(_C.Structure):
+    """k4lz4_chain_encoder_settings"""
+    _fields_ = [("chaining", _C.c_int32), ("level", _C.c_int32), ("blockSize", _C.c_int32), ("extraBlocks", _C.c_int32)]
+
+
+class ChainEncoderRecord(_C.Structure):
+    """k4lz4_chain_encoder"""
+    _fields_ = [("kind", _C.c_int32), ("level", _C.c_int32), ("blockSize", _C.c_int32), ("extraBlocks", _C.c_int32),
+                ("ringBytes", _C.c_int32), ("index", _C.c_int32), ("pointer", _C.c_int32), ("currentOffset", _C.c_uint32),
+                ("dictSize", _C.c_uint32), ("reserved", _C.c_int32), ("taken", _C.c_int64), ("blocks", _C.c_int64),
+                ("storeBytes", _C.c_int64)]
+
+
+def chain_encoder_record(chaining, level, blockSize: int, extraBlocks: int = 0, lib=None) -> ChainEncoderRecord:
+    """k4lz4_chain_encoder_init: host arithmetic, no device"""
+    lib = lib or _native.load_library()
+    rec = ChainEncoderRecord()
+    _native._check_plain(lib, lib.k4lz4_chain_encoder_init(_C.byref(rec), _C.byref(ChainEncoderSettings(1 if chaining else 0, int(level), int(blockSize),
+                                                                                                     int(extraBlocks)))))
+    return rec
+
+
+def encoder_record_table(records):
+    """per-stream lists of (bytes, force, allowCopy) -> (src, recOff, recLen, recFlags, firstRec, nRec), the record table of
+    k4lz4_chain_encode_batch"""
+    flat = [r for rs in records for r in rs]
+    n_rec = np.array([len(rs) for rs in records], np.uint32)
+    first = np.zeros(len(records), np.uint64)
+    if len(records) > 1:
+        first[1:] = np.cumsum(n_rec[:-1].astype(np.uint64))
+    views = [_ro_view(r[0], "source") for r in flat]
+    src, off, _ = pack_blocks(views) if views else (np.zeros(1, np.uint8), np.zeros(0, np.uint64), None)
+    rec_len = np.array([v.size for v in views], np.uint32)
+    rec_flags = np.array([(CENC_FORCE if r[1] else 0) | (CENC_ALLOW_COPY if r[2] else 0) for r in flat], np.uint32)
+    return src, np.ascontiguousarray(off, np.uint64), rec_len, rec_flags, first, n_rec
+
+
+def _ring_at(rec: ChainEncoderRecord) -> int:
+    """a store's layout: a chained fast stream's k4lz4_fast_chain_state (rounded to 256 bytes), then the ring"""
+    return (FAST_CHAIN_STATE.itemsize + 255) // 256 * 256 if rec.kind == 2 else 0
+
+
+class LZ4EncoderBatch:
+    """Many open ILZ4Encoders over host arrays (k4lz4_chain_encode_batch): settings is one (chaining, level, blockSize, extraBlocks)
+    per encoder, as LZ4Encoder.Create takes them.  The rings (and the fast chains' states) live in device memory (a torch tensor), the
+    counters in the host records; every call is synchronous."""
+
+    def __init__(self, settings, ctx: Optional[_native.Context] = None):
+        import torch
+        self.ctx = ctx or _native.default_context()
+        self.lib = self.ctx.lib
+        self.n = len(settings)
+        self.records = (ChainEncoderRecord * max(self.n, 1))(*[chain_encoder_record(c, int(l), b, e, self.lib) for c, l, b, e in settings])
+        sizes = np.array([r.storeBytes for r in self.records[:self.n]], np.int64)
+        self.store_off = np.concatenate(([0], np.cumsum(sizes[:-1]))).astype(np.uint64) if self.n else np.zeros(0, np.uint64)
+        self.store = torch.empty(int(sizes.sum()) + 256, dtype=torch.uint8, device=torch.device("cuda", self.ctx.device))
+        self._base = (self.store.data_ptr() + 255) // 256 * 256
+
+    def BlockSize(self, i: int = 0) -> int:
+        return int(self.records[i].blockSize)
+
+    def BytesReady(self, i: int = 0) -> int:
+        return int(self.records[i].pointer - self.records[i].index)
+
+    def Reset(self) -> None:
+        """every encoder becomes a fresh one"""
+        if self.n:
+            self.ctx.check(self.lib.k4lz4_chain_encode_batch(self.ctx.handle, self.records, _C.c_void_p(self._base), self.store_off.ctypes.data,
+                                                             None, None, None, None, 0, None, None, None, None, None, None, None, None, self.n,
+                                                             CENC_RESET, 0))
+
+    def Bound(self, records) -> List[int]:
+        out = []
+        for i, rs in enumerate(records):
+            _, _, rlen, rflags, _, _ = encoder_record_table([rs])
+            out.append(int(self.lib.k4lz4_chain_encode_bound(_C.byref(self.records[i]), rlen.ctypes.data, rflags.ctypes.data, len(rs))))
+        return out
+
+    def Run(self, records, caps=None, flags: int = 0):
+        """records[s]: the run of encoder s, a list of (bytes, forceEncode, allowCopy) -- one TopupAndEncode each (no bytes with
+        forceEncode: FlushAndEncode); an empty list leaves the encoder untouched.  caps[s]: the target's room (default: the bound).
+        -> (recLoaded per encoder, recOut per encoder, outLen, the bytes written per encoder)"""
+        n = self.n
+        assert len(records) == n
+        src, roff, rlen, rflags, first, nrec = encoder_record_table(records)
+        nr = int(rlen.size)
+        caps = np.array(self.Bound(records), np.uint64) if caps is None else np.ascontiguousarray(caps, np.uint64)
+        doff = np.concatenate(([0], np.cumsum(caps[:-1]))).astype(np.uint64) if n else np.zeros(0, np.uint64)
+        dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
+        loaded = np.zeros(max(nr, 1), np.int32)
+        rec_out = np.zeros(max(nr, 1), np.int32)
+        out = np.zeros(max(n, 1), np.int64)
+        p = lambda a: a.ctypes.data  # noqa: E731
+        flags |= _native.FLAG_X32 if LZ4Codec.Enforce32 else 0
+        self.ctx.check(self.lib.k4lz4_chain_encode_batch(self.ctx.handle, self.records, _C.c_void_p(self._base), p(self.store_off), p(src), p(roff),
+                                                         p(rlen), p(rflags), nr, p(first), p(nrec), p(dst), p(doff), p(caps), p(loaded), p(rec_out),
+                                                         p(out), n, CENC_RUN, flags))
+        cut = lambda a: [a[int(f):int(f) + int(k)].tolist() for f, k in zip(first, nrec)]  # noqa: E731
+        return cut(loaded), cut(rec_out), out[:n].tolist(), [dst[int(doff[i]):int(doff[i]) + max(int(out[i]), 0)].tobytes() for i in range(n)]
+
+    def write_records(self, i: int, piece, force: bool = False, allowCopy: bool = True):
+        """the writer's loop for one piece -- TopupAndEncode(forceEncode) until the piece is in -- as records: each offers what is left
+        (up to a block) and the library's model (k4lz4_chain_encode_plan) says what Topup takes and where the record leaves the ring"""
+        v = _ro_view(piece, "source")
+        cur, nxt = ChainEncoderRecord.from_buffer_copy(self.records[i]), ChainEncoderRecord()
+        flags = np.array([(CENC_FORCE if force else 0) | (CENC_ALLOW_COPY if allowCopy else 0)], np.uint32)
+        loaded = np.zeros(1, np.int32)
+        recs, pos = [], 0
+        while pos < v.size:
+            offer = np.array([min(v.size - pos, cur.blockSize)], np.uint32)
+            _native._check_plain(self.lib, self.lib.k4lz4_chain_encode_plan(_C.byref(cur), offer.ctypes.data, flags.ctypes.data, 1, _C.byref(nxt),
+                                                                           loaded.ctypes.data, None))
+            take = int(loaded[0])
+            recs.append((v[pos:pos + take], force, allowCopy))     # (a full block that was topped up but not encoded: no bytes, it encodes)
+            pos += take
+            cur, nxt = nxt, cur
+        return recs
+
+    def Write(self, pieces, force: bool = False, allowCopy: bool = True):
+        """pieces[s]: bytes for encoder s (None or empty: it sits the call out) -> per encoder the blocks the call wrote, [(recOut, bytes)]"""
+        records = [self.write_records(i, p, force, allowCopy) if p is not None and len(p) else [] for i, p in enumerate(pieces)]
+        return self.blocks_of(*self.Run(records)[1:])
+
+    def Flush(self, allowCopy: bool = True):
+        """FlushAndEncode for every encoder"""
+        return self.blocks_of(*self.Run([[(b"", True, allowCopy)] for _ in range(self.n)])[1:])
+
+    @staticmethod
+    def blocks_of(rec_out, out_len, data):
+        res = []
+        for ro, total, d in zip(rec_out, out_len, data):
+            if total < 0:
+                raise InvalidOperationException(f"code {total}")
+            at, blocks = 0, []
+            for o in ro:
+                if o:
+                    blocks.append((o, d[at:at + abs(o)]))
+                    at += abs(o)
+            res.append(blocks)
+        return res
+
+    def Ring(self, i: int) -> bytes:
+        """the ring of encoder i as the store holds it, from 0 to _inputPointer"""
+        r = self.records[i]
+        at = int(self._base - self.store.data_ptr() + self.store_off[i]) + _ring_at(r)
+        return self.store[at:at + int(r.pointer)].cpu().numpy().tobytes()
+
+    def State(self, i: int) -> np.ndarray:
+        """a chained fast encoder's stream context as the store holds it (FAST_CHAIN_STATE)"""
+        at = int(self._base - self.store.data_ptr() + self.store_off[i])
+        return np.frombuffer(self.store[at:at + FAST_CHAIN_STATE.itemsize].cpu().numpy().tobytes(), FAST_CHAIN_STATE).copy()
+
+
+class LZ4ChainEncoder:
+    """The ILZ4Encoder of one stream over a batch of one (k4lz4_chain_encode_batch): what LZ4Encoder.Create returns.  Topup keeps its
+    bytes on the host until the Encode that takes them -- one record, Topup and a forced Encode -- so the two work as separate calls."""
+
+    def __init__(self, chaining: bool, level: LZ4Level, blockSize: int, extraBlocks: int = 0, ctx: Optional[_native.Context] = None):
+        self._batch = LZ4EncoderBatch([(chaining, level, blockSize, extraBlocks)], ctx)
+        self._pending: List[np.ndarray] = []
+
+    @property
+    def BlockSize(self) -> int:
+        return self._batch.BlockSize(0)
+
+    @property
+    def BytesReady(self) -> int:
+        return self._batch.BytesReady(0) + sum(p.size for p in self._pending)
+
+    def Topup(self, source, offset: int = 0, length: Optional[int] = None) -> int:
+        """LZ4EncoderBase.cs:46-62"""
+        src = _ro_view(source, "source")
+        length = src.size - offset if length is None else int(length)
+        if length == 0:
+            return 0
+        space = self.BlockSize - self.BytesReady
+        if space <= 0:
+            return 0
+        chunk = min(space, length)
+        self._pending.append(src[offset:offset + chunk].copy())
+        return chunk
+
+    def Encode(self, target, offset: int = 0, length: Optional[int] = None, allowCopy: bool = False) -> int:
+        """LZ4EncoderBase.cs:66-88: the pending bytes as one block into target; negative: stored raw under allowCopy.  A target below
+        the library's bound for the block (its length under allowCopy, MaximumOutputSize otherwise) is refused before anything runs
+        (K4LZ4_CENC_TARGET): the exception is the reference's, and the encoder keeps the block for a retry with a larger target"""
+        dst = _rw_view(target, "target")
+        length = dst.size - offset if length is None else int(length)
+        if self.BytesReady <= 0:
+            return 0
+        piece = np.concatenate(self._pending) if self._pending else np.zeros(0, np.uint8)
+        run = [[(piece, True, allowCopy)]]
+        cap = min(max(length, 0), self._batch.Bound(run)[0])
+        _, rec_out, out_len, data = self._batch.Run(run, caps=[cap])
+        if out_len[0] < 0:
+            raise InvalidOperationException("Failed to encode chunk. Target buffer too small.")
+        self._pending = []
+        encoded = rec_out[0][0]
+        dst[offset:offset + abs(encoded)] = np.frombuffer(data[0], np.uint8)
+        return encoded
+
+
+class LZ4Encoder:
+    """Encoders/LZ4Encoder.cs"""
+
+    @staticmethod
+    def Create(chaining: bool, level: LZ4Level, blockSize: int, extraBlocks: int = 0, ctx: Optional[_native.Context] = None) -> LZ4ChainEncoder:
+        return LZ4ChainEncoder(chaining, level, blockSize, extraBlocks, ctx)
