@@ -2012,6 +2012,223 @@ int host_streams(Device device, k4lz4_ctx *ctx, const uint8_t *src, const uint64
     });
 }
 
+/* ---- the incremental readers and the per-stream queries: one device form, one host form, one query pair.
+ * The direct path's tables come out of ctx->d_frd at 64-byte steps.  A layout runs twice over the same Carve calls: without a base
+ * it measures what grow_scratch is asked for, with one it places the pointers -- the size cannot fall behind the arrays. */
+struct Carve {
+    uint8_t *const base;
+    size_t at = 0;
+    template <class T> void take(T *&p, size_t count)
+    {
+        p = base ? (T *)(base + at) : nullptr;
+        at += (count * sizeof(T) + 63) & ~(size_t)63;
+    }
+};
+
+void direct_layout(Carve &c, k4::FrFastArgs &f, size_t n, size_t nr)
+{
+    c.take(f.plan, n); c.take(f.done, n);
+    c.take(f.sSrcOff, n); c.take(f.sDstOff, n); c.take(f.sSrcLen, n); c.take(f.sDstCap, n); c.take(f.sOutLen, n);
+    c.take(f.srcOff, nr); c.take(f.dstOff, nr); c.take(f.hlen, nr); c.take(f.srcLen, nr); c.take(f.dstCap, nr); c.take(f.outLen, nr);
+    c.take(f.sum, nr); c.take(f.got, nr); c.take(f.lc, nr);
+}
+void direct_layout(Carve &c, k4::FrFeedFastArgs &ff, size_t n, size_t nr)
+{
+    direct_layout(c, ff.f, n, nr);
+    c.take(ff.tail, n); c.take(ff.want, n);
+}
+void direct_layout(Carve &c, k4::LsDirectArgs &f, size_t n, size_t nr)
+{
+    c.take(f.plan, n); c.take(f.done, n);
+    c.take(f.sSrcOff, n); c.take(f.sDstOff, n); c.take(f.sSrcLen, n); c.take(f.sDstCap, n); c.take(f.sOutLen, n);
+    c.take(f.srcOff, nr); c.take(f.dstOff, nr); c.take(f.srcLen, nr); c.take(f.dstCap, nr); c.take(f.outLen, nr); c.take(f.rawLen, nr);
+}
+void direct_layout(Carve &c, k4::LsFeedDirectArgs &f, size_t n, size_t nr)
+{
+    c.take(f.plan, n); c.take(f.done, n); c.take(f.head, n);
+    c.take(f.sSrcAddr, n); c.take(f.sDstAddr, n); c.take(f.sSrcLen, n); c.take(f.sDstCap, n); c.take(f.sOutLen, n);
+    c.take(f.srcAddr, nr); c.take(f.dstAddr, nr); c.take(f.srcLen, nr); c.take(f.dstCap, nr); c.take(f.outLen, nr); c.take(f.rawLen, nr);
+}
+
+/* What tells the four readers apart on the host.  Args: what the per-stream reader kernel (READ) takes; Direct: what the direct
+ * path's PLAN and COMMIT kernels take, table(d) the part of it that holds the tables; begin() hands the call's arrays to the direct
+ * path and served() hands the reader kernel what the commit left for it.  SUMS: block checksums between plan and decode.
+ * ADDRESSES: the rows hold addresses -- a row's source may be the stash, which TOPUP completes first --, the decoder's bases are null. */
+struct FrameReader {
+    using Args = k4::FrReadArgs; using Direct = k4::FrFastArgs;
+    static constexpr int WAVES = k4::FR_WAVES_PER_WG;
+    static constexpr bool SUMS = true, ADDRESSES = false;
+    static constexpr const char *ROWS_PASS = "k4lz4_frame_read_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows";
+    static constexpr auto PLAN = k4::k4_fr_plan_kernel, COMMIT = k4::k4_fr_commit_kernel;
+    static constexpr auto READ = k4::k4_fr_read_kernel;
+    static Args &reader(Args &a) { return a; }
+    static Direct &table(Direct &d) { return d; }
+    static void begin(Direct &d, const Args &a) { d.r = a; }
+    static void served(Args &a, const Direct &d) { a.done = d.done; }
+};
+struct FedFrameReader {
+    using Args = k4::FrFeedArgs; using Direct = k4::FrFeedFastArgs;
+    static constexpr int WAVES = k4::FR_WAVES_PER_WG;
+    static constexpr bool SUMS = true, ADDRESSES = false;
+    static constexpr const char *ROWS_PASS = "k4lz4_frame_read_fed_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows";
+    static constexpr auto PLAN = k4::k4_fr_feed_plan_kernel, COMMIT = k4::k4_fr_feed_commit_kernel;
+    static constexpr auto READ = k4::k4_fr_feed_kernel;
+    static k4::FrReadArgs &reader(Args &a) { return a.r; }
+    static k4::FrFastArgs &table(Direct &d) { return d.f; }
+    static void begin(Direct &d, const Args &a) { d.f.r = a.r; d.final = a.final; d.consumed = a.consumed; d.need = a.need; }
+    static void served(Args &a, const Direct &d) { a.r.done = d.f.done; }
+};
+struct LegacyReader {
+    using Args = k4::LsReadArgs; using Direct = k4::LsDirectArgs;
+    static constexpr int WAVES = k4::LS_WAVES_PER_WG;
+    static constexpr bool SUMS = false, ADDRESSES = false;
+    static constexpr const char *ROWS_PASS = "k4lz4_legacy_read_batch: the chunk table passes 2^31 rows";
+    static constexpr auto PLAN = k4::k4_ls_plan_kernel, COMMIT = k4::k4_ls_commit_kernel;
+    static constexpr auto READ = k4::k4_ls_read_kernel;
+    static Args &reader(Args &a) { return a; }
+    static Direct &table(Direct &d) { return d; }
+    static void begin(Direct &d, const Args &a) { d.r = a; }
+    static void served(Args &a, const Direct &d) { a.done = d.done; }
+};
+struct FedLegacyReader {
+    using Args = k4::LsFeedArgs; using Direct = k4::LsFeedDirectArgs;
+    static constexpr int WAVES = k4::LS_WAVES_PER_WG;
+    static constexpr bool SUMS = false, ADDRESSES = true;
+    static constexpr const char *ROWS_PASS = "k4lz4_legacy_read_fed_batch: the chunk table passes 2^31 rows";
+    static constexpr auto TOPUP = k4::k4_ls_feed_topup_kernel, PLAN = k4::k4_ls_feed_plan_kernel, COMMIT = k4::k4_ls_feed_commit_kernel;
+    static constexpr auto READ = k4::k4_ls_feed_kernel;
+    static k4::LsReadArgs &reader(Args &a) { return a.r; }
+    static Direct &table(Direct &d) { return d; }
+    static void begin(Direct &d, const Args &a) { d.f = a; }
+    static void served(Args &a, const Direct &d) { a.r.done = d.done; a.head = d.head; }
+};
+
+/* a reader's device form after its argument checks.  rows: the table rows per stream when the call takes the direct path (a READ
+ * that is not interactive), else 0.  The direct path: plan, block checksums, the batch decoder into dst and into the stores, check
+ * and commit; the table is bounded by maxCount, so nothing is read back.  Then the per-stream reader for what is left. */
+template <class F>
+int read_device(k4lz4_ctx *ctx, typename F::Args a, long long rows, void *stream)
+{
+    auto &r = F::reader(a);
+    const long long n = r.n;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    const dim3 waves((unsigned)((n + F::WAVES - 1) / F::WAVES)), wg(64 * F::WAVES);
+    if (rows > 0) {
+        if (n * rows > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, F::ROWS_PASS);
+        const size_t nr = (size_t)n * (size_t)rows;
+        typename F::Direct d{};
+        F::begin(d, a);
+        auto &t = F::table(d);
+        t.rows = rows;
+        Carve measure{nullptr};
+        direct_layout(measure, d, (size_t)n, nr);
+        int rc;
+        if ((rc = grow_scratch(ctx, &ctx->d_frd, &ctx->d_frd_cap, measure.at)) != K4LZ4_OK) return rc;
+        Carve place{ctx->d_frd};
+        direct_layout(place, d, (size_t)n, nr);
+        if constexpr (F::ADDRESSES) hipLaunchKernelGGL(F::TOPUP, waves, wg, 0, st, d);
+        hipLaunchKernelGGL(F::PLAN, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d);
+        K4_HIP(ctx, hipGetLastError());
+        if constexpr (F::SUMS)
+            if ((rc = k4lz4_xxh32_batch_device(ctx, r.src, t.srcOff, t.hlen, t.got, (int64_t)nr, 0, st)) != K4LZ4_OK) return rc;
+        if constexpr (F::ADDRESSES) {
+            if ((rc = launch(ctx, KIND_DECODE, nullptr, t.srcAddr, t.srcLen, nullptr, t.dstAddr, t.dstCap, t.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
+                (rc = launch(ctx, KIND_DECODE, nullptr, t.sSrcAddr, t.sSrcLen, nullptr, t.sDstAddr, t.sDstCap, t.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
+                return rc;
+        } else {
+            if ((rc = launch(ctx, KIND_DECODE, r.src, t.srcOff, t.srcLen, r.dst, t.dstOff, t.dstCap, t.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
+                (rc = launch(ctx, KIND_DECODE, r.src, t.sSrcOff, t.sSrcLen, r.store, t.sDstOff, t.sDstCap, t.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
+                return rc;
+        }
+        hipLaunchKernelGGL(F::COMMIT, waves, wg, 0, st, d);
+        F::served(a, d);
+    }
+    hipLaunchKernelGGL(F::READ, waves, wg, 0, st, a);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+/* the arrays of a reader's call: the caller's in the host form, their staged copies in what it hands its device form */
+struct ReadArrays {
+    const uint64_t *storeOff;
+    const uint8_t *src;
+    const uint64_t *srcOff, *srcLen;
+    const int64_t *final;                  /* final, consumed, need: the fed forms' (consumed == nullptr: not a fed form) */
+    uint8_t *dst;
+    const uint64_t *dstOff;
+    const int64_t *count;
+    int64_t *outLen, *consumed, *need;
+};
+
+/* a reader's host form after its argument checks.  sends: the op takes pieces -- they go up packed, and a stream that sits the call
+ * out (count < 0) sends nothing; fills: the op is READ -- slots of count bytes, outLen[i] of them for the caller;
+ * device(staged, maxCount, stream) is the device form */
+template <class Device>
+int host_read(k4lz4_ctx *ctx, const ReadArrays &h, int64_t n, bool sends, bool fills, Device device)
+{
+    const bool fed = h.consumed != nullptr;
+    int64_t maxCount = 0;
+    for (int64_t i = 0; fills && i < n; i++) maxCount = std::max(maxCount, h.count[i]);
+    for (int64_t i = 0; sends && i < n; i++)
+        if (h.count[i] >= 0 && h.srcLen[i] > 0 && !h.src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<int64_t> len0((size_t)n, 0), fin0((size_t)n, 0);
+    std::vector<uint64_t> off0((size_t)n, 0);
+    for (int64_t i = 0; sends && i < n; i++)
+        if (h.count[i] >= 0) { len0[(size_t)i] = (int64_t)h.srcLen[i]; off0[(size_t)i] = h.srcOff[i]; fin0[(size_t)i] = h.final ? h.final[i] : 0; }
+    HostStage s(ctx);
+    s.pack(h.src, off0.data(), len0.data(), n);
+    s.slots(n, [&](int64_t i) { return fills && h.count[i] > 0 ? (uint64_t)h.count[i] : 0u; }, false);
+    uint64_t *d_soff, *d_slen, *d_store, *d_doff;
+    int64_t *d_count, *d_out, *d_fin = nullptr, *d_cons = nullptr, *d_need = nullptr;
+    s.meta(&d_soff, n, s.in_off.data()); s.meta(&d_slen, n, len0.data()); s.meta(&d_store, n, h.storeOff); s.meta(&d_doff, n, s.slot.data());
+    s.meta(&d_count, n, h.count); s.meta(&d_out, n);
+    if (fed) { s.meta(&d_fin, n, fin0.data()); s.meta(&d_cons, n); s.meta(&d_need, n); }
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = device(ReadArrays{d_store, ctx->d_src, d_soff, d_slen, d_fin, ctx->d_dst, d_doff, d_count, d_out, d_cons, d_need}, maxCount,
+                     s.st)) != K4LZ4_OK)
+        return rc;
+    const size_t fed_bytes = fed ? (size_t)n * 8 : 0;
+    return s.finish({{h.outLen, d_out, (size_t)n * 8}, {h.consumed, d_cons, fed_bytes}, {h.need, d_need, fed_bytes}}, h.dst, h.dstOff,
+                    [&](int64_t i) { return fills && h.outLen[i] > 0 ? (size_t)h.outLen[i] : 0; });
+}
+
+/* the per-stream queries (k4lz4_frame_reader_query, k4lz4_legacy_reader_query, k4lz4_chain_decoder_query): words int64 per stream */
+using QueryKernel = void (*)(const uint8_t *, const uint64_t *, int64_t *, long long);
+int query_device(k4lz4_ctx *ctx, QueryKernel kernel, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out, void *stream)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, store, storeOff, out, (long long)n);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+using QueryDevice = int (*)(k4lz4_ctx *, const uint8_t *, const uint64_t *, int64_t, int64_t *, void *);
+int query_host(k4lz4_ctx *ctx, int64_t words, QueryDevice device, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    uint64_t *d_store;
+    int64_t *d_out;
+    s.meta(&d_store, n, storeOff); s.meta(&d_out, n * words);
+    int rc;
+    if ((rc = s.upload()) != K4LZ4_OK || (rc = device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
+    return s.finish({{out, d_out, (size_t)(n * words) * 8}});
+}
+
 /* ---- incremental frame writer: the host half of k4lz4_frame_write.hpp (the store's layout, the header, the ring model, the bound) */
 using k4::FW_XXH_BYTES; using k4::FW_CHAIN_LIMIT; using k4::FwAfter;
 using k4::fw_ring_at; using k4::fw_slot; using k4::fw_header; using k4::fw_opens; using k4::fw_model; using k4::fw_bound; using k4::fw_code;
@@ -3310,45 +3527,10 @@ int k4lz4_frame_read_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, u
     if (n > 0 && (r->storeBytes != k4::fr_store_bytes(r->settings.maxBlockSize) || r->settings.maxBlockSize != k4::fr_max_block(r->settings.maxBlockSize)))
         return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: the record was not made by k4lz4_frame_reader_init");
     if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    k4::FrReadArgs a{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op,
-                     (flags & K4LZ4_FREAD_INTERACTIVE) ? 1 : 0, r->settings.maxBlockSize, nullptr};
-    const long long rows = k4::fr_table_rows(maxCount);
-    if (op == K4LZ4_FREAD_READ && !a.interactive && rows > 0) {
-        /* the fast path: plan, block checksums, the batch decoder into dst and into the stores, verify and commit; the table is
-         * bounded by maxCount, so nothing is read back */
-        if (n * rows > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows");
-        int rc;
-        if ((rc = grow_scratch(ctx, &ctx->d_frd, &ctx->d_frd_cap, k4::fr_fast_scratch(n, rows))) != K4LZ4_OK) return rc;
-        const size_t nr = (size_t)n * (size_t)rows;
-        uint8_t *m = ctx->d_frd;
-        auto take = [&](size_t bytes) { uint8_t *q = m; m += (bytes + 63) & ~(size_t)63; return q; };
-        k4::FrFastArgs f{};
-        f.r = a; f.rows = rows;
-        f.plan = (k4::FrPlan *)take((size_t)n * sizeof(k4::FrPlan));
-        f.done = (uint32_t *)take((size_t)n * 4);
-        f.sSrcOff = (uint64_t *)take((size_t)n * 8); f.sDstOff = (uint64_t *)take((size_t)n * 8);
-        f.sSrcLen = (int32_t *)take((size_t)n * 4); f.sDstCap = (int32_t *)take((size_t)n * 4); f.sOutLen = (int32_t *)take((size_t)n * 4);
-        f.srcOff = (uint64_t *)take(nr * 8); f.dstOff = (uint64_t *)take(nr * 8); f.hlen = (uint64_t *)take(nr * 8);
-        f.srcLen = (int32_t *)take(nr * 4); f.dstCap = (int32_t *)take(nr * 4); f.outLen = (int32_t *)take(nr * 4);
-        f.sum = (uint32_t *)take(nr * 4); f.got = (uint32_t *)take(nr * 4); f.lc = (uint32_t *)take(nr * 4);
-        hipLaunchKernelGGL(k4::k4_fr_plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f);
-        K4_HIP(ctx, hipGetLastError());
-        if ((rc = k4lz4_xxh32_batch_device(ctx, src, f.srcOff, f.hlen, f.got, (int64_t)nr, 0, st)) != K4LZ4_OK ||
-            (rc = launch(ctx, KIND_DECODE, src, f.srcOff, f.srcLen, dst, f.dstOff, f.dstCap, f.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
-            (rc = launch(ctx, KIND_DECODE, src, f.sSrcOff, f.sSrcLen, store, f.sDstOff, f.sDstCap, f.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
-            return rc;
-        hipLaunchKernelGGL(k4::k4_fr_commit_kernel, dim3((unsigned)((n + k4::FR_WAVES_PER_WG - 1) / k4::FR_WAVES_PER_WG)),
-                           dim3(64 * k4::FR_WAVES_PER_WG), 0, st, f);
-        a.done = f.done;
-    }
-    hipLaunchKernelGGL(k4::k4_fr_read_kernel, dim3((unsigned)((n + k4::FR_WAVES_PER_WG - 1) / k4::FR_WAVES_PER_WG)), dim3(64 * k4::FR_WAVES_PER_WG),
-                       0, st, a);
-    K4_HIP(ctx, hipGetLastError());
-    mark_busy(ctx, st);
-    return K4LZ4_OK;
+    const int interactive = (flags & K4LZ4_FREAD_INTERACTIVE) ? 1 : 0;
+    return read_device<FrameReader>(ctx, {src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op, interactive,
+                                          r->settings.maxBlockSize, nullptr},
+                                    op == K4LZ4_FREAD_READ && !interactive ? k4::fr_table_rows(maxCount) : 0, stream);
 }
 
 int k4lz4_frame_read_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
@@ -3364,60 +3546,22 @@ int k4lz4_frame_read_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t 
     if (n > 0 && (r->storeBytes != k4::fr_store_bytes(r->settings.maxBlockSize) || r->settings.maxBlockSize != k4::fr_max_block(r->settings.maxBlockSize)))
         return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: the record was not made by k4lz4_frame_reader_init");
     if (n == 0) return K4LZ4_OK;
-    const bool reads = op != K4LZ4_FREAD_RESET;
-    int64_t maxCount = 0;
-    for (int64_t i = 0; op == K4LZ4_FREAD_READ && i < n; i++) maxCount = std::max(maxCount, count[i]);
-    for (int64_t i = 0; reads && i < n; i++)
-        if (count[i] >= 0 && srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    /* streams that sit the call out send nothing up */
-    std::vector<int64_t> len0((size_t)n, 0);
-    std::vector<uint64_t> off0((size_t)n, 0);
-    for (int64_t i = 0; reads && i < n; i++)
-        if (count[i] >= 0) { len0[(size_t)i] = (int64_t)srcLen[i]; off0[(size_t)i] = srcOff[i]; }
-    HostStage s(ctx);
-    s.pack(src, off0.data(), len0.data(), n);
-    s.slots(n, [&](int64_t i) { return op == K4LZ4_FREAD_READ && count[i] > 0 ? (uint64_t)count[i] : 0u; }, false);
-    uint64_t *d_soff, *d_slen, *d_store, *d_doff;
-    int64_t *d_count, *d_out;
-    s.meta(&d_soff, n, s.in_off.data()); s.meta(&d_slen, n, len0.data()); s.meta(&d_store, n, storeOff); s.meta(&d_doff, n, s.slot.data());
-    s.meta(&d_count, n, count); s.meta(&d_out, n);
-    int rc;
-    if ((rc = s.upload()) != K4LZ4_OK ||
-        (rc = k4lz4_frame_read_batch_device(ctx, r, store, d_store, ctx->d_src, d_soff, d_slen, ctx->d_dst, d_doff, d_count, d_out, n, op, flags,
-                                            maxCount, s.st)) != K4LZ4_OK)
-        return rc;
-    return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff,
-                    [&](int64_t i) { return op == K4LZ4_FREAD_READ && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+    return host_read(ctx, {storeOff, src, srcOff, srcLen, nullptr, dst, dstOff, count, outLen, nullptr, nullptr}, n,
+                     /* sends */ op != K4LZ4_FREAD_RESET, /* fills */ op == K4LZ4_FREAD_READ,
+                     [&](const ReadArrays &d, int64_t maxCount, hipStream_t st) {
+                         return k4lz4_frame_read_batch_device(ctx, r, store, d.storeOff, d.src, d.srcOff, d.srcLen, d.dst, d.dstOff, d.count,
+                                                              d.outLen, n, op, flags, maxCount, st);
+                     });
 }
 
 int k4lz4_frame_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out, void *stream)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    hipLaunchKernelGGL(k4::k4_fr_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, store, storeOff, out, (long long)n);
-    K4_HIP(ctx, hipGetLastError());
-    mark_busy(ctx, st);
-    return K4LZ4_OK;
+    return query_device(ctx, k4::k4_fr_query_kernel, store, storeOff, n, out, stream);
 }
 
 int k4lz4_frame_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    HostStage s(ctx);
-    uint64_t *d_store;
-    int64_t *d_out;
-    s.meta(&d_store, n, storeOff); s.meta(&d_out, n * K4LZ4_FRQ_WORDS);
-    int rc;
-    if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_frame_reader_query_device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
-    return s.finish({{out, d_out, (size_t)n * K4LZ4_FRQ_WORDS * 8}});
+    return query_host(ctx, K4LZ4_FRQ_WORDS, k4lz4_frame_reader_query_device, store, storeOff, n, out);
 }
 
 /* ---- the incremental frame reader fed its source in pieces (k4lz4_frame_feed.hpp) ------------------------- */
@@ -3446,46 +3590,10 @@ int k4lz4_frame_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *
     if ((rc = fed_args(ctx, r, store, storeOff, srcOff, srcLen, dst, dstOff, count, outLen, consumed, need, n, op, flags)) != K4LZ4_OK) return rc;
     if (n > 0 && op != K4LZ4_FREAD_RESET && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
     if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    k4::FrFeedArgs a{{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op,
-                      (flags & K4LZ4_FREAD_INTERACTIVE) ? 1 : 0, r->settings.maxBlockSize, nullptr},
-                     final, consumed, need};
-    const long long rows = k4::fr_table_rows(maxCount);
-    const dim3 waves((unsigned)((n + k4::FR_WAVES_PER_WG - 1) / k4::FR_WAVES_PER_WG)), wg(64 * k4::FR_WAVES_PER_WG);
-    if (op == K4LZ4_FREAD_READ && !a.r.interactive && rows > 0) {
-        /* the fast path over the records that are wholly in the pieces: 4.14's launches with the fed plan and commit kernels */
-        if (n * rows > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_fed_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows");
-        if ((rc = grow_scratch(ctx, &ctx->d_frd, &ctx->d_frd_cap, k4::fr_feed_fast_scratch(n, rows))) != K4LZ4_OK) return rc;
-        const size_t nr = (size_t)n * (size_t)rows;
-        uint8_t *m = ctx->d_frd;
-        auto take = [&](size_t bytes) { uint8_t *q = m; m += (bytes + 63) & ~(size_t)63; return q; };
-        k4::FrFeedFastArgs ff{};
-        k4::FrFastArgs &f = ff.f;
-        f.r = a.r; f.rows = rows;
-        ff.final = final; ff.consumed = consumed; ff.need = need;
-        f.plan = (k4::FrPlan *)take((size_t)n * sizeof(k4::FrPlan));
-        f.done = (uint32_t *)take((size_t)n * 4);
-        ff.tail = (uint32_t *)take((size_t)n * 4); ff.want = (uint32_t *)take((size_t)n * 4);
-        f.sSrcOff = (uint64_t *)take((size_t)n * 8); f.sDstOff = (uint64_t *)take((size_t)n * 8);
-        f.sSrcLen = (int32_t *)take((size_t)n * 4); f.sDstCap = (int32_t *)take((size_t)n * 4); f.sOutLen = (int32_t *)take((size_t)n * 4);
-        f.srcOff = (uint64_t *)take(nr * 8); f.dstOff = (uint64_t *)take(nr * 8); f.hlen = (uint64_t *)take(nr * 8);
-        f.srcLen = (int32_t *)take(nr * 4); f.dstCap = (int32_t *)take(nr * 4); f.outLen = (int32_t *)take(nr * 4);
-        f.sum = (uint32_t *)take(nr * 4); f.got = (uint32_t *)take(nr * 4); f.lc = (uint32_t *)take(nr * 4);
-        hipLaunchKernelGGL(k4::k4_fr_feed_plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ff);
-        K4_HIP(ctx, hipGetLastError());
-        if ((rc = k4lz4_xxh32_batch_device(ctx, src, f.srcOff, f.hlen, f.got, (int64_t)nr, 0, st)) != K4LZ4_OK ||
-            (rc = launch(ctx, KIND_DECODE, src, f.srcOff, f.srcLen, dst, f.dstOff, f.dstCap, f.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
-            (rc = launch(ctx, KIND_DECODE, src, f.sSrcOff, f.sSrcLen, store, f.sDstOff, f.sDstCap, f.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
-            return rc;
-        hipLaunchKernelGGL(k4::k4_fr_feed_commit_kernel, waves, wg, 0, st, ff);
-        a.r.done = f.done;
-    }
-    hipLaunchKernelGGL(k4::k4_fr_feed_kernel, waves, wg, 0, st, a);
-    K4_HIP(ctx, hipGetLastError());
-    mark_busy(ctx, st);
-    return K4LZ4_OK;
+    const int interactive = (flags & K4LZ4_FREAD_INTERACTIVE) ? 1 : 0;
+    return read_device<FedFrameReader>(ctx, {{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op, interactive,
+                                              r->settings.maxBlockSize, nullptr}, final, consumed, need},
+                                       op == K4LZ4_FREAD_READ && !interactive ? k4::fr_table_rows(maxCount) : 0, stream);
 }
 
 int k4lz4_frame_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
@@ -3495,30 +3603,12 @@ int k4lz4_frame_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint
     int rc;
     if ((rc = fed_args(ctx, r, store, storeOff, srcOff, srcLen, dst, dstOff, count, outLen, consumed, need, n, op, flags)) != K4LZ4_OK) return rc;
     if (n == 0) return K4LZ4_OK;
-    const bool reads = op != K4LZ4_FREAD_RESET;
-    int64_t maxCount = 0;
-    for (int64_t i = 0; op == K4LZ4_FREAD_READ && i < n; i++) maxCount = std::max(maxCount, count[i]);
-    for (int64_t i = 0; reads && i < n; i++)
-        if (count[i] >= 0 && srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    /* only the pieces go up; streams that sit the call out send nothing */
-    std::vector<int64_t> len0((size_t)n, 0), fin0((size_t)n, 0);
-    std::vector<uint64_t> off0((size_t)n, 0);
-    for (int64_t i = 0; reads && i < n; i++)
-        if (count[i] >= 0) { len0[(size_t)i] = (int64_t)srcLen[i]; off0[(size_t)i] = srcOff[i]; fin0[(size_t)i] = final ? final[i] : 0; }
-    HostStage s(ctx);
-    s.pack(src, off0.data(), len0.data(), n);
-    s.slots(n, [&](int64_t i) { return op == K4LZ4_FREAD_READ && count[i] > 0 ? (uint64_t)count[i] : 0u; }, false);
-    uint64_t *d_soff, *d_slen, *d_store, *d_doff;
-    int64_t *d_count, *d_out, *d_fin, *d_cons, *d_need;
-    s.meta(&d_soff, n, s.in_off.data()); s.meta(&d_slen, n, len0.data()); s.meta(&d_store, n, storeOff); s.meta(&d_doff, n, s.slot.data());
-    s.meta(&d_count, n, count); s.meta(&d_fin, n, fin0.data()); s.meta(&d_out, n); s.meta(&d_cons, n); s.meta(&d_need, n);
-    if ((rc = s.upload()) != K4LZ4_OK ||
-        (rc = k4lz4_frame_read_fed_batch_device(ctx, r, store, d_store, ctx->d_src, d_soff, d_slen, d_fin, ctx->d_dst, d_doff, d_count, d_out,
-                                                d_cons, d_need, n, op, flags, maxCount, s.st)) != K4LZ4_OK)
-        return rc;
-    return s.finish({{outLen, d_out, (size_t)n * 8}, {consumed, d_cons, (size_t)n * 8}, {need, d_need, (size_t)n * 8}}, dst, dstOff,
-                    [&](int64_t i) { return op == K4LZ4_FREAD_READ && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+    return host_read(ctx, {storeOff, src, srcOff, srcLen, final, dst, dstOff, count, outLen, consumed, need}, n,
+                     /* sends */ op != K4LZ4_FREAD_RESET, /* fills */ op == K4LZ4_FREAD_READ,
+                     [&](const ReadArrays &d, int64_t maxCount, hipStream_t st) {
+                         return k4lz4_frame_read_fed_batch_device(ctx, r, store, d.storeOff, d.src, d.srcOff, d.srcLen, d.final, d.dst, d.dstOff,
+                                                                  d.count, d.outLen, d.consumed, d.need, n, op, flags, maxCount, st);
+                     });
 }
 
 /* ---- LZ4Stream written and read piece by piece (k4lz4_legacy_stream.hpp) ---------------------------------- */
@@ -3672,43 +3762,10 @@ int k4lz4_legacy_read_batch_device(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r,
     if (n > 0 && (r->maxBlockSize < 16 || r->storeBytes != k4::ls_rd_store_bytes(r->maxBlockSize)))
         return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_batch: the record was not made by k4lz4_legacy_reader_init");
     if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    k4::LsReadArgs a{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op,
-                     (flags & K4LZ4_LREAD_INTERACTIVE) ? 1 : 0, r->maxBlockSize, nullptr};
-    const long long rows = k4::ls_table_rows(maxCount, r->maxBlockSize);
-    const unsigned wgrid = (unsigned)((n + k4::LS_WAVES_PER_WG - 1) / k4::LS_WAVES_PER_WG);
-    if (op == K4LZ4_LREAD_READ && !a.interactive && rows > 0) {
-        /* the direct path: plan, the batch decoder into dst and into the stores, check and commit; the table is bounded by
-         * maxCount, so nothing is read back */
-        if (n * rows > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_batch: the chunk table passes 2^31 rows");
-        int rc;
-        if ((rc = grow_scratch(ctx, &ctx->d_frd, &ctx->d_frd_cap, k4::ls_direct_scratch(n, rows))) != K4LZ4_OK) return rc;
-        const size_t nr = (size_t)n * (size_t)rows;
-        uint8_t *m = ctx->d_frd;
-        auto take = [&](size_t bytes) { uint8_t *q = m; m += (bytes + 63) & ~(size_t)63; return q; };
-        k4::LsDirectArgs f{};
-        f.r = a; f.rows = rows;
-        f.plan = (k4::LsPlan *)take((size_t)n * sizeof(k4::LsPlan));
-        f.done = (uint32_t *)take((size_t)n * 4);
-        f.sSrcOff = (uint64_t *)take((size_t)n * 8); f.sDstOff = (uint64_t *)take((size_t)n * 8);
-        f.sSrcLen = (int32_t *)take((size_t)n * 4); f.sDstCap = (int32_t *)take((size_t)n * 4); f.sOutLen = (int32_t *)take((size_t)n * 4);
-        f.srcOff = (uint64_t *)take(nr * 8); f.dstOff = (uint64_t *)take(nr * 8);
-        f.srcLen = (int32_t *)take(nr * 4); f.dstCap = (int32_t *)take(nr * 4); f.outLen = (int32_t *)take(nr * 4);
-        f.rawLen = (uint32_t *)take(nr * 4);
-        hipLaunchKernelGGL(k4::k4_ls_plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f);
-        K4_HIP(ctx, hipGetLastError());
-        if ((rc = launch(ctx, KIND_DECODE, src, f.srcOff, f.srcLen, dst, f.dstOff, f.dstCap, f.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
-            (rc = launch(ctx, KIND_DECODE, src, f.sSrcOff, f.sSrcLen, store, f.sDstOff, f.sDstCap, f.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
-            return rc;
-        hipLaunchKernelGGL(k4::k4_ls_commit_kernel, dim3(wgrid), dim3(64 * k4::LS_WAVES_PER_WG), 0, st, f);
-        a.done = f.done;
-    }
-    hipLaunchKernelGGL(k4::k4_ls_read_kernel, dim3(wgrid), dim3(64 * k4::LS_WAVES_PER_WG), 0, st, a);
-    K4_HIP(ctx, hipGetLastError());
-    mark_busy(ctx, st);
-    return K4LZ4_OK;
+    const int interactive = (flags & K4LZ4_LREAD_INTERACTIVE) ? 1 : 0;
+    return read_device<LegacyReader>(ctx, {src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op, interactive,
+                                           r->maxBlockSize, nullptr},
+                                     op == K4LZ4_LREAD_READ && !interactive ? k4::ls_table_rows(maxCount, r->maxBlockSize) : 0, stream);
 }
 
 int k4lz4_legacy_read_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
@@ -3720,59 +3777,22 @@ int k4lz4_legacy_read_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_
     if (n < 0 || (n > 0 && (!r || !store || !storeOff || !count || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
     if (n > 0 && op == K4LZ4_LREAD_READ && (!srcOff || !srcLen || !dst || !dstOff)) return fail(ctx, K4LZ4_E_ARG, "bad argument");
     if (n == 0) return K4LZ4_OK;
-    const bool reads = op == K4LZ4_LREAD_READ;
-    int64_t maxCount = 0;
-    for (int64_t i = 0; reads && i < n; i++) maxCount = std::max(maxCount, count[i]);
-    for (int64_t i = 0; reads && i < n; i++)
-        if (count[i] >= 0 && srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    /* streams that sit the call out send nothing up */
-    std::vector<int64_t> len0((size_t)n, 0);
-    std::vector<uint64_t> off0((size_t)n, 0);
-    for (int64_t i = 0; reads && i < n; i++)
-        if (count[i] >= 0) { len0[(size_t)i] = (int64_t)srcLen[i]; off0[(size_t)i] = srcOff[i]; }
-    HostStage s(ctx);
-    s.pack(src, off0.data(), len0.data(), n);
-    s.slots(n, [&](int64_t i) { return reads && count[i] > 0 ? (uint64_t)count[i] : 0u; }, false);
-    uint64_t *d_soff, *d_slen, *d_store, *d_doff;
-    int64_t *d_count, *d_out;
-    s.meta(&d_soff, n, s.in_off.data()); s.meta(&d_slen, n, len0.data()); s.meta(&d_store, n, storeOff); s.meta(&d_doff, n, s.slot.data());
-    s.meta(&d_count, n, count); s.meta(&d_out, n);
-    int rc;
-    if ((rc = s.upload()) != K4LZ4_OK ||
-        (rc = k4lz4_legacy_read_batch_device(ctx, r, store, d_store, ctx->d_src, d_soff, d_slen, ctx->d_dst, d_doff, d_count, d_out, n, op, flags,
-                                             maxCount, s.st)) != K4LZ4_OK)
-        return rc;
-    return s.finish({{outLen, d_out, (size_t)n * 8}}, dst, dstOff, [&](int64_t i) { return reads && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+    return host_read(ctx, {storeOff, src, srcOff, srcLen, nullptr, dst, dstOff, count, outLen, nullptr, nullptr}, n,
+                     /* sends */ op == K4LZ4_LREAD_READ, /* fills */ op == K4LZ4_LREAD_READ,
+                     [&](const ReadArrays &d, int64_t maxCount, hipStream_t st) {
+                         return k4lz4_legacy_read_batch_device(ctx, r, store, d.storeOff, d.src, d.srcOff, d.srcLen, d.dst, d.dstOff, d.count,
+                                                               d.outLen, n, op, flags, maxCount, st);
+                     });
 }
 
 int k4lz4_legacy_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out, void *stream)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    hipLaunchKernelGGL(k4::k4_ls_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, store, storeOff, out, (long long)n);
-    K4_HIP(ctx, hipGetLastError());
-    mark_busy(ctx, st);
-    return K4LZ4_OK;
+    return query_device(ctx, k4::k4_ls_query_kernel, store, storeOff, n, out, stream);
 }
 
 int k4lz4_legacy_reader_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    HostStage s(ctx);
-    uint64_t *d_store;
-    int64_t *d_out;
-    s.meta(&d_store, n, storeOff); s.meta(&d_out, n * K4LZ4_LSQ_WORDS);
-    int rc;
-    if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_legacy_reader_query_device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
-    return s.finish({{out, d_out, (size_t)n * K4LZ4_LSQ_WORDS * 8}});
+    return query_host(ctx, K4LZ4_LSQ_WORDS, k4lz4_legacy_reader_query_device, store, storeOff, n, out);
 }
 
 /* ---- the incremental LZ4Stream reader fed its source in pieces (k4lz4_legacy_feed.hpp) --------------------- */
@@ -3809,44 +3829,10 @@ int k4lz4_legacy_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_legacy_reader
     if ((rc = lfed_args(ctx, r, store, storeOff, srcOff, srcLen, dst, dstOff, count, outLen, consumed, need, n, op, flags)) != K4LZ4_OK) return rc;
     if (n > 0 && op == K4LZ4_LREAD_READ && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
     if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    k4::LsFeedArgs a{{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op,
-                      (flags & K4LZ4_LREAD_INTERACTIVE) ? 1 : 0, r->maxBlockSize, nullptr},
-                     final, consumed, need, nullptr};
-    const long long rows = k4::ls_table_rows(maxCount, r->maxBlockSize);
-    const dim3 waves((unsigned)((n + k4::LS_WAVES_PER_WG - 1) / k4::LS_WAVES_PER_WG)), wg(64 * k4::LS_WAVES_PER_WG);
-    if (op == K4LZ4_LREAD_READ && !a.r.interactive && rows > 0) {
-        /* the direct path: the kept chunks are completed, then 4.16's launches with the fed plan and commit kernels.  The rows hold
-         * addresses (a row's source may be a stash), so the decoder's bases are null. */
-        if (n * rows > 0x7fffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_read_fed_batch: the chunk table passes 2^31 rows");
-        if ((rc = grow_scratch(ctx, &ctx->d_frd, &ctx->d_frd_cap, k4::ls_feed_direct_scratch(n, rows))) != K4LZ4_OK) return rc;
-        const size_t nr = (size_t)n * (size_t)rows;
-        uint8_t *m = ctx->d_frd;
-        auto take = [&](size_t bytes) { uint8_t *q = m; m += (bytes + 63) & ~(size_t)63; return q; };
-        k4::LsFeedDirectArgs f{};
-        f.f = a; f.rows = rows;
-        f.plan = (k4::LsFeedPlan *)take((size_t)n * sizeof(k4::LsFeedPlan));
-        f.done = (uint32_t *)take((size_t)n * 4); f.head = (uint32_t *)take((size_t)n * 4);
-        f.sSrcAddr = (uint64_t *)take((size_t)n * 8); f.sDstAddr = (uint64_t *)take((size_t)n * 8);
-        f.sSrcLen = (int32_t *)take((size_t)n * 4); f.sDstCap = (int32_t *)take((size_t)n * 4); f.sOutLen = (int32_t *)take((size_t)n * 4);
-        f.srcAddr = (uint64_t *)take(nr * 8); f.dstAddr = (uint64_t *)take(nr * 8);
-        f.srcLen = (int32_t *)take(nr * 4); f.dstCap = (int32_t *)take(nr * 4); f.outLen = (int32_t *)take(nr * 4);
-        f.rawLen = (uint32_t *)take(nr * 4);
-        hipLaunchKernelGGL(k4::k4_ls_feed_topup_kernel, waves, wg, 0, st, f);
-        hipLaunchKernelGGL(k4::k4_ls_feed_plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f);
-        K4_HIP(ctx, hipGetLastError());
-        if ((rc = launch(ctx, KIND_DECODE, nullptr, f.srcAddr, f.srcLen, nullptr, f.dstAddr, f.dstCap, f.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
-            (rc = launch(ctx, KIND_DECODE, nullptr, f.sSrcAddr, f.sSrcLen, nullptr, f.sDstAddr, f.sDstCap, f.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
-            return rc;
-        hipLaunchKernelGGL(k4::k4_ls_feed_commit_kernel, waves, wg, 0, st, f);
-        a.r.done = f.done; a.head = f.head;
-    }
-    hipLaunchKernelGGL(k4::k4_ls_feed_kernel, waves, wg, 0, st, a);
-    K4_HIP(ctx, hipGetLastError());
-    mark_busy(ctx, st);
-    return K4LZ4_OK;
+    const int interactive = (flags & K4LZ4_LREAD_INTERACTIVE) ? 1 : 0;
+    return read_device<FedLegacyReader>(ctx, {{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op, interactive,
+                                               r->maxBlockSize, nullptr}, final, consumed, need, nullptr},
+                                        op == K4LZ4_LREAD_READ && !interactive ? k4::ls_table_rows(maxCount, r->maxBlockSize) : 0, stream);
 }
 
 int k4lz4_legacy_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
@@ -3856,30 +3842,12 @@ int k4lz4_legacy_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_legacy_reader *r, ui
     int rc;
     if ((rc = lfed_args(ctx, r, store, storeOff, srcOff, srcLen, dst, dstOff, count, outLen, consumed, need, n, op, flags)) != K4LZ4_OK) return rc;
     if (n == 0) return K4LZ4_OK;
-    const bool reads = op == K4LZ4_LREAD_READ;
-    int64_t maxCount = 0;
-    for (int64_t i = 0; reads && i < n; i++) maxCount = std::max(maxCount, count[i]);
-    for (int64_t i = 0; reads && i < n; i++)
-        if (count[i] >= 0 && srcLen[i] > 0 && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    /* only the pieces go up; streams that sit the call out send nothing */
-    std::vector<int64_t> len0((size_t)n, 0), fin0((size_t)n, 0);
-    std::vector<uint64_t> off0((size_t)n, 0);
-    for (int64_t i = 0; reads && i < n; i++)
-        if (count[i] >= 0) { len0[(size_t)i] = (int64_t)srcLen[i]; off0[(size_t)i] = srcOff[i]; fin0[(size_t)i] = final ? final[i] : 0; }
-    HostStage s(ctx);
-    s.pack(src, off0.data(), len0.data(), n);
-    s.slots(n, [&](int64_t i) { return reads && count[i] > 0 ? (uint64_t)count[i] : 0u; }, false);
-    uint64_t *d_soff, *d_slen, *d_store, *d_doff;
-    int64_t *d_count, *d_out, *d_fin, *d_cons, *d_need;
-    s.meta(&d_soff, n, s.in_off.data()); s.meta(&d_slen, n, len0.data()); s.meta(&d_store, n, storeOff); s.meta(&d_doff, n, s.slot.data());
-    s.meta(&d_count, n, count); s.meta(&d_fin, n, fin0.data()); s.meta(&d_out, n); s.meta(&d_cons, n); s.meta(&d_need, n);
-    if ((rc = s.upload()) != K4LZ4_OK ||
-        (rc = k4lz4_legacy_read_fed_batch_device(ctx, r, store, d_store, ctx->d_src, d_soff, d_slen, d_fin, ctx->d_dst, d_doff, d_count, d_out,
-                                                 d_cons, d_need, n, op, flags, maxCount, s.st)) != K4LZ4_OK)
-        return rc;
-    return s.finish({{outLen, d_out, (size_t)n * 8}, {consumed, d_cons, (size_t)n * 8}, {need, d_need, (size_t)n * 8}}, dst, dstOff,
-                    [&](int64_t i) { return reads && outLen[i] > 0 ? (size_t)outLen[i] : 0; });
+    return host_read(ctx, {storeOff, src, srcOff, srcLen, final, dst, dstOff, count, outLen, consumed, need}, n,
+                     /* sends */ op == K4LZ4_LREAD_READ, /* fills */ op == K4LZ4_LREAD_READ,
+                     [&](const ReadArrays &d, int64_t maxCount, hipStream_t st) {
+                         return k4lz4_legacy_read_fed_batch_device(ctx, r, store, d.storeOff, d.src, d.srcOff, d.srcLen, d.final, d.dst, d.dstOff,
+                                                                   d.count, d.outLen, d.consumed, d.need, n, op, flags, maxCount, st);
+                     });
 }
 
 /* ---- many open ILZ4Decoders advanced per call (k4lz4_chain_decoder.hpp) ------------------------------------ */
@@ -4059,31 +4027,12 @@ int k4lz4_chain_drain_batch(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t
 
 int k4lz4_chain_decoder_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out, void *stream)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    hipLaunchKernelGGL(k4::k4_cdec_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, store, storeOff, out, (long long)n);
-    K4_HIP(ctx, hipGetLastError());
-    mark_busy(ctx, st);
-    return K4LZ4_OK;
+    return query_device(ctx, k4::k4_cdec_query_kernel, store, storeOff, n, out, stream);
 }
 
 int k4lz4_chain_decoder_query(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out)
 {
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (n < 0 || (n > 0 && (!store || !storeOff || !out))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    HostStage s(ctx);
-    uint64_t *d_store;
-    int64_t *d_out;
-    s.meta(&d_store, n, storeOff); s.meta(&d_out, n * K4LZ4_CDQ_WORDS);
-    int rc;
-    if ((rc = s.upload()) != K4LZ4_OK || (rc = k4lz4_chain_decoder_query_device(ctx, store, d_store, n, d_out, s.st)) != K4LZ4_OK) return rc;
-    return s.finish({{out, d_out, (size_t)n * K4LZ4_CDQ_WORDS * 8}});
+    return query_host(ctx, K4LZ4_CDQ_WORDS, k4lz4_chain_decoder_query_device, store, storeOff, n, out);
 }
 
 /* ---- many open ILZ4Encoders advanced per call (k4lz4_chain_encoder.hpp) ------------------------------------ */

@@ -298,7 +298,6 @@ struct FrFeedFastArgs {
     int64_t *consumed, *need;
     uint32_t *tail, *want;
 };
-inline size_t fr_feed_fast_scratch(long long n, long long rows) { return fr_fast_scratch(n, rows) + (size_t)n * 8 + 256; }
 
 __global__ __launch_bounds__(256) void k4_fr_feed_plan_kernel(FrFeedFastArgs fa)
 {

@@ -385,11 +385,6 @@ struct FrFastArgs {
 };
 
 __host__ __device__ inline long long fr_table_rows(long long maxCount) { return maxCount > 0 ? maxCount / 65536 + 2 : 0; }
-/* bytes of device scratch the fast path takes for n streams */
-inline size_t fr_fast_scratch(long long n, long long rows)
-{
-    return 256 + (size_t)n * (sizeof(FrPlan) + 4 + 2 * 8 + 3 * 4 + 64) + (size_t)n * (size_t)rows * (3 * 8 + 3 * 4 + 3 * 4) + 1024;
-}
 
 __global__ __launch_bounds__(256) void k4_fr_plan_kernel(FrFastArgs a)
 {

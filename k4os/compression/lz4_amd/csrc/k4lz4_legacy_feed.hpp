@@ -300,11 +300,6 @@ struct LsFeedDirectArgs {
     int32_t *sSrcLen, *sDstCap, *sOutLen;
 };
 
-inline size_t ls_feed_direct_scratch(long long n, long long rows)
-{
-    return 256 + (size_t)n * (sizeof(LsFeedPlan) + 2 * 4 + 2 * 8 + 3 * 4 + 8 * 64) + (size_t)n * (size_t)rows * (2 * 8 + 4 * 4) + 6 * 64;
-}
-
 /* streams the direct path may take: they read, not interactively, with nothing pending in the buffer */
 __device__ __forceinline__ bool ls_feed_direct_ok(const LsReadArgs &r, long long s, const LsState *st)
 {

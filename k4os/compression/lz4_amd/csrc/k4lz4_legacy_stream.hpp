@@ -388,11 +388,6 @@ struct LsDirectArgs {
     int32_t *sSrcLen, *sDstCap, *sOutLen;
 };
 
-inline size_t ls_direct_scratch(long long n, long long rows)
-{
-    return 256 + (size_t)n * (sizeof(LsPlan) + 4 + 2 * 8 + 3 * 4 + 7 * 64) + (size_t)n * (size_t)rows * (2 * 8 + 4 * 4) + 6 * 64;
-}
-
 __global__ __launch_bounds__(256) void k4_ls_plan_kernel(LsDirectArgs a)
 {
     const long long s = (long long)blockIdx.x * 256 + threadIdx.x;

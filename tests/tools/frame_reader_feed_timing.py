@@ -51,7 +51,8 @@ def case(dc, name, frames, foff, flen, S, R, C, host, a):
     counts = torch.full((S,), C, dtype=torch.int64, device=dev)
     steps = [o_off + k * C for k in range(R)]
     foff_d = torch.from_numpy(np.asarray(foff, np.int64)).to(dev)
-    ends = [torch.from_numpy(np.asarray(flen, np.int64) * (k + 1) // P).to(dev) for k in range(P)]
+    flen_d = torch.as_tensor(flen, dtype=torch.int64).to(dev)          # (the frame encoder hands the lengths back on the device)
+    ends = [flen_d * (k + 1) // P for k in range(P)]
     fin = [torch.full((S,), int(k == P - 1), dtype=torch.int64, device=dev) for k in range(P)]
     last = {}
 
