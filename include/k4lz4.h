@@ -317,6 +317,37 @@ K4LZ4_API int k4lz4_encode_fast_chain_batch_device(k4lz4_ctx *ctx, const uint8_t
                                                    k4lz4_fast_chain_state *stateOut, uint8_t *dst, const uint64_t *dstOff,
                                                    int32_t *outLen, int64_t nBlocks, int flags, void *stream);
 
+/* Messages encoded against shared dictionaries, fast levels: the counterpart of k4lz4_decode_dict_batch.  Message i (srcLen[i]
+ * bytes at src + srcOff[i]) is encoded against entry dictIdx[i] of a list of nDict dictionaries (dictLen[d] bytes at
+ * dict + dictOff[d]) -- a list, not one dictionary per message, because the point is few dictionaries and many messages.  Block i is
+ * byte for byte what LZ4_loadDict(stream, dictionary, dictLen) followed by LZ4_compress_fast_continue(stream, src, dst, srcLen,
+ * dstCap, 1) writes (LL64.tools.cs:175-206, LL64.fast.cs:582-667: the usingExtDict arm, the dictionary does not lie in front of the
+ * message), and decodes with k4lz4_decode_dict_batch given the same dictionary.  Only a dictionary's last 64 KiB count; one of fewer
+ * than 8 bytes (dictLen 0 included) is valid and empty, as LZ4_loadDict has it.  The table of every distinct dictionary of the list
+ * is built once per call (16 KiB each, in the context's scratch), then one wavefront encodes each message.
+ * outLen[i] follows k4lz4_encode_batch: the bytes written, 0 for an empty message, -1 when the block does not fit dstCap[i]
+ * (limitedOutput returns 0 there); bytes of dst behind outLen[i] are not touched (behind a -1 the slot's content is unspecified in
+ * the _device form).
+ * Refused with K4LZ4_E_ARG: level >= K4LZ4_L03_HC (HC with a dictionary is LZ4HC_setExternalDict's search arm in four kernels: not
+ * done yet); K4LZ4_FLAG_X32 or a process under k4lz4_set_enforce32(1) (LL32's LZ4_loadDict has a 4-byte HASH_UNIT and hash4: no
+ * witness for it), and every other flag; a negative dictLen; a dictIdx outside [0, nDict).
+ * _device: src, dst, outLen, dict and the per-message arrays (srcOff, srcLen, dstOff, dstCap, dictIdx) are device pointers; the
+ * list's arrays (dictOff, dictLen) stay HOST arrays.  It runs asynchronously on `stream`.  It cannot look at dictIdx before it runs:
+ * a message whose dictIdx lies outside the list gets outLen -1, nothing of it is written, and the next synchronising call on the
+ * context (k4lz4_synchronize, any host-pointer call) returns K4LZ4_E_ARG.
+ * k4lz4_encode_dict_state, for tests: the stream context LZ4_loadDict left for entry d of the list of the context's most recent
+ * k4lz4_encode_dict_batch[_device] call -- hashTable word for word, currentOffset (65536), dictSize (the kept length) -- into a HOST
+ * struct; it waits for that call. */
+K4LZ4_API int k4lz4_encode_dict_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                      uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n,
+                                      int level, int flags, const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff,
+                                      const int32_t *dictLen, int32_t nDict);
+K4LZ4_API int k4lz4_encode_dict_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                             uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen,
+                                             int64_t n, int level, int flags, const int32_t *dictIdx, const uint8_t *dict,
+                                             const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, void *stream);
+K4LZ4_API int k4lz4_encode_dict_state(k4lz4_ctx *ctx, int32_t d, k4lz4_fast_chain_state *out);
+
 /* Frame writer on device-resident data: after k4lz4_encode_batch_device(..., K4LZ4_FLAG_ALLOW_COPY) and
  * k4lz4_xxh32_batch_device, lays the frames out (Frames/LZ4FrameWriter.cs:57-108 header, LZ4FrameWriter.async.cs:15-27
  * block records, :75-90 EndMark + content checksum).  The caller computes the positions (recOff, frameOff, tailOff) from

@@ -250,6 +250,43 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
         return out
 
     @staticmethod
+    def EncodeDictBatchPacked(src: np.ndarray, src_off: np.ndarray, src_len: np.ndarray, dst: np.ndarray,
+                              dst_off: np.ndarray, dst_cap: np.ndarray, dict_idx: np.ndarray, dictionaries: np.ndarray,
+                              dict_off: np.ndarray, dict_len: np.ndarray, level: LZ4Level = LZ4Level.L00_FAST, flags: int = 0,
+                              ctx: Optional[_native.Context] = None) -> np.ndarray:
+        """Batched LZ4_loadDict + LZ4_compress_fast_continue: message i is encoded against entry dict_idx[i] of the list
+        dictionaries[dict_off[d]:+dict_len[d]] (k4lz4_encode_dict_batch; fast levels only).  What it writes decodes with
+        DecodeDictBatchPacked given the same dictionary."""
+        ctx = ctx or _native.default_context()
+        out = np.empty(len(src_len), dtype=np.int32)
+        a = _batch_args(src, src_off, src_len, dst, dst_off, dst_cap, out)
+        dct = np.ascontiguousarray(dictionaries, dtype=np.uint8)
+        doff = np.ascontiguousarray(dict_off, dtype=np.uint64)
+        dlen = np.ascontiguousarray(dict_len, dtype=np.int32)
+        idx = np.ascontiguousarray(dict_idx, dtype=np.int32)
+        if len(doff) != len(dlen) or len(idx) != len(src_len):
+            raise ValueError("dict_off / dict_len must have one entry per dictionary, dict_idx one per message")
+        if len(doff) and int((doff + dlen.clip(min=0).astype(np.uint64)).max()) > dct.size:
+            raise ValueError("a dictionary exceeds the dictionary buffer")
+        ctx.check(ctx.lib.k4lz4_encode_dict_batch(ctx.handle, *a, int(level), flags, idx.ctypes.data if idx.size else None,
+                                                  _ptr(dct) if dct.size else None, doff.ctypes.data if doff.size else None,
+                                                  dlen.ctypes.data if dlen.size else None, len(doff)))
+        return out
+
+    @staticmethod
+    def EncodeDictBatch(sources: Sequence, dictionaries: Sequence, dictionary_index: Sequence[int],
+                        level: LZ4Level = LZ4Level.L00_FAST) -> List[Optional[bytes]]:
+        """Each message encoded against dictionaries[dictionary_index[i]] into a MaximumOutputSize target; None where it fails."""
+        blocks = [_ro_view(s, "source") for s in sources]
+        dicts = [_ro_view(d, "dictionary") for d in dictionaries]
+        src, soff, slen = pack_blocks(blocks)
+        dct, doff, dlen = pack_blocks(dicts)
+        caps = np.array([LZ4Codec.MaximumOutputSize(b.size) for b in blocks], dtype=np.int32)
+        dst, to = make_arena(caps)
+        out = LZ4Codec.EncodeDictBatchPacked(src, soff, slen, dst, to, caps, np.asarray(dictionary_index, dtype=np.int32), dct, doff, dlen, level)
+        return [None if n < 0 else dst[int(o):int(o) + int(n)].tobytes() for n, o in zip(out, to)]
+
+    @staticmethod
     def EncodeBatch(sources: Sequence, level: LZ4Level = LZ4Level.L00_FAST) -> List[Optional[bytes]]:
         """Each element as LZ4Codec.Encode into a MaximumOutputSize target; None where Encode < 0."""
         blocks = [_ro_view(s, "source") for s in sources]
@@ -267,6 +304,19 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
         dst, doff = make_arena(caps)
         out = LZ4Codec.DecodeBatchPacked(src, soff, slen, dst, doff, caps)
         return [None if n < 0 else dst[int(o):int(o) + int(n)].tobytes() for n, o in zip(out, doff)]
+
+
+def encode_dict_packed(src, src_off, src_len, dst, dst_off, dst_cap, dict_idx, dictionaries, dict_off, dict_len,
+                       level: LZ4Level = LZ4Level.L00_FAST, ctx: Optional[_native.Context] = None) -> np.ndarray:
+    """messages against shared dictionaries over host arrays: LZ4Codec.EncodeDictBatchPacked"""
+    return LZ4Codec.EncodeDictBatchPacked(src, src_off, src_len, dst, dst_off, dst_cap, dict_idx, dictionaries, dict_off, dict_len, level, 0, ctx)
+
+
+def encode_dict_device(dc, src, dst, dict_idx, dictionaries, dict_off, dict_len, out_len=None, level: LZ4Level = LZ4Level.L00_FAST):
+    """the same on HBM-resident data: `dc` a device.DeviceCodec, src / dst device.DeviceBatch, dict_idx (int32) and dictionaries
+    (uint8) torch tensors on the device, dict_off / dict_len host arrays; asynchronous on the current torch stream.  What it writes
+    decodes with DeviceCodec.decode_dict given the same dictionary."""
+    return dc.encode_dict(src, dst, dict_idx, dictionaries, dict_off, dict_len, out_len, level)
 
 
 def _raise_if_native_failed(lib):

@@ -20,6 +20,7 @@
 #include <new>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -46,6 +47,7 @@
 #include "k4lz4_chain_encoder.hpp"
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
+#include "k4lz4_dict_encode.hpp"
 
 constexpr int MAX_PARTS = 8;      /* a big host-pointer call is staged, run and brought back in up to this many parts */
 
@@ -155,6 +157,13 @@ struct k4lz4_ctx {
     std::vector<uint8_t> h_fw;
     uint8_t *d_fw = nullptr; size_t d_fw_cap = 0;
     hipEvent_t ev_fw = nullptr;
+    /* messages against shared dictionaries (k4lz4_dict_encode.hpp): the prepared tables (16 KiB per distinct dictionary), the list's
+     * per-entry words and the dispatch order, grow-only; the host copy of the words as h_chain's; and which table and what dictSize
+     * the most recent call gave every entry of its list (k4lz4_encode_dict_state) */
+    std::vector<uint8_t> h_denc;
+    uint8_t *d_denc = nullptr; size_t d_denc_cap = 0;
+    hipEvent_t ev_denc = nullptr;
+    std::vector<uint32_t> denc_table, denc_kept;
 };
 
 /* a few helper threads for the staging copies of big host-pointer calls (memcpy between the caller's pageable memory and
@@ -264,6 +273,8 @@ int take_device_status(k4lz4_ctx *ctx)
     (void)hipMemset(ctx->d_status, 0, sizeof v);
     const bool nomem = (v & k4::DEV_STATUS_HC_SCRATCH) != 0, timeout = (v & k4::DEV_STATUS_PIPE_TIMEOUT) != 0;
     std::string msg;
+    if (!nomem && !timeout && (v & k4::DEV_STATUS_DICT_INDEX))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch_device: a dictIdx outside the dictionary list: those messages report -1");
     if (nomem) msg += "HC scratch reserved with k4lz4_ctx_reserve_hc was too small for the batch: its blocks were not encoded";
     if (timeout) msg += std::string(nomem ? "; " : "") + "a wave gave up waiting for its partner wave (a decoder pair, or the waves that parse one block at HC level 3: scheduling time-out, not corrupt data): the affected blocks report failure";
     return fail(ctx, nomem ? K4LZ4_E_NOMEM : K4LZ4_E_HIP, msg.c_str());
@@ -2025,6 +2036,101 @@ struct Carve {
     }
 };
 
+/* ---- messages against shared dictionaries (k4lz4_encode_dict_batch, k4lz4_dict_encode.hpp) ------------------------------------
+ * The list's entries that keep the same bytes (same kept start, same kept length; every dictionary of fewer than 8 bytes is the
+ * empty one) share one table.  used: which entries the messages refer to (the host form knows), or nullptr: all of them. */
+struct DictList {
+    std::vector<uint64_t> keptOff;            /* per entry */
+    std::vector<uint32_t> keptLen, table;
+    std::vector<uint32_t> rep;                /* per table: an entry that has it */
+};
+
+int dict_list(k4lz4_ctx *ctx, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, const uint8_t *used, DictList &l)
+{
+    l.keptOff.assign((size_t)nDict, 0); l.keptLen.assign((size_t)nDict, 0); l.table.assign((size_t)nDict, 0xffffffffu); l.rep.clear();
+    std::map<std::pair<uint64_t, uint32_t>, uint32_t> seen;
+    for (int32_t d = 0; d < nDict; d++) {
+        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: negative dictLen");
+        if (used && !used[d]) continue;
+        const uint32_t len = (uint32_t)dictLen[d];
+        if (len >= 8u) {                                                  /* LZ4_loadDict: below HASH_UNIT nothing is kept */
+            l.keptLen[(size_t)d] = std::min<uint32_t>(len, 65536u);
+            l.keptOff[(size_t)d] = dictOff[d] + (len - l.keptLen[(size_t)d]);
+        }
+        const auto key = std::make_pair(l.keptOff[(size_t)d], l.keptLen[(size_t)d]);
+        auto it = seen.find(key);
+        if (it == seen.end()) { it = seen.emplace(key, (uint32_t)l.rep.size()).first; l.rep.push_back((uint32_t)d); }
+        l.table[(size_t)d] = it->second;
+    }
+    return K4LZ4_OK;
+}
+
+int dict_encode_flags(k4lz4_ctx *ctx, int level, int flags)
+{
+    if (level >= K4LZ4_L03_HC) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: HC levels with a dictionary are not supported");
+    if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: the 32-bit engine's LZ4_loadDict (LZ4Codec.Enforce32) is not supported");
+    if (flags) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: it takes no flags");
+    return K4LZ4_OK;
+}
+
+/* all pointers but the list are device pointers; load, order, encode on `stream` */
+int dict_encode_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst, const uint64_t *dstOff,
+                    const int32_t *dstCap, int32_t *outLen, int64_t n, const int32_t *dictIdx, const uint8_t *dict, const DictList &l,
+                    hipStream_t stream)
+{
+    if (n > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: more than 2^32 - 1 messages");
+    const size_t nd = l.table.size(), nt = std::max<size_t>(l.rep.size(), 1);
+    if (!ctx->ev_denc) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_denc, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_denc));            /* the previous upload of the host words is over */
+    /* layout: [ticket, hist: 64 + 2 * COST_BUCKETS words] [tables] [per table: keptOff, keptLen] [per entry: keptOff, keptLen, table]
+     * [cost[n], order[n]]; the part that goes up from the host is the one between the tables and cost[] */
+    Carve m{nullptr};
+    auto layout = [&](Carve &cv, uint32_t *&head, uint32_t *&tables, uint64_t *&toff, uint32_t *&tlen, uint64_t *&eoff, uint32_t *&elen,
+                      uint32_t *&etab, uint32_t *&cost, uint32_t *&order) {
+        cv.take(head, 64 + 2 * k4::COST_BUCKETS + 16); cv.take(tables, nt * 4096);
+        cv.take(toff, nt); cv.take(tlen, nt); cv.take(eoff, nd); cv.take(elen, nd); cv.take(etab, nd);
+        cv.take(cost, (size_t)n); cv.take(order, (size_t)n);
+    };
+    uint32_t *head, *tables, *tlen, *elen, *etab, *cost, *order;
+    uint64_t *toff, *eoff;
+    layout(m, head, tables, toff, tlen, eoff, elen, etab, cost, order);
+    int rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_denc, &ctx->d_denc_cap, m.at + 64)) != K4LZ4_OK) return rc;
+    Carve dv{ctx->d_denc};
+    layout(dv, head, tables, toff, tlen, eoff, elen, etab, cost, order);
+    const size_t up_at = (size_t)((uint8_t *)toff - ctx->d_denc), up_bytes = (size_t)((uint8_t *)cost - (uint8_t *)toff);
+    try { ctx->h_denc.assign(up_bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    {
+        uint8_t *h = ctx->h_denc.data() - up_at;                          /* host image of the same layout */
+        uint64_t *h_toff = (uint64_t *)(h + ((uint8_t *)toff - ctx->d_denc)), *h_eoff = (uint64_t *)(h + ((uint8_t *)eoff - ctx->d_denc));
+        uint32_t *h_tlen = (uint32_t *)(h + ((uint8_t *)tlen - ctx->d_denc)), *h_elen = (uint32_t *)(h + ((uint8_t *)elen - ctx->d_denc)),
+                 *h_etab = (uint32_t *)(h + ((uint8_t *)etab - ctx->d_denc));
+        for (size_t t = 0; t < l.rep.size(); t++) { h_toff[t] = l.keptOff[l.rep[t]]; h_tlen[t] = l.keptLen[l.rep[t]]; }
+        for (size_t d = 0; d < nd; d++) { h_eoff[d] = l.keptOff[d]; h_elen[d] = l.keptLen[d]; h_etab[d] = l.table[d]; }
+    }
+    ctx->denc_table = l.table; ctx->denc_kept = l.keptLen;
+    K4_HIP(ctx, order_after_ctx(ctx, stream));
+    K4_HIP(ctx, hipMemcpyAsync(ctx->d_denc + up_at, ctx->h_denc.data(), up_bytes, hipMemcpyHostToDevice, stream));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_denc, stream));
+    K4_HIP(ctx, hipMemsetAsync(head, 0, (64 + 2 * k4::COST_BUCKETS + 16) * 4, stream));
+    hipLaunchKernelGGL(k4::k4_dict_load_kernel, dim3((unsigned)nt), dim3(k4::DICT_LOAD_THREADS), 0, stream, k4::DictLoadArgs{dict, toff, tlen, tables});
+    rc = K4LZ4_OK;
+    if (n > 0) {
+        k4::BatchArgs o{};
+        o.srcLen = srcLen; o.n = n; o.cost = cost; o.hist = head + 64; o.order_out = order;
+        const unsigned g256 = (unsigned)((n + 255) / 256);
+        hipLaunchKernelGGL(k4::k4_dict_cost_kernel, dim3(g256), dim3(256), 0, stream, o);
+        hipLaunchKernelGGL(k4::k4_order_kernel, dim3(g256), dim3(256), 0, stream, o, 0xffffffffu);
+        k4::DictEncArgs a{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, dictIdx, dict, eoff, elen, etab, tables, order, head, ctx->d_status, n, (int)nd};
+        const int64_t wgs = std::min<int64_t>((n + k4::FAST_CHAIN_WAVES_PER_WG - 1) / k4::FAST_CHAIN_WAVES_PER_WG, ctx->cu_count);
+        hipLaunchKernelGGL(k4::k4_dict_encode_kernel, dim3((unsigned)wgs), dim3(64 * k4::FAST_CHAIN_WAVES_PER_WG), 0, stream, a);
+    }
+    if (hipGetLastError() != hipSuccess) rc = fail(ctx, K4LZ4_E_HIP, "k4lz4_encode_dict_batch: kernel launch failed");
+    mark_busy(ctx, stream);
+    return rc;
+}
+
 void direct_layout(Carve &c, k4::FrFastArgs &f, size_t n, size_t nr)
 {
     c.take(f.plan, n); c.take(f.done, n);
@@ -2396,6 +2502,8 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_fw) (void)hipFree(ctx->d_fw);
     if (ctx->ev_fw) (void)hipEventDestroy(ctx->ev_fw);
     if (ctx->ev_chain) (void)hipEventDestroy(ctx->ev_chain);
+    if (ctx->d_denc) (void)hipFree(ctx->d_denc);
+    if (ctx->ev_denc) (void)hipEventDestroy(ctx->ev_denc);
     if (ctx->d_pk_meta) (void)hipFree(ctx->d_pk_meta);
     delete ctx;
 }
@@ -2842,6 +2950,90 @@ int k4lz4_encode_fast_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint
 
 
 /* ---- frame reader (k4lz4_frame_read.hpp) ---------------------------------------------------------------- */
+static int dict_encode_args(k4lz4_ctx *ctx, const void *src, const void *srcOff, const void *srcLen, const void *dst, const void *dstOff,
+                            const void *dstCap, const void *outLen, int64_t n, int level, int flags, const void *dictIdx, const void *dict,
+                            const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict)
+{
+    int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
+    if (rc != K4LZ4_OK || (rc = dict_encode_flags(ctx, level, flags)) != K4LZ4_OK) return rc;
+    if (nDict < 0 || (nDict > 0 && (!dictOff || !dictLen)) || (n > 0 && !dictIdx)) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: bad dictionary list");
+    for (int32_t d = 0; d < nDict; d++) {
+        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: negative dictLen");
+        if (dictLen[d] > 0 && !dict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: NULL dictionary buffer");
+    }
+    return K4LZ4_OK;
+}
+
+int k4lz4_encode_dict_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                                   const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+                                   const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen,
+                                   int32_t nDict, void *stream)
+{
+    int rc = dict_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
+    if (rc != K4LZ4_OK) return rc;
+    DictList l;
+    if ((rc = dict_list(ctx, dictOff, dictLen, nDict, nullptr, l)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    return dict_encode_run(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx, dict, l, (hipStream_t)stream);
+}
+
+int k4lz4_encode_dict_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                            const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+                            const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict)
+{
+    int rc = dict_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
+    if (rc != K4LZ4_OK) return rc;
+    std::vector<uint8_t> used((size_t)nDict, 0);
+    for (int64_t i = 0; i < n; i++) {
+        if (dictIdx[i] < 0 || dictIdx[i] >= nDict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: a dictIdx outside the dictionary list");
+        used[(size_t)dictIdx[i]] = 1;
+    }
+    DictList l;
+    if ((rc = dict_list(ctx, dictOff, dictLen, nDict, used.data(), l)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    s.span(src, srcOff, n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(srcLen[i], 0); });
+    /* the kept bytes of every dictionary in use go up behind the messages, at 16-byte steps of the same buffer */
+    DictList staged = l;
+    std::vector<uint64_t> at_of((size_t)l.rep.size(), 0);
+    for (size_t t = 0; t < l.rep.size(); t++) {
+        const uint32_t d = l.rep[t];
+        if (!l.keptLen[d]) continue;
+        at_of[t] = (s.in_bytes + 15u) & ~(uint64_t)15u;
+        s.ups.push_back(HostStage::Up{&ctx->d_src, at_of[t], dict + l.keptOff[d], (size_t)l.keptLen[d]});
+        s.in_bytes = at_of[t] + l.keptLen[d];
+    }
+    for (int32_t e = 0; e < nDict; e++)
+        if (used[(size_t)e]) staged.keptOff[(size_t)e] = at_of[l.table[(size_t)e]];
+    s.slots(n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(dstCap[i], 0); }, false);
+    uint64_t *d_off, *d_doff;
+    int32_t *d_len, *d_cap, *d_out, *d_idx;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, srcLen); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_cap, n, dstCap);
+    s.meta(&d_idx, n, dictIdx); s.meta(&d_out, n);
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = dict_encode_run(ctx, ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, n, d_idx, ctx->d_src, staged, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
+                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
+}
+
+int k4lz4_encode_dict_state(k4lz4_ctx *ctx, int32_t d, k4lz4_fast_chain_state *out)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (!out || d < 0 || (size_t)d >= ctx->denc_table.size() || ctx->denc_table[(size_t)d] == 0xffffffffu || !ctx->d_denc)
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_state: no such dictionary in the context's most recent k4lz4_encode_dict_batch call");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
+    Carve c{ctx->d_denc};
+    uint32_t *head, *tables;
+    c.take(head, 64 + 2 * k4::COST_BUCKETS + 16); c.take(tables, 4096);
+    K4_HIP(ctx, hipMemcpy(out->hashTable, tables + 4096ull * ctx->denc_table[(size_t)d], sizeof out->hashTable, hipMemcpyDeviceToHost));
+    out->currentOffset = k4::DICT_START;
+    out->dictSize = ctx->denc_kept[(size_t)d];
+    out->reserved[0] = out->reserved[1] = 0;
+    return K4LZ4_OK;
+}
+
 int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
                              uint64_t *outSize, int32_t *outStatus, void *stream)
 {

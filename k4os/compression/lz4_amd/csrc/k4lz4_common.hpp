@@ -157,7 +157,8 @@ constexpr int PROF_STRIDE = 16;
  * context's trouble is never reported to -- or cleared by -- another context on the same device.  The host reads and
  * clears it whenever it synchronises (k4lz4_synchronize, every host-pointer call) and reports all the bits it finds;
  * the affected blocks' outLen only say "failed". */
-enum : uint32_t { DEV_STATUS_PIPE_TIMEOUT = 1u, DEV_STATUS_HC_SCRATCH = 2u };
+enum : uint32_t { DEV_STATUS_PIPE_TIMEOUT = 1u, DEV_STATUS_HC_SCRATCH = 2u,
+                  DEV_STATUS_DICT_INDEX = 4u /* k4lz4_encode_dict_batch_device: a dictIdx outside the list (the host form refuses it before it runs) */ };
 constexpr int HC_NO_SCRATCH = -0x7ffffff1;   /* LLxx-level result of an HC block that was not encoded for want of scratch (<= 0: failure) */
 __device__ __forceinline__ void dev_status_raise(uint32_t *status, uint32_t bits)
 {

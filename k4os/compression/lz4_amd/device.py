@@ -85,6 +85,37 @@ class DeviceCodec:
         out_len = self.new_out_len(src.n) if out_len is None else out_len
         return self._call(self.lib.k4lz4_decode_batch_device, src, dst, out_len, flags)
 
+    def decode_dict(self, src: DeviceBatch, dst: DeviceBatch, dictionaries: torch.Tensor, dict_off: torch.Tensor, dict_len: torch.Tensor,
+                    out_len: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+        """block i decoded against dictionaries[dict_off[i]:+dict_len[i]] (k4lz4_decode_dict_batch_device; device tensors: uint8,
+        int64 holding uint64 offsets, int32)"""
+        out_len = self.new_out_len(src.n) if out_len is None else out_len
+        assert dict_off.numel() == dict_len.numel() == src.n and dict_len.dtype == torch.int32
+        return self._call(lambda *a: self.lib.k4lz4_decode_dict_batch_device(*a[:-1], _dp(dictionaries), _dp(dict_off), _dp(dict_len), a[-1]),
+                          src, dst, out_len, flags)
+
+    def encode_dict(self, src: DeviceBatch, dst: DeviceBatch, dict_idx: torch.Tensor, dictionaries: torch.Tensor, dict_off: np.ndarray,
+                    dict_len: np.ndarray, out_len: Optional[torch.Tensor] = None, level: LZ4Level = LZ4Level.L00_FAST,
+                    flags: int = 0) -> torch.Tensor:
+        """message i encoded against entry dict_idx[i] (device int32 tensor) of the list dictionaries[dict_off[d]:+dict_len[d]]
+        (device bytes; the list's two arrays are HOST arrays): k4lz4_encode_dict_batch_device, fast levels only"""
+        out_len = self.new_out_len(src.n) if out_len is None else out_len
+        doff = np.ascontiguousarray(dict_off, dtype=np.uint64)
+        dlen = np.ascontiguousarray(dict_len, dtype=np.int32)
+        assert doff.size == dlen.size and dict_idx.numel() == src.n and dict_idx.dtype == torch.int32
+        if doff.size and int((doff + dlen.clip(min=0).astype(np.uint64)).max()) > dictionaries.numel():
+            raise ValueError("a dictionary exceeds the dictionary buffer")
+        return self._call(self.lib.k4lz4_encode_dict_batch_device, src, dst, out_len, int(level), flags, _dp(dict_idx), _dp(dictionaries),
+                          doff.ctypes.data if doff.size else None, dlen.ctypes.data if dlen.size else None, int(doff.size))
+
+    def dict_state(self, d: int) -> np.ndarray:
+        """the stream context LZ4_loadDict left for entry d of the most recent encode_dict call's list (k4lz4_encode_dict_state):
+        one FAST_CHAIN_STATE record.  Waits for that call."""
+        from .encoders import FAST_CHAIN_STATE
+        st = np.zeros(1, FAST_CHAIN_STATE)
+        self.ctx.check(self.lib.k4lz4_encode_dict_state(self.ctx.handle, int(d), st.ctypes.data))
+        return st
+
     def pickle(self, src: DeviceBatch, dst: DeviceBatch, out_len: Optional[torch.Tensor] = None,
                level: LZ4Level = LZ4Level.L00_FAST, flags: int = 0) -> torch.Tensor:
         out_len = self.new_out_len(src.n) if out_len is None else out_len
