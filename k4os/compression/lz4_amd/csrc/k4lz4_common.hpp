@@ -223,6 +223,16 @@ __device__ __forceinline__ void agent_acquire()             /* what other workgr
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
 #endif
 }
+/* a word of LDS that other waves of the workgroup write, read anew at every call -- as an LDS access: a volatile access through a
+ * plain pointer stays a FLAT one even where the pointer can only be an LDS one (the compiler does not retype volatile accesses) */
+__device__ __forceinline__ uint32_t lds_peek(const uint32_t *p)
+{
+#ifndef K4_HOST_EMU
+    return *(const volatile __attribute__((address_space(3))) uint32_t *)p;
+#else
+    return *(const volatile uint32_t *)p;
+#endif
+}
 __device__ __forceinline__ uint32_t agent_peek(const uint32_t *p)
 {
 #ifndef K4_HOST_EMU

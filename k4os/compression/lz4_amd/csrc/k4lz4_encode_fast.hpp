@@ -388,7 +388,7 @@ struct SegRun {
  * After 64 misses the schedule's step grows (LL64.fast.cs:156-172); those rounds probe the strided
  * positions and stop at their first sequence.
  */
-template <bool BYU16, bool PROF = false, bool X32 = false, bool PAIRS = true, bool MORE = false, bool N2 = true>
+template <bool BYU16, bool PROF = false, bool X32 = false, bool PAIRS = true, bool MORE = false, bool N2 = true, bool GTAB = false>
 __device__ __forceinline__ int encode_fast_block(const uint8_t *src, int src_len, uint8_t *dst, int dst_cap,
                                                  uint32_t accel, uint32_t *ldsw, int lane, unsigned long long *pc = nullptr,
                                                  bool dry_arg = false, uint32_t *seq_count = nullptr, uint32_t *gtab = nullptr,
@@ -412,10 +412,12 @@ __device__ __forceinline__ int encode_fast_block(const uint8_t *src, int src_len
     const uint32_t U = (uint32_t)src_len;
     typedef FastTable<BYU16 ? 1 : (X32 ? 2 : 0)> Table;
     Table tab;
-    /* the table normally lives in LDS; `gtab` (16 KiB of global memory) lets more blocks run per CU */
-    uint32_t *const tabmem = gtab ? gtab : ldsw;
+    /* the table normally lives in LDS; GTAB: in `gtab` (16 KiB of global memory), which lets more blocks run per CU.  Which of the two
+     * is the instantiation's business, not a look at `gtab` here: a pointer that is either an LDS or a memory one is a generic pointer,
+     * and every table access through it a FLAT instruction instead of an LDS or a global one */
+    uint32_t *const tabmem = GTAB ? gtab : ldsw;
     tab.t = (decltype(tab.t))tabmem;
-    uint32_t *const seen = gtab ? ldsw : ldsw + 4096;       /* bit h: a lane of the current window hashed to h */
+    uint32_t *const seen = GTAB ? ldsw : ldsw + 4096;       /* bit h: a lane of the current window hashed to h */
     uint2 *const rec = (uint2 *)(seen + ENCODE_SCRATCH_BYTES / 4);        /* the pending sequences */
     uint32_t *const pace_mine = seen + ENCODE_SCRATCH_BYTES / 4 + ENCODE_REC_DWORDS;
     if (K4_PACE) Pace::begin(pace_words, pace_mine, lane);
@@ -587,7 +589,7 @@ __device__ __forceinline__ int encode_fast_block(const uint8_t *src, int src_len
              * one (3.76 / 4.10 ms); taking it for three of every four 64-byte steps of the cursor -- a round's cursor is as
              * good as a coin here -- evens the two out (3.90 / 3.93 ms, +4.5 % on the encode call).  Only without the
              * late-blocks-first priorities (Pace, k4lz4_common.hpp: K4LZ4_NO_PACE), which do the same and more by measurement. */
-            if (gtab && !(K4_PACE && pace_words)) { if (((ip0 >> 6) & 3u) < (uint32_t)K4_GTAB_DUTY) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+            if (GTAB && !(K4_PACE && pace_words)) { if (((ip0 >> 6) & 3u) < (uint32_t)K4_GTAB_DUTY) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
 #endif
             const uint32_t pos = pos_n;
             const bool valid = valid_n;
@@ -966,15 +968,15 @@ __device__ __forceinline__ int encode_fast_block(const uint8_t *src, int src_len
 }
 
 /* LL64.LZ4_compress_fast (LL64.fast.cs:517-576): table type by input size */
-template <bool PAIRS = true, bool MORE = false, bool N2 = true>
+template <bool PAIRS = true, bool MORE = false, bool N2 = true, bool GTAB = false>
 __device__ __forceinline__ int compress_fast_block(const uint8_t *src, int src_len, uint8_t *dst, int dst_cap,
                                                    int accel, uint32_t *ldsw, int lane, uint32_t *gtab = nullptr, bool x32 = false,
                                                    uint32_t *pace = nullptr, SegRun *sr = nullptr)
 {
     const uint32_t a = accel < 1 ? 1u : (accel > 65536 ? 65536u : (uint32_t)accel);
-    if (src_len < LIMIT_64K) return encode_fast_block<true, false, false, PAIRS, MORE, N2>(src, src_len, dst, dst_cap, a, ldsw, lane, nullptr, false, nullptr, gtab, pace);   /* (never cut) */
-    if (x32) return encode_fast_block<false, false, true, PAIRS, MORE, N2>(src, src_len, dst, dst_cap, a, ldsw, lane, nullptr, false, nullptr, gtab, pace, sr);
-    return encode_fast_block<false, false, false, PAIRS, MORE, N2>(src, src_len, dst, dst_cap, a, ldsw, lane, nullptr, false, nullptr, gtab, pace, sr);
+    if (src_len < LIMIT_64K) return encode_fast_block<true, false, false, PAIRS, MORE, N2, GTAB>(src, src_len, dst, dst_cap, a, ldsw, lane, nullptr, false, nullptr, gtab, pace);   /* (never cut) */
+    if (x32) return encode_fast_block<false, false, true, PAIRS, MORE, N2, GTAB>(src, src_len, dst, dst_cap, a, ldsw, lane, nullptr, false, nullptr, gtab, pace, sr);
+    return encode_fast_block<false, false, false, PAIRS, MORE, N2, GTAB>(src, src_len, dst, dst_cap, a, ldsw, lane, nullptr, false, nullptr, gtab, pace, sr);
 }
 
 /* LZ4Codec.Encode mapping (LZ4Codec.cs:40-52) */
@@ -1176,12 +1178,12 @@ __device__ __forceinline__ void encode_fast_gtab_kernel_body(const BatchArgs &a,
         SegFirst f = seg_first_of(a, b);
         const int c = cap < 0 ? 0 : (f.cut && (uint32_t)cap > f.cap ? (int)f.cap : cap);
         if (src_len > 0 || (a.flags & FLAG_RAW_RETURN))
-            ret = compress_fast_block<false, false, false>(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], c, a.accel, stage, lane,
+            ret = compress_fast_block<false, false, false, true>(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], c, a.accel, stage, lane,
                                              a.gtab + 4096ull * (unsigned long long)slot, (a.flags & FLAG_X32) != 0, a.pace, &f.run);
         seg_first_done(a, b, f, ret, lane);
     } else
     if (src_len > 0 || (a.flags & FLAG_RAW_RETURN))
-        ret = compress_fast_block<false, false, false>(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], cap < 0 ? 0 : cap, a.accel, stage, lane,
+        ret = compress_fast_block<false, false, false, true>(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], cap < 0 ? 0 : cap, a.accel, stage, lane,
                                          a.gtab + 4096ull * (unsigned long long)slot, (a.flags & FLAG_X32) != 0, a.pace);
     if (lane == 0) a.outLen[b] = codec_encode_result(src_len, ret, a.flags);
     if (a.prof) prof_place<true>(a.prof + PROF_STRIDE * b, 9, lane);
@@ -1213,9 +1215,13 @@ __global__ __launch_bounds__(64) void k4_encode_fast_prof_kernel(BatchArgs a)
     const int src_len = a.srcLen[b];
     const int cap = a.dstCap[b];
     int ret = 0;
-    if (src_len > 0 && src_len < LIMIT_64K)
-        ret = encode_fast_block<true, true>(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], cap < 0 ? 0 : cap, 1u, tab, lane, a.prof + PROF_STRIDE * b,
-                                            false, nullptr, a.gtab ? a.gtab + 4096ull * (unsigned long long)blockIdx.x : nullptr);
+    if (src_len > 0 && src_len < LIMIT_64K) {
+        if (a.gtab)
+            ret = encode_fast_block<true, true, false, true, false, true, true>(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], cap < 0 ? 0 : cap, 1u, tab, lane,
+                                                                                a.prof + PROF_STRIDE * b, false, nullptr, a.gtab + 4096ull * (unsigned long long)blockIdx.x);
+        else
+            ret = encode_fast_block<true, true>(a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], cap < 0 ? 0 : cap, 1u, tab, lane, a.prof + PROF_STRIDE * b);
+    }
     if (lane == 0) a.outLen[b] = codec_encode_result(src_len, ret, a.flags);
 }
 

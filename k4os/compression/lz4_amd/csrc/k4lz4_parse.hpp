@@ -975,7 +975,7 @@ __device__ __forceinline__ uint32_t parse_block(const uint8_t *src, const uint32
             return nrec;
         }
         if (GT && ctl && ctl->free_slots && (++mig_tick & 15u) == 0u) {
-            const uint32_t fs = uni(*(volatile uint32_t *)ctl->free_slots);
+            const uint32_t fs = uni(lds_peek(ctl->free_slots));
             if (fs) {
                 const uint32_t sl = (uint32_t)__ffs((int)fs) - 1u;
                 uint32_t old = 0u;
@@ -1077,15 +1077,17 @@ __device__ __forceinline__ int parse_one(const BatchArgs &a, const ParseArgs &p,
         wave_sync();
     };
     uint32_t *gt = p.gtab + 4096ull * ((unsigned long long)blockIdx.x * PARSE_MAX_WAVES + wave);
-    uint32_t *table = in_lds ? lds + 4096u * wave : gt;
-    bool table_in_lds = in_lds;
+    /* Where the table is: LDS table `tslot` of the workgroup, or (-1) `gt`.  An index and not one pointer that is either: a pointer
+     * that may point into LDS or into memory is a generic one, and every look-up and put through it a FLAT access -- through the
+     * vector-memory path, counted against both memory counters, waited for with count-0 waits -- in both forms of parse_block. */
+    int tslot = in_lds ? (int)wave : -1;
     int my_slot = -1;                            /* an LDS table this wave moved into (to be given back) */
     ParseCtl ctl = {};
     ctl.free_slots = in_lds ? nullptr : free_slots; ctl.claimed = -1; ctl.resume = false;
     ctl.rec_cap = U32 ? PARSE_REC_STRIDE : 0u;
     for (;;) {
-        if (table_in_lds) n = parse_block<K, false, false, TT, SEG>(src, (uint32_t)src_len, recs, table, seen, lane, pc, nullptr, (U32 || ctl.resume) ? &ctl : nullptr, sr);
-        else n = parse_block<K, true, false, TT, SEG>(src, (uint32_t)src_len, recs, table, seen, lane, pc, nullptr, &ctl, sr);
+        if (tslot >= 0) n = parse_block<K, false, false, TT, SEG>(src, (uint32_t)src_len, recs, lds + 4096u * (uint32_t)tslot, seen, lane, pc, nullptr, (U32 || ctl.resume) ? &ctl : nullptr, sr);
+        else n = parse_block<K, true, false, TT, SEG>(src, (uint32_t)src_len, recs, gt, seen, lane, pc, nullptr, &ctl, sr);
         if (U32 && ctl.claimed == PARSE_FLUSH) {
             if (p.inline_emit) write_out(n);
             if (!room) { n = 0u; break; }            /* the output does not fit (:251-255, :346-350): the block fails, no need to go on */
@@ -1099,7 +1101,7 @@ __device__ __forceinline__ int parse_one(const BatchArgs &a, const ParseArgs &p,
             for (int k = lane; k < 1024; k += 64) ((uint4 *)slot)[k] = ((const uint4 *)gt)[k];
             wave_sync();
             my_slot = ctl.claimed;
-            table = slot; table_in_lds = true;
+            tslot = my_slot;
             ctl.resume = true; ctl.free_slots = nullptr; ctl.claimed = -1;
             continue;
         }

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64 * ENCODE_WAVES_PER_WG) __attribute__((amdgpu_wav
         if (lane == 0) { agent_publish(r.snap_pub, SEG_NONE); g.items[it].cut = 0u; g.items[it].stop = 0u; g.items[it].state = 3u; g.items[it].bytes = 0; }
         return;
     }
-    const int ret = compress_fast_block<false, false, false>(a.src + a.srcOff[b], U, a.dst + a.dstOff[b] + s.start, (int)(end - s.start), a.accel, stages[wave], lane,
+    const int ret = compress_fast_block<false, false, false, true>(a.src + a.srcOff[b], U, a.dst + a.dstOff[b] + s.start, (int)(end - s.start), a.accel, stages[wave], lane,
                                                              g.tables + 4096ull * (unsigned long long)it, (a.flags & FLAG_X32) != 0, a.pace, &r);
     if (lane == 0) {
         g.items[it].cut = r.cut; g.items[it].stop = r.stop; g.items[it].state = ret > 0 ? r.state : 3u; g.items[it].bytes = ret;
