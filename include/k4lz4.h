@@ -128,6 +128,23 @@ K4LZ4_API int k4lz4_host_unregister(void *ptr);
  * pseudo-random well-formed inputs; mismatches[0..2] = rounds in which they disagreed (token chain of the decoder, hop
  * chain of the fast encoder, its variant with pair fall-backs).  All zero on a healthy build. */
 K4LZ4_API int k4lz4_selftest_chains(k4lz4_ctx *ctx, int waves, int rounds, uint32_t seed, uint32_t mismatches[3]);
+/* Diagnostic, no counterpart in the reference: which decoder kernel the most recent decode or unpickle launch of ctx used (the
+ * launcher chooses by blocks per CU; a call of more blocks than one launch takes reports its last launch), with
+ * K4LZ4_DECODE_KERNEL_PACE or-ed in when that launch ran with the late-blocks-first priorities.  K4LZ4_DECODE_KERNEL_NONE before
+ * the first such launch (also for a NULL ctx).  Recorded on the host when the launch is enqueued: it does not wait. */
+enum k4lz4_decode_kernel {
+    K4LZ4_DECODE_KERNEL_NONE = 0,
+    K4LZ4_DECODE_KERNEL_PAIR2 = 1,          /* k4_decode_pair2_kernel: two waves per block, the token chain two links per hop */
+    K4LZ4_DECODE_KERNEL_PAIR = 2,           /* k4_decode_pair_kernel: two waves per block, one link per hop */
+    K4LZ4_DECODE_KERNEL_SINGLE = 3,         /* k4_decode_kernel: one wave per block */
+    K4LZ4_DECODE_KERNEL_DENSE = 4,          /* k4_decode_dense_kernel: one wave per block, seven waves per SIMD */
+    K4LZ4_DECODE_KERNEL_PROF = 5,           /* an instrumented twin (k4lz4_profile_batch_device) */
+    K4LZ4_DECODE_KERNEL_UNPICKLE_PAIR2 = 9, /* k4_unpickle_pair2_kernel */
+    K4LZ4_DECODE_KERNEL_UNPICKLE_PAIR = 10, /* k4_unpickle_pair_kernel */
+    K4LZ4_DECODE_KERNEL_UNPICKLE_SINGLE = 11, /* k4_unpickle_kernel */
+    K4LZ4_DECODE_KERNEL_PACE = 64           /* flag: a.pace was armed for the launch */
+};
+K4LZ4_API int k4lz4_last_decode_kernel(const k4lz4_ctx *ctx);
 
 /* LZ4Codec.MaximumOutputSize (LZ4Codec.cs:30-31) == LL.LZ4_compressBound (Engine/LL.tools.cs:38-40).
  * Pure host arithmetic. */

@@ -21,6 +21,10 @@ FLAG_PARTIAL = 32
 FLAG_X32 = 128
 FLAG_ALLOW_COPY = 64
 FLAG_SEGMENTS = 256
+# enum k4lz4_decode_kernel (k4lz4_last_decode_kernel, a diagnostic)
+DECODE_KERNEL_NONE, DECODE_KERNEL_PAIR2, DECODE_KERNEL_PAIR, DECODE_KERNEL_SINGLE, DECODE_KERNEL_DENSE, DECODE_KERNEL_PROF = 0, 1, 2, 3, 4, 5
+DECODE_KERNEL_UNPICKLE_PAIR2, DECODE_KERNEL_UNPICKLE_PAIR, DECODE_KERNEL_UNPICKLE_SINGLE = 9, 10, 11
+DECODE_KERNEL_PACE = 64
 
 _u8p = C.c_void_p
 _BATCH = [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
@@ -43,6 +47,7 @@ SYMBOLS = {
     "k4lz4_host_register": (C.c_int, [C.c_void_p, C.c_size_t]),
     "k4lz4_host_unregister": (C.c_int, [C.c_void_p]),
     "k4lz4_selftest_chains": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "k4lz4_last_decode_kernel": (C.c_int, [C.c_void_p]),
     "k4lz4_set_enforce32": (None, [C.c_int]),
     "k4lz4_get_enforce32": (C.c_int, []),
     "k4lz4_compress_bound": (C.c_int, [C.c_int]),
@@ -245,6 +250,10 @@ class Context:
 
     def synchronize(self, stream: int = 0):
         self.check(self.lib.k4lz4_synchronize(self.handle, C.c_void_p(stream)))
+
+    def last_decode_kernel(self) -> int:
+        """DECODE_KERNEL_* of this context's most recent decode / unpickle launch, DECODE_KERNEL_PACE or-ed in (a diagnostic)"""
+        return int(self.lib.k4lz4_last_decode_kernel(self.handle))
 
     def close(self):
         if getattr(self, "handle", None):

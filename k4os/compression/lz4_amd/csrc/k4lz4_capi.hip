@@ -118,6 +118,7 @@ struct k4lz4_ctx {
     int lds_floor_per_cu = 8;             /* K4LZ4_LDS_FLOOR: blocks per CU the LDS-table kernel gets at least */
     int cost_pct = 48;                    /* K4LZ4_COST_PCT: the LDS-table kernel's share of a batch's estimated cost (k4_order_kernel) */
     int dec_parts = 4, dec_parts_direct = 8;   /* K4LZ4_DEC_PARTS, K4LZ4_DEC_PARTS_DIRECT: parts of a big decode-like host-pointer call (2..MAX_PARTS); with a registered destination */
+    int last_decode_kernel = 0;           /* k4lz4_last_decode_kernel: enum k4lz4_decode_kernel of the latest KIND_DECODE / KIND_UNPICKLE launch (launch()) */
     int hop2_max_per_cu = 12;             /* K4LZ4_HOP2_MAX: pair decoders follow the token chain two links per hop in launches of up to this many blocks per CU */
     bool hc_cand_lds = true;              /* K4LZ4_HC_CAND_MEM unsets it: blocks of at most 64 KiB get their candidate records by k4_hc_cand_kernel (from memory) */
     int hc_cand_dynlds = 0;               /* K4LZ4_HC_CAND_DYNLDS (a measurement switch): bytes of unused LDS per workgroup of k4_hc_cand_kernel, i.e. fewer of them per CU */
@@ -841,30 +842,46 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
                                     dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, stream, a);
             break;
         case KIND_DECODE:
+            ctx->last_decode_kernel = a.pace ? K4LZ4_DECODE_KERNEL_PACE : 0;
             if (a.prof && ctx->prof_pair && !ctx->prof_stamp) {
+                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_PROF;
                 hipLaunchKernelGGL(k4::k4_decode_pair_prof_kernel, dim3((unsigned)((cnt + k4::DECODE_PAIRS_PER_WG - 1) / k4::DECODE_PAIRS_PER_WG)),
                                    dim3(128 * k4::DECODE_PAIRS_PER_WG), 0, stream, a);
             }
-            else if (a.prof && !ctx->prof_stamp) hipLaunchKernelGGL(k4::k4_decode_prof_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
-            else if (cnt > 24 * (int64_t)ctx->cu_count)   /* more blocks than can be resident (6 waves x 4 SIMDs per CU) */
+            else if (a.prof && !ctx->prof_stamp) {
+                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_PROF;
+                hipLaunchKernelGGL(k4::k4_decode_prof_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
+            }
+            else if (cnt > 24 * (int64_t)ctx->cu_count) { /* more blocks than can be resident (6 waves x 4 SIMDs per CU) */
+                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_DENSE;
                 hipLaunchKernelGGL(k4::k4_decode_dense_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
+            }
             else if (cnt <= 16 * (int64_t)ctx->cu_count && !ctx->no_pair) {
                 /* at most half the chip's wave slots (8 per SIMD at 64 VGPRs) are needed: two waves per block, one
                  * parsing ahead of the one that copies */
+                ctx->last_decode_kernel |= hop2 ? K4LZ4_DECODE_KERNEL_PAIR2 : K4LZ4_DECODE_KERNEL_PAIR;
                 hipLaunchKernelGGL(hop2 ? k4::k4_decode_pair2_kernel : k4::k4_decode_pair_kernel, dim3((unsigned)((cnt + k4::DECODE_PAIRS_PER_WG - 1) / k4::DECODE_PAIRS_PER_WG)),
                                    dim3(128 * k4::DECODE_PAIRS_PER_WG), 0, stream, a);
             }
-            else hipLaunchKernelGGL(k4::k4_decode_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
+            else {
+                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_SINGLE;
+                hipLaunchKernelGGL(k4::k4_decode_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
+            }
             break;
         case KIND_PICKLE:
             hipLaunchKernelGGL(k4::k4_pickle_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, a);
             break;
         case KIND_UNPICKLE:
+            ctx->last_decode_kernel = a.pace ? K4LZ4_DECODE_KERNEL_PACE : 0;
             if (cnt <= 64 * (int64_t)ctx->cu_count && !ctx->no_pair) {
+                ctx->last_decode_kernel |= hop2 ? K4LZ4_DECODE_KERNEL_UNPICKLE_PAIR2 : K4LZ4_DECODE_KERNEL_UNPICKLE_PAIR;
                 hipLaunchKernelGGL(hop2 ? k4::k4_unpickle_pair2_kernel : k4::k4_unpickle_pair_kernel, dim3((unsigned)((cnt + k4::DECODE_PAIRS_PER_WG - 1) / k4::DECODE_PAIRS_PER_WG)),
                                    dim3(128 * k4::DECODE_PAIRS_PER_WG), 0, stream, a);
             }
-            else hipLaunchKernelGGL(k4::k4_unpickle_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
+            else {
+                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_UNPICKLE_SINGLE;
+                hipLaunchKernelGGL(k4::k4_unpickle_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
+            }
             break;        case KIND_WRAP:         /* (wraps are closed above, behind the encoder kernels) */
             break;
         }
@@ -2607,6 +2624,8 @@ int k4lz4_selftest_chains(k4lz4_ctx *ctx, int waves, int rounds, uint32_t seed, 
     K4_HIP(ctx, e);
     return K4LZ4_OK;
 }
+
+int k4lz4_last_decode_kernel(const k4lz4_ctx *ctx) { return ctx ? ctx->last_decode_kernel : K4LZ4_DECODE_KERNEL_NONE; }
 
 int k4lz4_last_status(void) { return tl_status; }
 

@@ -171,7 +171,9 @@ def test_partial_and_dictionary_decode_vs_compiled_reference(ref, syslz4):
 
 def test_long_length_fields_vs_compiled_reference(ref, oracle):
     """length fields that are long runs of 255 (4 KiB of random bytes: 17 bytes; 70 000 equal bytes: 274), whole, cut and damaged
-    inside the runs: LZ4_decompress_safe's return value (error position included) and bytes, against LL64.dec.cs compiled here"""
+    inside the runs: LZ4_decompress_safe's return value (error position included) and bytes, against LL64.dec.cs compiled here.
+    Through host pointers a guard assertion checks the download's scatter, not the kernel (a write outside a slot stays in the
+    context's device buffer); the device-arena tests (tests/test_gpu_decoder_variants.py) are the ones that watch the kernel."""
     from stream_cases import long_field_streams
     cases = long_field_streams(oracle, np.random.default_rng(78))
     src, soff, slen = pack_blocks([c for c, _, _ in cases])
