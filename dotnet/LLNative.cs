@@ -50,6 +50,14 @@ namespace K4os.Compression.LZ4.Engine
 		[DllImport(Lib)] public static extern int k4lz4_decode_dict_batch(
 			IntPtr ctx, byte* src, ulong* srcOff, int* srcLen, byte* dst, ulong* dstOff, int* dstCap, int* outLen, long n, int flags,
 			byte* dict, ulong* dictOff, int* dictLen);
+		// messages against shared dictionaries at L03_HC .. L09_HC (DESIGN.md 4.21); the fast levels' pair is in LZ4Codec.DictBatch.cs
+		[DllImport(Lib)] public static extern int k4lz4_encode_dict_hc_batch(
+			IntPtr ctx, byte* src, ulong* srcOff, int* srcLen, byte* dst, ulong* dstOff, int* dstCap, int* outLen, long n, int level, int flags,
+			int* dictIdx, byte* dict, ulong* dictOff, int* dictLen, int nDict);
+		[DllImport(Lib)] public static extern int k4lz4_encode_dict_hc_batch_device(
+			IntPtr ctx, byte* src, ulong* srcOff, int* srcLen, byte* dst, ulong* dstOff, int* dstCap, int* outLen, long n, int level, int flags,
+			int* dictIdx, byte* dict, ulong* dictOff, int* dictLen, int nDict, IntPtr stream);
+		[DllImport(Lib)] public static extern int k4lz4_encode_dict_hc_state(IntPtr ctx, int d, uint* hashTable, ushort* chainTable, int* keptLen);
 
 		// ---- LZ4Pickler envelope
 		[DllImport(Lib)] public static extern int k4lz4_pickle_bound(int srcLen);

@@ -2,7 +2,9 @@
 // LZ4Codec.Decode(source, target, dictionary): k4lz4_encode_dict_batch (include/k4lz4.h, DESIGN.md 4.20).  Message i is encoded
 // against dictionaries[dictionaryIndex[i]]; its block is what LL64.LZ4_loadDict followed by LL64.LZ4_compress_fast_continue on that
 // stream writes (Engine/x64/LL64.tools.cs:175-206, LL64.fast.cs:582-667) and decodes with Decode(source, target, dictionary) given
-// the same dictionary.  Fast levels only; not under LZ4Codec.Enforce32.  Compile-unverified.
+// the same dictionary.  At L03_HC .. L09_HC the call is k4lz4_encode_dict_hc_batch (DESIGN.md 4.21) and the block is what
+// LL.LZ4_loadDictHC followed by LL64.LZ4_compress_HC_continue writes; L10_OPT and up are refused (no sound witness for the optimal
+// parser with a dictionary).  Not under LZ4Codec.Enforce32.  Compile-unverified.
 using System;
 using System.Runtime.InteropServices;
 using K4os.Compression.LZ4.Engine;
@@ -25,7 +27,7 @@ namespace K4os.Compression.LZ4
 	{
 		/// <summary>Compresses n messages, message i against dictionaries[dictionaryOffsets[d] .. +dictionaryLengths[d]) with
 		/// d = dictionaryIndex[i].  encodedLengths[i]: bytes written, 0 for an empty message, -1 when the block does not fit its
-		/// target.  Only a dictionary's last 64 KiB count; one of fewer than 8 bytes is an empty dictionary.</summary>
+		/// target.  Only a dictionary's last 64 KiB count; at the fast levels one of fewer than 8 bytes is an empty dictionary.</summary>
 		public static unsafe void EncodeBatch(
 			ReadOnlySpan<byte> source, ReadOnlySpan<ulong> sourceOffsets, ReadOnlySpan<int> sourceLengths,
 			Span<byte> target, ReadOnlySpan<ulong> targetOffsets, ReadOnlySpan<int> targetLengths,
@@ -34,7 +36,7 @@ namespace K4os.Compression.LZ4
 			ReadOnlySpan<int> dictionaryIndex, LZ4Level level = LZ4Level.L00_FAST)
 		{
 			var n = ValidateBatch(source.Length, sourceOffsets, sourceLengths, target.Length, targetOffsets, targetLengths, encodedLengths.Length);
-			if (level >= LZ4Level.L03_HC) throw new ArgumentException("HC levels with a dictionary are not supported", nameof(level));
+			if (level >= LZ4Level.L10_OPT) throw new ArgumentException("levels 10 - 12 with a dictionary are not supported", nameof(level));
 			if (dictionaryIndex.Length != n || dictionaryOffsets.Length != dictionaryLengths.Length)
 				throw new ArgumentException("dictionary vectors differ in length");
 			for (var d = 0; d < dictionaryLengths.Length; d++)
@@ -50,7 +52,9 @@ namespace K4os.Compression.LZ4
 			fixed (ulong* so = sourceOffsets, to = targetOffsets, dof = dictionaryOffsets)
 			fixed (int* sl = sourceLengths, tl = targetLengths, ol = encodedLengths, dl = dictionaryLengths, di = dictionaryIndex)
 				LLNative.ThrowIfFailed(
-					DictBatchNative.k4lz4_encode_dict_batch(ctx, s, so, sl, t, to, tl, ol, n, (int) level, 0, di, dc, dof, dl, dictionaryLengths.Length), ctx);
+					level >= LZ4Level.L03_HC
+						? LLNative.k4lz4_encode_dict_hc_batch(ctx, s, so, sl, t, to, tl, ol, n, (int) level, 0, di, dc, dof, dl, dictionaryLengths.Length)
+						: DictBatchNative.k4lz4_encode_dict_batch(ctx, s, so, sl, t, to, tl, ol, n, (int) level, 0, di, dc, dof, dl, dictionaryLengths.Length), ctx);
 		}
 
 		/// <summary>Convenience form: every message compressed into a fresh array against dictionaries[dictionaryIndex[i]].</summary>
@@ -86,7 +90,7 @@ namespace K4os.Compression.LZ4
 			}
 			for (var d = 0; d < dictionaries.Length; d++)
 			{
-				var kept = Math.Min(dictionaries[d].Length, 65536);      // LZ4_loadDict keeps the last 64 KiB
+				var kept = Math.Min(dictionaries[d].Length, 65536);      // LZ4_loadDict and LZ4_loadDictHC keep the last 64 KiB
 				dictOff[d] = (ulong) cp; dictLen[d] = kept;
 				Buffer.BlockCopy(dictionaries[d], dictionaries[d].Length - kept, dct, cp, kept);
 				cp += kept;

@@ -345,8 +345,8 @@ K4LZ4_API int k4lz4_encode_fast_chain_batch_device(k4lz4_ctx *ctx, const uint8_t
  * outLen[i] follows k4lz4_encode_batch: the bytes written, 0 for an empty message, -1 when the block does not fit dstCap[i]
  * (limitedOutput returns 0 there); bytes of dst behind outLen[i] are not touched (behind a -1 the slot's content is unspecified in
  * the _device form).
- * Refused with K4LZ4_E_ARG: level >= K4LZ4_L03_HC (HC with a dictionary is LZ4HC_setExternalDict's search arm in four kernels: not
- * done yet); K4LZ4_FLAG_X32 or a process under k4lz4_set_enforce32(1) (LL32's LZ4_loadDict has a 4-byte HASH_UNIT and hash4: no
+ * Refused with K4LZ4_E_ARG: level >= K4LZ4_L03_HC (the hash-chain levels are k4lz4_encode_dict_hc_batch's, below);
+ * K4LZ4_FLAG_X32 or a process under k4lz4_set_enforce32(1) (LL32's LZ4_loadDict has a 4-byte HASH_UNIT and hash4: no
  * witness for it), and every other flag; a negative dictLen; a dictIdx outside [0, nDict).
  * _device: src, dst, outLen, dict and the per-message arrays (srcOff, srcLen, dstOff, dstCap, dictIdx) are device pointers; the
  * list's arrays (dictOff, dictLen) stay HOST arrays.  It runs asynchronously on `stream`.  It cannot look at dictIdx before it runs:
@@ -364,6 +364,35 @@ K4LZ4_API int k4lz4_encode_dict_batch_device(k4lz4_ctx *ctx, const uint8_t *src,
                                              int64_t n, int level, int flags, const int32_t *dictIdx, const uint8_t *dict,
                                              const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, void *stream);
 K4LZ4_API int k4lz4_encode_dict_state(k4lz4_ctx *ctx, int32_t d, k4lz4_fast_chain_state *out);
+
+/* The same at the hash-chain levels K4LZ4_L03_HC .. K4LZ4_L09_HC: block i is byte for byte what LZ4_resetStreamHC_fast(stream, level),
+ * LZ4_loadDictHC(stream, dictionary, dictLen), LZ4_compress_HC_continue(stream, src, dst, srcLen, dstCap) write in that order
+ * (LL.high.cs:74-88, :124-140, :187-207; LL64.high.cs:1259-1311 and the matchIndex < dictLimit arm of LZ4HC_InsertAndGetWiderMatch),
+ * and decodes with k4lz4_decode_dict_batch given the same dictionary.  Arguments, the host and _device forms, outLen and the
+ * treatment of a dictIdx outside the list are k4lz4_encode_dict_batch's.  Only a dictionary's last 64 KiB count; every length is
+ * valid, 0 .. 3 bytes included (nothing of such a dictionary enters the chain, as LZ4_loadDictHC has it).
+ * Scratch, in the context, grow-only: 256 KiB per DISTINCT dictionary of the list (hash heads 32768 x 4 bytes, chain deltas
+ * 65536 x 2 bytes, built once per call and shared by all messages of that dictionary), 8 bytes per message (dispatch order), and
+ * 256 KiB per wavefront of the encode launch (its table of message positions) -- one wavefront per message up to eight per
+ * compute unit, so at most 512 MiB on a 256-CU device however many messages the call has; nothing per message grows with the
+ * dictionary's length or the message's.
+ * Refused with K4LZ4_E_ARG: level < K4LZ4_L03_HC (k4lz4_encode_dict_batch); level >= K4LZ4_L10_OPT (the optimal parser with a
+ * dictionary: the only witness a test can reach, liblz4 1.9.3, and the reference differ there on about 0.3 % of inputs, so there is
+ * nothing to pin the bytes against); K4LZ4_FLAG_X32 or a process under k4lz4_set_enforce32(1), and every other flag; a negative
+ * dictLen, n or nDict; in the host form a dictIdx outside [0, nDict).
+ * k4lz4_encode_dict_hc_state, for tests: what LZ4_loadDictHC left for entry d of the list of the context's most recent
+ * k4lz4_encode_dict_hc_batch[_device] call, into HOST arrays: hashTable (32768 words: the index 65536 + k of the latest kept position
+ * with the hash, 0 for none), chainTable (65536 halfwords: slot k is the delta of kept position k for k < keptLen - 3, 0xFFFF
+ * elsewhere) and the kept length; it waits for that call. */
+K4LZ4_API int k4lz4_encode_dict_hc_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                         uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n,
+                                         int level, int flags, const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff,
+                                         const int32_t *dictLen, int32_t nDict);
+K4LZ4_API int k4lz4_encode_dict_hc_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                                uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen,
+                                                int64_t n, int level, int flags, const int32_t *dictIdx, const uint8_t *dict,
+                                                const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, void *stream);
+K4LZ4_API int k4lz4_encode_dict_hc_state(k4lz4_ctx *ctx, int32_t d, uint32_t *hashTable, uint16_t *chainTable, int32_t *keptLen);
 
 /* Frame writer on device-resident data: after k4lz4_encode_batch_device(..., K4LZ4_FLAG_ALLOW_COPY) and
  * k4lz4_xxh32_batch_device, lays the frames out (Frames/LZ4FrameWriter.cs:57-108 header, LZ4FrameWriter.async.cs:15-27

@@ -96,6 +96,9 @@ SYMBOLS = {
     "k4lz4_encode_dict_batch": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int32]),
     "k4lz4_encode_dict_batch_device": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "k4lz4_encode_dict_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "k4lz4_encode_dict_hc_batch": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "k4lz4_encode_dict_hc_batch_device": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "k4lz4_encode_dict_hc_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "k4lz4_wrap_bound": (C.c_int, [C.c_int]),
     "k4lz4_wrap_batch": (C.c_int, _BATCH + [C.c_int, C.c_int]),
     "k4lz4_wrap_batch_device": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p]),

@@ -254,8 +254,9 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
                               dst_off: np.ndarray, dst_cap: np.ndarray, dict_idx: np.ndarray, dictionaries: np.ndarray,
                               dict_off: np.ndarray, dict_len: np.ndarray, level: LZ4Level = LZ4Level.L00_FAST, flags: int = 0,
                               ctx: Optional[_native.Context] = None) -> np.ndarray:
-        """Batched LZ4_loadDict + LZ4_compress_fast_continue: message i is encoded against entry dict_idx[i] of the list
-        dictionaries[dict_off[d]:+dict_len[d]] (k4lz4_encode_dict_batch; fast levels only).  What it writes decodes with
+        """Message i is encoded against entry dict_idx[i] of the list dictionaries[dict_off[d]:+dict_len[d]]: below L03_HC batched
+        LZ4_loadDict + LZ4_compress_fast_continue (k4lz4_encode_dict_batch), at L03_HC .. L09_HC batched LZ4_loadDictHC +
+        LZ4_compress_HC_continue (k4lz4_encode_dict_hc_batch; levels 10 - 12 are refused).  What it writes decodes with
         DecodeDictBatchPacked given the same dictionary."""
         ctx = ctx or _native.default_context()
         out = np.empty(len(src_len), dtype=np.int32)
@@ -268,9 +269,9 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
             raise ValueError("dict_off / dict_len must have one entry per dictionary, dict_idx one per message")
         if len(doff) and int((doff + dlen.clip(min=0).astype(np.uint64)).max()) > dct.size:
             raise ValueError("a dictionary exceeds the dictionary buffer")
-        ctx.check(ctx.lib.k4lz4_encode_dict_batch(ctx.handle, *a, int(level), flags, idx.ctypes.data if idx.size else None,
-                                                  _ptr(dct) if dct.size else None, doff.ctypes.data if doff.size else None,
-                                                  dlen.ctypes.data if dlen.size else None, len(doff)))
+        fn = ctx.lib.k4lz4_encode_dict_hc_batch if int(level) >= int(LZ4Level.L03_HC) else ctx.lib.k4lz4_encode_dict_batch
+        ctx.check(fn(ctx.handle, *a, int(level), flags, idx.ctypes.data if idx.size else None, _ptr(dct) if dct.size else None,
+                     doff.ctypes.data if doff.size else None, dlen.ctypes.data if dlen.size else None, len(doff)))
         return out
 
     @staticmethod

@@ -48,6 +48,7 @@
 #include "k4lz4_xxh32.hpp"
 #include "k4lz4_selftest.hpp"
 #include "k4lz4_dict_encode.hpp"
+#include "k4lz4_dict_encode_hc.hpp"
 
 constexpr int MAX_PARTS = 8;      /* a big host-pointer call is staged, run and brought back in up to this many parts */
 
@@ -165,6 +166,12 @@ struct k4lz4_ctx {
     uint8_t *d_denc = nullptr; size_t d_denc_cap = 0;
     hipEvent_t ev_denc = nullptr;
     std::vector<uint32_t> denc_table, denc_kept;
+    /* the same at the hash-chain levels (k4lz4_dict_encode_hc.hpp): the tables of the distinct dictionaries (256 KiB each), the list's
+     * words, the dispatch order and the wave slots' tables (256 KiB per wave of the encode launch), grow-only */
+    std::vector<uint8_t> h_dhc;
+    uint8_t *d_dhc = nullptr; size_t d_dhc_cap = 0;
+    hipEvent_t ev_dhc = nullptr;
+    std::vector<uint32_t> dhc_table, dhc_kept;
 };
 
 /* a few helper threads for the staging copies of big host-pointer calls (memcpy between the caller's pageable memory and
@@ -2148,6 +2155,135 @@ int dict_encode_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, 
     return rc;
 }
 
+/* ---- the same at the hash-chain levels (k4lz4_encode_dict_hc_batch, k4lz4_dict_encode_hc.hpp) ----------------
+ * LZ4_loadDictHC keeps the last 64 KiB of a dictionary of any length, down to one byte: entries that keep the same bytes share one
+ * pair of tables. */
+int dict_hc_list(k4lz4_ctx *ctx, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, const uint8_t *used, DictList &l)
+{
+    l.keptOff.assign((size_t)nDict, 0); l.keptLen.assign((size_t)nDict, 0); l.table.assign((size_t)nDict, 0xffffffffu); l.rep.clear();
+    std::map<std::pair<uint64_t, uint32_t>, uint32_t> seen;
+    for (int32_t d = 0; d < nDict; d++) {
+        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: negative dictLen");
+        if (used && !used[d]) continue;
+        const uint32_t len = (uint32_t)dictLen[d];
+        if (len > 0u) {
+            l.keptLen[(size_t)d] = std::min<uint32_t>(len, 65536u);
+            l.keptOff[(size_t)d] = dictOff[d] + (len - l.keptLen[(size_t)d]);
+        }
+        const auto key = std::make_pair(l.keptOff[(size_t)d], l.keptLen[(size_t)d]);
+        auto it = seen.find(key);
+        if (it == seen.end()) { it = seen.emplace(key, (uint32_t)l.rep.size()).first; l.rep.push_back((uint32_t)d); }
+        l.table[(size_t)d] = it->second;
+    }
+    return K4LZ4_OK;
+}
+
+constexpr int DHC_WGS_PER_CU = 2;      /* eight waves per CU: the wave slots' tables are 256 KiB each */
+constexpr size_t DHC_HEAD_WORDS = 64 + 2 * k4::COST_BUCKETS + 16;
+
+/* all pointers but the list are device pointers; load, order, encode on `stream` */
+int dict_hc_encode_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst, const uint64_t *dstOff,
+                       const int32_t *dstCap, int32_t *outLen, int64_t n, int level, const int32_t *dictIdx, const uint8_t *dict,
+                       const DictList &l, hipStream_t stream)
+{
+    if (n > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: more than 2^32 - 1 messages");
+    const size_t nd = l.table.size(), nt = std::max<size_t>(l.rep.size(), 1);
+    const int64_t wgs = std::min<int64_t>((n + k4::DHC_WAVES_PER_WG - 1) / k4::DHC_WAVES_PER_WG, (int64_t)ctx->cu_count * DHC_WGS_PER_CU);
+    const size_t nslots = (size_t)wgs * k4::DHC_WAVES_PER_WG;
+    if (!ctx->ev_dhc) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_dhc, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_dhc));             /* the previous upload of the host words is over */
+    /* layout: [ticket, hist] [tables] [per table: keptOff, keptLen] [per entry: keptOff, keptLen, table] [cost[n], order[n]] [slots];
+     * the part that goes up from the host is the one between the tables and cost[] */
+    uint32_t *head, *tlen, *elen, *etab, *cost, *order;
+    uint64_t *toff, *eoff;
+    uint8_t *tables, *slots;
+    auto layout = [&](Carve &cv) {
+        cv.take(head, DHC_HEAD_WORDS); cv.take(tables, nt * (size_t)k4::DHC_TABLE_BYTES);
+        cv.take(toff, nt); cv.take(tlen, nt); cv.take(eoff, nd); cv.take(elen, nd); cv.take(etab, nd);
+        cv.take(cost, (size_t)n); cv.take(order, (size_t)n); cv.take(slots, nslots * (size_t)k4::DHC_TABLE_BYTES);
+    };
+    Carve m{nullptr};
+    layout(m);
+    int rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_dhc, &ctx->d_dhc_cap, m.at + 64)) != K4LZ4_OK) return rc;
+    Carve dv{ctx->d_dhc};
+    layout(dv);
+    const size_t up_at = (size_t)((uint8_t *)toff - ctx->d_dhc), up_bytes = (size_t)((uint8_t *)cost - (uint8_t *)toff);
+    try { ctx->h_dhc.assign(up_bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    {
+        uint8_t *h = ctx->h_dhc.data() - up_at;                           /* host image of the same layout */
+        uint64_t *h_toff = (uint64_t *)(h + ((uint8_t *)toff - ctx->d_dhc)), *h_eoff = (uint64_t *)(h + ((uint8_t *)eoff - ctx->d_dhc));
+        uint32_t *h_tlen = (uint32_t *)(h + ((uint8_t *)tlen - ctx->d_dhc)), *h_elen = (uint32_t *)(h + ((uint8_t *)elen - ctx->d_dhc)),
+                 *h_etab = (uint32_t *)(h + ((uint8_t *)etab - ctx->d_dhc));
+        for (size_t t = 0; t < l.rep.size(); t++) { h_toff[t] = l.keptOff[l.rep[t]]; h_tlen[t] = l.keptLen[l.rep[t]]; }
+        for (size_t d = 0; d < nd; d++) { h_eoff[d] = l.keptOff[d]; h_elen[d] = l.keptLen[d]; h_etab[d] = l.table[d]; }
+    }
+    ctx->dhc_table = l.table; ctx->dhc_kept = l.keptLen;
+    K4_HIP(ctx, order_after_ctx(ctx, stream));
+    K4_HIP(ctx, hipMemcpyAsync(ctx->d_dhc + up_at, ctx->h_dhc.data(), up_bytes, hipMemcpyHostToDevice, stream));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_dhc, stream));
+    K4_HIP(ctx, hipMemsetAsync(head, 0, DHC_HEAD_WORDS * 4, stream));
+    hipLaunchKernelGGL(k4::k4_dict_hc_load_kernel, dim3((unsigned)nt), dim3(k4::DHC_LOAD_THREADS), 0, stream, k4::DictHcLoadArgs{dict, toff, tlen, tables});
+    rc = K4LZ4_OK;
+    if (n > 0) {
+        /* the wave slots' heads start at zero (a wave leaves them so behind every message); the chain halves are written before they are read */
+        K4_HIP(ctx, hipMemsetAsync(slots, 0, nslots * (size_t)k4::DHC_TABLE_BYTES, stream));
+        k4::BatchArgs o{};
+        o.srcLen = srcLen; o.n = n; o.cost = cost; o.hist = head + 64; o.order_out = order;
+        const unsigned g256 = (unsigned)((n + 255) / 256);
+        hipLaunchKernelGGL(k4::k4_dict_cost_kernel, dim3(g256), dim3(256), 0, stream, o);
+        hipLaunchKernelGGL(k4::k4_order_kernel, dim3(g256), dim3(256), 0, stream, o, 0xffffffffu);
+        k4::DictHcEncArgs a{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, dictIdx, dict, eoff, elen, etab, tables, slots, order, head,
+                            ctx->d_status, n, (int)nd, level};
+        hipLaunchKernelGGL(k4::k4_dict_hc_encode_kernel, dim3((unsigned)wgs), dim3(64 * k4::DHC_WAVES_PER_WG), 0, stream, a);
+    }
+    if (hipGetLastError() != hipSuccess) rc = fail(ctx, K4LZ4_E_HIP, "k4lz4_encode_dict_hc_batch: kernel launch failed");
+    mark_busy(ctx, stream);
+    return rc;
+}
+
+/* the host-pointer form of both dictionary encoders: the messages' span, behind it the kept bytes of every dictionary in use.
+ * list: dict_list or dict_hc_list; run: the device-pointer run over the staged buffers */
+template <class LIST, class RUN>
+int dict_encode_host(k4lz4_ctx *ctx, const char *who, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                            const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, const int32_t *dictIdx,
+                            const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, LIST list, RUN run)
+{
+    int rc;
+    std::vector<uint8_t> used((size_t)nDict, 0);
+    for (int64_t i = 0; i < n; i++) {
+        if (dictIdx[i] < 0 || dictIdx[i] >= nDict) return fail(ctx, K4LZ4_E_ARG, (std::string(who) + ": a dictIdx outside the dictionary list").c_str());
+        used[(size_t)dictIdx[i]] = 1;
+    }
+    DictList l;
+    if ((rc = list(ctx, dictOff, dictLen, nDict, used.data(), l)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    s.span(src, srcOff, n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(srcLen[i], 0); });
+    /* the kept bytes of every dictionary in use go up behind the messages, at 16-byte steps of the same buffer */
+    DictList staged = l;
+    std::vector<uint64_t> at_of((size_t)l.rep.size(), 0);
+    for (size_t t = 0; t < l.rep.size(); t++) {
+        const uint32_t d = l.rep[t];
+        if (!l.keptLen[d]) continue;
+        at_of[t] = (s.in_bytes + 15u) & ~(uint64_t)15u;
+        s.ups.push_back(HostStage::Up{&ctx->d_src, at_of[t], dict + l.keptOff[d], (size_t)l.keptLen[d]});
+        s.in_bytes = at_of[t] + l.keptLen[d];
+    }
+    for (int32_t e = 0; e < nDict; e++)
+        if (used[(size_t)e]) staged.keptOff[(size_t)e] = at_of[l.table[(size_t)e]];
+    s.slots(n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(dstCap[i], 0); }, false);
+    uint64_t *d_off, *d_doff;
+    int32_t *d_len, *d_cap, *d_out, *d_idx;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, srcLen); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_cap, n, dstCap);
+    s.meta(&d_idx, n, dictIdx); s.meta(&d_out, n);
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = run(ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, d_idx, staged, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
+                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
+}
+
 void direct_layout(Carve &c, k4::FrFastArgs &f, size_t n, size_t nr)
 {
     c.take(f.plan, n); c.take(f.done, n);
@@ -2521,6 +2657,8 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->ev_chain) (void)hipEventDestroy(ctx->ev_chain);
     if (ctx->d_denc) (void)hipFree(ctx->d_denc);
     if (ctx->ev_denc) (void)hipEventDestroy(ctx->ev_denc);
+    if (ctx->d_dhc) (void)hipFree(ctx->d_dhc);
+    if (ctx->ev_dhc) (void)hipEventDestroy(ctx->ev_dhc);
     if (ctx->d_pk_meta) (void)hipFree(ctx->d_pk_meta);
     delete ctx;
 }
@@ -3002,38 +3140,12 @@ int k4lz4_encode_dict_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *
 {
     int rc = dict_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
     if (rc != K4LZ4_OK) return rc;
-    std::vector<uint8_t> used((size_t)nDict, 0);
-    for (int64_t i = 0; i < n; i++) {
-        if (dictIdx[i] < 0 || dictIdx[i] >= nDict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: a dictIdx outside the dictionary list");
-        used[(size_t)dictIdx[i]] = 1;
-    }
-    DictList l;
-    if ((rc = dict_list(ctx, dictOff, dictLen, nDict, used.data(), l)) != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    HostStage s(ctx);
-    s.span(src, srcOff, n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(srcLen[i], 0); });
-    /* the kept bytes of every dictionary in use go up behind the messages, at 16-byte steps of the same buffer */
-    DictList staged = l;
-    std::vector<uint64_t> at_of((size_t)l.rep.size(), 0);
-    for (size_t t = 0; t < l.rep.size(); t++) {
-        const uint32_t d = l.rep[t];
-        if (!l.keptLen[d]) continue;
-        at_of[t] = (s.in_bytes + 15u) & ~(uint64_t)15u;
-        s.ups.push_back(HostStage::Up{&ctx->d_src, at_of[t], dict + l.keptOff[d], (size_t)l.keptLen[d]});
-        s.in_bytes = at_of[t] + l.keptLen[d];
-    }
-    for (int32_t e = 0; e < nDict; e++)
-        if (used[(size_t)e]) staged.keptOff[(size_t)e] = at_of[l.table[(size_t)e]];
-    s.slots(n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(dstCap[i], 0); }, false);
-    uint64_t *d_off, *d_doff;
-    int32_t *d_len, *d_cap, *d_out, *d_idx;
-    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, srcLen); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_cap, n, dstCap);
-    s.meta(&d_idx, n, dictIdx); s.meta(&d_out, n);
-    if ((rc = s.upload()) != K4LZ4_OK ||
-        (rc = dict_encode_run(ctx, ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, n, d_idx, ctx->d_src, staged, s.st)) != K4LZ4_OK)
-        return rc;
-    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
-                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
+    return dict_encode_host(ctx, "k4lz4_encode_dict_batch", src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx, dict, dictOff, dictLen,
+                            nDict, dict_list,
+                            [&](const uint8_t *ds, const uint64_t *doff, const int32_t *dlen, uint8_t *dd, const uint64_t *ddoff, const int32_t *dcap,
+                                int32_t *dout, const int32_t *didx, const DictList &staged, hipStream_t st) {
+                                return dict_encode_run(ctx, ds, doff, dlen, dd, ddoff, dcap, dout, n, didx, ds, staged, st);
+                            });
 }
 
 int k4lz4_encode_dict_state(k4lz4_ctx *ctx, int32_t d, k4lz4_fast_chain_state *out)
@@ -3050,6 +3162,73 @@ int k4lz4_encode_dict_state(k4lz4_ctx *ctx, int32_t d, k4lz4_fast_chain_state *o
     out->currentOffset = k4::DICT_START;
     out->dictSize = ctx->denc_kept[(size_t)d];
     out->reserved[0] = out->reserved[1] = 0;
+    return K4LZ4_OK;
+}
+
+/* ---- k4lz4_encode_dict_hc_batch (k4lz4_dict_encode_hc.hpp) --------------------------------------------------- */
+static int dict_hc_encode_args(k4lz4_ctx *ctx, const void *src, const void *srcOff, const void *srcLen, const void *dst, const void *dstOff,
+                               const void *dstCap, const void *outLen, int64_t n, int level, int flags, const void *dictIdx, const void *dict,
+                               const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict)
+{
+    int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
+    if (rc != K4LZ4_OK) return rc;
+    if (level < K4LZ4_L03_HC)
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: levels below 3 are k4lz4_encode_dict_batch's (LZ4_loadDict + LZ4_compress_fast_continue)");
+    if (level >= K4LZ4_L10_OPT)
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: levels 10 - 12 with a dictionary are not supported (no sound witness for the optimal parser in this mode)");
+    if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: the 32-bit engine (LZ4Codec.Enforce32) is not supported");
+    if (flags) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: it takes no flags");
+    if (nDict < 0 || (nDict > 0 && (!dictOff || !dictLen)) || (n > 0 && !dictIdx)) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: bad dictionary list");
+    for (int32_t d = 0; d < nDict; d++) {
+        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: negative dictLen");
+        if (dictLen[d] > 0 && !dict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: NULL dictionary buffer");
+    }
+    return K4LZ4_OK;
+}
+
+int k4lz4_encode_dict_hc_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                                      const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+                                      const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen,
+                                      int32_t nDict, void *stream)
+{
+    int rc = dict_hc_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
+    if (rc != K4LZ4_OK) return rc;
+    DictList l;
+    if ((rc = dict_hc_list(ctx, dictOff, dictLen, nDict, nullptr, l)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    return dict_hc_encode_run(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, dictIdx, dict, l, (hipStream_t)stream);
+}
+
+int k4lz4_encode_dict_hc_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                               const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+                               const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict)
+{
+    int rc = dict_hc_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
+    if (rc != K4LZ4_OK) return rc;
+    return dict_encode_host(ctx, "k4lz4_encode_dict_hc_batch", src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx, dict, dictOff, dictLen,
+                            nDict, dict_hc_list,
+                            [&](const uint8_t *ds, const uint64_t *doff, const int32_t *dlen, uint8_t *dd, const uint64_t *ddoff, const int32_t *dcap,
+                                int32_t *dout, const int32_t *didx, const DictList &staged, hipStream_t st) {
+                                return dict_hc_encode_run(ctx, ds, doff, dlen, dd, ddoff, dcap, dout, n, level, didx, ds, staged, st);
+                            });
+}
+
+int k4lz4_encode_dict_hc_state(k4lz4_ctx *ctx, int32_t d, uint32_t *hashTable, uint16_t *chainTable, int32_t *keptLen)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (!hashTable || !chainTable || !keptLen || d < 0 || (size_t)d >= ctx->dhc_table.size() || ctx->dhc_table[(size_t)d] == 0xffffffffu || !ctx->d_dhc)
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_state: no such dictionary in the context's most recent k4lz4_encode_dict_hc_batch call");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
+    Carve c{ctx->d_dhc};
+    uint32_t *head;
+    uint8_t *tables;
+    c.take(head, DHC_HEAD_WORDS); c.take(tables, (size_t)k4::DHC_TABLE_BYTES);
+    const uint8_t *t = tables + (size_t)k4::DHC_TABLE_BYTES * ctx->dhc_table[(size_t)d];
+    K4_HIP(ctx, hipMemcpy(hashTable, t, (size_t)k4::DHC_HEADS * 4, hipMemcpyDeviceToHost));
+    K4_HIP(ctx, hipMemcpy(chainTable, t + (size_t)k4::DHC_HEADS * 4, (size_t)k4::DHC_CHAIN * 2, hipMemcpyDeviceToHost));
+    *keptLen = (int32_t)ctx->dhc_kept[(size_t)d];
     return K4LZ4_OK;
 }
 

@@ -98,15 +98,24 @@ class DeviceCodec:
                     dict_len: np.ndarray, out_len: Optional[torch.Tensor] = None, level: LZ4Level = LZ4Level.L00_FAST,
                     flags: int = 0) -> torch.Tensor:
         """message i encoded against entry dict_idx[i] (device int32 tensor) of the list dictionaries[dict_off[d]:+dict_len[d]]
-        (device bytes; the list's two arrays are HOST arrays): k4lz4_encode_dict_batch_device, fast levels only"""
+        (device bytes; the list's two arrays are HOST arrays): k4lz4_encode_dict_batch_device below L03_HC,
+        k4lz4_encode_dict_hc_batch_device at L03_HC .. L09_HC"""
         out_len = self.new_out_len(src.n) if out_len is None else out_len
         doff = np.ascontiguousarray(dict_off, dtype=np.uint64)
         dlen = np.ascontiguousarray(dict_len, dtype=np.int32)
         assert doff.size == dlen.size and dict_idx.numel() == src.n and dict_idx.dtype == torch.int32
         if doff.size and int((doff + dlen.clip(min=0).astype(np.uint64)).max()) > dictionaries.numel():
             raise ValueError("a dictionary exceeds the dictionary buffer")
-        return self._call(self.lib.k4lz4_encode_dict_batch_device, src, dst, out_len, int(level), flags, _dp(dict_idx), _dp(dictionaries),
+        fn = self.lib.k4lz4_encode_dict_hc_batch_device if int(level) >= int(LZ4Level.L03_HC) else self.lib.k4lz4_encode_dict_batch_device
+        return self._call(fn, src, dst, out_len, int(level), flags, _dp(dict_idx), _dp(dictionaries),
                           doff.ctypes.data if doff.size else None, dlen.ctypes.data if dlen.size else None, int(doff.size))
+
+    def dict_hc_state(self, d: int):
+        """what LZ4_loadDictHC left for entry d of the most recent encode_dict call's list at an HC level (k4lz4_encode_dict_hc_state):
+        (hashTable: 32768 x uint32, chainTable: 65536 x uint16, kept length).  Waits for that call."""
+        heads, chain, kept = np.zeros(32768, np.uint32), np.zeros(65536, np.uint16), np.zeros(1, np.int32)
+        self.ctx.check(self.lib.k4lz4_encode_dict_hc_state(self.ctx.handle, int(d), heads.ctypes.data, chain.ctypes.data, kept.ctypes.data))
+        return heads, chain, int(kept[0])
 
     def dict_state(self, d: int) -> np.ndarray:
         """the stream context LZ4_loadDict left for entry d of the most recent encode_dict call's list (k4lz4_encode_dict_state):
