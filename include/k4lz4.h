@@ -394,6 +394,70 @@ K4LZ4_API int k4lz4_encode_dict_hc_batch_device(k4lz4_ctx *ctx, const uint8_t *s
                                                 const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, void *stream);
 K4LZ4_API int k4lz4_encode_dict_hc_state(k4lz4_ctx *ctx, int32_t d, uint32_t *hashTable, uint16_t *chainTable, int32_t *keptLen);
 
+/* Dictionaries that stay prepared on the device: k4lz4_dict_set.  The two calls above load their list anew on every
+ * call; a set is the same list loaded once -- created, then only read, by any number of later encode and decode calls of any context
+ * on its device, on any stream -- and freed with k4lz4_dict_set_destroy.  It cannot be appended to or changed.
+ * For every entry it keeps, in one device allocation of its own: the last 64 KiB of the dictionary's bytes (every length down to one
+ * byte), and per family of `families` the per-entry words and the tables the encode kernels take: K4LZ4_DICT_FAST is LZ4_loadDict's
+ * table (16 KiB per distinct dictionary; below 8 bytes a dictionary is the empty one), K4LZ4_DICT_HC is LZ4_loadDictHC's heads and
+ * chain (256 KiB per distinct dictionary; every length counts).  Entries that keep the same range of `dict` share a region and, within
+ * a family, a table -- the rules of k4lz4_encode_dict_batch and k4lz4_encode_dict_hc_batch.
+ * k4lz4_dict_set_create: dict, dictOff and dictLen are host pointers.  It returns after the bytes are copied and the tables are
+ * built; the caller may free or overwrite `dict` at once.  Refused with K4LZ4_E_ARG: families 0 or with unknown bits, a negative
+ * nDict or dictLen, a NULL array that is needed.  _device: dict is a device pointer, valid once `stream` reaches this point; dictOff
+ * and dictLen stay host arrays; it too returns only after the set is complete (it synchronises `stream`).
+ * k4lz4_dict_set_destroy waits for every call on the set's device that may still read it; NULL is a no-op.
+ * k4lz4_dict_set_info: out[0] nDict, [1] distinct tables of the fast family, [2] of the HC family (0: family absent), [3] device bytes
+ * held, [4] families, [5] device ordinal, [6] load-kernel launches so far for the fast family, [7] for the HC family: the last two
+ * are what create launched and stay there -- no later call loads anything.
+ * k4lz4_dict_set_layout, host arithmetic without a GPU and what create itself uses: per entry the kept length (min(dictLen, 65536)),
+ * where its kept bytes lie in the set's allocation (every distinct kept range at the next 64-byte step, in list order; an empty one
+ * takes no room), its table in either family (-1: family absent), and the allocation's size.  Any output pointer may be NULL.
+ * k4lz4_dict_set_state / _hc_state: k4lz4_encode_dict_state / k4lz4_encode_dict_hc_state for entry d of the set -- read from the set,
+ * so they do not depend on any context's most recent call. */
+enum { K4LZ4_DICT_FAST = 1, K4LZ4_DICT_HC = 2 };
+typedef struct k4lz4_dict_set k4lz4_dict_set;
+K4LZ4_API int k4lz4_dict_set_create(k4lz4_ctx *ctx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict,
+                                    int families, k4lz4_dict_set **set);
+K4LZ4_API int k4lz4_dict_set_create_device(k4lz4_ctx *ctx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen,
+                                           int32_t nDict, int families, k4lz4_dict_set **set, void *stream);
+K4LZ4_API void k4lz4_dict_set_destroy(k4lz4_dict_set *set);
+K4LZ4_API int k4lz4_dict_set_info(const k4lz4_dict_set *set, int64_t out[8]);
+K4LZ4_API int k4lz4_dict_set_layout(const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, int families, int32_t *keptLen,
+                                    uint64_t *keptAt, int32_t *tableFast, int32_t *tableHc, uint64_t *bytes);
+K4LZ4_API int k4lz4_dict_set_state(const k4lz4_dict_set *set, int32_t d, k4lz4_fast_chain_state *out);
+K4LZ4_API int k4lz4_dict_set_hc_state(const k4lz4_dict_set *set, int32_t d, uint32_t *hashTable, uint16_t *chainTable, int32_t *keptLen);
+
+/* k4lz4_encode_dict_batch (level 0 .. 2) and k4lz4_encode_dict_hc_batch (level 3 .. 9) with the list being a set: block i is byte for
+ * byte what those calls write for the same list, outLen and the untouched bytes behind it are theirs, and so is a dictIdx outside
+ * [0, nDict): K4LZ4_E_ARG up front in the host form; in the _device form outLen -1, nothing written, and K4LZ4_E_ARG at the next
+ * synchronising call on the context.  The call loads nothing: it launches the cost, order and encode kernels on the set's memory; the
+ * context's scratch carries the ticket and histogram words, cost and order and the HC wave slots (it is the scratch of the per-call
+ * calls, so their state queries refuse after a set call).  The host form stages the messages only.
+ * Refused with K4LZ4_E_ARG: a level whose family the set was created without; level >= K4LZ4_L10_OPT; K4LZ4_FLAG_X32 or a process
+ * under k4lz4_set_enforce32(1), and every other flag; a set on another device than the context's. */
+K4LZ4_API int k4lz4_encode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                         uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n,
+                                         int level, int flags, const int32_t *dictIdx, const k4lz4_dict_set *set);
+K4LZ4_API int k4lz4_encode_dictset_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                                uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen,
+                                                int64_t n, int level, int flags, const int32_t *dictIdx, const k4lz4_dict_set *set,
+                                                void *stream);
+
+/* k4lz4_decode_dict_batch with message i's dictionary being entry dictIdx[i] of the set; dictIdx[i] == -1: no dictionary.  The flags
+ * are that call's (K4LZ4_FLAG_PARTIAL included) and so are the decoder kernels.  The kept bytes are all a decoder can ask for: a
+ * match offset is at most 65535, so nothing in front of a dictionary's last 64 KiB is reachable, and with 64 KiB present the
+ * before-start check cannot fire where it would not have fired with the whole dictionary.  The dictionary is always external to the
+ * target (never its prefix).  Any other index outside [0, nDict) is treated as by the encode call: K4LZ4_E_ARG up front in the host
+ * form; in the _device form (dictIdx a device pointer) that message is not decoded -- outLen -1, its slot untouched -- and the next
+ * synchronising call on the context returns K4LZ4_E_ARG.  A set of either family serves. */
+K4LZ4_API int k4lz4_decode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                         uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n,
+                                         int flags, const int32_t *dictIdx, const k4lz4_dict_set *set);
+K4LZ4_API int k4lz4_decode_dictset_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                                uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen,
+                                                int64_t n, int flags, const int32_t *dictIdx, const k4lz4_dict_set *set, void *stream);
+
 /* Frame writer on device-resident data: after k4lz4_encode_batch_device(..., K4LZ4_FLAG_ALLOW_COPY) and
  * k4lz4_xxh32_batch_device, lays the frames out (Frames/LZ4FrameWriter.cs:57-108 header, LZ4FrameWriter.async.cs:15-27
  * block records, :75-90 EndMark + content checksum).  The caller computes the positions (recOff, frameOff, tailOff) from

@@ -2,7 +2,7 @@
 block API: LZ4Codec.Encode / Decode, LZ4Pickler.Pickle / Unpickle and their batch forms.
 All compute runs in hand-written HIP kernels (csrc/) reached through the C ABI of libk4lz4.so
 (include/k4lz4.h).  There is no CPU fallback."""
-from .codec import LZ4Codec, LZ4Level, pack_blocks, make_arena, encode_dict_packed, encode_dict_device
+from .codec import LZ4Codec, LZ4Level, pack_blocks, make_arena, encode_dict_packed, encode_dict_device, encode_dictset_device, DictionarySet, DICT_FAST, DICT_HC
 from .pickler import LZ4Pickler, InvalidDataException
 from .encoders import (LZ4BlockEncoder, LZ4HighChainEncoder, LZ4FastChainEncoder, LZ4BlockDecoder, EncoderAction, InvalidOperationException, TopupAndEncode,
                        FlushAndEncode, DecodeAndDrain, encode_fast_chain_packed, encode_fast_chain_device, fast_chain_blocks,
@@ -27,4 +27,5 @@ __all__ = ["LZ4Codec", "LZ4Level", "LZ4Pickler", "InvalidDataException", "Native
            "wrap_device", "unwrap_device", "encode_legacy_streams_device", "legacy_stream_sizes_device", "decode_legacy_streams_device",
            "LZ4StreamWriterBatch", "LegacyWriterDevice", "LZ4StreamReaderBatch", "LegacyReaderDevice",
            "LZ4StreamFedReaderBatch", "LegacyFedReaderDevice", "LZ4ChainDecoder", "LZ4Decoder", "LZ4ChainDecoderBatch",
-           "LZ4EncoderBatch", "LZ4ChainEncoder", "LZ4Encoder", "encode_dict_packed", "encode_dict_device"]
+           "LZ4EncoderBatch", "LZ4ChainEncoder", "LZ4Encoder", "encode_dict_packed", "encode_dict_device", "encode_dictset_device", "DictionarySet",
+           "DICT_FAST", "DICT_HC"]

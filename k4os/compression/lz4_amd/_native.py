@@ -99,6 +99,20 @@ SYMBOLS = {
     "k4lz4_encode_dict_hc_batch": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int32]),
     "k4lz4_encode_dict_hc_batch_device": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "k4lz4_encode_dict_hc_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # k4lz4_dict_set: ctx, dict, dictOff, dictLen, nDict, families, &set [, stream]
+    "k4lz4_dict_set_create": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
+    "k4lz4_dict_set_create_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "k4lz4_dict_set_destroy": (None, [C.c_void_p]),
+    "k4lz4_dict_set_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "k4lz4_dict_set_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_dict_set_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "k4lz4_dict_set_hc_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ... level, flags, dictIdx, set [, stream]
+    "k4lz4_encode_dictset_batch": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "k4lz4_encode_dictset_batch_device": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ... flags, dictIdx, set [, stream]
+    "k4lz4_decode_dictset_batch": (C.c_int, _BATCH + [C.c_int, C.c_void_p, C.c_void_p]),
+    "k4lz4_decode_dictset_batch_device": (C.c_int, _BATCH + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "k4lz4_wrap_bound": (C.c_int, [C.c_int]),
     "k4lz4_wrap_batch": (C.c_int, _BATCH + [C.c_int, C.c_int]),
     "k4lz4_wrap_batch_device": (C.c_int, _BATCH + [C.c_int, C.c_int, C.c_void_p]),

@@ -251,16 +251,27 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
 
     @staticmethod
     def EncodeDictBatchPacked(src: np.ndarray, src_off: np.ndarray, src_len: np.ndarray, dst: np.ndarray,
-                              dst_off: np.ndarray, dst_cap: np.ndarray, dict_idx: np.ndarray, dictionaries: np.ndarray,
-                              dict_off: np.ndarray, dict_len: np.ndarray, level: LZ4Level = LZ4Level.L00_FAST, flags: int = 0,
+                              dst_off: np.ndarray, dst_cap: np.ndarray, dict_idx: np.ndarray, dictionaries,
+                              dict_off: Optional[np.ndarray] = None, dict_len: Optional[np.ndarray] = None,
+                              level: LZ4Level = LZ4Level.L00_FAST, flags: int = 0,
                               ctx: Optional[_native.Context] = None) -> np.ndarray:
         """Message i is encoded against entry dict_idx[i] of the list dictionaries[dict_off[d]:+dict_len[d]]: below L03_HC batched
         LZ4_loadDict + LZ4_compress_fast_continue (k4lz4_encode_dict_batch), at L03_HC .. L09_HC batched LZ4_loadDictHC +
         LZ4_compress_HC_continue (k4lz4_encode_dict_hc_batch; levels 10 - 12 are refused).  What it writes decodes with
-        DecodeDictBatchPacked given the same dictionary."""
-        ctx = ctx or _native.default_context()
+        DecodeDictBatchPacked given the same dictionary.  `dictionaries` may be a DictionarySet instead (dict_off / dict_len stay None):
+        the same blocks from dictionaries that are already prepared on the device (k4lz4_encode_dictset_batch)."""
+        ctx = ctx or (dictionaries.ctx if isinstance(dictionaries, DictionarySet) else _native.default_context())
         out = np.empty(len(src_len), dtype=np.int32)
         a = _batch_args(src, src_off, src_len, dst, dst_off, dst_cap, out)
+        if isinstance(dictionaries, DictionarySet):
+            if dict_off is not None or dict_len is not None:
+                raise ValueError("a DictionarySet has its own offsets and lengths")
+            idx = np.ascontiguousarray(dict_idx, dtype=np.int32)
+            if len(idx) != len(src_len):
+                raise ValueError("dict_idx must have one entry per message")
+            ctx.check(ctx.lib.k4lz4_encode_dictset_batch(ctx.handle, *a, int(level), flags, idx.ctypes.data if idx.size else None,
+                                                         dictionaries.handle))
+            return out
         dct = np.ascontiguousarray(dictionaries, dtype=np.uint8)
         doff = np.ascontiguousarray(dict_off, dtype=np.uint64)
         dlen = np.ascontiguousarray(dict_len, dtype=np.int32)
@@ -277,15 +288,33 @@ class LZ4Codec(metaclass=_LZ4CodecMeta):
     @staticmethod
     def EncodeDictBatch(sources: Sequence, dictionaries: Sequence, dictionary_index: Sequence[int],
                         level: LZ4Level = LZ4Level.L00_FAST) -> List[Optional[bytes]]:
-        """Each message encoded against dictionaries[dictionary_index[i]] into a MaximumOutputSize target; None where it fails."""
+        """Each message encoded against dictionaries[dictionary_index[i]] into a MaximumOutputSize target; None where it fails.
+        `dictionaries`: a sequence of byte strings, or a DictionarySet."""
         blocks = [_ro_view(s, "source") for s in sources]
-        dicts = [_ro_view(d, "dictionary") for d in dictionaries]
         src, soff, slen = pack_blocks(blocks)
-        dct, doff, dlen = pack_blocks(dicts)
+        if isinstance(dictionaries, DictionarySet):
+            dct, doff, dlen = dictionaries, None, None
+        else:
+            dct, doff, dlen = pack_blocks([_ro_view(d, "dictionary") for d in dictionaries])
         caps = np.array([LZ4Codec.MaximumOutputSize(b.size) for b in blocks], dtype=np.int32)
         dst, to = make_arena(caps)
         out = LZ4Codec.EncodeDictBatchPacked(src, soff, slen, dst, to, caps, np.asarray(dictionary_index, dtype=np.int32), dct, doff, dlen, level)
         return [None if n < 0 else dst[int(o):int(o) + int(n)].tobytes() for n, o in zip(out, to)]
+
+    @staticmethod
+    def DecodeDictSetBatchPacked(src: np.ndarray, src_off: np.ndarray, src_len: np.ndarray, dst: np.ndarray, dst_off: np.ndarray,
+                                 dst_cap: np.ndarray, dict_idx: np.ndarray, dictionaries: "DictionarySet", flags: int = 0,
+                                 ctx: Optional[_native.Context] = None) -> np.ndarray:
+        """DecodeDictBatchPacked with block i's dictionary being entry dict_idx[i] of a DictionarySet, -1 for none
+        (k4lz4_decode_dictset_batch): only the blocks go up."""
+        ctx = ctx or dictionaries.ctx
+        out = np.empty(len(src_len), dtype=np.int32)
+        a = _batch_args(src, src_off, src_len, dst, dst_off, dst_cap, out)
+        idx = np.ascontiguousarray(dict_idx, dtype=np.int32)
+        if len(idx) != len(src_len):
+            raise ValueError("dict_idx must have one entry per block")
+        ctx.check(ctx.lib.k4lz4_decode_dictset_batch(ctx.handle, *a, flags, idx.ctypes.data if idx.size else None, dictionaries.handle))
+        return out
 
     @staticmethod
     def EncodeBatch(sources: Sequence, level: LZ4Level = LZ4Level.L00_FAST) -> List[Optional[bytes]]:
@@ -318,6 +347,108 @@ def encode_dict_device(dc, src, dst, dict_idx, dictionaries, dict_off, dict_len,
     (uint8) torch tensors on the device, dict_off / dict_len host arrays; asynchronous on the current torch stream.  What it writes
     decodes with DeviceCodec.decode_dict given the same dictionary."""
     return dc.encode_dict(src, dst, dict_idx, dictionaries, dict_off, dict_len, out_len, level)
+
+
+def encode_dictset_device(dc, src, dst, dict_idx, dictionaries: "DictionarySet", out_len=None, level: LZ4Level = LZ4Level.L00_FAST):
+    """encode_dict_device against a DictionarySet: nothing is loaded per call.  Decodes with DeviceCodec.decode_dictset."""
+    return dc.encode_dictset(src, dst, dict_idx, dictionaries, out_len, level)
+
+
+DICT_FAST, DICT_HC = 1, 2        # K4LZ4_DICT_FAST, K4LZ4_DICT_HC
+
+
+class DictionarySet:
+    """k4lz4_dict_set: dictionaries prepared on the device once -- their last 64 KiB, and per family of `families` the tables
+    LZ4_loadDict (DICT_FAST, levels below L03_HC) or LZ4_loadDictHC (DICT_HC, L03_HC .. L09_HC) leave -- for any number of later
+    EncodeDictBatch[Packed] / DeviceCodec.encode_dictset / decode_dictset calls.  It is never changed after it is built.
+
+    dictionaries: a sequence of bytes-likes; or, with dict_off / dict_len (host arrays), one packed buffer: a numpy array, or a
+    device tensor of uint8 (anything with data_ptr(): the bytes are taken on `owner`'s current stream).  owner: a DeviceCodec or a
+    Context (default: the thread's); any context on the same device may use the set.  The caller's buffers are free once the
+    constructor returns."""
+
+    def __init__(self, dictionaries, dict_off=None, dict_len=None, families: int = DICT_FAST | DICT_HC, owner=None):
+        self.handle = None
+        self.ctx = getattr(owner, "ctx", owner) or _native.default_context()
+        lib = self.ctx.lib
+        if dict_off is None:
+            dictionaries, dict_off, dict_len = pack_blocks([_ro_view(d, "dictionary") for d in dictionaries])
+        doff = np.ascontiguousarray(dict_off, dtype=np.uint64)
+        dlen = np.ascontiguousarray(dict_len, dtype=np.int32)
+        if doff.size != dlen.size:
+            raise ValueError("dict_off / dict_len must have one entry per dictionary")
+        on_device = hasattr(dictionaries, "data_ptr")
+        size = int(dictionaries.numel()) if on_device else 0
+        if not on_device:
+            dictionaries = np.ascontiguousarray(dictionaries, dtype=np.uint8)
+            size = dictionaries.size
+        if doff.size and int((doff + dlen.clip(min=0).astype(np.uint64)).max()) > size:
+            raise ValueError("a dictionary exceeds the dictionary buffer")
+        h = C.c_void_p()
+        lists = (doff.ctypes.data if doff.size else None, dlen.ctypes.data if dlen.size else None, int(doff.size), int(families), C.byref(h))
+        if on_device:
+            stream = owner._stream() if hasattr(owner, "_stream") else 0
+            rc = lib.k4lz4_dict_set_create_device(self.ctx.handle, dictionaries.data_ptr() if size else None, *lists, C.c_void_p(stream))
+        else:
+            rc = lib.k4lz4_dict_set_create(self.ctx.handle, _ptr(dictionaries) if size else None, *lists)
+        self.ctx.check(rc)
+        self.handle = h
+        self.n = int(doff.size)
+        self.families = int(families)
+
+    @staticmethod
+    def layout(dict_off, dict_len, families: int = DICT_FAST | DICT_HC):
+        """k4lz4_dict_set_layout (no GPU): per entry (kept length, where its kept bytes lie in the set's memory, its table in the fast
+        family, in the HC family; -1: family absent), and the device bytes a set of this list holds"""
+        lib = _native.load_library()
+        doff = np.ascontiguousarray(dict_off, dtype=np.uint64)
+        dlen = np.ascontiguousarray(dict_len, dtype=np.int32)
+        n = int(dlen.size)
+        kept, at = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64)
+        tfast, thc, total = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(1, np.uint64)
+        _native._check_plain(lib, lib.k4lz4_dict_set_layout(doff.ctypes.data if n else None, dlen.ctypes.data if n else None, n if doff.size == n else -1,
+                                                            int(families), kept.ctypes.data, at.ctypes.data, tfast.ctypes.data, thc.ctypes.data,
+                                                            total.ctypes.data))
+        return kept[:n], at[:n], tfast[:n], thc[:n], int(total[0])
+
+    @property
+    def info(self) -> dict:
+        """k4lz4_dict_set_info; the load counters are what the constructor launched: no later call loads anything"""
+        v = np.zeros(8, np.int64)
+        _native._check_plain(self.ctx.lib, self.ctx.lib.k4lz4_dict_set_info(self.handle, v.ctypes.data))
+        names = ("nDict", "fast_tables", "hc_tables", "device_bytes", "families", "device", "fast_loads", "hc_loads")
+        return {k: int(x) for k, x in zip(names, v)}
+
+    def state(self, d: int) -> np.ndarray:
+        """the stream context LZ4_loadDict left for entry d (k4lz4_dict_set_state): one FAST_CHAIN_STATE record"""
+        from .encoders import FAST_CHAIN_STATE
+        st = np.zeros(1, FAST_CHAIN_STATE)
+        _native._check_plain(self.ctx.lib, self.ctx.lib.k4lz4_dict_set_state(self.handle, int(d), st.ctypes.data))
+        return st
+
+    def hc_state(self, d: int):
+        """what LZ4_loadDictHC left for entry d (k4lz4_dict_set_hc_state): (hashTable: 32768 x uint32, chainTable: 65536 x uint16, kept length)"""
+        heads, chain, kept = np.zeros(32768, np.uint32), np.zeros(65536, np.uint16), np.zeros(1, np.int32)
+        _native._check_plain(self.ctx.lib, self.ctx.lib.k4lz4_dict_set_hc_state(self.handle, int(d), heads.ctypes.data, chain.ctypes.data, kept.ctypes.data))
+        return heads, chain, int(kept[0])
+
+    def close(self):
+        """k4lz4_dict_set_destroy: waits for the calls that still read the set"""
+        if getattr(self, "handle", None):
+            self.ctx.lib.k4lz4_dict_set_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _raise_if_native_failed(lib):

@@ -49,6 +49,7 @@
 #include "k4lz4_selftest.hpp"
 #include "k4lz4_dict_encode.hpp"
 #include "k4lz4_dict_encode_hc.hpp"
+#include "k4lz4_dict_set.hpp"
 
 constexpr int MAX_PARTS = 8;      /* a big host-pointer call is staged, run and brought back in up to this many parts */
 
@@ -172,6 +173,32 @@ struct k4lz4_ctx {
     uint8_t *d_dhc = nullptr; size_t d_dhc_cap = 0;
     hipEvent_t ev_dhc = nullptr;
     std::vector<uint32_t> dhc_table, dhc_kept;
+    /* k4lz4_decode_dictset_batch_device: the per-message dictionary words k4_dict_pick_kernel writes, and its copy of dstCap; grow-only */
+    uint8_t *d_dpick = nullptr; size_t d_dpick_cap = 0;
+};
+
+/* k4lz4_dict_set: one device allocation that nothing writes after create.  Carved at 64-byte steps in this order:
+ * the kept bytes of every distinct dictionary; the entries' words for the decoders; per family the words and tables its load and
+ * encode kernels take.  The host keeps what the queries and the argument checks need. */
+struct k4lz4_dict_set {
+    struct Family {
+        bool on = false;
+        uint64_t *toff = nullptr, *eoff = nullptr;          /* device: per table / per entry, where the kept bytes start in buf */
+        uint32_t *tlen = nullptr, *elen = nullptr, *etab = nullptr;
+        uint8_t *tables = nullptr;
+        std::vector<uint32_t> table, kept;                  /* host, per entry */
+        int64_t ntables = 0, loads = 0;
+    };
+    int device = -1;
+    int32_t nDict = 0;
+    int families = 0;
+    uint8_t *buf = nullptr;
+    uint64_t bytes = 0;
+    uint64_t *dec_off = nullptr;                            /* device, per entry: the kept bytes for the decoders */
+    int32_t *dec_len = nullptr;
+    std::vector<uint64_t> keptAt;                           /* host, per entry */
+    std::vector<int32_t> keptLen;
+    Family fast, hc;
 };
 
 /* a few helper threads for the staging copies of big host-pointer calls (memcpy between the caller's pageable memory and
@@ -2660,6 +2687,7 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_dhc) (void)hipFree(ctx->d_dhc);
     if (ctx->ev_dhc) (void)hipEventDestroy(ctx->ev_dhc);
     if (ctx->d_pk_meta) (void)hipFree(ctx->d_pk_meta);
+    if (ctx->d_dpick) (void)hipFree(ctx->d_dpick);
     delete ctx;
 }
 
@@ -3230,6 +3258,368 @@ int k4lz4_encode_dict_hc_state(k4lz4_ctx *ctx, int32_t d, uint32_t *hashTable, u
     K4_HIP(ctx, hipMemcpy(chainTable, t + (size_t)k4::DHC_HEADS * 4, (size_t)k4::DHC_CHAIN * 2, hipMemcpyDeviceToHost));
     *keptLen = (int32_t)ctx->dhc_kept[(size_t)d];
     return K4LZ4_OK;
+}
+
+/* ---- k4lz4_dict_set (k4lz4_dict_set.hpp) ---------------------------------------------------------------------
+ * Which bytes are kept is dict_hc_list's rule (the last 64 KiB of every length down to one byte: the decoders need them whatever the
+ * families), and that list is the HC family's; dict_list is the fast family's (below 8 bytes: the empty table, dictSize 0).  Every
+ * distinct kept range gets a region of the set's memory at the next 64-byte step. */
+struct DictSetPlan {
+    DictList bytes, fast;
+    std::vector<uint64_t> regionAt;        /* per distinct kept range (= per HC table) */
+    uint64_t total = 0;
+};
+
+static void dict_set_carve(Carve &c, const DictSetPlan &p, size_t nd, int families, k4lz4_dict_set &s, std::vector<uint64_t> &regionAt)
+{
+    uint8_t *b;
+    regionAt.assign(p.bytes.rep.size(), 0);
+    for (size_t t = 0; t < p.bytes.rep.size(); t++) { regionAt[t] = c.at; c.take(b, (size_t)p.bytes.keptLen[p.bytes.rep[t]]); }
+    c.take(b, 64);                                                        /* nothing lies right behind the last dictionary byte */
+    c.take(s.dec_off, nd); c.take(s.dec_len, nd);
+    auto family = [&](k4lz4_dict_set::Family &f, size_t nt, size_t table_bytes) {
+        c.take(f.toff, nt); c.take(f.tlen, nt); c.take(f.eoff, nd); c.take(f.elen, nd); c.take(f.etab, nd);
+        c.take(f.tables, nt * table_bytes);
+    };
+    if (families & K4LZ4_DICT_FAST) family(s.fast, std::max<size_t>(p.fast.rep.size(), 1), 4096u * 4u);
+    if (families & K4LZ4_DICT_HC) family(s.hc, std::max<size_t>(p.bytes.rep.size(), 1), (size_t)k4::DHC_TABLE_BYTES);
+}
+
+static int dict_set_plan(k4lz4_ctx *ctx, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, int families, DictSetPlan &p)
+{
+    if (families == 0 || (families & ~(K4LZ4_DICT_FAST | K4LZ4_DICT_HC)))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_dict_set: families is a mask of K4LZ4_DICT_FAST and K4LZ4_DICT_HC, at least one of them");
+    if (nDict < 0 || (nDict > 0 && (!dictOff || !dictLen))) return fail(ctx, K4LZ4_E_ARG, "k4lz4_dict_set: bad dictionary list");
+    for (int32_t d = 0; d < nDict; d++)
+        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_dict_set: negative dictLen");
+    int rc;
+    try {
+        if ((rc = dict_hc_list(ctx, dictOff, dictLen, nDict, nullptr, p.bytes)) != K4LZ4_OK) return rc;
+        if ((families & K4LZ4_DICT_FAST) && (rc = dict_list(ctx, dictOff, dictLen, nDict, nullptr, p.fast)) != K4LZ4_OK) return rc;
+        Carve m{nullptr};
+        k4lz4_dict_set measure;
+        dict_set_carve(m, p, (size_t)nDict, families, measure, p.regionAt);
+        p.total = m.at;
+    } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    return K4LZ4_OK;
+}
+
+int k4lz4_dict_set_layout(const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, int families, int32_t *keptLen, uint64_t *keptAt,
+                          int32_t *tableFast, int32_t *tableHc, uint64_t *bytes)
+{
+    DictSetPlan p;
+    const int rc = dict_set_plan(nullptr, dictOff, dictLen, nDict, families, p);
+    if (rc != K4LZ4_OK) return rc;
+    for (int32_t d = 0; d < nDict; d++) {
+        if (keptLen) keptLen[d] = (int32_t)p.bytes.keptLen[(size_t)d];
+        if (keptAt) keptAt[d] = p.regionAt[p.bytes.table[(size_t)d]];
+        if (tableFast) tableFast[d] = (families & K4LZ4_DICT_FAST) ? (int32_t)p.fast.table[(size_t)d] : -1;
+        if (tableHc) tableHc[d] = (families & K4LZ4_DICT_HC) ? (int32_t)p.bytes.table[(size_t)d] : -1;
+    }
+    if (bytes) *bytes = p.total;
+    return K4LZ4_OK;
+}
+
+void k4lz4_dict_set_destroy(k4lz4_dict_set *set)
+{
+    if (!set) return;
+    /* calls that read the set may still run on any stream of its device: they are waited for */
+    if (set->buf && hipSetDevice(set->device) == hipSuccess) { (void)hipDeviceSynchronize(); (void)hipFree(set->buf); }
+    (void)hipGetLastError();
+    delete set;
+}
+
+/* dict: a host pointer, or a device pointer that is valid once st reaches this point */
+static int dict_set_create(k4lz4_ctx *ctx, const uint8_t *dict, bool on_device, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict,
+                           int families, k4lz4_dict_set **out, hipStream_t st)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (!out) return fail(ctx, K4LZ4_E_ARG, "k4lz4_dict_set_create: NULL result pointer");
+    *out = nullptr;
+    DictSetPlan p;
+    int rc = dict_set_plan(ctx, dictOff, dictLen, nDict, families, p);
+    if (rc != K4LZ4_OK) return rc;
+    for (int32_t d = 0; d < nDict; d++)
+        if (dictLen[d] > 0 && !dict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_dict_set_create: NULL dictionary buffer");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    struct Deleter { void operator()(k4lz4_dict_set *s) const { k4lz4_dict_set_destroy(s); } };
+    std::unique_ptr<k4lz4_dict_set, Deleter> s(new (std::nothrow) k4lz4_dict_set);
+    if (!s) return fail(ctx, K4LZ4_E_NOMEM, "out of host memory");
+    const size_t nd = (size_t)nDict;
+    std::vector<uint64_t> dec_off, w_toff[2], w_eoff[2];
+    std::vector<int32_t> dec_len;
+    std::vector<uint32_t> w_tlen[2], w_elen[2], w_etab[2];
+    try {
+        s->device = ctx->device; s->nDict = nDict; s->families = families; s->bytes = p.total;
+        s->keptAt.resize(nd); s->keptLen.resize(nd);
+        for (size_t d = 0; d < nd; d++) { s->keptAt[d] = p.regionAt[p.bytes.table[d]]; s->keptLen[d] = (int32_t)p.bytes.keptLen[d]; }
+        dec_off = s->keptAt; dec_len = s->keptLen;
+        for (int k = 0; k < 2; k++) {
+            if (!(families & (k ? K4LZ4_DICT_HC : K4LZ4_DICT_FAST))) continue;
+            const DictList &l = k ? p.bytes : p.fast;
+            k4lz4_dict_set::Family &f = k ? s->hc : s->fast;
+            f.on = true; f.table = l.table; f.kept = l.keptLen; f.ntables = (int64_t)std::max<size_t>(l.rep.size(), 1);
+            w_toff[k].assign((size_t)f.ntables, 0); w_tlen[k].assign((size_t)f.ntables, 0);     /* an empty list: one empty table */
+            w_eoff[k].assign(nd, 0); w_elen[k].assign(nd, 0); w_etab[k].assign(nd, 0);
+            for (size_t d = 0; d < nd; d++) {
+                w_elen[k][d] = l.keptLen[d]; w_etab[k][d] = l.table[d];
+                w_eoff[k][d] = l.keptLen[d] ? s->keptAt[d] : 0;
+            }
+            for (size_t t = 0; t < l.rep.size(); t++) { w_toff[k][t] = w_eoff[k][l.rep[t]]; w_tlen[k][t] = l.keptLen[l.rep[t]]; }
+        }
+    } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    if (hipMalloc((void **)&s->buf, (size_t)p.total) != hipSuccess) { (void)hipGetLastError(); s->buf = nullptr; return fail(ctx, K4LZ4_E_NOMEM, "out of device memory"); }
+    Carve cv{s->buf};
+    std::vector<uint64_t> at;
+    dict_set_carve(cv, p, nd, families, *s, at);
+    for (size_t t = 0; t < p.bytes.rep.size(); t++) {
+        const uint32_t d = p.bytes.rep[t];
+        if (p.bytes.keptLen[d])
+            K4_HIP(ctx, hipMemcpyAsync(s->buf + at[t], dict + p.bytes.keptOff[d], (size_t)p.bytes.keptLen[d],
+                                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    }
+    auto up = [&](void *dev, const void *host, size_t bytes) {
+        return bytes ? hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+    };
+    K4_HIP(ctx, up(s->dec_off, dec_off.data(), nd * 8));
+    K4_HIP(ctx, up(s->dec_len, dec_len.data(), nd * 4));
+    for (int k = 0; k < 2; k++) {
+        k4lz4_dict_set::Family &f = k ? s->hc : s->fast;
+        if (!f.on) continue;
+        const size_t nt = (size_t)f.ntables;
+        K4_HIP(ctx, up(f.toff, w_toff[k].data(), nt * 8));
+        K4_HIP(ctx, up(f.tlen, w_tlen[k].data(), nt * 4));
+        K4_HIP(ctx, up(f.eoff, w_eoff[k].data(), nd * 8));
+        K4_HIP(ctx, up(f.elen, w_elen[k].data(), nd * 4));
+        K4_HIP(ctx, up(f.etab, w_etab[k].data(), nd * 4));
+        if (k) hipLaunchKernelGGL(k4::k4_dict_hc_load_kernel, dim3((unsigned)nt), dim3(k4::DHC_LOAD_THREADS), 0, st, k4::DictHcLoadArgs{s->buf, f.toff, f.tlen, f.tables});
+        else hipLaunchKernelGGL(k4::k4_dict_load_kernel, dim3((unsigned)nt), dim3(k4::DICT_LOAD_THREADS), 0, st, k4::DictLoadArgs{s->buf, f.toff, f.tlen, (uint32_t *)f.tables});
+        if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(st); return fail(ctx, K4LZ4_E_HIP, "k4lz4_dict_set_create: kernel launch failed"); }
+        f.loads++;
+    }
+    K4_HIP(ctx, hipStreamSynchronize(st));                               /* the host words above and the caller's bytes are free again */
+    *out = s.release();
+    return K4LZ4_OK;
+}
+
+int k4lz4_dict_set_create(k4lz4_ctx *ctx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, int families,
+                          k4lz4_dict_set **set)
+{
+    return dict_set_create(ctx, dict, false, dictOff, dictLen, nDict, families, set, ctx ? ctx->stream : nullptr);
+}
+
+int k4lz4_dict_set_create_device(k4lz4_ctx *ctx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict,
+                                 int families, k4lz4_dict_set **set, void *stream)
+{
+    return dict_set_create(ctx, dict, true, dictOff, dictLen, nDict, families, set, (hipStream_t)stream);
+}
+
+int k4lz4_dict_set_info(const k4lz4_dict_set *set, int64_t out[8])
+{
+    if (!set || !out) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_dict_set_info: NULL argument");
+    out[0] = set->nDict; out[1] = set->fast.ntables; out[2] = set->hc.ntables; out[3] = (int64_t)set->bytes;
+    out[4] = set->families; out[5] = set->device; out[6] = set->fast.loads; out[7] = set->hc.loads;
+    return K4LZ4_OK;
+}
+
+int k4lz4_dict_set_state(const k4lz4_dict_set *set, int32_t d, k4lz4_fast_chain_state *out)
+{
+    if (!set || !out || d < 0 || d >= set->nDict || !set->fast.on)
+        return fail(nullptr, K4LZ4_E_ARG, "k4lz4_dict_set_state: no such dictionary, or a set without K4LZ4_DICT_FAST");
+    K4_HIP(nullptr, hipSetDevice(set->device));
+    K4_HIP(nullptr, hipMemcpy(out->hashTable, set->fast.tables + 16384ull * set->fast.table[(size_t)d], sizeof out->hashTable, hipMemcpyDeviceToHost));
+    out->currentOffset = k4::DICT_START;
+    out->dictSize = set->fast.kept[(size_t)d];
+    out->reserved[0] = out->reserved[1] = 0;
+    return K4LZ4_OK;
+}
+
+int k4lz4_dict_set_hc_state(const k4lz4_dict_set *set, int32_t d, uint32_t *hashTable, uint16_t *chainTable, int32_t *keptLen)
+{
+    if (!set || !hashTable || !chainTable || !keptLen || d < 0 || d >= set->nDict || !set->hc.on)
+        return fail(nullptr, K4LZ4_E_ARG, "k4lz4_dict_set_hc_state: no such dictionary, or a set without K4LZ4_DICT_HC");
+    K4_HIP(nullptr, hipSetDevice(set->device));
+    const uint8_t *t = set->hc.tables + (size_t)k4::DHC_TABLE_BYTES * set->hc.table[(size_t)d];
+    K4_HIP(nullptr, hipMemcpy(hashTable, t, (size_t)k4::DHC_HEADS * 4, hipMemcpyDeviceToHost));
+    K4_HIP(nullptr, hipMemcpy(chainTable, t + (size_t)k4::DHC_HEADS * 4, (size_t)k4::DHC_CHAIN * 2, hipMemcpyDeviceToHost));
+    *keptLen = (int32_t)set->hc.kept[(size_t)d];
+    return K4LZ4_OK;
+}
+
+static int dictset_encode_args(k4lz4_ctx *ctx, const void *src, const void *srcOff, const void *srcLen, const void *dst, const void *dstOff,
+                               const void *dstCap, const void *outLen, int64_t n, int level, int flags, const void *dictIdx, const k4lz4_dict_set *set)
+{
+    int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
+    if (rc != K4LZ4_OK) return rc;
+    if (!set) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: set is NULL");
+    if (level >= K4LZ4_L10_OPT)
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: levels 10 - 12 with a dictionary are not supported (no sound witness for the optimal parser in this mode)");
+    if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: the 32-bit engine (LZ4Codec.Enforce32) is not supported");
+    if (flags) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: it takes no flags");
+    if (!(level >= K4LZ4_L03_HC ? set->hc.on : set->fast.on))
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: the set was created without this level's family (K4LZ4_DICT_FAST below level 3, K4LZ4_DICT_HC from there)");
+    if (set->device != ctx->device) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: the set lives on another device than the context");
+    if (n > 0 && !dictIdx) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: NULL dictIdx");
+    if (n > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: more than 2^32 - 1 messages");
+    return K4LZ4_OK;
+}
+
+/* all pointers are device pointers; order and encode on `stream` -- no list words go up, no table is built, neither ev_denc nor ev_dhc
+ * is waited for.  The context's scratch (d_denc below level 3, d_dhc from there) carries the ticket and histogram words, cost and
+ * order and the HC wave slots, laid out for this call: what the per-call calls left there for their state queries is gone. */
+static int dictset_encode_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst, const uint64_t *dstOff,
+                              const int32_t *dstCap, int32_t *outLen, int64_t n, int level, const int32_t *dictIdx, const k4lz4_dict_set *set,
+                              hipStream_t stream)
+{
+    if (n == 0) return K4LZ4_OK;
+    const bool hc = level >= K4LZ4_L03_HC;
+    const k4lz4_dict_set::Family &f = hc ? set->hc : set->fast;
+    const int64_t wgs = hc ? std::min<int64_t>((n + k4::DHC_WAVES_PER_WG - 1) / k4::DHC_WAVES_PER_WG, (int64_t)ctx->cu_count * DHC_WGS_PER_CU)
+                           : std::min<int64_t>((n + k4::FAST_CHAIN_WAVES_PER_WG - 1) / k4::FAST_CHAIN_WAVES_PER_WG, ctx->cu_count);
+    const size_t nslots = hc ? (size_t)wgs * k4::DHC_WAVES_PER_WG : 0;
+    uint32_t *head, *cost, *order;
+    uint8_t *slots;
+    auto layout = [&](Carve &cv) {
+        cv.take(head, DHC_HEAD_WORDS); cv.take(cost, (size_t)n); cv.take(order, (size_t)n); cv.take(slots, nslots * (size_t)k4::DHC_TABLE_BYTES);
+    };
+    static_assert(DHC_HEAD_WORDS == 64 + 2 * k4::COST_BUCKETS + 16, "both families' ticket and histogram words");
+    Carve m{nullptr};
+    layout(m);
+    uint8_t **scratch = hc ? &ctx->d_dhc : &ctx->d_denc;
+    int rc;
+    if ((rc = grow_scratch(ctx, scratch, hc ? &ctx->d_dhc_cap : &ctx->d_denc_cap, m.at + 64)) != K4LZ4_OK) return rc;
+    Carve dv{*scratch};
+    layout(dv);
+    if (hc) { ctx->dhc_table.clear(); ctx->dhc_kept.clear(); } else { ctx->denc_table.clear(); ctx->denc_kept.clear(); }
+    K4_HIP(ctx, order_after_ctx(ctx, stream));
+    K4_HIP(ctx, hipMemsetAsync(head, 0, DHC_HEAD_WORDS * 4, stream));
+    /* the wave slots' heads start at zero (a wave leaves them so behind every message); the chain halves are written before they are read */
+    if (hc) K4_HIP(ctx, hipMemsetAsync(slots, 0, nslots * (size_t)k4::DHC_TABLE_BYTES, stream));
+    k4::BatchArgs o{};
+    o.srcLen = srcLen; o.n = n; o.cost = cost; o.hist = head + 64; o.order_out = order;
+    const unsigned g256 = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(k4::k4_dict_cost_kernel, dim3(g256), dim3(256), 0, stream, o);
+    hipLaunchKernelGGL(k4::k4_order_kernel, dim3(g256), dim3(256), 0, stream, o, 0xffffffffu);
+    if (hc) {
+        k4::DictHcEncArgs a{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, dictIdx, set->buf, f.eoff, f.elen, f.etab, f.tables, slots, order, head,
+                            ctx->d_status, n, (int)set->nDict, level};
+        hipLaunchKernelGGL(k4::k4_dict_hc_encode_kernel, dim3((unsigned)wgs), dim3(64 * k4::DHC_WAVES_PER_WG), 0, stream, a);
+    } else {
+        k4::DictEncArgs a{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, dictIdx, set->buf, f.eoff, f.elen, f.etab, (const uint32_t *)f.tables, order, head,
+                          ctx->d_status, n, (int)set->nDict};
+        hipLaunchKernelGGL(k4::k4_dict_encode_kernel, dim3((unsigned)wgs), dim3(64 * k4::FAST_CHAIN_WAVES_PER_WG), 0, stream, a);
+    }
+    rc = hipGetLastError() != hipSuccess ? fail(ctx, K4LZ4_E_HIP, "k4lz4_encode_dictset_batch: kernel launch failed") : K4LZ4_OK;
+    mark_busy(ctx, stream);
+    return rc;
+}
+
+int k4lz4_encode_dictset_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                                      const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+                                      const int32_t *dictIdx, const k4lz4_dict_set *set, void *stream)
+{
+    const int rc = dictset_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, set);
+    if (rc != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    return dictset_encode_run(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, dictIdx, set, (hipStream_t)stream);
+}
+
+int k4lz4_encode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                               const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+                               const int32_t *dictIdx, const k4lz4_dict_set *set)
+{
+    int rc = dictset_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, set);
+    if (rc != K4LZ4_OK) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (dictIdx[i] < 0 || dictIdx[i] >= set->nDict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: a dictIdx outside the dictionary list");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);                                                     /* the messages only: no dictionary byte goes up */
+    s.span(src, srcOff, n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(srcLen[i], 0); });
+    s.slots(n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(dstCap[i], 0); }, false);
+    uint64_t *d_off, *d_doff;
+    int32_t *d_len, *d_cap, *d_out, *d_idx;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, srcLen); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_cap, n, dstCap);
+    s.meta(&d_idx, n, dictIdx); s.meta(&d_out, n);
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = dictset_encode_run(ctx, ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, n, level, d_idx, set, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
+                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
+}
+
+static int dictset_decode_args(k4lz4_ctx *ctx, const void *src, const void *srcOff, const void *srcLen, const void *dst, const void *dstOff,
+                               const void *dstCap, const void *outLen, int64_t n, const void *dictIdx, const k4lz4_dict_set *set)
+{
+    const int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
+    if (rc != K4LZ4_OK) return rc;
+    if (!set) return fail(ctx, K4LZ4_E_ARG, "k4lz4_decode_dictset_batch: set is NULL");
+    if (set->device != ctx->device) return fail(ctx, K4LZ4_E_ARG, "k4lz4_decode_dictset_batch: the set lives on another device than the context");
+    if (n > 0 && !dictIdx) return fail(ctx, K4LZ4_E_ARG, "k4lz4_decode_dictset_batch: NULL dictIdx");
+    return K4LZ4_OK;
+}
+
+int k4lz4_decode_dictset_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                                      const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int flags,
+                                      const int32_t *dictIdx, const k4lz4_dict_set *set, void *stream)
+{
+    int rc = dictset_decode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx, set);
+    if (rc != K4LZ4_OK || n == 0) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    k4::DictPickArgs a{};
+    auto layout = [&](Carve &cv) { cv.take(a.dictOff, (size_t)n); cv.take(a.dictLen, (size_t)n); cv.take(a.cap, (size_t)n); cv.take(a.dictMode, (size_t)n); };
+    Carve m{nullptr};
+    layout(m);
+    if ((rc = grow_scratch(ctx, &ctx->d_dpick, &ctx->d_dpick_cap, m.at + 64)) != K4LZ4_OK) return rc;
+    Carve dv{ctx->d_dpick};
+    layout(dv);
+    a.dictIdx = dictIdx; a.entryOff = set->dec_off; a.entryLen = set->dec_len; a.dstCap = dstCap; a.outLen = outLen; a.status = ctx->d_status;
+    a.n = n; a.nDict = set->nDict; a.phase = 0;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (grid.x == 0 || n > 0x7fffffffll * 256) return fail(ctx, K4LZ4_E_ARG, "k4lz4_decode_dictset_batch: too many messages");
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    hipLaunchKernelGGL(k4::k4_dict_pick_kernel, grid, dim3(256), 0, st, a);
+    mark_busy(ctx, st);
+    const DictArgs dd{set->buf, a.dictOff, a.dictLen, a.dictMode};
+    rc = launch(ctx, KIND_DECODE, src, srcOff, srcLen, dst, dstOff, a.cap, outLen, n, 0, flags, st, &dd);
+    a.phase = 1;
+    hipLaunchKernelGGL(k4::k4_dict_pick_kernel, grid, dim3(256), 0, st, a);
+    if (hipGetLastError() != hipSuccess && rc == K4LZ4_OK) rc = fail(ctx, K4LZ4_E_HIP, "k4lz4_decode_dictset_batch: kernel launch failed");
+    mark_busy(ctx, st);
+    return rc;
+}
+
+int k4lz4_decode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                               const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int flags, const int32_t *dictIdx,
+                               const k4lz4_dict_set *set)
+{
+    int rc = dictset_decode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx, set);
+    if (rc != K4LZ4_OK) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (dictIdx[i] < -1 || dictIdx[i] >= set->nDict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_decode_dictset_batch: a dictIdx outside the dictionary list");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    /* the pick kernel's arithmetic, on the host; the dictionaries are where they have been since create */
+    std::vector<uint64_t> h_off((size_t)n, 0);
+    std::vector<int32_t> h_len((size_t)n, 0);
+    std::vector<signed char> h_mode((size_t)n, 2);
+    for (int64_t i = 0; i < n; i++)
+        if (dictIdx[i] >= 0) { h_off[(size_t)i] = set->keptAt[(size_t)dictIdx[i]]; h_len[(size_t)i] = set->keptLen[(size_t)dictIdx[i]]; }
+    HostStage s(ctx);
+    s.span(src, srcOff, n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(srcLen[i], 0); });
+    s.slots(n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(dstCap[i], 0); }, true);
+    uint64_t *d_off, *d_doff, *d_dictoff;
+    int32_t *d_len, *d_cap, *d_out, *d_dictlen;
+    signed char *d_mode;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, srcLen); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_cap, n, dstCap);
+    s.meta(&d_dictoff, n, h_off.data()); s.meta(&d_dictlen, n, h_len.data()); s.meta(&d_mode, n, h_mode.data()); s.meta(&d_out, n);
+    if ((rc = s.upload()) != K4LZ4_OK) return rc;
+    const DictArgs dd{set->buf, d_dictoff, d_dictlen, d_mode};
+    if ((rc = launch(ctx, KIND_DECODE, ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, n, 0, flags, s.st, &dd)) != K4LZ4_OK) return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
+                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
 }
 
 int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,

@@ -110,6 +110,22 @@ class DeviceCodec:
         return self._call(fn, src, dst, out_len, int(level), flags, _dp(dict_idx), _dp(dictionaries),
                           doff.ctypes.data if doff.size else None, dlen.ctypes.data if dlen.size else None, int(doff.size))
 
+    def encode_dictset(self, src: DeviceBatch, dst: DeviceBatch, dict_idx: torch.Tensor, dictionaries, out_len: Optional[torch.Tensor] = None,
+                       level: LZ4Level = LZ4Level.L00_FAST, flags: int = 0) -> torch.Tensor:
+        """encode_dict with the list being a codec.DictionarySet (k4lz4_encode_dictset_batch_device): the same blocks, and nothing is
+        loaded per call -- the cost, order and encode kernels run on the set's memory"""
+        out_len = self.new_out_len(src.n) if out_len is None else out_len
+        assert dict_idx.numel() == src.n and dict_idx.dtype == torch.int32
+        return self._call(self.lib.k4lz4_encode_dictset_batch_device, src, dst, out_len, int(level), flags, _dp(dict_idx), dictionaries.handle)
+
+    def decode_dictset(self, src: DeviceBatch, dst: DeviceBatch, dict_idx: torch.Tensor, dictionaries, out_len: Optional[torch.Tensor] = None,
+                       flags: int = 0) -> torch.Tensor:
+        """block i decoded against entry dict_idx[i] (device int32 tensor; -1: no dictionary) of a codec.DictionarySet
+        (k4lz4_decode_dictset_batch_device)"""
+        out_len = self.new_out_len(src.n) if out_len is None else out_len
+        assert dict_idx.numel() == src.n and dict_idx.dtype == torch.int32
+        return self._call(self.lib.k4lz4_decode_dictset_batch_device, src, dst, out_len, flags, _dp(dict_idx), dictionaries.handle)
+
     def dict_hc_state(self, d: int):
         """what LZ4_loadDictHC left for entry d of the most recent encode_dict call's list at an HC level (k4lz4_encode_dict_hc_state):
         (hashTable: 32768 x uint32, chainTable: 65536 x uint16, kept length).  Waits for that call."""
