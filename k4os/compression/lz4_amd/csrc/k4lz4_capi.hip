@@ -160,19 +160,18 @@ struct k4lz4_ctx {
     std::vector<uint8_t> h_fw;
     uint8_t *d_fw = nullptr; size_t d_fw_cap = 0;
     hipEvent_t ev_fw = nullptr;
-    /* messages against shared dictionaries (k4lz4_dict_encode.hpp): the prepared tables (16 KiB per distinct dictionary), the list's
-     * per-entry words and the dispatch order, grow-only; the host copy of the words as h_chain's; and which table and what dictSize
-     * the most recent call gave every entry of its list (k4lz4_encode_dict_state) */
-    std::vector<uint8_t> h_denc;
-    uint8_t *d_denc = nullptr; size_t d_denc_cap = 0;
-    hipEvent_t ev_denc = nullptr;
-    std::vector<uint32_t> denc_table, denc_kept;
-    /* the same at the hash-chain levels (k4lz4_dict_encode_hc.hpp): the tables of the distinct dictionaries (256 KiB each), the list's
-     * words, the dispatch order and the wave slots' tables (256 KiB per wave of the encode launch), grow-only */
-    std::vector<uint8_t> h_dhc;
-    uint8_t *d_dhc = nullptr; size_t d_dhc_cap = 0;
-    hipEvent_t ev_dhc = nullptr;
-    std::vector<uint32_t> dhc_table, dhc_kept;
+    /* messages against shared dictionaries, per family of levels (fast: k4lz4_dict_encode.hpp, 16 KiB of tables per distinct
+     * dictionary; HC: k4lz4_dict_encode_hc.hpp, 256 KiB each and as much per wave of the encode launch).  dev: the tables, the
+     * list's words, the dispatch order and the wave slots, grow-only (dict_layout); host: the copy of the words that goes up,
+     * rewritten only after ev says the previous upload is over; table, kept: which table and what kept length the most recent
+     * call gave every entry of its list (the state queries) -- empty after a call against a k4lz4_dict_set.  The families share
+     * nothing: neither disturbs what the other left for its query. */
+    struct DictScratch {
+        std::vector<uint8_t> host;
+        uint8_t *dev = nullptr; size_t cap = 0;
+        hipEvent_t ev = nullptr;
+        std::vector<uint32_t> table, kept;
+    } dict_fast, dict_hc;
     /* k4lz4_decode_dictset_batch_device: the per-message dictionary words k4_dict_pick_kernel writes, and its copy of dstCap; grow-only */
     uint8_t *d_dpick = nullptr; size_t d_dpick_cap = 0;
 };
@@ -2087,228 +2086,310 @@ struct Carve {
     }
 };
 
-/* ---- messages against shared dictionaries (k4lz4_encode_dict_batch, k4lz4_dict_encode.hpp) ------------------------------------
- * The list's entries that keep the same bytes (same kept start, same kept length; every dictionary of fewer than 8 bytes is the
- * empty one) share one table.  used: which entries the messages refer to (the host form knows), or nullptr: all of them. */
+/* the end of a host form whose items are blocks in slots of dstCap bytes: outLen comes down, and of every slot the outLen bytes
+ * if they fit */
+int finish_blocks(HostStage &s, int32_t *outLen, const int32_t *d_out, int64_t n, uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap)
+{
+    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
+                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
+}
+
+/* ---- messages against shared dictionaries: k4lz4_encode_dict_batch below level 3 (k4lz4_dict_encode.hpp),
+ * k4lz4_encode_dict_hc_batch at levels 3 - 9 (k4lz4_dict_encode_hc.hpp), k4lz4_encode_dictset_batch at both against a
+ * k4lz4_dict_set (k4lz4_dict_set.hpp); each in a host form and a device form.  They are one path: what differs between the two
+ * families of levels stands in DictFamily, and a call's own list differs from a set in where dict_encode_run takes the tables
+ * and the entries' words from. */
 struct DictList {
     std::vector<uint64_t> keptOff;            /* per entry */
     std::vector<uint32_t> keptLen, table;
     std::vector<uint32_t> rep;                /* per table: an entry that has it */
 };
 
-int dict_list(k4lz4_ctx *ctx, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, const uint8_t *used, DictList &l)
-{
-    l.keptOff.assign((size_t)nDict, 0); l.keptLen.assign((size_t)nDict, 0); l.table.assign((size_t)nDict, 0xffffffffu); l.rep.clear();
-    std::map<std::pair<uint64_t, uint32_t>, uint32_t> seen;
-    for (int32_t d = 0; d < nDict; d++) {
-        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: negative dictLen");
-        if (used && !used[d]) continue;
-        const uint32_t len = (uint32_t)dictLen[d];
-        if (len >= 8u) {                                                  /* LZ4_loadDict: below HASH_UNIT nothing is kept */
-            l.keptLen[(size_t)d] = std::min<uint32_t>(len, 65536u);
-            l.keptOff[(size_t)d] = dictOff[d] + (len - l.keptLen[(size_t)d]);
-        }
-        const auto key = std::make_pair(l.keptOff[(size_t)d], l.keptLen[(size_t)d]);
-        auto it = seen.find(key);
-        if (it == seen.end()) { it = seen.emplace(key, (uint32_t)l.rep.size()).first; l.rep.push_back((uint32_t)d); }
-        l.table[(size_t)d] = it->second;
-    }
-    return K4LZ4_OK;
-}
+/* a call's messages, output slots and indices: the caller's pointers, or in the run device pointers */
+struct DictBatch {
+    const uint8_t *src; const uint64_t *srcOff; const int32_t *srcLen;
+    uint8_t *dst; const uint64_t *dstOff; const int32_t *dstCap;
+    int32_t *outLen; int64_t n; const int32_t *dictIdx;
+};
 
-int dict_encode_flags(k4lz4_ctx *ctx, int level, int flags)
-{
-    if (level >= K4LZ4_L03_HC) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: HC levels with a dictionary are not supported");
-    if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
-        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: the 32-bit engine's LZ4_loadDict (LZ4Codec.Enforce32) is not supported");
-    if (flags) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: it takes no flags");
-    return K4LZ4_OK;
-}
+/* where a call's dictionaries come from: a set, or its own list (dict: the buffer the list's offsets refer to) */
+struct DictSource {
+    bool of_set;
+    const k4lz4_dict_set *set;
+    const uint8_t *dict; const uint64_t *dictOff; const int32_t *dictLen; int32_t nDict;
+};
 
-/* all pointers but the list are device pointers; load, order, encode on `stream` */
-int dict_encode_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst, const uint64_t *dstOff,
-                    const int32_t *dstCap, int32_t *outLen, int64_t n, const int32_t *dictIdx, const uint8_t *dict, const DictList &l,
-                    hipStream_t stream)
-{
-    if (n > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: more than 2^32 - 1 messages");
-    const size_t nd = l.table.size(), nt = std::max<size_t>(l.rep.size(), 1);
-    if (!ctx->ev_denc) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_denc, hipEventDisableTiming));
-    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_denc));            /* the previous upload of the host words is over */
-    /* layout: [ticket, hist: 64 + 2 * COST_BUCKETS words] [tables] [per table: keptOff, keptLen] [per entry: keptOff, keptLen, table]
-     * [cost[n], order[n]]; the part that goes up from the host is the one between the tables and cost[] */
-    Carve m{nullptr};
-    auto layout = [&](Carve &cv, uint32_t *&head, uint32_t *&tables, uint64_t *&toff, uint32_t *&tlen, uint64_t *&eoff, uint32_t *&elen,
-                      uint32_t *&etab, uint32_t *&cost, uint32_t *&order) {
-        cv.take(head, 64 + 2 * k4::COST_BUCKETS + 16); cv.take(tables, nt * 4096);
-        cv.take(toff, nt); cv.take(tlen, nt); cv.take(eoff, nd); cv.take(elen, nd); cv.take(etab, nd);
-        cv.take(cost, (size_t)n); cv.take(order, (size_t)n);
-    };
-    uint32_t *head, *tables, *tlen, *elen, *etab, *cost, *order;
-    uint64_t *toff, *eoff;
-    layout(m, head, tables, toff, tlen, eoff, elen, etab, cost, order);
-    int rc;
-    if ((rc = grow_scratch(ctx, &ctx->d_denc, &ctx->d_denc_cap, m.at + 64)) != K4LZ4_OK) return rc;
-    Carve dv{ctx->d_denc};
-    layout(dv, head, tables, toff, tlen, eoff, elen, etab, cost, order);
-    const size_t up_at = (size_t)((uint8_t *)toff - ctx->d_denc), up_bytes = (size_t)((uint8_t *)cost - (uint8_t *)toff);
-    try { ctx->h_denc.assign(up_bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
-    {
-        uint8_t *h = ctx->h_denc.data() - up_at;                          /* host image of the same layout */
-        uint64_t *h_toff = (uint64_t *)(h + ((uint8_t *)toff - ctx->d_denc)), *h_eoff = (uint64_t *)(h + ((uint8_t *)eoff - ctx->d_denc));
-        uint32_t *h_tlen = (uint32_t *)(h + ((uint8_t *)tlen - ctx->d_denc)), *h_elen = (uint32_t *)(h + ((uint8_t *)elen - ctx->d_denc)),
-                 *h_etab = (uint32_t *)(h + ((uint8_t *)etab - ctx->d_denc));
-        for (size_t t = 0; t < l.rep.size(); t++) { h_toff[t] = l.keptOff[l.rep[t]]; h_tlen[t] = l.keptLen[l.rep[t]]; }
-        for (size_t d = 0; d < nd; d++) { h_eoff[d] = l.keptOff[d]; h_elen[d] = l.keptLen[d]; h_etab[d] = l.table[d]; }
-    }
-    ctx->denc_table = l.table; ctx->denc_kept = l.keptLen;
-    K4_HIP(ctx, order_after_ctx(ctx, stream));
-    K4_HIP(ctx, hipMemcpyAsync(ctx->d_denc + up_at, ctx->h_denc.data(), up_bytes, hipMemcpyHostToDevice, stream));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_denc, stream));
-    K4_HIP(ctx, hipMemsetAsync(head, 0, (64 + 2 * k4::COST_BUCKETS + 16) * 4, stream));
-    hipLaunchKernelGGL(k4::k4_dict_load_kernel, dim3((unsigned)nt), dim3(k4::DICT_LOAD_THREADS), 0, stream, k4::DictLoadArgs{dict, toff, tlen, tables});
-    rc = K4LZ4_OK;
-    if (n > 0) {
-        k4::BatchArgs o{};
-        o.srcLen = srcLen; o.n = n; o.cost = cost; o.hist = head + 64; o.order_out = order;
-        const unsigned g256 = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(k4::k4_dict_cost_kernel, dim3(g256), dim3(256), 0, stream, o);
-        hipLaunchKernelGGL(k4::k4_order_kernel, dim3(g256), dim3(256), 0, stream, o, 0xffffffffu);
-        k4::DictEncArgs a{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, dictIdx, dict, eoff, elen, etab, tables, order, head, ctx->d_status, n, (int)nd};
-        const int64_t wgs = std::min<int64_t>((n + k4::FAST_CHAIN_WAVES_PER_WG - 1) / k4::FAST_CHAIN_WAVES_PER_WG, ctx->cu_count);
-        hipLaunchKernelGGL(k4::k4_dict_encode_kernel, dim3((unsigned)wgs), dim3(64 * k4::FAST_CHAIN_WAVES_PER_WG), 0, stream, a);
-    }
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, K4LZ4_E_HIP, "k4lz4_encode_dict_batch: kernel launch failed");
-    mark_busy(ctx, stream);
-    return rc;
-}
+/* a family's scratch (k4lz4_ctx::DictScratch::dev), at 64-byte steps in this order: [ticket, hist] [tables] [per table: keptOff,
+ * keptLen] [per entry: keptOff, keptLen, table] [cost[n], order[n]] [wave slots].  What goes up from the host lies between the
+ * tables and cost[].  A call against a set finds tables and words in the set: nt = nd = 0, and those parts take no room. */
+constexpr size_t DICT_HEAD_WORDS = 64 + 2 * k4::COST_BUCKETS + 16;
+struct DictLayout {
+    uint32_t *head;
+    uint8_t *tables;
+    uint64_t *toff; uint32_t *tlen; uint64_t *eoff; uint32_t *elen, *etab;
+    uint32_t *cost, *order;
+    uint8_t *slots;
+};
 
-/* ---- the same at the hash-chain levels (k4lz4_encode_dict_hc_batch, k4lz4_dict_encode_hc.hpp) ----------------
- * LZ4_loadDictHC keeps the last 64 KiB of a dictionary of any length, down to one byte: entries that keep the same bytes share one
- * pair of tables. */
-int dict_hc_list(k4lz4_ctx *ctx, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, const uint8_t *used, DictList &l)
-{
-    l.keptOff.assign((size_t)nDict, 0); l.keptLen.assign((size_t)nDict, 0); l.table.assign((size_t)nDict, 0xffffffffu); l.rep.clear();
-    std::map<std::pair<uint64_t, uint32_t>, uint32_t> seen;
-    for (int32_t d = 0; d < nDict; d++) {
-        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: negative dictLen");
-        if (used && !used[d]) continue;
-        const uint32_t len = (uint32_t)dictLen[d];
-        if (len > 0u) {
-            l.keptLen[(size_t)d] = std::min<uint32_t>(len, 65536u);
-            l.keptOff[(size_t)d] = dictOff[d] + (len - l.keptLen[(size_t)d]);
-        }
-        const auto key = std::make_pair(l.keptOff[(size_t)d], l.keptLen[(size_t)d]);
-        auto it = seen.find(key);
-        if (it == seen.end()) { it = seen.emplace(key, (uint32_t)l.rep.size()).first; l.rep.push_back((uint32_t)d); }
-        l.table[(size_t)d] = it->second;
-    }
-    return K4LZ4_OK;
-}
+/* what the encode kernels read of the dictionaries: the kept bytes' buffer, the entries' words, the tables */
+struct DictTables { const uint8_t *dict; const uint64_t *eoff; const uint32_t *elen, *etab; const uint8_t *tables; int nd; };
 
 constexpr int DHC_WGS_PER_CU = 2;      /* eight waves per CU: the wave slots' tables are 256 KiB each */
-constexpr size_t DHC_HEAD_WORDS = 64 + 2 * k4::COST_BUCKETS + 16;
 
-/* all pointers but the list are device pointers; load, order, encode on `stream` */
-int dict_hc_encode_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst, const uint64_t *dstOff,
-                       const int32_t *dstCap, int32_t *outLen, int64_t n, int level, const int32_t *dictIdx, const uint8_t *dict,
-                       const DictList &l, hipStream_t stream)
+void dict_fast_load(hipStream_t st, unsigned nt, const uint8_t *dict, const uint64_t *toff, const uint32_t *tlen, uint8_t *tables)
 {
-    if (n > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: more than 2^32 - 1 messages");
-    const size_t nd = l.table.size(), nt = std::max<size_t>(l.rep.size(), 1);
-    const int64_t wgs = std::min<int64_t>((n + k4::DHC_WAVES_PER_WG - 1) / k4::DHC_WAVES_PER_WG, (int64_t)ctx->cu_count * DHC_WGS_PER_CU);
-    const size_t nslots = (size_t)wgs * k4::DHC_WAVES_PER_WG;
-    if (!ctx->ev_dhc) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_dhc, hipEventDisableTiming));
-    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_dhc));             /* the previous upload of the host words is over */
-    /* layout: [ticket, hist] [tables] [per table: keptOff, keptLen] [per entry: keptOff, keptLen, table] [cost[n], order[n]] [slots];
-     * the part that goes up from the host is the one between the tables and cost[] */
-    uint32_t *head, *tlen, *elen, *etab, *cost, *order;
-    uint64_t *toff, *eoff;
-    uint8_t *tables, *slots;
-    auto layout = [&](Carve &cv) {
-        cv.take(head, DHC_HEAD_WORDS); cv.take(tables, nt * (size_t)k4::DHC_TABLE_BYTES);
-        cv.take(toff, nt); cv.take(tlen, nt); cv.take(eoff, nd); cv.take(elen, nd); cv.take(etab, nd);
-        cv.take(cost, (size_t)n); cv.take(order, (size_t)n); cv.take(slots, nslots * (size_t)k4::DHC_TABLE_BYTES);
-    };
-    Carve m{nullptr};
-    layout(m);
-    int rc;
-    if ((rc = grow_scratch(ctx, &ctx->d_dhc, &ctx->d_dhc_cap, m.at + 64)) != K4LZ4_OK) return rc;
-    Carve dv{ctx->d_dhc};
-    layout(dv);
-    const size_t up_at = (size_t)((uint8_t *)toff - ctx->d_dhc), up_bytes = (size_t)((uint8_t *)cost - (uint8_t *)toff);
-    try { ctx->h_dhc.assign(up_bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
-    {
-        uint8_t *h = ctx->h_dhc.data() - up_at;                           /* host image of the same layout */
-        uint64_t *h_toff = (uint64_t *)(h + ((uint8_t *)toff - ctx->d_dhc)), *h_eoff = (uint64_t *)(h + ((uint8_t *)eoff - ctx->d_dhc));
-        uint32_t *h_tlen = (uint32_t *)(h + ((uint8_t *)tlen - ctx->d_dhc)), *h_elen = (uint32_t *)(h + ((uint8_t *)elen - ctx->d_dhc)),
-                 *h_etab = (uint32_t *)(h + ((uint8_t *)etab - ctx->d_dhc));
-        for (size_t t = 0; t < l.rep.size(); t++) { h_toff[t] = l.keptOff[l.rep[t]]; h_tlen[t] = l.keptLen[l.rep[t]]; }
-        for (size_t d = 0; d < nd; d++) { h_eoff[d] = l.keptOff[d]; h_elen[d] = l.keptLen[d]; h_etab[d] = l.table[d]; }
+    hipLaunchKernelGGL(k4::k4_dict_load_kernel, dim3(nt), dim3(k4::DICT_LOAD_THREADS), 0, st, k4::DictLoadArgs{dict, toff, tlen, (uint32_t *)tables});
+}
+void dict_hc_load(hipStream_t st, unsigned nt, const uint8_t *dict, const uint64_t *toff, const uint32_t *tlen, uint8_t *tables)
+{
+    hipLaunchKernelGGL(k4::k4_dict_hc_load_kernel, dim3(nt), dim3(k4::DHC_LOAD_THREADS), 0, st, k4::DictHcLoadArgs{dict, toff, tlen, tables});
+}
+void dict_fast_encode(hipStream_t st, unsigned wgs, const DictBatch &b, const DictTables &t, const DictLayout &w, uint32_t *status, int)
+{
+    k4::DictEncArgs a{b.src, b.srcOff, b.srcLen, b.dst, b.dstOff, b.dstCap, b.outLen, b.dictIdx, t.dict, t.eoff, t.elen, t.etab,
+                      (const uint32_t *)t.tables, w.order, w.head, status, b.n, t.nd};
+    hipLaunchKernelGGL(k4::k4_dict_encode_kernel, dim3(wgs), dim3(64 * k4::FAST_CHAIN_WAVES_PER_WG), 0, st, a);
+}
+void dict_hc_encode(hipStream_t st, unsigned wgs, const DictBatch &b, const DictTables &t, const DictLayout &w, uint32_t *status, int level)
+{
+    k4::DictHcEncArgs a{b.src, b.srcOff, b.srcLen, b.dst, b.dstOff, b.dstCap, b.outLen, b.dictIdx, t.dict, t.eoff, t.elen, t.etab,
+                        t.tables, w.slots, w.order, w.head, status, b.n, t.nd, level};
+    hipLaunchKernelGGL(k4::k4_dict_hc_encode_kernel, dim3(wgs), dim3(64 * k4::DHC_WAVES_PER_WG), 0, st, a);
+}
+
+/* what differs between the fast levels (LZ4_loadDict + LZ4_compress_fast_continue) and the HC levels (LZ4_loadDictHC +
+ * LZ4_compress_HC_continue) */
+struct DictFamily {
+    const char *who;               /* the entry point that takes a list, for messages */
+    const char *other_levels;       /* how it refuses the other family's levels */
+    uint32_t min_kept;              /* the shortest dictionary of which anything is kept (LZ4_loadDict: HASH_UNIT; LZ4_loadDictHC: a byte) */
+    size_t table_bytes;             /* per distinct dictionary */
+    int waves_per_wg, wgs_per_cu;   /* the encode launch: a workgroup per so many messages, at most so many per CU */
+    bool slots;                     /* every wave of the encode launch works in a table of its own, zeroed before the launch */
+    void (*load)(hipStream_t st, unsigned nt, const uint8_t *dict, const uint64_t *toff, const uint32_t *tlen, uint8_t *tables);
+    void (*encode)(hipStream_t st, unsigned wgs, const DictBatch &b, const DictTables &t, const DictLayout &w, uint32_t *status, int level);
+    k4lz4_ctx::DictScratch k4lz4_ctx::*scratch;
+    k4lz4_dict_set::Family k4lz4_dict_set::*in_set;
+};
+const DictFamily FAMILY_FAST{"k4lz4_encode_dict_batch", ": HC levels with a dictionary are not supported", 8u, 4096u * 4u,
+                             k4::FAST_CHAIN_WAVES_PER_WG, 1, false, dict_fast_load, dict_fast_encode, &k4lz4_ctx::dict_fast, &k4lz4_dict_set::fast};
+const DictFamily FAMILY_HC{"k4lz4_encode_dict_hc_batch",
+                           ": levels below 3 are k4lz4_encode_dict_batch's (LZ4_loadDict + LZ4_compress_fast_continue)", 1u,
+                           (size_t)k4::DHC_TABLE_BYTES, k4::DHC_WAVES_PER_WG, DHC_WGS_PER_CU, true, dict_hc_load, dict_hc_encode,
+                           &k4lz4_ctx::dict_hc, &k4lz4_dict_set::hc};
+
+const DictFamily &dict_family(int level) { return level >= K4LZ4_L03_HC ? FAMILY_HC : FAMILY_FAST; }
+const char *dict_caller(const DictFamily &fam, bool of_set) { return of_set ? "k4lz4_encode_dictset_batch" : fam.who; }
+
+/* which bytes of every dictionary are kept -- the last 64 KiB, of one shorter than min_kept nothing -- and which entries share a
+ * table: those that keep the same bytes (same kept start, same kept length; the empty ones are one).  used: which entries the
+ * messages refer to (the host form knows), or nullptr: all of them. */
+int dict_list(k4lz4_ctx *ctx, uint32_t min_kept, const char *who, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict,
+              const uint8_t *used, DictList &l)
+{
+    l.keptOff.assign((size_t)nDict, 0); l.keptLen.assign((size_t)nDict, 0); l.table.assign((size_t)nDict, 0xffffffffu); l.rep.clear();
+    std::map<std::pair<uint64_t, uint32_t>, uint32_t> seen;
+    for (int32_t d = 0; d < nDict; d++) {
+        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": negative dictLen");
+        if (used && !used[d]) continue;
+        const uint32_t len = (uint32_t)dictLen[d];
+        if (len >= min_kept) {
+            l.keptLen[(size_t)d] = std::min<uint32_t>(len, 65536u);
+            l.keptOff[(size_t)d] = dictOff[d] + (len - l.keptLen[(size_t)d]);
+        }
+        const auto key = std::make_pair(l.keptOff[(size_t)d], l.keptLen[(size_t)d]);
+        auto it = seen.find(key);
+        if (it == seen.end()) { it = seen.emplace(key, (uint32_t)l.rep.size()).first; l.rep.push_back((uint32_t)d); }
+        l.table[(size_t)d] = it->second;
     }
-    ctx->dhc_table = l.table; ctx->dhc_kept = l.keptLen;
+    return K4LZ4_OK;
+}
+
+/* a list's words for a family's load and encode kernels: per table where its kept bytes start and how many they are, per entry
+ * the same and its table.  The arrays come zeroed: an empty list still has one (empty) table */
+void dict_words(const DictList &l, uint64_t *toff, uint32_t *tlen, uint64_t *eoff, uint32_t *elen, uint32_t *etab)
+{
+    for (size_t t = 0; t < l.rep.size(); t++) { toff[t] = l.keptOff[l.rep[t]]; tlen[t] = l.keptLen[l.rep[t]]; }
+    for (size_t d = 0; d < l.table.size(); d++) { eoff[d] = l.keptOff[d]; elen[d] = l.keptLen[d]; etab[d] = l.table[d]; }
+}
+
+void dict_layout(Carve &c, DictLayout &w, const DictFamily &fam, size_t nt, size_t nd, size_t n, size_t nslots)
+{
+    c.take(w.head, DICT_HEAD_WORDS); c.take(w.tables, nt * fam.table_bytes);
+    c.take(w.toff, nt); c.take(w.tlen, nt); c.take(w.eoff, nd); c.take(w.elen, nd); c.take(w.etab, nd);
+    c.take(w.cost, n); c.take(w.order, n); c.take(w.slots, nslots * fam.table_bytes);
+}
+
+/* every refusal of the six encode calls that needs no device; b's and s's pointers are the caller's */
+int dict_encode_args(k4lz4_ctx *ctx, const DictFamily &fam, int level, int flags, const DictBatch &b, const DictSource &s)
+{
+    auto refuse = [&](const char *why) { return fail(ctx, K4LZ4_E_ARG, std::string(dict_caller(fam, s.of_set)) + why); };
+    const int rc = check_batch_args(ctx, b.src, b.srcOff, b.srcLen, b.dst, b.dstOff, b.dstCap, b.outLen, b.n);
+    if (rc != K4LZ4_OK) return rc;
+    if (s.of_set && !s.set) return refuse(": set is NULL");
+    if (!s.of_set && &dict_family(level) != &fam) return refuse(fam.other_levels);
+    if (level >= K4LZ4_L10_OPT)
+        return refuse(": levels 10 - 12 with a dictionary are not supported (no sound witness for the optimal parser in this mode)");
+    if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
+        return refuse(": the 32-bit engine (LZ4Codec.Enforce32) is not supported");
+    if (flags) return refuse(": it takes no flags");
+    if (s.of_set) {
+        if (!(s.set->*fam.in_set).on)
+            return refuse(": the set was created without this level's family (K4LZ4_DICT_FAST below level 3, K4LZ4_DICT_HC from there)");
+        if (s.set->device != ctx->device) return refuse(": the set lives on another device than the context");
+        if (b.n > 0 && !b.dictIdx) return refuse(": NULL dictIdx");
+        if (b.n > 0xffffffffll) return refuse(": more than 2^32 - 1 messages");
+        return K4LZ4_OK;
+    }
+    if (s.nDict < 0 || (s.nDict > 0 && (!s.dictOff || !s.dictLen)) || (b.n > 0 && !b.dictIdx)) return refuse(": bad dictionary list");
+    for (int32_t d = 0; d < s.nDict; d++) {
+        if (s.dictLen[d] < 0) return refuse(": negative dictLen");
+        if (s.dictLen[d] > 0 && !s.dict) return refuse(": NULL dictionary buffer");
+    }
+    return K4LZ4_OK;
+}
+
+/* all of b's pointers are device pointers; load, order, encode on `stream`.  With a list -- the call's own, its offsets into the
+ * device buffer dict -- the list's words go up once the previous upload is over, the load kernel builds the tables (also for
+ * no messages), and the family's scratch remembers them for the state query.  With a set the tables and words are the set's:
+ * nothing goes up, nothing is waited for, no messages are nothing to do, and the scratch, laid out anew, remembers nothing. */
+int dict_encode_run(k4lz4_ctx *ctx, const DictFamily &fam, int level, const DictBatch &b, const uint8_t *dict, const DictList *list,
+                    const k4lz4_dict_set *set, hipStream_t stream)
+{
+    const char *const who = dict_caller(fam, !list);
+    const int64_t n = b.n;
+    if (!list && n == 0) return K4LZ4_OK;
+    if (n > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": more than 2^32 - 1 messages");      /* (of a set the argument check said so) */
+    k4lz4_ctx::DictScratch &sc = ctx->*fam.scratch;
+    const size_t nd = list ? list->table.size() : 0, nt = list ? std::max<size_t>(list->rep.size(), 1) : 0;
+    const int64_t wgs = std::min<int64_t>((n + fam.waves_per_wg - 1) / fam.waves_per_wg, (int64_t)ctx->cu_count * fam.wgs_per_cu);
+    const size_t nslots = fam.slots ? (size_t)wgs * (size_t)fam.waves_per_wg : 0;
+    if (list) {
+        if (!sc.ev) K4_HIP(ctx, hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming));
+        else K4_HIP(ctx, hipEventSynchronize(sc.ev));               /* the previous upload of the host words is over */
+    }
+    DictLayout w;
+    Carve m{nullptr};
+    dict_layout(m, w, fam, nt, nd, (size_t)n, nslots);
+    int rc;
+    if ((rc = grow_scratch(ctx, &sc.dev, &sc.cap, m.at + 64)) != K4LZ4_OK) return rc;
+    Carve dv{sc.dev};
+    dict_layout(dv, w, fam, nt, nd, (size_t)n, nslots);
+    const size_t up_bytes = (size_t)((uint8_t *)w.cost - (uint8_t *)w.toff);
+    if (list) {
+        try { sc.host.assign(up_bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+        auto host = [&](auto *p) { return (decltype(p))(sc.host.data() + ((uint8_t *)p - (uint8_t *)w.toff)); };      /* host image of the same layout */
+        dict_words(*list, host(w.toff), host(w.tlen), host(w.eoff), host(w.elen), host(w.etab));
+        sc.table = list->table; sc.kept = list->keptLen;
+    } else {
+        sc.table.clear(); sc.kept.clear();
+    }
     K4_HIP(ctx, order_after_ctx(ctx, stream));
-    K4_HIP(ctx, hipMemcpyAsync(ctx->d_dhc + up_at, ctx->h_dhc.data(), up_bytes, hipMemcpyHostToDevice, stream));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_dhc, stream));
-    K4_HIP(ctx, hipMemsetAsync(head, 0, DHC_HEAD_WORDS * 4, stream));
-    hipLaunchKernelGGL(k4::k4_dict_hc_load_kernel, dim3((unsigned)nt), dim3(k4::DHC_LOAD_THREADS), 0, stream, k4::DictHcLoadArgs{dict, toff, tlen, tables});
-    rc = K4LZ4_OK;
+    if (list) {
+        K4_HIP(ctx, hipMemcpyAsync(w.toff, sc.host.data(), up_bytes, hipMemcpyHostToDevice, stream));
+        K4_HIP(ctx, hipEventRecord(sc.ev, stream));
+    }
+    K4_HIP(ctx, hipMemsetAsync(w.head, 0, DICT_HEAD_WORDS * 4, stream));
+    if (list) fam.load(stream, (unsigned)nt, dict, w.toff, w.tlen, w.tables);
     if (n > 0) {
         /* the wave slots' heads start at zero (a wave leaves them so behind every message); the chain halves are written before they are read */
-        K4_HIP(ctx, hipMemsetAsync(slots, 0, nslots * (size_t)k4::DHC_TABLE_BYTES, stream));
+        if (fam.slots) K4_HIP(ctx, hipMemsetAsync(w.slots, 0, nslots * fam.table_bytes, stream));
         k4::BatchArgs o{};
-        o.srcLen = srcLen; o.n = n; o.cost = cost; o.hist = head + 64; o.order_out = order;
+        o.srcLen = b.srcLen; o.n = n; o.cost = w.cost; o.hist = w.head + 64; o.order_out = w.order;
         const unsigned g256 = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL(k4::k4_dict_cost_kernel, dim3(g256), dim3(256), 0, stream, o);
         hipLaunchKernelGGL(k4::k4_order_kernel, dim3(g256), dim3(256), 0, stream, o, 0xffffffffu);
-        k4::DictHcEncArgs a{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, dictIdx, dict, eoff, elen, etab, tables, slots, order, head,
-                            ctx->d_status, n, (int)nd, level};
-        hipLaunchKernelGGL(k4::k4_dict_hc_encode_kernel, dim3((unsigned)wgs), dim3(64 * k4::DHC_WAVES_PER_WG), 0, stream, a);
+        const k4lz4_dict_set::Family *f = list ? nullptr : &(set->*fam.in_set);
+        const DictTables t = list ? DictTables{dict, w.eoff, w.elen, w.etab, w.tables, (int)nd}
+                                  : DictTables{set->buf, f->eoff, f->elen, f->etab, f->tables, (int)set->nDict};
+        fam.encode(stream, (unsigned)wgs, b, t, w, ctx->d_status, level);
     }
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, K4LZ4_E_HIP, "k4lz4_encode_dict_hc_batch: kernel launch failed");
+    rc = hipGetLastError() != hipSuccess ? fail(ctx, K4LZ4_E_HIP, std::string(who) + ": kernel launch failed") : K4LZ4_OK;
     mark_busy(ctx, stream);
     return rc;
 }
 
-/* the host-pointer form of both dictionary encoders: the messages' span, behind it the kept bytes of every dictionary in use.
- * list: dict_list or dict_hc_list; run: the device-pointer run over the staged buffers */
-template <class LIST, class RUN>
-int dict_encode_host(k4lz4_ctx *ctx, const char *who, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
-                            const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, const int32_t *dictIdx,
-                            const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, LIST list, RUN run)
+/* the device forms: the caller's pointers are device pointers, but for the list's two arrays */
+int dict_encode_device(k4lz4_ctx *ctx, const DictFamily &fam, int level, int flags, const DictBatch &b, const DictSource &s, void *stream)
 {
-    int rc;
-    std::vector<uint8_t> used((size_t)nDict, 0);
-    for (int64_t i = 0; i < n; i++) {
-        if (dictIdx[i] < 0 || dictIdx[i] >= nDict) return fail(ctx, K4LZ4_E_ARG, (std::string(who) + ": a dictIdx outside the dictionary list").c_str());
-        used[(size_t)dictIdx[i]] = 1;
-    }
+    int rc = dict_encode_args(ctx, fam, level, flags, b, s);
+    if (rc != K4LZ4_OK) return rc;
     DictList l;
-    if ((rc = list(ctx, dictOff, dictLen, nDict, used.data(), l)) != K4LZ4_OK) return rc;
+    if (!s.of_set && (rc = dict_list(ctx, fam.min_kept, fam.who, s.dictOff, s.dictLen, s.nDict, nullptr, l)) != K4LZ4_OK) return rc;
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    HostStage s(ctx);
-    s.span(src, srcOff, n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(srcLen[i], 0); });
-    /* the kept bytes of every dictionary in use go up behind the messages, at 16-byte steps of the same buffer */
-    DictList staged = l;
-    std::vector<uint64_t> at_of((size_t)l.rep.size(), 0);
-    for (size_t t = 0; t < l.rep.size(); t++) {
-        const uint32_t d = l.rep[t];
-        if (!l.keptLen[d]) continue;
-        at_of[t] = (s.in_bytes + 15u) & ~(uint64_t)15u;
-        s.ups.push_back(HostStage::Up{&ctx->d_src, at_of[t], dict + l.keptOff[d], (size_t)l.keptLen[d]});
-        s.in_bytes = at_of[t] + l.keptLen[d];
+    return dict_encode_run(ctx, fam, level, b, s.dict, s.of_set ? nullptr : &l, s.set, (hipStream_t)stream);
+}
+
+/* the host forms: the messages' span goes up and, with a list, behind it the kept bytes of every dictionary in use; the run
+ * works on the staged buffers */
+int dict_encode_host(k4lz4_ctx *ctx, const DictFamily &fam, int level, int flags, const DictBatch &b, const DictSource &s)
+{
+    int rc = dict_encode_args(ctx, fam, level, flags, b, s);
+    if (rc != K4LZ4_OK) return rc;
+    const int32_t nDict = s.of_set ? s.set->nDict : s.nDict;
+    std::vector<uint8_t> used(s.of_set ? 0 : (size_t)nDict, 0);
+    for (int64_t i = 0; i < b.n; i++) {
+        if (b.dictIdx[i] < 0 || b.dictIdx[i] >= nDict)
+            return fail(ctx, K4LZ4_E_ARG, std::string(dict_caller(fam, s.of_set)) + ": a dictIdx outside the dictionary list");
+        if (!s.of_set) used[(size_t)b.dictIdx[i]] = 1;
     }
-    for (int32_t e = 0; e < nDict; e++)
-        if (used[(size_t)e]) staged.keptOff[(size_t)e] = at_of[l.table[(size_t)e]];
-    s.slots(n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(dstCap[i], 0); }, false);
+    if (s.of_set && b.n == 0) return K4LZ4_OK;
+    DictList l;
+    if (!s.of_set && (rc = dict_list(ctx, fam.min_kept, fam.who, s.dictOff, s.dictLen, nDict, used.data(), l)) != K4LZ4_OK) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage st(ctx);
+    st.span(b.src, b.srcOff, b.n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(b.srcLen[i], 0); });
+    if (!s.of_set) {
+        /* the kept bytes of every dictionary in use go up behind the messages, at 16-byte steps of the same buffer: there the
+         * list's offsets point from here on */
+        std::vector<uint64_t> at_of(l.rep.size(), 0);
+        for (size_t t = 0; t < l.rep.size(); t++) {
+            const uint32_t d = l.rep[t];
+            if (!l.keptLen[d]) continue;
+            at_of[t] = (st.in_bytes + 15u) & ~(uint64_t)15u;
+            st.ups.push_back(HostStage::Up{&ctx->d_src, at_of[t], s.dict + l.keptOff[d], (size_t)l.keptLen[d]});
+            st.in_bytes = at_of[t] + l.keptLen[d];
+        }
+        for (size_t e = 0; e < l.table.size(); e++)
+            if (used[e]) l.keptOff[e] = at_of[l.table[e]];
+    }
+    st.slots(b.n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(b.dstCap[i], 0); }, false);
     uint64_t *d_off, *d_doff;
     int32_t *d_len, *d_cap, *d_out, *d_idx;
-    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, srcLen); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_cap, n, dstCap);
-    s.meta(&d_idx, n, dictIdx); s.meta(&d_out, n);
-    if ((rc = s.upload()) != K4LZ4_OK ||
-        (rc = run(ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, d_idx, staged, s.st)) != K4LZ4_OK)
-        return rc;
-    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
-                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
+    st.meta(&d_off, b.n, st.in_off.data()); st.meta(&d_len, b.n, b.srcLen); st.meta(&d_doff, b.n, st.slot.data()); st.meta(&d_cap, b.n, b.dstCap);
+    st.meta(&d_idx, b.n, b.dictIdx); st.meta(&d_out, b.n);
+    if ((rc = st.upload()) != K4LZ4_OK) return rc;
+    const DictBatch staged{ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, b.n, d_idx};
+    if ((rc = dict_encode_run(ctx, fam, level, staged, ctx->d_src, s.of_set ? nullptr : &l, s.set, st.st)) != K4LZ4_OK) return rc;
+    return finish_blocks(st, b.outLen, d_out, b.n, b.dst, b.dstOff, b.dstCap);
+}
+
+/* the table the family's most recent call with a list of its own gave entry d of that list, or nullptr */
+const uint8_t *dict_loaded_table(k4lz4_ctx *ctx, const DictFamily &fam, int32_t d)
+{
+    const k4lz4_ctx::DictScratch &sc = ctx->*fam.scratch;
+    if (d < 0 || (size_t)d >= sc.table.size() || sc.table[(size_t)d] == 0xffffffffu || !sc.dev) return nullptr;
+    Carve c{sc.dev};
+    DictLayout w;
+    dict_layout(c, w, fam, 1, 0, 0, 0);
+    return w.tables + fam.table_bytes * sc.table[(size_t)d];
+}
+
+/* what the state queries answer from a table on the device: of a call's own list, or of a set (then without a context) */
+int dict_fast_state(k4lz4_ctx *ctx, const uint8_t *table, uint32_t kept, k4lz4_fast_chain_state *out)
+{
+    K4_HIP(ctx, hipMemcpy(out->hashTable, table, sizeof out->hashTable, hipMemcpyDeviceToHost));
+    out->currentOffset = k4::DICT_START;
+    out->dictSize = kept;
+    out->reserved[0] = out->reserved[1] = 0;
+    return K4LZ4_OK;
+}
+int dict_hc_state(k4lz4_ctx *ctx, const uint8_t *table, uint32_t kept, uint32_t *hashTable, uint16_t *chainTable, int32_t *keptLen)
+{
+    K4_HIP(ctx, hipMemcpy(hashTable, table, (size_t)k4::DHC_HEADS * 4, hipMemcpyDeviceToHost));
+    K4_HIP(ctx, hipMemcpy(chainTable, table + (size_t)k4::DHC_HEADS * 4, (size_t)k4::DHC_CHAIN * 2, hipMemcpyDeviceToHost));
+    *keptLen = (int32_t)kept;
+    return K4LZ4_OK;
 }
 
 void direct_layout(Carve &c, k4::FrFastArgs &f, size_t n, size_t nr)
@@ -2682,10 +2763,10 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_fw) (void)hipFree(ctx->d_fw);
     if (ctx->ev_fw) (void)hipEventDestroy(ctx->ev_fw);
     if (ctx->ev_chain) (void)hipEventDestroy(ctx->ev_chain);
-    if (ctx->d_denc) (void)hipFree(ctx->d_denc);
-    if (ctx->ev_denc) (void)hipEventDestroy(ctx->ev_denc);
-    if (ctx->d_dhc) (void)hipFree(ctx->d_dhc);
-    if (ctx->ev_dhc) (void)hipEventDestroy(ctx->ev_dhc);
+    for (k4lz4_ctx::DictScratch *sc : {&ctx->dict_fast, &ctx->dict_hc}) {
+        if (sc->dev) (void)hipFree(sc->dev);
+        if (sc->ev) (void)hipEventDestroy(sc->ev);
+    }
     if (ctx->d_pk_meta) (void)hipFree(ctx->d_pk_meta);
     if (ctx->d_dpick) (void)hipFree(ctx->d_dpick);
     delete ctx;
@@ -3134,85 +3215,22 @@ int k4lz4_encode_fast_chain_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint
 }
 
 
-/* ---- frame reader (k4lz4_frame_read.hpp, DESIGN.md 4.11) ---------------------------------------------------------------- */
-static int dict_encode_args(k4lz4_ctx *ctx, const void *src, const void *srcOff, const void *srcLen, const void *dst, const void *dstOff,
-                            const void *dstCap, const void *outLen, int64_t n, int level, int flags, const void *dictIdx, const void *dict,
-                            const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict)
-{
-    int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
-    if (rc != K4LZ4_OK || (rc = dict_encode_flags(ctx, level, flags)) != K4LZ4_OK) return rc;
-    if (nDict < 0 || (nDict > 0 && (!dictOff || !dictLen)) || (n > 0 && !dictIdx)) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: bad dictionary list");
-    for (int32_t d = 0; d < nDict; d++) {
-        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: negative dictLen");
-        if (dictLen[d] > 0 && !dict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_batch: NULL dictionary buffer");
-    }
-    return K4LZ4_OK;
-}
-
+/* ---- messages against shared dictionaries: the entry points of the path above the C ABI ------------- */
 int k4lz4_encode_dict_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
                                    const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
                                    const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen,
                                    int32_t nDict, void *stream)
 {
-    int rc = dict_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
-    if (rc != K4LZ4_OK) return rc;
-    DictList l;
-    if ((rc = dict_list(ctx, dictOff, dictLen, nDict, nullptr, l)) != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    return dict_encode_run(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx, dict, l, (hipStream_t)stream);
+    return dict_encode_device(ctx, FAMILY_FAST, level, flags, DictBatch{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx},
+                              DictSource{false, nullptr, dict, dictOff, dictLen, nDict}, stream);
 }
 
 int k4lz4_encode_dict_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
                             const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
                             const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict)
 {
-    int rc = dict_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
-    if (rc != K4LZ4_OK) return rc;
-    return dict_encode_host(ctx, "k4lz4_encode_dict_batch", src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx, dict, dictOff, dictLen,
-                            nDict, dict_list,
-                            [&](const uint8_t *ds, const uint64_t *doff, const int32_t *dlen, uint8_t *dd, const uint64_t *ddoff, const int32_t *dcap,
-                                int32_t *dout, const int32_t *didx, const DictList &staged, hipStream_t st) {
-                                return dict_encode_run(ctx, ds, doff, dlen, dd, ddoff, dcap, dout, n, didx, ds, staged, st);
-                            });
-}
-
-int k4lz4_encode_dict_state(k4lz4_ctx *ctx, int32_t d, k4lz4_fast_chain_state *out)
-{
-    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (!out || d < 0 || (size_t)d >= ctx->denc_table.size() || ctx->denc_table[(size_t)d] == 0xffffffffu || !ctx->d_denc)
-        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_state: no such dictionary in the context's most recent k4lz4_encode_dict_batch call");
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
-    Carve c{ctx->d_denc};
-    uint32_t *head, *tables;
-    c.take(head, 64 + 2 * k4::COST_BUCKETS + 16); c.take(tables, 4096);
-    K4_HIP(ctx, hipMemcpy(out->hashTable, tables + 4096ull * ctx->denc_table[(size_t)d], sizeof out->hashTable, hipMemcpyDeviceToHost));
-    out->currentOffset = k4::DICT_START;
-    out->dictSize = ctx->denc_kept[(size_t)d];
-    out->reserved[0] = out->reserved[1] = 0;
-    return K4LZ4_OK;
-}
-
-/* ---- k4lz4_encode_dict_hc_batch (k4lz4_dict_encode_hc.hpp) --------------------------------------------------- */
-static int dict_hc_encode_args(k4lz4_ctx *ctx, const void *src, const void *srcOff, const void *srcLen, const void *dst, const void *dstOff,
-                               const void *dstCap, const void *outLen, int64_t n, int level, int flags, const void *dictIdx, const void *dict,
-                               const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict)
-{
-    int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
-    if (rc != K4LZ4_OK) return rc;
-    if (level < K4LZ4_L03_HC)
-        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: levels below 3 are k4lz4_encode_dict_batch's (LZ4_loadDict + LZ4_compress_fast_continue)");
-    if (level >= K4LZ4_L10_OPT)
-        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: levels 10 - 12 with a dictionary are not supported (no sound witness for the optimal parser in this mode)");
-    if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
-        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: the 32-bit engine (LZ4Codec.Enforce32) is not supported");
-    if (flags) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: it takes no flags");
-    if (nDict < 0 || (nDict > 0 && (!dictOff || !dictLen)) || (n > 0 && !dictIdx)) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: bad dictionary list");
-    for (int32_t d = 0; d < nDict; d++) {
-        if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: negative dictLen");
-        if (dictLen[d] > 0 && !dict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_batch: NULL dictionary buffer");
-    }
-    return K4LZ4_OK;
+    return dict_encode_host(ctx, FAMILY_FAST, level, flags, DictBatch{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx},
+                            DictSource{false, nullptr, dict, dictOff, dictLen, nDict});
 }
 
 int k4lz4_encode_dict_hc_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
@@ -3220,50 +3238,60 @@ int k4lz4_encode_dict_hc_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const 
                                       const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen,
                                       int32_t nDict, void *stream)
 {
-    int rc = dict_hc_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
-    if (rc != K4LZ4_OK) return rc;
-    DictList l;
-    if ((rc = dict_hc_list(ctx, dictOff, dictLen, nDict, nullptr, l)) != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    return dict_hc_encode_run(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, dictIdx, dict, l, (hipStream_t)stream);
+    return dict_encode_device(ctx, FAMILY_HC, level, flags, DictBatch{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx},
+                              DictSource{false, nullptr, dict, dictOff, dictLen, nDict}, stream);
 }
 
 int k4lz4_encode_dict_hc_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
                                const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
                                const int32_t *dictIdx, const uint8_t *dict, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict)
 {
-    int rc = dict_hc_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, dict, dictOff, dictLen, nDict);
-    if (rc != K4LZ4_OK) return rc;
-    return dict_encode_host(ctx, "k4lz4_encode_dict_hc_batch", src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx, dict, dictOff, dictLen,
-                            nDict, dict_hc_list,
-                            [&](const uint8_t *ds, const uint64_t *doff, const int32_t *dlen, uint8_t *dd, const uint64_t *ddoff, const int32_t *dcap,
-                                int32_t *dout, const int32_t *didx, const DictList &staged, hipStream_t st) {
-                                return dict_hc_encode_run(ctx, ds, doff, dlen, dd, ddoff, dcap, dout, n, level, didx, ds, staged, st);
-                            });
+    return dict_encode_host(ctx, FAMILY_HC, level, flags, DictBatch{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx},
+                            DictSource{false, nullptr, dict, dictOff, dictLen, nDict});
+}
+
+int k4lz4_encode_dictset_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                                      const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+                                      const int32_t *dictIdx, const k4lz4_dict_set *set, void *stream)
+{
+    return dict_encode_device(ctx, dict_family(level), level, flags, DictBatch{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx},
+                              DictSource{true, set, nullptr, nullptr, nullptr, 0}, stream);
+}
+
+int k4lz4_encode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                               const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+                               const int32_t *dictIdx, const k4lz4_dict_set *set)
+{
+    return dict_encode_host(ctx, dict_family(level), level, flags, DictBatch{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, dictIdx},
+                            DictSource{true, set, nullptr, nullptr, nullptr, 0});
+}
+
+int k4lz4_encode_dict_state(k4lz4_ctx *ctx, int32_t d, k4lz4_fast_chain_state *out)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    const uint8_t *table = out ? dict_loaded_table(ctx, FAMILY_FAST, d) : nullptr;
+    if (!table)
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_state: no such dictionary in the context's most recent k4lz4_encode_dict_batch call");
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
+    return dict_fast_state(ctx, table, ctx->dict_fast.kept[(size_t)d], out);
 }
 
 int k4lz4_encode_dict_hc_state(k4lz4_ctx *ctx, int32_t d, uint32_t *hashTable, uint16_t *chainTable, int32_t *keptLen)
 {
     if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
-    if (!hashTable || !chainTable || !keptLen || d < 0 || (size_t)d >= ctx->dhc_table.size() || ctx->dhc_table[(size_t)d] == 0xffffffffu || !ctx->d_dhc)
+    const uint8_t *table = hashTable && chainTable && keptLen ? dict_loaded_table(ctx, FAMILY_HC, d) : nullptr;
+    if (!table)
         return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dict_hc_state: no such dictionary in the context's most recent k4lz4_encode_dict_hc_batch call");
     K4_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
-    Carve c{ctx->d_dhc};
-    uint32_t *head;
-    uint8_t *tables;
-    c.take(head, DHC_HEAD_WORDS); c.take(tables, (size_t)k4::DHC_TABLE_BYTES);
-    const uint8_t *t = tables + (size_t)k4::DHC_TABLE_BYTES * ctx->dhc_table[(size_t)d];
-    K4_HIP(ctx, hipMemcpy(hashTable, t, (size_t)k4::DHC_HEADS * 4, hipMemcpyDeviceToHost));
-    K4_HIP(ctx, hipMemcpy(chainTable, t + (size_t)k4::DHC_HEADS * 4, (size_t)k4::DHC_CHAIN * 2, hipMemcpyDeviceToHost));
-    *keptLen = (int32_t)ctx->dhc_kept[(size_t)d];
-    return K4LZ4_OK;
+    return dict_hc_state(ctx, table, ctx->dict_hc.kept[(size_t)d], hashTable, chainTable, keptLen);
 }
 
 /* ---- k4lz4_dict_set (k4lz4_dict_set.hpp) ---------------------------------------------------------------------
- * Which bytes are kept is dict_hc_list's rule (the last 64 KiB of every length down to one byte: the decoders need them whatever the
- * families), and that list is the HC family's; dict_list is the fast family's (below 8 bytes: the empty table, dictSize 0).  Every
- * distinct kept range gets a region of the set's memory at the next 64-byte step. */
+ * Which bytes are kept is the HC family's rule (the last 64 KiB of every length down to one byte: the decoders need them whatever
+ * the families), and that dict_list is the HC family's; the fast family has its own (below 8 bytes: the empty table, dictSize 0).
+ * Every distinct kept range gets a region of the set's memory at the next 64-byte step. */
 struct DictSetPlan {
     DictList bytes, fast;
     std::vector<uint64_t> regionAt;        /* per distinct kept range (= per HC table) */
@@ -3277,12 +3305,14 @@ static void dict_set_carve(Carve &c, const DictSetPlan &p, size_t nd, int famili
     for (size_t t = 0; t < p.bytes.rep.size(); t++) { regionAt[t] = c.at; c.take(b, (size_t)p.bytes.keptLen[p.bytes.rep[t]]); }
     c.take(b, 64);                                                        /* nothing lies right behind the last dictionary byte */
     c.take(s.dec_off, nd); c.take(s.dec_len, nd);
-    auto family = [&](k4lz4_dict_set::Family &f, size_t nt, size_t table_bytes) {
+    auto family = [&](const DictFamily &fam, const DictList &l) {
+        k4lz4_dict_set::Family &f = s.*fam.in_set;
+        const size_t nt = std::max<size_t>(l.rep.size(), 1);
         c.take(f.toff, nt); c.take(f.tlen, nt); c.take(f.eoff, nd); c.take(f.elen, nd); c.take(f.etab, nd);
-        c.take(f.tables, nt * table_bytes);
+        c.take(f.tables, nt * fam.table_bytes);
     };
-    if (families & K4LZ4_DICT_FAST) family(s.fast, std::max<size_t>(p.fast.rep.size(), 1), 4096u * 4u);
-    if (families & K4LZ4_DICT_HC) family(s.hc, std::max<size_t>(p.bytes.rep.size(), 1), (size_t)k4::DHC_TABLE_BYTES);
+    if (families & K4LZ4_DICT_FAST) family(FAMILY_FAST, p.fast);
+    if (families & K4LZ4_DICT_HC) family(FAMILY_HC, p.bytes);
 }
 
 static int dict_set_plan(k4lz4_ctx *ctx, const uint64_t *dictOff, const int32_t *dictLen, int32_t nDict, int families, DictSetPlan &p)
@@ -3294,8 +3324,10 @@ static int dict_set_plan(k4lz4_ctx *ctx, const uint64_t *dictOff, const int32_t 
         if (dictLen[d] < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_dict_set: negative dictLen");
     int rc;
     try {
-        if ((rc = dict_hc_list(ctx, dictOff, dictLen, nDict, nullptr, p.bytes)) != K4LZ4_OK) return rc;
-        if ((families & K4LZ4_DICT_FAST) && (rc = dict_list(ctx, dictOff, dictLen, nDict, nullptr, p.fast)) != K4LZ4_OK) return rc;
+        if ((rc = dict_list(ctx, FAMILY_HC.min_kept, "k4lz4_dict_set", dictOff, dictLen, nDict, nullptr, p.bytes)) != K4LZ4_OK) return rc;
+        if ((families & K4LZ4_DICT_FAST) &&
+            (rc = dict_list(ctx, FAMILY_FAST.min_kept, "k4lz4_dict_set", dictOff, dictLen, nDict, nullptr, p.fast)) != K4LZ4_OK)
+            return rc;
         Carve m{nullptr};
         k4lz4_dict_set measure;
         dict_set_carve(m, p, (size_t)nDict, families, measure, p.regionAt);
@@ -3356,16 +3388,13 @@ static int dict_set_create(k4lz4_ctx *ctx, const uint8_t *dict, bool on_device, 
         dec_off = s->keptAt; dec_len = s->keptLen;
         for (int k = 0; k < 2; k++) {
             if (!(families & (k ? K4LZ4_DICT_HC : K4LZ4_DICT_FAST))) continue;
-            const DictList &l = k ? p.bytes : p.fast;
+            DictList l = k ? p.bytes : p.fast;
             k4lz4_dict_set::Family &f = k ? s->hc : s->fast;
             f.on = true; f.table = l.table; f.kept = l.keptLen; f.ntables = (int64_t)std::max<size_t>(l.rep.size(), 1);
+            for (size_t d = 0; d < nd; d++) l.keptOff[d] = l.keptLen[d] ? s->keptAt[d] : 0;     /* the kept bytes lie in the set's memory */
             w_toff[k].assign((size_t)f.ntables, 0); w_tlen[k].assign((size_t)f.ntables, 0);     /* an empty list: one empty table */
             w_eoff[k].assign(nd, 0); w_elen[k].assign(nd, 0); w_etab[k].assign(nd, 0);
-            for (size_t d = 0; d < nd; d++) {
-                w_elen[k][d] = l.keptLen[d]; w_etab[k][d] = l.table[d];
-                w_eoff[k][d] = l.keptLen[d] ? s->keptAt[d] : 0;
-            }
-            for (size_t t = 0; t < l.rep.size(); t++) { w_toff[k][t] = w_eoff[k][l.rep[t]]; w_tlen[k][t] = l.keptLen[l.rep[t]]; }
+            dict_words(l, w_toff[k].data(), w_tlen[k].data(), w_eoff[k].data(), w_elen[k].data(), w_etab[k].data());
         }
     } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
     if (hipMalloc((void **)&s->buf, (size_t)p.total) != hipSuccess) { (void)hipGetLastError(); s->buf = nullptr; return fail(ctx, K4LZ4_E_NOMEM, "out of device memory"); }
@@ -3392,8 +3421,7 @@ static int dict_set_create(k4lz4_ctx *ctx, const uint8_t *dict, bool on_device, 
         K4_HIP(ctx, up(f.eoff, w_eoff[k].data(), nd * 8));
         K4_HIP(ctx, up(f.elen, w_elen[k].data(), nd * 4));
         K4_HIP(ctx, up(f.etab, w_etab[k].data(), nd * 4));
-        if (k) hipLaunchKernelGGL(k4::k4_dict_hc_load_kernel, dim3((unsigned)nt), dim3(k4::DHC_LOAD_THREADS), 0, st, k4::DictHcLoadArgs{s->buf, f.toff, f.tlen, f.tables});
-        else hipLaunchKernelGGL(k4::k4_dict_load_kernel, dim3((unsigned)nt), dim3(k4::DICT_LOAD_THREADS), 0, st, k4::DictLoadArgs{s->buf, f.toff, f.tlen, (uint32_t *)f.tables});
+        (k ? FAMILY_HC : FAMILY_FAST).load(st, (unsigned)nt, s->buf, f.toff, f.tlen, f.tables);
         if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(st); return fail(ctx, K4LZ4_E_HIP, "k4lz4_dict_set_create: kernel launch failed"); }
         f.loads++;
     }
@@ -3427,11 +3455,7 @@ int k4lz4_dict_set_state(const k4lz4_dict_set *set, int32_t d, k4lz4_fast_chain_
     if (!set || !out || d < 0 || d >= set->nDict || !set->fast.on)
         return fail(nullptr, K4LZ4_E_ARG, "k4lz4_dict_set_state: no such dictionary, or a set without K4LZ4_DICT_FAST");
     K4_HIP(nullptr, hipSetDevice(set->device));
-    K4_HIP(nullptr, hipMemcpy(out->hashTable, set->fast.tables + 16384ull * set->fast.table[(size_t)d], sizeof out->hashTable, hipMemcpyDeviceToHost));
-    out->currentOffset = k4::DICT_START;
-    out->dictSize = set->fast.kept[(size_t)d];
-    out->reserved[0] = out->reserved[1] = 0;
-    return K4LZ4_OK;
+    return dict_fast_state(nullptr, set->fast.tables + FAMILY_FAST.table_bytes * set->fast.table[(size_t)d], set->fast.kept[(size_t)d], out);
 }
 
 int k4lz4_dict_set_hc_state(const k4lz4_dict_set *set, int32_t d, uint32_t *hashTable, uint16_t *chainTable, int32_t *keptLen)
@@ -3439,114 +3463,8 @@ int k4lz4_dict_set_hc_state(const k4lz4_dict_set *set, int32_t d, uint32_t *hash
     if (!set || !hashTable || !chainTable || !keptLen || d < 0 || d >= set->nDict || !set->hc.on)
         return fail(nullptr, K4LZ4_E_ARG, "k4lz4_dict_set_hc_state: no such dictionary, or a set without K4LZ4_DICT_HC");
     K4_HIP(nullptr, hipSetDevice(set->device));
-    const uint8_t *t = set->hc.tables + (size_t)k4::DHC_TABLE_BYTES * set->hc.table[(size_t)d];
-    K4_HIP(nullptr, hipMemcpy(hashTable, t, (size_t)k4::DHC_HEADS * 4, hipMemcpyDeviceToHost));
-    K4_HIP(nullptr, hipMemcpy(chainTable, t + (size_t)k4::DHC_HEADS * 4, (size_t)k4::DHC_CHAIN * 2, hipMemcpyDeviceToHost));
-    *keptLen = (int32_t)set->hc.kept[(size_t)d];
-    return K4LZ4_OK;
-}
-
-static int dictset_encode_args(k4lz4_ctx *ctx, const void *src, const void *srcOff, const void *srcLen, const void *dst, const void *dstOff,
-                               const void *dstCap, const void *outLen, int64_t n, int level, int flags, const void *dictIdx, const k4lz4_dict_set *set)
-{
-    int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
-    if (rc != K4LZ4_OK) return rc;
-    if (!set) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: set is NULL");
-    if (level >= K4LZ4_L10_OPT)
-        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: levels 10 - 12 with a dictionary are not supported (no sound witness for the optimal parser in this mode)");
-    if ((flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed))
-        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: the 32-bit engine (LZ4Codec.Enforce32) is not supported");
-    if (flags) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: it takes no flags");
-    if (!(level >= K4LZ4_L03_HC ? set->hc.on : set->fast.on))
-        return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: the set was created without this level's family (K4LZ4_DICT_FAST below level 3, K4LZ4_DICT_HC from there)");
-    if (set->device != ctx->device) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: the set lives on another device than the context");
-    if (n > 0 && !dictIdx) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: NULL dictIdx");
-    if (n > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: more than 2^32 - 1 messages");
-    return K4LZ4_OK;
-}
-
-/* all pointers are device pointers; order and encode on `stream` -- no list words go up, no table is built, neither ev_denc nor ev_dhc
- * is waited for.  The context's scratch (d_denc below level 3, d_dhc from there) carries the ticket and histogram words, cost and
- * order and the HC wave slots, laid out for this call: what the per-call calls left there for their state queries is gone. */
-static int dictset_encode_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst, const uint64_t *dstOff,
-                              const int32_t *dstCap, int32_t *outLen, int64_t n, int level, const int32_t *dictIdx, const k4lz4_dict_set *set,
-                              hipStream_t stream)
-{
-    if (n == 0) return K4LZ4_OK;
-    const bool hc = level >= K4LZ4_L03_HC;
-    const k4lz4_dict_set::Family &f = hc ? set->hc : set->fast;
-    const int64_t wgs = hc ? std::min<int64_t>((n + k4::DHC_WAVES_PER_WG - 1) / k4::DHC_WAVES_PER_WG, (int64_t)ctx->cu_count * DHC_WGS_PER_CU)
-                           : std::min<int64_t>((n + k4::FAST_CHAIN_WAVES_PER_WG - 1) / k4::FAST_CHAIN_WAVES_PER_WG, ctx->cu_count);
-    const size_t nslots = hc ? (size_t)wgs * k4::DHC_WAVES_PER_WG : 0;
-    uint32_t *head, *cost, *order;
-    uint8_t *slots;
-    auto layout = [&](Carve &cv) {
-        cv.take(head, DHC_HEAD_WORDS); cv.take(cost, (size_t)n); cv.take(order, (size_t)n); cv.take(slots, nslots * (size_t)k4::DHC_TABLE_BYTES);
-    };
-    static_assert(DHC_HEAD_WORDS == 64 + 2 * k4::COST_BUCKETS + 16, "both families' ticket and histogram words");
-    Carve m{nullptr};
-    layout(m);
-    uint8_t **scratch = hc ? &ctx->d_dhc : &ctx->d_denc;
-    int rc;
-    if ((rc = grow_scratch(ctx, scratch, hc ? &ctx->d_dhc_cap : &ctx->d_denc_cap, m.at + 64)) != K4LZ4_OK) return rc;
-    Carve dv{*scratch};
-    layout(dv);
-    if (hc) { ctx->dhc_table.clear(); ctx->dhc_kept.clear(); } else { ctx->denc_table.clear(); ctx->denc_kept.clear(); }
-    K4_HIP(ctx, order_after_ctx(ctx, stream));
-    K4_HIP(ctx, hipMemsetAsync(head, 0, DHC_HEAD_WORDS * 4, stream));
-    /* the wave slots' heads start at zero (a wave leaves them so behind every message); the chain halves are written before they are read */
-    if (hc) K4_HIP(ctx, hipMemsetAsync(slots, 0, nslots * (size_t)k4::DHC_TABLE_BYTES, stream));
-    k4::BatchArgs o{};
-    o.srcLen = srcLen; o.n = n; o.cost = cost; o.hist = head + 64; o.order_out = order;
-    const unsigned g256 = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k4::k4_dict_cost_kernel, dim3(g256), dim3(256), 0, stream, o);
-    hipLaunchKernelGGL(k4::k4_order_kernel, dim3(g256), dim3(256), 0, stream, o, 0xffffffffu);
-    if (hc) {
-        k4::DictHcEncArgs a{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, dictIdx, set->buf, f.eoff, f.elen, f.etab, f.tables, slots, order, head,
-                            ctx->d_status, n, (int)set->nDict, level};
-        hipLaunchKernelGGL(k4::k4_dict_hc_encode_kernel, dim3((unsigned)wgs), dim3(64 * k4::DHC_WAVES_PER_WG), 0, stream, a);
-    } else {
-        k4::DictEncArgs a{src, srcOff, srcLen, dst, dstOff, dstCap, outLen, dictIdx, set->buf, f.eoff, f.elen, f.etab, (const uint32_t *)f.tables, order, head,
-                          ctx->d_status, n, (int)set->nDict};
-        hipLaunchKernelGGL(k4::k4_dict_encode_kernel, dim3((unsigned)wgs), dim3(64 * k4::FAST_CHAIN_WAVES_PER_WG), 0, stream, a);
-    }
-    rc = hipGetLastError() != hipSuccess ? fail(ctx, K4LZ4_E_HIP, "k4lz4_encode_dictset_batch: kernel launch failed") : K4LZ4_OK;
-    mark_busy(ctx, stream);
-    return rc;
-}
-
-int k4lz4_encode_dictset_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
-                                      const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
-                                      const int32_t *dictIdx, const k4lz4_dict_set *set, void *stream)
-{
-    const int rc = dictset_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, set);
-    if (rc != K4LZ4_OK) return rc;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    return dictset_encode_run(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, dictIdx, set, (hipStream_t)stream);
-}
-
-int k4lz4_encode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
-                               const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
-                               const int32_t *dictIdx, const k4lz4_dict_set *set)
-{
-    int rc = dictset_encode_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, dictIdx, set);
-    if (rc != K4LZ4_OK) return rc;
-    for (int64_t i = 0; i < n; i++)
-        if (dictIdx[i] < 0 || dictIdx[i] >= set->nDict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_dictset_batch: a dictIdx outside the dictionary list");
-    if (n == 0) return K4LZ4_OK;
-    K4_HIP(ctx, hipSetDevice(ctx->device));
-    HostStage s(ctx);                                                     /* the messages only: no dictionary byte goes up */
-    s.span(src, srcOff, n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(srcLen[i], 0); });
-    s.slots(n, [&](int64_t i) { return (uint64_t)std::max<int32_t>(dstCap[i], 0); }, false);
-    uint64_t *d_off, *d_doff;
-    int32_t *d_len, *d_cap, *d_out, *d_idx;
-    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, srcLen); s.meta(&d_doff, n, s.slot.data()); s.meta(&d_cap, n, dstCap);
-    s.meta(&d_idx, n, dictIdx); s.meta(&d_out, n);
-    if ((rc = s.upload()) != K4LZ4_OK ||
-        (rc = dictset_encode_run(ctx, ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, n, level, d_idx, set, s.st)) != K4LZ4_OK)
-        return rc;
-    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
-                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
+    return dict_hc_state(nullptr, set->hc.tables + FAMILY_HC.table_bytes * set->hc.table[(size_t)d], set->hc.kept[(size_t)d], hashTable, chainTable,
+                         keptLen);
 }
 
 static int dictset_decode_args(k4lz4_ctx *ctx, const void *src, const void *srcOff, const void *srcLen, const void *dst, const void *dstOff,
@@ -3618,9 +3536,10 @@ int k4lz4_decode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_
     if ((rc = s.upload()) != K4LZ4_OK) return rc;
     const DictArgs dd{set->buf, d_dictoff, d_dictlen, d_mode};
     if ((rc = launch(ctx, KIND_DECODE, ctx->d_src, d_off, d_len, ctx->d_dst, d_doff, d_cap, d_out, n, 0, flags, s.st, &dd)) != K4LZ4_OK) return rc;
-    return s.finish({{outLen, d_out, (size_t)n * 4}}, dst, dstOff,
-                    [&](int64_t i) { return outLen[i] > 0 && outLen[i] <= dstCap[i] ? (size_t)outLen[i] : 0; });
+    return finish_blocks(s, outLen, d_out, n, dst, dstOff, dstCap);
 }
+
+/* ---- frame reader (k4lz4_frame_read.hpp, DESIGN.md 4.11) ---------------------------------------------------------------- */
 
 int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
                              uint64_t *outSize, int32_t *outStatus, void *stream)

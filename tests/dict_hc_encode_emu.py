@@ -1,6 +1,6 @@
 """The HC dictionary encoder's kernels (k4lz4_dict_encode_hc.hpp) under the host wave emulator: tests/emu/emu_dict_encode_hc.cpp +
 tests/emu/emu_runtime.cpp, built by g++ into a library of its own.  The list of distinct dictionaries is planned here the way
-k4lz4_capi.hip's dict_hc_list plans it.  Test infrastructure only."""
+k4lz4_capi.hip's dict_list plans it for the HC family.  Test infrastructure only."""
 from __future__ import annotations
 
 import ctypes as C
@@ -48,7 +48,7 @@ def lib():
 
 
 def plan(dict_off, dict_len):
-    """per entry (kept offset, kept length, table) and per distinct table (kept offset, kept length): dict_hc_list of k4lz4_capi.hip.
+    """per entry (kept offset, kept length, table) and per distinct table (kept offset, kept length): the HC family's dict_list of k4lz4_capi.hip.
     Every byte of a dictionary counts, down to one (LZ4_loadDictHC keeps what LZ4_loadDict drops)"""
     nd = len(dict_len)
     kept_off, kept_len, table = np.zeros(nd, np.uint64), np.zeros(nd, np.uint32), np.zeros(nd, np.uint32)

@@ -110,7 +110,7 @@ def test_equal_ranges_share_a_table_and_the_families_differ_below_eight_bytes():
 
 
 def test_interleaved_keeps_equal_bytes_at_two_places_as_the_per_call_lists_do():
-    """dict_list and dict_hc_list tell entries apart by the range they keep, not by content: the set follows them, so a set call
+    """dict_list tells entries apart, in both families, by the range they keep, not by content: the set follows them, so a set call
     gives every entry the table the per-call call gives it"""
     _, off, ln = next(l for l in LISTS if l[0] == "dict_encode_cases:interleaved")
     _, at, tf, th, _ = DictionarySet.layout(off, ln, DICT_FAST | DICT_HC)

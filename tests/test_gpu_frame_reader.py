@@ -41,6 +41,10 @@ class Readers:
         if not host:
             self.d_src = torch.from_numpy(self.src).to(dc.device)
             self.d = [torch.from_numpy(a.astype(np.int64)).to(dc.device) for a in (self.store_off, self.src_off, self.src_len)]
+        else:
+            # the host form works on the context's own stream, which does not wait for torch's: the 0xA5 fill of the stores has to
+            # be over before RESET writes them, or it overwrites the streams it reaches late
+            torch.cuda.synchronize()
         self.call(F.FREAD_RESET, np.zeros(self.n, np.int64), False)
 
     def call(self, op, counts, interactive):
