@@ -57,7 +57,7 @@ namespace K4os.Compression.LZ4.Encoders
 	}
 
 	/// <summary>Many open decoders; every call advances all of them.</summary>
-	public sealed unsafe class LZ4ChainDecoderBatch: IDisposable
+	public sealed unsafe partial class LZ4ChainDecoderBatch: IDisposable
 	{
 		private readonly IntPtr _ctx;
 		private readonly ChainDecoderNative.Record[] _records;

@@ -64,7 +64,7 @@ namespace K4os.Compression.LZ4.Encoders
 	}
 
 	/// <summary>Many open encoders; every call advances all of them.</summary>
-	public sealed unsafe class LZ4EncoderBatch: IDisposable
+	public sealed unsafe partial class LZ4EncoderBatch: IDisposable
 	{
 		private readonly IntPtr _ctx;
 		private readonly ChainEncoderNative.Record[] _records;

@@ -997,6 +997,7 @@ enum k4lz4_chain_decode_op { K4LZ4_CDEC_RUN = 0, K4LZ4_CDEC_RESET = 1 };
 #define K4LZ4_CDEC_NOT_RUN      (-5)   /* a record behind a failing one */
 #define K4LZ4_CDEC_RANGE        (-6)   /* Drain threw: the range is not inside what is ready */
 #define K4LZ4_CDEC_NO_DECODER   (-7)   /* the store was never reset */
+#define K4LZ4_CDEC_DICT_INDEX   (-8)   /* k4lz4_chain_decoder_open_dictset_device: dictIdx[s] is outside the set; the store is untouched */
 
 /* k4lz4_chain_decoder_query: int64 words per stream */
 enum { K4LZ4_CDQ_BYTES_READY = 0,      /* BytesReady */
@@ -1140,6 +1141,51 @@ K4LZ4_API int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encode
                                               const uint32_t *recFlags, int64_t nRecords, const uint64_t *firstRec, const uint32_t *nRec,
                                               uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int32_t *recLoaded,
                                               int32_t *recOut, int64_t *outLen, int64_t n, int op, int flags, void *stream);
+
+/* ---- Chained encoders and decoders opened from a prepared dictionary set -----------------------------------
+ * "Open" makes fresh streams, as RESET does, and primes those that name an entry of a k4lz4_dict_set -- dictIdx[s] = e >= 0; -1: a
+ * fresh stream without a dictionary -- in one call and one launch per side.  d = min(dictLen, 65536) is what the entry keeps.
+ *
+ * Encoder.  Stream s is LZ4Encoder.Create(...)'s object with this done before its first TopupAndEncode: the kept bytes copied to
+ * ring positions [0, d), _inputIndex = _inputPointer = d, and LZ4_loadDict(stream, ring, d) (fast chain) or
+ * LZ4_loadDictHC(stream, ring, d) (HC chain, the level kept).  The dictionary is the stream's PREFIX, not an external dictionary:
+ * the first block follows it in the ring, may extend a match backwards into it, and it stays in the window until 64 KiB of content
+ * have pushed it out.  Fast chain: an entry that keeps fewer than 8 bytes is the empty dictionary -- the ring stays empty, the state
+ * is the zeroed table with currentOffset 65536 and dictSize 0; otherwise index = pointer = dictSize = d and currentOffset = 65536,
+ * and the store's k4lz4_fast_chain_state is the set's table for the entry with those two words.  HC chain: every length counts,
+ * down to one byte (the tables are a function of the ring's bytes), at K4LZ4_L03_HC .. K4LZ4_L09_HC; a stream at K4LZ4_L10_OPT or
+ * above is refused with an entry (the optimal parser has no witness behind a dictionary yet) and opens without
+ * one.  A later plain RESET gives a fresh stream without a dictionary.  A set of either family serves HC encoders and decoders; a
+ * chained fast encoder needs K4LZ4_DICT_FAST in the set.
+ *   k4lz4_chain_encoder_open_plan   host arithmetic, no device: the record as open leaves it for an entry of dictLen bytes
+ *                                   (dictLen < 0: no dictionary).  K4LZ4_E_ARG, the record as it was: NULL, not a record of
+ *                                   k4lz4_chain_encoder_init, dictLen >= 0 on an independent encoder or at K4LZ4_L10_OPT or above
+ *   k4lz4_chain_encoder_open_dictset[_device]   enc, storeOff and dictIdx are host arrays in both forms, store a device pointer.  The
+ *                                   host form is synchronous, _device enqueues on `stream` and returns; the records are advanced at
+ *                                   once.  K4LZ4_E_ARG before anything is enqueued, every record as it was: an index outside
+ *                                   [-1, nDict); an index >= 0 on an independent encoder (LZ4BlockEncoder has no dictionary), on
+ *                                   a stream at K4LZ4_L10_OPT or above, or on a chained fast stream when the set lacks the
+ *                                   fast family or the process is under Enforce32 (k4lz4_set_enforce32; the call takes no flags); a
+ *                                   set on another device than the context; a misaligned store; a record that
+ *                                   k4lz4_chain_encoder_init did not make.
+ *
+ * Decoder.  Stream s is LZ4Decoder.Create(...)'s object after one Inject(kept bytes): geometry, BytesReady, the counters and the
+ * code (K4LZ4_CDEC_INJECT for an independent decoder whose B + 8 is shorter than the entry) are that record's.  outLen[s] is the
+ * bytes injected (0 for -1 or an empty entry) or the code.
+ *   k4lz4_chain_decoder_open_dictset          dec and dictIdx are host arrays; an index outside [-1, nDict) is K4LZ4_E_ARG up front
+ *   k4lz4_chain_decoder_open_dictset_device   dec, storeOff, dictIdx and outLen are device pointers; such an index leaves that store
+ *                                   untouched, sets outLen[s] = K4LZ4_CDEC_DICT_INDEX and makes the next synchronising call return
+ *                                   K4LZ4_E_ARG (as k4lz4_decode_dictset_batch_device) */
+K4LZ4_API int k4lz4_chain_encoder_open_plan(k4lz4_chain_encoder *e, int32_t dictLen);
+K4LZ4_API int k4lz4_chain_encoder_open_dictset(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff,
+                                               const int32_t *dictIdx, const k4lz4_dict_set *set, int64_t n);
+K4LZ4_API int k4lz4_chain_encoder_open_dictset_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff,
+                                                      const int32_t *dictIdx, const k4lz4_dict_set *set, int64_t n, void *stream);
+K4LZ4_API int k4lz4_chain_decoder_open_dictset(k4lz4_ctx *ctx, const k4lz4_chain_decoder *dec, uint8_t *store, const uint64_t *storeOff,
+                                               const int32_t *dictIdx, const k4lz4_dict_set *set, int64_t *outLen, int64_t n);
+K4LZ4_API int k4lz4_chain_decoder_open_dictset_device(k4lz4_ctx *ctx, const k4lz4_chain_decoder *dec, uint8_t *store,
+                                                      const uint64_t *storeOff, const int32_t *dictIdx, const k4lz4_dict_set *set,
+                                                      int64_t *outLen, int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

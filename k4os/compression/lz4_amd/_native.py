@@ -174,6 +174,12 @@ SYMBOLS = {
     "k4lz4_chain_table_rows": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "k4lz4_chain_encode_batch": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int]),
     "k4lz4_chain_encode_batch_device": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    # open from a k4lz4_dict_set: ctx, enc | dec, store, storeOff, dictIdx, set, [outLen,] n [, stream]
+    "k4lz4_chain_encoder_open_plan": (C.c_int, [C.c_void_p, C.c_int32]),
+    "k4lz4_chain_encoder_open_dictset": (C.c_int, [C.c_void_p] * 6 + [C.c_int64]),
+    "k4lz4_chain_encoder_open_dictset_device": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]),
+    "k4lz4_chain_decoder_open_dictset": (C.c_int, [C.c_void_p] * 7 + [C.c_int64]),
+    "k4lz4_chain_decoder_open_dictset_device": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_void_p]),
 }
 
 

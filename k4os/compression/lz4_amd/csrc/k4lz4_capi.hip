@@ -50,6 +50,7 @@
 #include "k4lz4_dict_encode.hpp"
 #include "k4lz4_dict_encode_hc.hpp"
 #include "k4lz4_dict_set.hpp"
+#include "k4lz4_chain_open.hpp"
 
 constexpr int MAX_PARTS = 8;      /* a big host-pointer call is staged, run and brought back in up to this many parts */
 
@@ -4795,6 +4796,17 @@ int k4lz4_chain_table_rows(int kind, int64_t dictLen, int64_t currentOffset, con
     return K4LZ4_OK;
 }
 
+/* is the record one that k4lz4_chain_encoder_init made and the calls advanced? */
+static bool ce_record_ok(const k4lz4_chain_encoder &e)
+{
+    k4lz4_chain_encoder probe;
+    const k4lz4_chain_encoder_settings back{e.kind != 0, e.kind == 2 ? 0 : e.kind == 1 ? std::max<int32_t>(e.level, K4LZ4_L03_HC) : e.level,
+                                            e.blockSize, e.extraBlocks};
+    k4::ce_init(probe, back);
+    return !(e.kind < 0 || e.kind > 2 || probe.kind != e.kind || probe.blockSize != e.blockSize || probe.ringBytes != e.ringBytes ||
+             probe.storeBytes != e.storeBytes || e.index < 0 || e.index > e.pointer || e.pointer > e.ringBytes);
+}
+
 int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
                                     const uint64_t *recOff, const uint32_t *recLen, const uint32_t *recFlags, int64_t nRecords,
                                     const uint64_t *firstRec, const uint32_t *nRec, uint8_t *dst, const uint64_t *dstOff,
@@ -4809,13 +4821,7 @@ int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, ui
     if ((uintptr_t)store & 255u) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: the store is not 256-byte aligned");
     for (int64_t i = 0; i < n; i++) {
         if (storeOff[i] & 255u) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a stream's store is not 256-byte aligned");
-        k4lz4_chain_encoder probe;
-        const k4lz4_chain_encoder_settings back{enc[i].kind != 0, enc[i].kind == 2 ? 0 : enc[i].kind == 1 ? std::max<int32_t>(enc[i].level, K4LZ4_L03_HC) : enc[i].level,
-                                                enc[i].blockSize, enc[i].extraBlocks};
-        k4::ce_init(probe, back);
-        if (enc[i].kind < 0 || enc[i].kind > 2 || probe.kind != enc[i].kind || probe.blockSize != enc[i].blockSize || probe.ringBytes != enc[i].ringBytes ||
-            probe.storeBytes != enc[i].storeBytes || enc[i].index < 0 || enc[i].index > enc[i].pointer || enc[i].pointer > enc[i].ringBytes)
-            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a record was not made by k4lz4_chain_encoder_init");
+        if (!ce_record_ok(enc[i])) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a record was not made by k4lz4_chain_encoder_init");
     }
     const bool x32 = (flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed);
     hipStream_t st = (hipStream_t)stream;
@@ -5087,6 +5093,159 @@ int k4lz4_chain_encode_batch(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *
     for (int64_t i = 0; i < n; i++)
         for (uint32_t r = 0; r < nRec[i]; r++) { recLoaded[firstRec[i] + r] = h_loaded[(size_t)(firstRec[i] + r)]; recOut[firstRec[i] + r] = h_rout[(size_t)(firstRec[i] + r)]; }
     return K4LZ4_OK;
+}
+
+/* ---- chained encoders and decoders opened from a dictionary set (k4lz4_chain_open.hpp) --------------------- */
+/* the record of a fresh stream (what RESET leaves), then LZ4_loadDict's / LZ4_loadDictHC's effect on it for dictLen bytes (< 0: none) */
+static void ce_open_record(k4lz4_chain_encoder &e, int32_t dictLen)
+{
+    e.index = e.pointer = 0; e.currentOffset = e.dictSize = 0; e.taken = e.blocks = 0;
+    if (dictLen < 0 || e.kind == 0) return;
+    const int32_t d = std::min<int32_t>(dictLen, 65536);
+    if (e.kind == 2) {
+        e.currentOffset = k4::OPEN_CURRENT_OFFSET;           /* whatever the length: LZ4_resetStream, currentOffset += 64 KB */
+        if (d < (int32_t)FAMILY_FAST.min_kept) return;       /* below HASH_UNIT nothing is loaded: the ring stays empty too */
+        e.dictSize = (uint32_t)d;
+    }
+    e.index = e.pointer = d;
+}
+
+/* the optimal parser's levels are not opened from a dictionary: the case list's forced 12-byte block left the witness there (the
+ * parser searches a block of exactly MFLIMIT bytes once, LL64.high.cs:823-837; the kernels search none below MFLIMIT + 1), and a
+ * level without a witness is not shipped */
+static bool ce_open_no_witness(const k4lz4_chain_encoder &e) { return e.kind == 1 && e.level >= K4LZ4_L10_OPT; }
+static const char *const CE_OPEN_NO_OPT = ": levels from K4LZ4_L10_OPT on are not opened from a dictionary (L03_HC .. L09_HC and the fast chain are)";
+
+int k4lz4_chain_encoder_open_plan(k4lz4_chain_encoder *e, int32_t dictLen)
+{
+    if (!e || !ce_record_ok(*e)) return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_encoder_open_plan: not a record of k4lz4_chain_encoder_init");
+    if (e->kind == 0 && dictLen >= 0)
+        return fail(nullptr, K4LZ4_E_ARG, "k4lz4_chain_encoder_open_plan: an independent encoder (LZ4BlockEncoder) has no dictionary");
+    if (ce_open_no_witness(*e) && dictLen >= 0) return fail(nullptr, K4LZ4_E_ARG, std::string("k4lz4_chain_encoder_open_plan") + CE_OPEN_NO_OPT);
+    ce_open_record(*e, dictLen);
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_encoder_open_dictset_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff,
+                                            const int32_t *dictIdx, const k4lz4_dict_set *set, int64_t n, void *stream)
+{
+    const char *who = "k4lz4_chain_encoder_open_dictset";
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && (!enc || !store || !storeOff || !dictIdx || !set))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    if (set->device != ctx->device) return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": the set lives on another device than the context");
+    if ((uintptr_t)store & 255u) return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": the store is not 256-byte aligned");
+    const bool x32 = g_enforce32.load(std::memory_order_relaxed) != 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (storeOff[i] & 255u) return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": a stream's store is not 256-byte aligned");
+        if (!ce_record_ok(enc[i])) return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": a record was not made by k4lz4_chain_encoder_init");
+        const int32_t di = dictIdx[i];
+        if (di < -1 || di >= set->nDict) return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": a dictIdx outside the set");
+        if (di < 0) continue;
+        if (enc[i].kind == 0) return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": an independent encoder (LZ4BlockEncoder) has no dictionary");
+        if (ce_open_no_witness(enc[i])) return fail(ctx, K4LZ4_E_ARG, std::string(who) + CE_OPEN_NO_OPT);
+        if (enc[i].kind == 2 && !set->fast.on)
+            return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": a chained fast encoder needs a set created with K4LZ4_DICT_FAST");
+        if (enc[i].kind == 2 && x32)
+            return fail(ctx, K4LZ4_E_ARG, std::string(who) + ": the 32-bit engine's chained encoder (LZ4Codec.Enforce32) is not supported");
+    }
+    /* ---- the plan: host arithmetic, nothing enqueued yet */
+    std::vector<k4::CeOpenStream> rows((size_t)n);
+    std::vector<k4lz4_chain_encoder> after(enc, enc + n);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t di = dictIdx[i];
+        k4lz4_chain_encoder &e = after[(size_t)i];
+        ce_open_record(e, di >= 0 ? set->keptLen[(size_t)di] : -1);
+        k4::CeOpenStream &r = rows[(size_t)i];
+        r = k4::CeOpenStream{};
+        r.ring = storeOff[i] + (uint64_t)k4::ce_ring_at(e);
+        r.keptLen = (uint32_t)e.pointer;                     /* what the ring holds in front of the first block */
+        if (r.keptLen) r.kept = set->keptAt[(size_t)di];
+        if (e.kind != 2) continue;
+        r.state = storeOff[i];
+        r.fast = e.dictSize ? 1u : 2u;
+        if (e.dictSize) r.table = (uint64_t)(set->fast.tables - set->buf) + (uint64_t)FAMILY_FAST.table_bytes * set->fast.table[(size_t)di];
+        r.currentOffset = e.currentOffset; r.dictSize = e.dictSize;
+    }
+    const size_t bytes = rows.size() * sizeof(k4::CeOpenStream);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->ev_fw) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fw, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fw));           /* the previous upload of the host plan is over */
+    try { ctx->h_fw.assign(bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, bytes + 64)) != K4LZ4_OK) return rc;
+    memcpy(ctx->h_fw.data(), rows.data(), bytes);
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    K4_HIP(ctx, hipMemcpyAsync(ctx->d_fw, ctx->h_fw.data(), bytes, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
+    hipLaunchKernelGGL(k4::k4_ce_open_kernel, dim3((unsigned)n), dim3(k4::OPEN_WAVE), 0, st, (const k4::CeOpenStream *)ctx->d_fw, store,
+                       (const uint8_t *)set->buf, (long long)n);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    std::copy(after.begin(), after.end(), enc);
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_encoder_open_dictset(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, uint8_t *store, const uint64_t *storeOff, const int32_t *dictIdx,
+                                     const k4lz4_dict_set *set, int64_t n)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    const int rc = k4lz4_chain_encoder_open_dictset_device(ctx, enc, store, storeOff, dictIdx, set, n, ctx->stream);
+    if (rc == K4LZ4_OK && n > 0) K4_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+
+static int cdec_open_args(k4lz4_ctx *ctx, const void *dec, const void *store, const void *storeOff, const void *dictIdx, const k4lz4_dict_set *set,
+                          const void *outLen, int64_t n)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && (!dec || !store || !storeOff || !dictIdx || !set || !outLen))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n > 0 && set->device != ctx->device)
+        return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decoder_open_dictset: the set lives on another device than the context");
+    if (n > 0 && ((uintptr_t)store & 255u)) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decoder_open_dictset: the store is not 256-byte aligned");
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_decoder_open_dictset_device(k4lz4_ctx *ctx, const k4lz4_chain_decoder *dec, uint8_t *store, const uint64_t *storeOff,
+                                            const int32_t *dictIdx, const k4lz4_dict_set *set, int64_t *outLen, int64_t n, void *stream)
+{
+    const int rc = cdec_open_args(ctx, dec, store, storeOff, dictIdx, set, outLen, n);
+    if (rc != K4LZ4_OK || n == 0) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    const k4::CdOpenArgs a{(const k4::CdRecord *)dec, store, storeOff, dictIdx, set->buf, set->dec_off, set->dec_len, outLen, ctx->d_status,
+                           (long long)n, set->nDict};
+    hipLaunchKernelGGL(k4::k4_cdec_open_kernel, dim3((unsigned)n), dim3(k4::OPEN_WAVE), 0, st, a);
+    K4_HIP(ctx, hipGetLastError());
+    mark_busy(ctx, st);
+    return K4LZ4_OK;
+}
+
+int k4lz4_chain_decoder_open_dictset(k4lz4_ctx *ctx, const k4lz4_chain_decoder *dec, uint8_t *store, const uint64_t *storeOff,
+                                     const int32_t *dictIdx, const k4lz4_dict_set *set, int64_t *outLen, int64_t n)
+{
+    int rc = cdec_open_args(ctx, dec, store, storeOff, dictIdx, set, outLen, n);
+    if (rc != K4LZ4_OK || n == 0) return rc;
+    for (int64_t i = 0; i < n; i++) {
+        if (storeOff[i] & 255u) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decoder_open_dictset: a stream's store is not 256-byte aligned");
+        if (dec[i].blockSize != k4::cd_block_size(dec[i].blockSize) || dec[i].extraBlocks < 0 || (dec[i].chaining & ~1) ||
+            dec[i].storeBytes != k4::cd_store_bytes(dec[i].blockSize, dec[i].extraBlocks, dec[i].chaining != 0))
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decoder_open_dictset: a record was not made by k4lz4_chain_decoder_init");
+        if (dictIdx[i] < -1 || dictIdx[i] >= set->nDict) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_decoder_open_dictset: a dictIdx outside the set");
+    }
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    k4lz4_chain_decoder *d_dec;
+    uint64_t *d_store;
+    int32_t *d_idx;
+    int64_t *d_out;
+    s.meta(&d_dec, n, dec); s.meta(&d_store, n, storeOff); s.meta(&d_idx, n, dictIdx); s.meta(&d_out, n);
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = k4lz4_chain_decoder_open_dictset_device(ctx, d_dec, store, d_store, d_idx, set, d_out, n, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outLen, d_out, (size_t)n * 8}});
 }
 
 }  // extern "C"

@@ -279,6 +279,16 @@ class ChainDecoderDevice:
             _dp(out_len), self.n, 1, 0, C.c_void_p(self.dc._stream())))
         return out_len
 
+    def open(self, dict_idx: torch.Tensor, dictionaries, out_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """k4lz4_chain_decoder_open_dictset_device: every store becomes a fresh decoder, and decoder s with dict_idx[s] = e >= 0 (an
+        int32 device tensor; -1: none) one after Inject(the bytes entry e of `dictionaries`, a DictionarySet, keeps).  out_len[s]: the
+        bytes injected or a code; an index outside the set leaves its store untouched and reports CDEC_DICT_INDEX"""
+        out_len = torch.empty(self.n, dtype=torch.int64, device=self.dc.device) if out_len is None else out_len
+        self.dc.ctx.check(self.dc.lib.k4lz4_chain_decoder_open_dictset_device(
+            self.dc.ctx.handle, _dp(self.records), _dp(self.store), _dp(self.store_off), _dp(dict_idx), dictionaries.handle, _dp(out_len), self.n,
+            C.c_void_p(self.dc._stream())))
+        return out_len
+
     def run(self, src, rec_off, rec_len, rec_block_size, first_rec, n_rec, rec_out, out_len, dst=None, dst_off=None, dst_cap=None):
         """one run per decoder: decoder s owns records first_rec[s] .. + n_rec[s] of the table (rec_off uint64, rec_len uint32 with
         bit 31 = Inject, rec_block_size int32 or None).  With dst / dst_off / dst_cap (uint64) the records' bytes are drained.
@@ -335,6 +345,16 @@ class ChainEncoderDevice:
         self.dc.ctx.check(self.dc.lib.k4lz4_chain_encode_batch_device(
             self.dc.ctx.handle, self.records, C.c_void_p(self._base), self.store_off.ctypes.data, None, None, None, None, 0, None, None, None, None,
             None, None, None, None, self.n, 1, 0, C.c_void_p(self.dc._stream())))
+
+    def open(self, dict_idx, dictionaries) -> None:
+        """k4lz4_chain_encoder_open_dictset_device: every encoder becomes a fresh one, and encoder s with dict_idx[s] = e >= 0 (a host
+        array; -1: none) starts with the bytes entry e of `dictionaries` (a DictionarySet) keeps as its prefix"""
+        idx = np.ascontiguousarray(dict_idx, np.int32)
+        if idx.size != self.n:
+            raise ValueError("dict_idx must have one entry per encoder")
+        self.dc.ctx.check(self.dc.lib.k4lz4_chain_encoder_open_dictset_device(
+            self.dc.ctx.handle, self.records, C.c_void_p(self._base), self.store_off.ctypes.data, idx.ctypes.data, dictionaries.handle, self.n,
+            C.c_void_p(self.dc._stream())))
 
     def run(self, src, rec_off, rec_len, rec_flags, first_rec, n_rec, dst, dst_off, dst_cap, rec_loaded, rec_out, out_len, flags: int = 0):
         """one run per encoder: encoder s owns records first_rec[s] .. + n_rec[s] of the table (rec_off uint64, rec_len and rec_flags

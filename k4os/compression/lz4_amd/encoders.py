@@ -617,6 +617,7 @@ def DecodeAndDrain(decoder: Union[LZ4BlockDecoder, "LZ4ChainDecoder"], source, t
 CDEC_RUN, CDEC_RESET = 0, 1
 CDEC_DRAIN = 1
 CDEC_DECODE, CDEC_INJECT, CDEC_BLOCK_SIZE, CDEC_TARGET, CDEC_NOT_RUN, CDEC_RANGE, CDEC_NO_DECODER = -1, -2, -3, -4, -5, -6, -7
+CDEC_DICT_INDEX = -8
 CDQ_BYTES_READY, CDQ_BLOCK_SIZE, CDQ_RECORDS, CDQ_BYTES, CDQ_CODE, CDQ_CHAINING, CDQ_EXTRA_BLOCKS, CDQ_MOVES, CDQ_WORDS = range(9)
 CDEC_INJECT_BIT = 0x80000000
 
@@ -688,6 +689,18 @@ class LZ4ChainDecoderBatch:
         self.ctx.check(self.lib.k4lz4_chain_decode_batch(self.ctx.handle, recs, _C.c_void_p(self._base), off.ctypes.data, None, None, None, None, 0,
                                                          None, None, None, None, None, None, out.ctypes.data, idx.size, CDEC_RESET, 0))
 
+    def open(self, dict_idx, dictionaries) -> List[int]:
+        """k4lz4_chain_decoder_open_dictset: every store becomes a fresh decoder, and decoder s with dict_idx[s] = e >= 0 one after
+        Inject(the bytes entry e of `dictionaries`, a DictionarySet, keeps); -1: no dictionary.  -> per decoder the bytes injected, or
+        CDEC_INJECT (an independent decoder shorter than the entry)"""
+        idx = np.ascontiguousarray(dict_idx, np.int32)
+        if idx.size != self.n:
+            raise ValueError("dict_idx must have one entry per decoder")
+        out = np.zeros(max(self.n, 1), np.int64)
+        self.ctx.check(self.lib.k4lz4_chain_decoder_open_dictset(self.ctx.handle, self.records, _C.c_void_p(self._base), self.store_off.ctypes.data,
+                                                                 idx.ctypes.data, dictionaries.handle, out.ctypes.data, self.n))
+        return out[:self.n].tolist()
+
     def Run(self, records, drain: bool = False, caps=None):
         """records[s]: the run of decoder s, a list of (inject, bytes, blockSize) -- Decode(source, length, blockSize), or Inject where
         the first word is true; an empty list leaves the decoder untouched.  With drain the bytes of every record are appended to a
@@ -734,9 +747,15 @@ class LZ4ChainDecoder:
     """Decoder for dependent blocks (LZ4ChainDecoder.cs): the ILZ4Decoder of one stream, a batch of one underneath.  With
     chaining=False the same store is an LZ4BlockDecoder on the device (LZ4Decoder.Create uses the host class for that)."""
 
-    def __init__(self, blockSize: int = 65536, extraBlocks: int = 0, ctx: Optional[_native.Context] = None, chaining: bool = True):
+    def __init__(self, blockSize: int = 65536, extraBlocks: int = 0, ctx: Optional[_native.Context] = None, chaining: bool = True,
+                 dictionary=None):
+        """dictionary: (DictionarySet, index) -- the decoder starts as one that was given Inject(the entry's kept bytes)"""
         self._batch = LZ4ChainDecoderBatch([(chaining, blockSize, extraBlocks)], ctx)
         self._block_size = int(self._batch.records[0].blockSize)
+        if dictionary is not None:
+            code = self._batch.open([int(dictionary[1])], dictionary[0])[0]
+            if code < 0:
+                raise InvalidOperationException(f"code {code}")
 
     @property
     def BlockSize(self) -> int:
@@ -780,7 +799,11 @@ class LZ4Decoder:
     """Encoders/LZ4Decoder.cs"""
 
     @staticmethod
-    def Create(chaining: bool, blockSize: int, extraBlocks: int = 0):
+    def Create(chaining: bool, blockSize: int, extraBlocks: int = 0, dictionary=None):
+        """dictionary: (DictionarySet, index): the decoder after one Inject of the entry's kept bytes, taken from the set on the
+        device (an independent decoder then lives on the device too)"""
+        if dictionary is not None:
+            return LZ4ChainDecoder(blockSize, extraBlocks, getattr(dictionary[0], "ctx", None), bool(chaining), dictionary)
         return LZ4ChainDecoder(blockSize, extraBlocks) if chaining else LZ4BlockDecoder(blockSize)
 
 
@@ -860,6 +883,16 @@ class LZ4EncoderBatch:
             self.ctx.check(self.lib.k4lz4_chain_encode_batch(self.ctx.handle, self.records, _C.c_void_p(self._base), self.store_off.ctypes.data,
                                                              None, None, None, None, 0, None, None, None, None, None, None, None, None, self.n,
                                                              CENC_RESET, 0))
+
+    def open(self, dict_idx, dictionaries) -> None:
+        """k4lz4_chain_encoder_open_dictset: every encoder becomes a fresh one, and encoder s with dict_idx[s] = e >= 0 starts with
+        the bytes entry e of `dictionaries` (a DictionarySet) keeps as its prefix -- LZ4_loadDict / LZ4_loadDictHC on the ring; -1: no
+        dictionary"""
+        idx = np.ascontiguousarray(dict_idx, np.int32)
+        if idx.size != self.n:
+            raise ValueError("dict_idx must have one entry per encoder")
+        self.ctx.check(self.lib.k4lz4_chain_encoder_open_dictset(self.ctx.handle, self.records, _C.c_void_p(self._base), self.store_off.ctypes.data,
+                                                                 idx.ctypes.data, dictionaries.handle, self.n))
 
     def Bound(self, records) -> List[int]:
         out = []
@@ -947,9 +980,13 @@ class LZ4ChainEncoder:
     """The ILZ4Encoder of one stream over a batch of one (k4lz4_chain_encode_batch): what LZ4Encoder.Create returns.  Topup keeps its
     bytes on the host until the Encode that takes them -- one record, Topup and a forced Encode -- so the two work as separate calls."""
 
-    def __init__(self, chaining: bool, level: LZ4Level, blockSize: int, extraBlocks: int = 0, ctx: Optional[_native.Context] = None):
-        self._batch = LZ4EncoderBatch([(chaining, level, blockSize, extraBlocks)], ctx)
+    def __init__(self, chaining: bool, level: LZ4Level, blockSize: int, extraBlocks: int = 0, ctx: Optional[_native.Context] = None,
+                 dictionary=None):
+        """dictionary: (DictionarySet, index) -- the stream starts with the entry's kept bytes as its prefix"""
+        self._batch = LZ4EncoderBatch([(chaining, level, blockSize, extraBlocks)], ctx or getattr(dictionary and dictionary[0], "ctx", None))
         self._pending: List[np.ndarray] = []
+        if dictionary is not None:
+            self._batch.open([int(dictionary[1])], dictionary[0])
 
     @property
     def BlockSize(self) -> int:
@@ -996,5 +1033,6 @@ class LZ4Encoder:
     """Encoders/LZ4Encoder.cs"""
 
     @staticmethod
-    def Create(chaining: bool, level: LZ4Level, blockSize: int, extraBlocks: int = 0, ctx: Optional[_native.Context] = None) -> LZ4ChainEncoder:
-        return LZ4ChainEncoder(chaining, level, blockSize, extraBlocks, ctx)
+    def Create(chaining: bool, level: LZ4Level, blockSize: int, extraBlocks: int = 0, ctx: Optional[_native.Context] = None,
+               dictionary=None) -> LZ4ChainEncoder:
+        return LZ4ChainEncoder(chaining, level, blockSize, extraBlocks, ctx, dictionary)
