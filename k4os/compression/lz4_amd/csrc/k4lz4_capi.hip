@@ -140,7 +140,9 @@ struct k4lz4_ctx {
     bool parse_persist = true;            /* K4LZ4_NO_PERSIST: batches beyond one residency in launches of one residency each (round 5) instead of one persistent launch */
     bool parse_inline_emit = true;        /* K4LZ4_NO_INLINE_EMIT: the blocks' bytes by k4_emit_kernel behind the parse instead of by the parsing waves themselves */
     bool parse_migrate = true;            /* K4LZ4_NO_MIGRATE: blocks whose table lives in memory stay there (k4lz4_parse.hpp, ParseCtl) */
-    bool parse_pcost = false;             /* K4LZ4_PCOST: the parse's own cost estimate (k4_pcost_kernel) orders the blocks; measured: costs more than it gains */
+    bool parse_pcost = true;              /* K4LZ4_NO_PCOST: the one-kernel encoder's sequence count over 256 bytes orders the two-step encoder's blocks, as before
+                                           * the parse's own estimate (k4lz4_parse.hpp, ParseCost) did; K4LZ4_PCOST, which used to switch that on, still may be set */
+    k4::ParseCost pcost_fit = k4::PCOST_FIT;      /* K4LZ4_PCOST_FIT: sample,max_rounds,round,slow,seq,group,lazy,long,base (the fields of ParseCost) for trying another fit */
     int parse_waves = 16;                 /* K4LZ4_PARSE_WAVES: blocks per workgroup (= per CU) of the parse kernel, at most PARSE_MAX_WAVES */
     bool trace = false;         /* K4LZ4_TRACE: host-pointer calls print where their time went (stderr) */
     /* chained HC streams (k4lz4_encode_hc_chain_batch*): the block table, built on the host, and its copy on the device; the
@@ -696,11 +698,20 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
             a.dictMode = dd->mode ? dd->mode + first : nullptr;
         }
         if (reorder && parse_path && kind == KIND_ENCODE && ctx->parse_pcost) {
-            /* the two-kernel encoder's own estimate and order (k4lz4_parse.hpp, k4_pcost_kernel) */
+            /* the two-kernel encoder's own estimate and order (k4lz4_parse.hpp, ParseCost): one workgroup of sixteen waves per CU at
+             * most, its seven tables in memory at the front of the parse kernels' scratch (which those kernels, behind it on the
+             * stream, lay out anew) */
+            const int64_t wgs = std::min<int64_t>((cnt + k4::PARSE_MAX_WAVES - 1) / k4::PARSE_MAX_WAVES, ctx->cu_count);
+            const size_t need = (size_t)wgs * (k4::PARSE_MAX_WAVES - k4::PARSE_LDS_TABLES) * 16384;
+            if (need > ctx->d_parse_cap) K4_HIP(ctx, hipStreamSynchronize(stream));
+            const int rcp = grow(ctx, &ctx->d_parse, &ctx->d_parse_cap, need, false);
+            if (rcp != K4LZ4_OK) return rcp;
             a.cost = d_cost; a.hist = d_hist; a.order_out = d_order;
             K4_HIP(ctx, hipMemsetAsync(d_hist, 0, 2 * k4::PCOST_BUCKETS * 4, stream));
-            hipLaunchKernelGGL(k4::k4_pcost_kernel, dim3((unsigned)((cnt + k4::PCOST_WAVES_PER_WG - 1) / k4::PCOST_WAVES_PER_WG)), dim3(64 * k4::PCOST_WAVES_PER_WG), 0, stream, a);
-            hipLaunchKernelGGL(k4::k4_porder_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a);
+            k4::ParseCost pc = ctx->pcost_fit;
+            pc.tables = (uint32_t *)ctx->d_parse;
+            hipLaunchKernelGGL(static_cast<void (*)(k4::BatchArgs, k4::ParseCost)>(k4::k4_cost_kernel), dim3((unsigned)wgs), dim3(64 * k4::PARSE_MAX_WAVES), 0, stream, a, pc);
+            hipLaunchKernelGGL(k4::k4_order_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, 0xffffffffu, 1);
             a.order = d_order;
         }
         else if (reorder) {
@@ -2702,7 +2713,12 @@ int k4lz4_ctx_create(k4lz4_ctx **out, int device)
     ctx->parse_big = getenv("K4LZ4_NO_PARSE_BIG") == nullptr;
     ctx->parse_seg = getenv("K4LZ4_NO_PARSE_SEG") == nullptr;
     ctx->hc_records = getenv("K4LZ4_NO_HC_RECORDS") == nullptr;
-    ctx->parse_pcost = getenv("K4LZ4_PCOST") != nullptr;
+    ctx->parse_pcost = getenv("K4LZ4_NO_PCOST") == nullptr || getenv("K4LZ4_PCOST") != nullptr;
+    if (const char *e = getenv("K4LZ4_PCOST_FIT")) {
+        unsigned v[9];
+        if (sscanf(e, "%u,%u,%u,%u,%u,%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8]) == 9 && v[0] >= k4::PARSE_MIN_LEN && v[0] < 65536u)
+            ctx->pcost_fit = k4::ParseCost{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], nullptr};
+    }
     ctx->parse_migrate = getenv("K4LZ4_NO_MIGRATE") == nullptr;
     ctx->parse_inline_emit = getenv("K4LZ4_NO_INLINE_EMIT") == nullptr;
     if (const char *e = getenv("K4LZ4_PARSE_WAVES")) ctx->parse_waves = std::max(1, std::min(k4::PARSE_MAX_WAVES, atoi(e)));

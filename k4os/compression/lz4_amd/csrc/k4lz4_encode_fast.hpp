@@ -993,13 +993,16 @@ __device__ __forceinline__ int codec_encode_result(int src_len, int ret, int fla
  * estimated by running the encoder without output over its first COST_SAMPLE bytes and scaling
  * the sequence count to the block length; blocks are then bucketed by cost (k4_order_kernel).
  */
-/* The sample: 256 bytes for the two-step encoder's batches (blocks under 64 KiB, all resident at once: the order only decides which
+/* (The two-step encoder's batches are ordered by its own estimate since round 7 -- k4lz4_parse.hpp, ParseCost --; what follows about
+ * them holds behind K4LZ4_NO_PCOST.)
+ * The sample: 256 bytes for the two-step encoder's batches (blocks under 64 KiB, all resident at once: the order only decides which
  * nine of a workgroup's sixteen start with their table in LDS, and the estimate is part of the timed call -- 512 bytes cost the bench
  * batch 1 % more than their better order brings), 512 for everything else (ragged batches of pickles: the split between the
  * kernels and the longest-first order hang on it; with 256 rank 0's share of configs[3] comes out at 96 or at 120 ms from one
  * run to the next, with 512 at 98-106, gpurun_out/r96). */
 constexpr int COST_SAMPLE = 512, COST_SAMPLE_PARSE = 256;
 constexpr int COST_BUCKETS = 64;
+constexpr int COST_BUCKETS_FINE = 512;         /* the two-step encoder's own estimate (k4lz4_parse.hpp) */
 
 __device__ __forceinline__ uint32_t cost_bucket(unsigned long long cost)
 {
@@ -1043,14 +1046,50 @@ __device__ __forceinline__ unsigned long long bucket_cost(uint32_t bkt)
     return ((bkt & 1u) ? 7ull : 5ull) << (l - 1u);            /* 1.25 x 2^l / 1.75 x 2^l, times four */
 }
 
+/* How many blocks lie in the buckets above bucket k, for the NB counts at hist: before[k] + above[(NB - 1 - k) >> 6].  Every wave of
+ * the workgroup takes 64 counts at a time from the expensive end into its lanes, scans them there (wave_inclusive_scan) and leaves
+ * the chunk's total in LDS; the first wave then scans the totals.  before: NB words of LDS, above: NB / 64.  Called by all threads. */
+template <int NB>
+__device__ __forceinline__ void suffix_counts(const uint32_t *hist, uint32_t *before, uint32_t *above)
+{
+    static_assert(NB % 64 == 0 && NB <= 4096, "whole waves of counts; their totals fit one wave");
+    const uint32_t lane = (uint32_t)lane_id(), wave = uni(threadIdx.x >> 6), waves = blockDim.x >> 6;
+    for (uint32_t c = wave; c < (uint32_t)NB / 64u; c += waves) {
+        const uint32_t k = (uint32_t)NB - 1u - (64u * c + lane);
+        const uint32_t v = hist[k], incl = wave_inclusive_scan(v);
+        before[k] = incl - v;
+        if (lane == 63u) above[c] = incl;
+    }
+    __syncthreads();
+    if (wave == 0u) {
+        const uint32_t v = lane < (uint32_t)NB / 64u ? above[lane] : 0u, incl = wave_inclusive_scan(v);
+        if (lane < (uint32_t)NB / 64u) above[lane] = incl - v;
+    }
+    __syncthreads();
+}
+
 /* order[] = block indices, most expensive bucket first.  Its first thread also says where the second encoder kernel's part of
  * that order begins (hist[2 * COST_BUCKETS]): the most expensive blocks that hold `first` hundredths of the batch's COST go
  * to the LDS-table kernel -- for blocks of one size that is the same share of their number, for a ragged batch a few big
  * ones --, but never fewer than `total` of them (one residency of that kernel), when the batch has that many.
  * `lds_max`: the number of slots the host launched the LDS-table kernel with -- the count decided here never exceeds it
- * (the rounding-up of a bucket's part could otherwise give one more, and that block would be encoded by neither kernel). */
-__global__ __launch_bounds__(256) void k4_order_kernel(BatchArgs a, uint32_t lds_max = 0xffffffffu)
+ * (the rounding-up of a bucket's part could otherwise give one more, and that block would be encoded by neither kernel).
+ * `fine`: the costs are the two-step encoder's (k4lz4_parse.hpp, pcost_bucket: COST_BUCKETS_FINE buckets, no split). */
+template <int NB>
+__device__ __forceinline__ void order_by_bucket(const BatchArgs &a)
 {
+    __shared__ uint32_t before[NB], above[NB / 64];
+    suffix_counts<NB>(a.hist, before, above);
+    const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (b >= a.n) return;
+    const uint32_t bkt = a.cost[b];
+    const uint32_t pos = before[bkt] + above[((uint32_t)NB - 1u - bkt) >> 6] + atomicAdd(&a.hist[NB + bkt], 1u);
+    a.order_out[pos] = (uint32_t)b;
+}
+
+__global__ __launch_bounds__(256) void k4_order_kernel(BatchArgs a, uint32_t lds_max = 0xffffffffu, int fine = 0)
+{
+    if (fine) { order_by_bucket<COST_BUCKETS_FINE>(a); return; }
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.first != 0u) {
         unsigned long long all = 0;
         for (uint32_t k = 0; k < (uint32_t)COST_BUCKETS; k++) all += (unsigned long long)a.hist[k] * bucket_cost(k);
@@ -1067,13 +1106,7 @@ __global__ __launch_bounds__(256) void k4_order_kernel(BatchArgs a, uint32_t lds
         if (cnt > (unsigned long long)lds_max) cnt = (unsigned long long)lds_max;
         a.hist[2 * COST_BUCKETS] = (uint32_t)cnt;
     }
-    const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (b >= a.n) return;
-    const uint32_t bkt = a.cost[b];
-    uint32_t before = 0;
-    for (uint32_t k = bkt + 1u; k < (uint32_t)COST_BUCKETS; k++) before += a.hist[k];
-    const uint32_t pos = before + atomicAdd(&a.hist[COST_BUCKETS + bkt], 1u);
-    a.order_out[pos] = (uint32_t)b;
+    order_by_bucket<COST_BUCKETS>(a);
 }
 
 constexpr int ENCODE_WAVES_PER_WG = 2;      /* blocks per workgroup; measured 1: 53.1, 2: 54.2, 4: 54.3 GiB/s on the bench batch */

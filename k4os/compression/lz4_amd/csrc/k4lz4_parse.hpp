@@ -147,7 +147,7 @@ constexpr uint32_t HOP_LONG = 0x100u, HOP_LAZY = 0x200u, HOP_END = 0x400u, HOP_I
  * LL64.LZ4_compress_generic (byU16, noDict, acceleration 1) for one block, sequences only.  `tab`: the block's 8192 x u16
  * table (LDS, or global memory with GT), `seen`: PARSE_SEEN_DWORDS dwords of LDS.  Returns the number of records written.
  */
-struct ParseStats { uint32_t rounds, slow, groups, lazies, longs; };
+struct ParseStats { uint32_t rounds, slow, groups, lazies, longs; uint32_t covered, max_rounds; };      /* covered: where a DRY run that was given max_rounds != 0 stopped */
 constexpr int PARSE_FLUSH = -2;      /* ParseCtl::claimed: the record slot is nearly full -- write the records out, then resume */
 
 /* A block whose table lives in memory may move into an LDS table that another block of its workgroup has finished with: the
@@ -188,7 +188,7 @@ __device__ __forceinline__ uint32_t parse_block(const uint8_t *src, const uint32
     Table tab;
     tab.t = (decltype(tab.t))tabv;
     constexpr uint32_t SEEN_SHIFT = TT == 1 ? 1u : 0u;          /* hash value -> bit of `seen` */
-    ParseStats st = {0u, 0u, 0u, 0u, 0u};
+    ParseStats st = {0u, 0u, 0u, 0u, 0u, U, DRY && stats ? uni(stats->max_rounds) : 0u};
 #define K4_ST(field, v) do { if (DRY) st.field += (v); } while (0)
 #ifdef K4_PARSE_PROF
     /* diagnostic build: cycles per phase of a round (each phase ends by draining its own memory traffic) and event counts */
@@ -990,6 +990,7 @@ __device__ __forceinline__ uint32_t parse_block(const uint8_t *src, const uint32
                 }
             }
         }
+        if (DRY && st.max_rounds && uni(st.rounds) >= st.max_rounds) { st.covered = uni(c); break; }      /* (the cost estimate: a sample of so many rounds) */
         const bool plain = sj == 0u && c + 64u * (uint32_t)K + 28u <= U;
         /* (the search's limit: probes up to sbase + 65 are contiguous, the window ends at c + 63) */
         if (K == 1 && plain && c + 63u <= sbase + 65u) {
@@ -1214,63 +1215,87 @@ __global__ __launch_bounds__(64 * PARSE_MAX_WAVES) void k4_parse_big_kernel(Batc
  * block whose table lives in memory pays about two more trips to memory per round (the look-up, the wait for its puts), so the
  * seven of sixteen waves per workgroup that have no LDS table should get the blocks that are through soonest WITH that penalty --
  * few rounds count for more there than few sequences.  The estimate: the parse itself, without output, over the block's first
- * bytes, in cycles by what it met (rounds, sequences, groups of equal hashes, stops for them, matches counted in memory; weights
- * fitted to the phase probe, profiles/r5*_parse_probe.txt), scaled to the block's length, plus the penalty per round.  The order
- * is by that figure, most expensive first, in 16 steps per octave.
+ * bytes, in nanoseconds by what it met (rounds, strided rounds, sequences, groups of equal hashes, stops for them, matches counted
+ * in memory), scaled to the block's length, plus what every block of that length takes.  The weights are a least-squares fit
+ * (none negative) of the sample's counts to the time the 384 different blocks of the bench batch took with an LDS table by their
+ * stamps (experiments/parse_cost_order/); a start in memory multiplied those times by 1.13 whatever the class, so it does not
+ * change the order and is left out.  The order is by that figure, most expensive first, in 32 steps per octave: the classes that
+ * have to be told apart lie 4-10 % apart.
+ *
+ * The sample is short because the estimate is part of the timed call, and a round of the parse takes its 3-5 us however few
+ * waves a CU holds: the kernel lasts as long as the sample with the most rounds.  So every block of a residency of the parse kernel
+ * is estimated at once, in that kernel's shape -- sixteen waves per workgroup, nine tables in LDS, seven in memory (`tables`,
+ * 16 KiB per wave) --, not nine per CU and then the rest; and the sample ends after `max_rounds` rounds wherever they have got to
+ * in its `sample` bytes (ParseStats::covered: data without matches, where the search strides, is through 2 KiB in fewer), which
+ * bounds the kernel's time and costs the fit nothing.  Measured per sample and round limit: experiments/parse_cost_order/.
  */
-constexpr uint32_t PCOST_SAMPLE = 3072u;
-constexpr int PCOST_BUCKETS = 512;               /* 16 per octave from 2^8 on */
-constexpr int PCOST_WAVES_PER_WG = 8;
+struct ParseCost {
+    uint32_t sample, max_rounds;                       /* the bytes of every block that are parsed, and the rounds after which that stops, if sooner */
+    uint32_t round, slow, seq, group, lazy, lng;       /* ns per event of a 64 KiB block's parse, for events counted in `sample` bytes */
+    uint32_t base;                                     /* ns per 64 KiB whatever they hold */
+    uint32_t *tables;                                  /* (PARSE_MAX_WAVES - PARSE_LDS_TABLES) x 16 KiB per workgroup of the launch */
+};
+constexpr ParseCost PCOST_FIT = {2048u, 10u, 999u, 0u, 104u, 0u, 18u, 181u, 835300u, nullptr};
+constexpr int PCOST_BUCKETS = COST_BUCKETS_FINE;               /* 32 per octave from 2^14 ns on */
+constexpr int PCOST_WAVES_PER_WG = PARSE_MAX_WAVES;
 
 __device__ __forceinline__ uint32_t pcost_bucket(unsigned long long cost)
 {
-    if (cost < 256ull) return 0u;
+    if (cost < 16384ull) return 0u;
     const uint32_t l = 63u - (uint32_t)__clzll((long long)cost);
-    const uint32_t b = 16u * (l - 8u) + (uint32_t)((cost >> (l - 4u)) & 15ull) + 1u;
+    const uint32_t b = 32u * (l - 14u) + (uint32_t)((cost >> (l - 5u)) & 31ull) + 1u;
     return b < (uint32_t)PCOST_BUCKETS ? b : (uint32_t)PCOST_BUCKETS - 1u;
 }
 
-__global__ __launch_bounds__(64 * PCOST_WAVES_PER_WG) void k4_pcost_kernel(BatchArgs a)
+/* one block per wave and turn: a.cost[b] = bucket of block b, a.hist[bucket]++ (`far`: the workgroup's tables in memory) */
+__device__ __forceinline__ void parse_cost_body(const BatchArgs &a, const ParseCost &pc, uint32_t *lds, uint32_t *far)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[PCOST_WAVES_PER_WG][4096 + PARSE_SEEN_DWORDS];
     const int lane = lane_id();
     const uint32_t wave = uni(threadIdx.x >> 6);
-    const long long b = (long long)blockIdx.x * PCOST_WAVES_PER_WG + (long long)wave;
-    if (b >= a.n) return;
-    const int src_len = a.srcLen[b];
-    unsigned long long cost = 0ull;
-    if (src_len >= (int)PARSE_MIN_LEN && src_len < LIMIT_64K) {
-        const uint32_t sample = (uint32_t)src_len < PCOST_SAMPLE ? (uint32_t)src_len : PCOST_SAMPLE;
-        ParseStats st;
-        const uint32_t nseq = parse_block<1, false, true>(a.src + a.srcOff[b], sample, nullptr, (uint16_t *)lds[wave], lds[wave] + 4096, lane, nullptr, &st);
-        const unsigned long long cyc = 6500ull * st.rounds + 3000ull * st.slow + 120ull * nseq + 150ull * st.groups + 480ull * st.lazies + 1500ull * st.longs;
-        cost = cyc * (unsigned long long)(uint32_t)src_len / sample;
-    } else if (src_len > 0) {
-        cost = 120ull * (unsigned long long)(uint32_t)src_len;              /* (the one-kernel encoder's blocks: by length) */
-    }
-    if (lane == 0) {
-        const uint32_t bkt = pcost_bucket(cost);
-        a.cost[b] = bkt;
-        atomicAdd(&a.hist[bkt], 1u);
+    uint32_t *seen = lds + 4096u * (uint32_t)PARSE_LDS_TABLES + (uint32_t)PARSE_SEEN_DWORDS * wave;
+    for (long long b = (long long)blockIdx.x * PARSE_MAX_WAVES + (long long)wave; b < a.n; b += (long long)gridDim.x * PARSE_MAX_WAVES) {
+        const int src_len = a.srcLen[b];
+        unsigned long long cost = 0ull;
+        if (src_len >= (int)PARSE_MIN_LEN && src_len < LIMIT_64K) {
+            const uint32_t sample = (uint32_t)src_len < pc.sample ? (uint32_t)src_len : pc.sample;
+            const uint8_t *src = a.src + a.srcOff[b];
+            ParseStats st;
+            st.max_rounds = pc.max_rounds;
+            uint32_t nseq;
+            if (wave < (uint32_t)PARSE_LDS_TABLES) nseq = parse_block<1, false, true>(src, sample, nullptr, lds + 4096u * wave, seen, lane, nullptr, &st);
+            else nseq = parse_block<1, true, true>(src, sample, nullptr, far + 4096u * (wave - (uint32_t)PARSE_LDS_TABLES), seen, lane, nullptr, &st);
+            const unsigned long long ns = (unsigned long long)pc.round * st.rounds + (unsigned long long)pc.slow * st.slow + (unsigned long long)pc.seq * nseq +
+                                          (unsigned long long)pc.group * st.groups + (unsigned long long)pc.lazy * st.lazies + (unsigned long long)pc.lng * st.longs;
+            cost = ns * (unsigned long long)(uint32_t)src_len / (st.covered ? st.covered : 1u) + (((unsigned long long)pc.base * (unsigned long long)(uint32_t)src_len) >> 16);
+        } else if (src_len > 0) {
+            cost = 40ull * (unsigned long long)(uint32_t)src_len;               /* (the one-kernel encoder's blocks: by length, ~2.6 ms per 64 KiB) */
+        }
+        if (lane == 0) {
+            const uint32_t bkt = pcost_bucket(cost);
+            a.cost[b] = bkt;
+            atomicAdd(&a.hist[bkt], 1u);
+        }
     }
 }
 
-/* order[] = block indices, most expensive bucket first (hist: PCOST_BUCKETS counts, then PCOST_BUCKETS cursors, zeroed) */
-__global__ __launch_bounds__(256) void k4_porder_kernel(BatchArgs a)
+/* the two-step encoder's form of k4_cost_kernel (k4lz4_encode_fast.hpp); at most one workgroup per CU is worth launching */
+__global__ __launch_bounds__(64 * PARSE_MAX_WAVES) void k4_cost_kernel(BatchArgs a, ParseCost pc)
 {
-    __shared__ uint32_t before[PCOST_BUCKETS];
-    for (int k = (int)threadIdx.x; k < PCOST_BUCKETS; k += 256) before[k] = a.hist[k];
-    __syncthreads();
-    if (threadIdx.x == 0) {                     /* suffix sums: blocks in more expensive buckets */
-        uint32_t acc = 0u;
-        for (int k = PCOST_BUCKETS - 1; k >= 0; k--) { const uint32_t c = before[k]; before[k] = acc; acc += c; }
-    }
-    __syncthreads();
-    const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (b >= a.n) return;
-    const uint32_t bkt = a.cost[b];
-    a.order_out[before[bkt] + atomicAdd(&a.hist[PCOST_BUCKETS + bkt], 1u)] = (uint32_t)b;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[4096 * PARSE_LDS_TABLES + PARSE_SEEN_DWORDS * PARSE_MAX_WAVES];
+    parse_cost_body(a, pc, lds, pc.tables + 4096ull * (unsigned long long)(PARSE_MAX_WAVES - PARSE_LDS_TABLES) * (unsigned long long)blockIdx.x);
 }
+
+#ifdef K4_HOST_EMU
+/* the emulator launches the estimate and its order under these names (PCOST_WAVES_PER_WG waves a workgroup, 256 threads), without
+ * tables in memory: static storage of the emulating thread stands in for them */
+inline void k4_pcost_kernel(BatchArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds[4096 * PARSE_LDS_TABLES + PARSE_SEEN_DWORDS * PARSE_MAX_WAVES];
+    __shared__ __attribute__((aligned(16))) uint32_t far[4096 * (PARSE_MAX_WAVES - PARSE_LDS_TABLES)];
+    parse_cost_body(a, PCOST_FIT, lds, far);
+}
+inline void k4_porder_kernel(BatchArgs a) { k4_order_kernel(a, 0xffffffffu, 1); }
+#endif
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 
