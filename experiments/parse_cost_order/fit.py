@@ -17,7 +17,7 @@ ub = np.ascontiguousarray(blocks[uidx])
 off = (np.arange(384, dtype=np.uint64) * bs); lens = np.full(384, bs, np.int32)
 def stats(o, l):
     out = np.zeros((384, 8), np.uint32)
-    lib.study_stats(ub.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_void_p(off.ctypes.data), C.c_void_p(lens.ctypes.data), C.c_longlong(384), C.c_uint32(o), C.c_uint32(l), C.c_void_p(out.ctypes.data), C.c_int(8), C.c_uint32(0))
+    lib.study_stats(ub.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_void_p(off.ctypes.data), C.c_void_p(lens.ctypes.data), C.c_longlong(384), C.c_uint32(o), C.c_uint32(l), C.c_void_p(out.ctypes.data), C.c_int(8), C.c_uint32(0), C.c_int(0))     # (form 0: the block's own table; the sample's: fit_sample_table.py)
     return out[:, :6].astype(np.float64), out[:, 6].astype(np.float64)
 # truth
 b = np.arange(n); u = (b % 12) * 32 + (b // 12) % 32

@@ -699,19 +699,12 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
         }
         if (reorder && parse_path && kind == KIND_ENCODE && ctx->parse_pcost) {
             /* the two-kernel encoder's own estimate and order (k4lz4_parse.hpp, ParseCost): one workgroup of sixteen waves per CU at
-             * most, its seven tables in memory at the front of the parse kernels' scratch (which those kernels, behind it on the
-             * stream, lay out anew) */
+             * most, every wave's table in LDS; the order's workgroups each place a stretch of the batch (k4_order_kernel) */
             const int64_t wgs = std::min<int64_t>((cnt + k4::PARSE_MAX_WAVES - 1) / k4::PARSE_MAX_WAVES, ctx->cu_count);
-            const size_t need = (size_t)wgs * (k4::PARSE_MAX_WAVES - k4::PARSE_LDS_TABLES) * 16384;
-            if (need > ctx->d_parse_cap) K4_HIP(ctx, hipStreamSynchronize(stream));
-            const int rcp = grow(ctx, &ctx->d_parse, &ctx->d_parse_cap, need, false);
-            if (rcp != K4LZ4_OK) return rcp;
             a.cost = d_cost; a.hist = d_hist; a.order_out = d_order;
-            K4_HIP(ctx, hipMemsetAsync(d_hist, 0, 2 * k4::PCOST_BUCKETS * 4, stream));
-            k4::ParseCost pc = ctx->pcost_fit;
-            pc.tables = (uint32_t *)ctx->d_parse;
-            hipLaunchKernelGGL(static_cast<void (*)(k4::BatchArgs, k4::ParseCost)>(k4::k4_cost_kernel), dim3((unsigned)wgs), dim3(64 * k4::PARSE_MAX_WAVES), 0, stream, a, pc);
-            hipLaunchKernelGGL(k4::k4_order_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, 0xffffffffu, 1);
+            K4_HIP(ctx, hipMemsetAsync(d_hist, 0, k4::PCOST_BUCKETS * 4, stream));
+            hipLaunchKernelGGL(static_cast<void (*)(k4::BatchArgs, k4::ParseCost)>(k4::k4_cost_kernel), dim3((unsigned)wgs), dim3(64 * k4::PARSE_MAX_WAVES), 0, stream, a, ctx->pcost_fit);
+            hipLaunchKernelGGL(k4::k4_order_kernel, dim3(k4::order_workgroups(cnt)), dim3(256), 0, stream, a, 0xffffffffu, 1);
             a.order = d_order;
         }
         else if (reorder) {
@@ -726,7 +719,7 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
             k4::BatchArgs ao = a;
             ao.first = two_kernels ? (uint32_t)ctx->cost_pct : 0u;
             ao.total = (uint32_t)((int64_t)ctx->lds_floor_per_cu * (int64_t)ctx->cu_count);
-            hipLaunchKernelGGL(k4::k4_order_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, ao, (uint32_t)lds_share(ctx, cnt));
+            hipLaunchKernelGGL(k4::k4_order_kernel, dim3(k4::order_workgroups(cnt)), dim3(256), 0, stream, ao, (uint32_t)lds_share(ctx, cnt));
             a.order = d_order;
             if (two_kernels) a.split = d_hist + 2 * k4::COST_BUCKETS;
         }
@@ -2310,7 +2303,7 @@ int dict_encode_run(k4lz4_ctx *ctx, const DictFamily &fam, int level, const Dict
         o.srcLen = b.srcLen; o.n = n; o.cost = w.cost; o.hist = w.head + 64; o.order_out = w.order;
         const unsigned g256 = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL(k4::k4_dict_cost_kernel, dim3(g256), dim3(256), 0, stream, o);
-        hipLaunchKernelGGL(k4::k4_order_kernel, dim3(g256), dim3(256), 0, stream, o, 0xffffffffu);
+        hipLaunchKernelGGL(k4::k4_order_kernel, dim3(k4::order_workgroups(n)), dim3(256), 0, stream, o, 0xffffffffu);
         const k4lz4_dict_set::Family *f = list ? nullptr : &(set->*fam.in_set);
         const DictTables t = list ? DictTables{dict, w.eoff, w.elen, w.etab, w.tables, (int)nd}
                                   : DictTables{set->buf, f->eoff, f->elen, f->etab, f->tables, (int)set->nDict};
@@ -2717,7 +2710,7 @@ int k4lz4_ctx_create(k4lz4_ctx **out, int device)
     if (const char *e = getenv("K4LZ4_PCOST_FIT")) {
         unsigned v[9];
         if (sscanf(e, "%u,%u,%u,%u,%u,%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8]) == 9 && v[0] >= k4::PARSE_MIN_LEN && v[0] < 65536u)
-            ctx->pcost_fit = k4::ParseCost{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], nullptr};
+            ctx->pcost_fit = k4::ParseCost{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
     }
     ctx->parse_migrate = getenv("K4LZ4_NO_MIGRATE") == nullptr;
     ctx->parse_inline_emit = getenv("K4LZ4_NO_INLINE_EMIT") == nullptr;

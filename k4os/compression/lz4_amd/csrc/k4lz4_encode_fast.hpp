@@ -41,6 +41,7 @@ template <int TYPE> struct FastTable;
 
 template <> struct FastTable<1> {   /* byU16: 8192 x u16, hash4 >> 19 (LL.tools.cs:46-51) */
     uint16_t *t;
+    static constexpr int ZERO_UINT4 = 1024;      /* the table in 16-byte pieces */
     __device__ __forceinline__ static uint32_t hash(const uint8_t *p) { return (ld32u(p) * 2654435761u) >> (32 - 13); }
     /* same hash from bytes already in registers: seq = bytes p..p+3, n0 = bytes p+4..p+7 */
     __device__ __forceinline__ static uint32_t hash_of(uint32_t seq, uint32_t) { return (seq * 2654435761u) >> (32 - 13); }
@@ -67,6 +68,7 @@ template <> struct FastTable<1> {   /* byU16: 8192 x u16, hash4 >> 19 (LL.tools.
 };
 template <> struct FastTable<0> {  /* byU32: 4096 x u32, hash5 (LL.tools.cs:53-58, LL64.tools.cs:135-143) */
     uint32_t *t;
+    static constexpr int ZERO_UINT4 = 1024;      /* the table in 16-byte pieces */
     __device__ __forceinline__ static uint32_t hash(const uint8_t *p)
     {
         return (uint32_t)(((ld64u(p) << 24) * 889523592379ull) >> (64 - 12));
@@ -80,10 +82,25 @@ template <> struct FastTable<0> {  /* byU32: 4096 x u32, hash5 (LL.tools.cs:53-5
 };
 template <> struct FastTable<2> {  /* byU32: 4096 x u32, hash4 >> 20: x32/LL32.tools.cs:141-148 has no hash5 arm; x32/LL32.fast.cs:543-545 */
     uint32_t *t;
+    static constexpr int ZERO_UINT4 = 1024;      /* the table in 16-byte pieces */
     __device__ __forceinline__ static uint32_t hash(const uint8_t *p) { return (ld32u(p) * 2654435761u) >> (32 - 12); }
     __device__ __forceinline__ static uint32_t hash_of(uint32_t seq, uint32_t) { return (seq * 2654435761u) >> (32 - 12); }
     __device__ __forceinline__ uint32_t get(uint32_t h) const { return t[h]; }
     __device__ __forceinline__ void put(uint32_t h, uint32_t pos) const { t[h] = pos; }
+};
+/* TYPE 3: the cost sample's own table (k4lz4_parse.hpp, ParseCost): u16 positions like byU16, a shorter hash of the same four bytes.
+ * No reference code stands behind it: a sample of at most 2 KiB produces counts, never bytes, and 4096 slots hold its positions about
+ * as apart as 8192 do -- at 8 KiB a wave, so that all sixteen waves of a workgroup have their table in LDS. */
+#ifndef K4_SAMPLE_HASH_BITS
+#define K4_SAMPLE_HASH_BITS 12
+#endif
+template <> struct FastTable<3> {
+    static constexpr int ZERO_UINT4 = (2 << K4_SAMPLE_HASH_BITS) / 16;
+    uint16_t *t;
+    __device__ __forceinline__ static uint32_t hash(const uint8_t *p) { return (ld32u(p) * 2654435761u) >> (32 - K4_SAMPLE_HASH_BITS); }
+    __device__ __forceinline__ static uint32_t hash_of(uint32_t seq, uint32_t) { return (seq * 2654435761u) >> (32 - K4_SAMPLE_HASH_BITS); }
+    __device__ __forceinline__ uint32_t get(uint32_t h) const { return t[h]; }
+    __device__ __forceinline__ void put(uint32_t h, uint32_t pos) const { t[h] = (uint16_t)pos; }
 };
 
 /* distance from the search start to the j-th probe of LL64.fast.cs:156-172
@@ -1075,16 +1092,77 @@ __device__ __forceinline__ void suffix_counts(const uint32_t *hist, uint32_t *be
  * `lds_max`: the number of slots the host launched the LDS-table kernel with -- the count decided here never exceeds it
  * (the rounding-up of a bucket's part could otherwise give one more, and that block would be encoded by neither kernel).
  * `fine`: the costs are the two-step encoder's (k4lz4_parse.hpp, pcost_bucket: COST_BUCKETS_FINE buckets, no split). */
+/* A stable counting sort: inside a bucket the blocks stand in the order of their indices, so the same costs give the same order
+ * whenever and however the launch runs (a place handed out by a returning atomic on a word in memory -- as it was -- is the order of
+ * arrival, and costs a trip to one of a few dozen contended addresses per block).  The batch is cut into one stretch of indices
+ * per workgroup (a multiple of 256); a workgroup counts, per bucket, the blocks in front of its stretch -- straight from cost[],
+ * which is a few KiB of cached reads for a batch of thousands, instead of waiting for other workgroups' counts --, then places its
+ * stretch 256 blocks at a time: a block's place is what lies in dearer buckets, plus its bucket's blocks before the stretch and in
+ * the stretch so far, plus those in the waves below its own, plus those in the lanes below its own.  Launched with 256 threads. */
+constexpr int ORDER_MAX_WGS = 256;           /* more of them only read more of cost[] each for their count of what lies in front */
+/* Workgroups to launch k4_order_kernel with for n blocks.  Every workgroup counts what lies in front of its stretch, n x workgroups / 2
+ * reads of cost[] in all: one workgroup per 256 blocks while that stays below 2^23 reads (65 536 blocks with 256 workgroups), fewer
+ * and longer stretches beyond, never fewer than 16 -- a batch of 2^24 blocks then costs each workgroup one pass over cost[]. */
+inline unsigned order_workgroups(long long n)
+{
+    long long g = (n + 255) / 256;
+    if (g > ORDER_MAX_WGS) g = ORDER_MAX_WGS;
+    const long long bound = n > 0 ? (1ll << 24) / n : ORDER_MAX_WGS;
+    if (g > bound) g = bound < 16 ? 16 : bound;
+    return (unsigned)(g < 1 ? 1 : g);
+}
+constexpr int ORDER_COPIES = 8;              /* counters per bucket while the blocks in front are counted: a batch of one bucket would
+                                              * otherwise add to one LDS word from every lane */
 template <int NB>
 __device__ __forceinline__ void order_by_bucket(const BatchArgs &a)
 {
     __shared__ uint32_t before[NB], above[NB / 64];
+    __shared__ uint32_t base[ORDER_COPIES][NB], wcnt[4][NB];
+    const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id(), wave = uni(threadIdx.x >> 6);
+    for (uint32_t k = tid; k < (uint32_t)(ORDER_COPIES * NB); k += 256u) (&base[0][0])[k] = 0u;
+    for (uint32_t k = tid; k < (uint32_t)(4 * NB); k += 256u) (&wcnt[0][0])[k] = 0u;
     suffix_counts<NB>(a.hist, before, above);
-    const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (b >= a.n) return;
-    const uint32_t bkt = a.cost[b];
-    const uint32_t pos = before[bkt] + above[((uint32_t)NB - 1u - bkt) >> 6] + atomicAdd(&a.hist[NB + bkt], 1u);
-    a.order_out[pos] = (uint32_t)b;
+    const long long per = (((long long)a.n + (long long)gridDim.x - 1) / (long long)gridDim.x + 255) & ~255ll;
+    /* (the stretches are whole multiples of 256, so the last workgroups of a launch may have none: lo = hi = n, nothing read) */
+    if ((long long)blockIdx.x * per >= (long long)a.n) return;
+    const long long lo = (long long)blockIdx.x * per, hi = lo + per < (long long)a.n ? lo + per : (long long)a.n;
+    for (long long i = (long long)tid; i < lo; i += 256) {
+        const uint32_t bkt = a.cost[i];
+        atomicAdd(&base[lane & (uint32_t)(ORDER_COPIES - 1)][bkt < (uint32_t)NB ? bkt : (uint32_t)NB - 1u], 1u);
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < (uint32_t)NB; k += 256u) {
+        uint32_t s = before[k] + above[((uint32_t)NB - 1u - k) >> 6];
+        for (int c = 0; c < ORDER_COPIES; c++) s += base[c][k];
+        base[0][k] = s;
+    }
+    __syncthreads();
+    for (long long i0 = lo; i0 < hi; i0 += 256) {
+        const long long b = i0 + (long long)tid;
+        const bool have = b < hi;
+        uint32_t bkt = 0xffffffffu;
+        if (have) { bkt = a.cost[b]; if (bkt >= (uint32_t)NB) bkt = (uint32_t)NB - 1u; }
+        /* the lanes of the wave with this lane's bucket: how many lie below it, how many there are */
+        uint32_t rank = 0u, cnt = 0u;
+        unsigned long long todo = ballot(have);
+        while (todo) {
+            const uint32_t v = readlane_u32(bkt, ctz64(todo));
+            const unsigned long long m = ballot(bkt == v);
+            if (bkt == v) { rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); cnt = (uint32_t)__popcll(m); }
+            todo &= ~m;
+        }
+        const bool leader = have && rank == 0u;
+        if (leader) wcnt[wave][bkt] = cnt;
+        __syncthreads();
+        if (have) {
+            uint32_t pos = base[0][bkt] + rank;
+            for (uint32_t w = 0; w < wave; w++) pos += wcnt[w][bkt];
+            if ((long long)pos < (long long)a.n) a.order_out[pos] = (uint32_t)b;       /* (always, while hist[] counts cost[]) */
+        }
+        __syncthreads();
+        if (leader) { atomicAdd(&base[0][bkt], cnt); wcnt[wave][bkt] = 0u; }
+        __syncthreads();
+    }
 }
 
 __global__ __launch_bounds__(256) void k4_order_kernel(BatchArgs a, uint32_t lds_max = 0xffffffffu, int fine = 0)

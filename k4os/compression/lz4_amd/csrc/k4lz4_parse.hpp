@@ -170,7 +170,9 @@ struct ParseCtl {
  * changes with a byU32 table (round 6): a candidate more than 65 535 bytes back is no match (LL64.fast.cs:219-224; it is still put over),
  * one bit of `seen` per hash value, hash5 reads five bytes, and a match length no longer fits the record's 16 bits -- 0xffff there says
  * "this or more", counted again where the record is written out.  The record slot of a block holds PARSE_REC_STRIDE records: a longer
- * block returns to its caller when the slot is nearly full (ParseCtl::flush, like a table migration), has them written out and goes on. */
+ * block returns to its caller when the slot is nearly full (ParseCtl::flush, like a table migration), has them written out and goes on.
+ * 3 = the cost sample's table (DRY runs only: FastTable<3>, 2^K4_SAMPLE_HASH_BITS u16 slots, one bit of `seen` per hash value): the
+ * zeroing above the rounds and the `seen` shift go by the table, everything else is the byU16 code. */
 /* SEG (byU32 blocks only): the block is one of several runs over a big block (k4lz4_encode_fast.hpp, SegRun; k4lz4_segments.hpp says who
  * gets what).  The run starts at sr->begin as a fresh encoder would; a warm run (emit_from != 0) writes no record before its CUT -- its
  * first match end at or behind emit_from --, where it publishes cut and table and goes on as the block's encoder; every run stops at
@@ -184,10 +186,12 @@ __device__ __forceinline__ uint32_t parse_block(const uint8_t *src, const uint32
     static_assert(!SEG || (TT != 1 && K == 1 && !DRY), "segments: byU32 blocks, one sub-window per round");
     typedef FastTable<TT> Table;
     static_assert(TT == 1 || K == 1, "byU32 tables: one sub-window per round");
-    constexpr bool U32 = TT != 1;
+    static_assert(TT != 3 || (DRY && !GT && K == 1), "the sample's table: dry runs in LDS only");
+    constexpr bool U32 = TT == 0 || TT == 2;
     Table tab;
     tab.t = (decltype(tab.t))tabv;
     constexpr uint32_t SEEN_SHIFT = TT == 1 ? 1u : 0u;          /* hash value -> bit of `seen` */
+    static_assert(TT != 3 || (1 << K4_SAMPLE_HASH_BITS) <= 32 * PARSE_SEEN_DWORDS, "one bit of `seen` per hash value of the sample's table");
     ParseStats st = {0u, 0u, 0u, 0u, 0u, U, DRY && stats ? uni(stats->max_rounds) : 0u};
 #define K4_ST(field, v) do { if (DRY) st.field += (v); } while (0)
 #ifdef K4_PARSE_PROF
@@ -229,7 +233,7 @@ __device__ __forceinline__ uint32_t parse_block(const uint8_t *src, const uint32
     const unsigned long long me = 1ull << lane, below_me = me - 1ull;
 
     const bool resumed = ctl && ctl->resume;
-    if (!resumed) for (int k = lane; k < 1024; k += 64) ((uint4 *)tabv)[k] = make_uint4(0u, 0u, 0u, 0u);     /* LZ4_initStream; put(hash(0), 0) stores a 0 (:119-122) */
+    if (!resumed) for (int k = lane; k < Table::ZERO_UINT4; k += 64) ((uint4 *)tabv)[k] = make_uint4(0u, 0u, 0u, 0u);     /* LZ4_initStream; put(hash(0), 0) stores a 0 (:119-122) */
     for (int k = lane; k < PARSE_SEEN_DWORDS; k += 64) seen[k] = 0u;
     wave_sync();
 
@@ -1224,20 +1228,25 @@ __global__ __launch_bounds__(64 * PARSE_MAX_WAVES) void k4_parse_big_kernel(Batc
  *
  * The sample is short because the estimate is part of the timed call, and a round of the parse takes its 3-5 us however few
  * waves a CU holds: the kernel lasts as long as the sample with the most rounds.  So every block of a residency of the parse kernel
- * is estimated at once, in that kernel's shape -- sixteen waves per workgroup, nine tables in LDS, seven in memory (`tables`,
- * 16 KiB per wave) --, not nine per CU and then the rest; and the sample ends after `max_rounds` rounds wherever they have got to
- * in its `sample` bytes (ParseStats::covered: data without matches, where the search strides, is through 2 KiB in fewer), which
- * bounds the kernel's time and costs the fit nothing.  Measured per sample and round limit: experiments/parse_cost_order/.
+ * is estimated at once, sixteen waves per workgroup, not nine per CU and then the rest; and the sample ends after `max_rounds`
+ * rounds wherever they have got to in its `sample` bytes (ParseStats::covered: data without matches, where the search strides, is
+ * through 2 KiB in fewer), which bounds the kernel's time and costs the fit nothing.
+ *   The sample's table is its own (FastTable<3>: a 12-bit hash of the same four bytes, 8 KiB a wave): nothing the sample produces
+ * reaches the output, its positions are 2048 at the most, and so all sixteen tables of a workgroup lie in LDS (128 KiB + the
+ * `seen` sets) -- no table in memory to zero and to miss on, one form of the parse for every wave.  The weights are fitted to
+ * that table's counts.  Measured per sample, round limit and hash width: experiments/parse_cost_order/.
  */
 struct ParseCost {
     uint32_t sample, max_rounds;                       /* the bytes of every block that are parsed, and the rounds after which that stops, if sooner */
     uint32_t round, slow, seq, group, lazy, lng;       /* ns per event of a 64 KiB block's parse, for events counted in `sample` bytes */
     uint32_t base;                                     /* ns per 64 KiB whatever they hold */
-    uint32_t *tables;                                  /* (PARSE_MAX_WAVES - PARSE_LDS_TABLES) x 16 KiB per workgroup of the launch */
 };
-constexpr ParseCost PCOST_FIT = {2048u, 10u, 999u, 0u, 104u, 0u, 18u, 181u, 835300u, nullptr};
+constexpr ParseCost PCOST_FIT = {2048u, 12u, 1166u, 0u, 85u, 0u, 42u, 131u, 739622u};
 constexpr int PCOST_BUCKETS = COST_BUCKETS_FINE;               /* 32 per octave from 2^14 ns on */
 constexpr int PCOST_WAVES_PER_WG = PARSE_MAX_WAVES;
+constexpr int PCOST_TABLE_DWORDS = FastTable<3>::ZERO_UINT4 * 4;
+constexpr int PCOST_LDS_DWORDS = (PCOST_TABLE_DWORDS + PARSE_SEEN_DWORDS) * PCOST_WAVES_PER_WG;
+static_assert(PCOST_LDS_DWORDS * 4 <= 160 * 1024, "sixteen sample tables and their `seen` sets in one CU's LDS");
 
 __device__ __forceinline__ uint32_t pcost_bucket(unsigned long long cost)
 {
@@ -1247,12 +1256,12 @@ __device__ __forceinline__ uint32_t pcost_bucket(unsigned long long cost)
     return b < (uint32_t)PCOST_BUCKETS ? b : (uint32_t)PCOST_BUCKETS - 1u;
 }
 
-/* one block per wave and turn: a.cost[b] = bucket of block b, a.hist[bucket]++ (`far`: the workgroup's tables in memory) */
-__device__ __forceinline__ void parse_cost_body(const BatchArgs &a, const ParseCost &pc, uint32_t *lds, uint32_t *far)
+/* one block per wave and turn: a.cost[b] = bucket of block b, a.hist[bucket]++ (lds: PCOST_LDS_DWORDS, the tables first) */
+__device__ __forceinline__ void parse_cost_body(const BatchArgs &a, const ParseCost &pc, uint32_t *lds)
 {
     const int lane = lane_id();
     const uint32_t wave = uni(threadIdx.x >> 6);
-    uint32_t *seen = lds + 4096u * (uint32_t)PARSE_LDS_TABLES + (uint32_t)PARSE_SEEN_DWORDS * wave;
+    uint32_t *seen = lds + (uint32_t)PCOST_TABLE_DWORDS * (uint32_t)PCOST_WAVES_PER_WG + (uint32_t)PARSE_SEEN_DWORDS * wave;
     for (long long b = (long long)blockIdx.x * PARSE_MAX_WAVES + (long long)wave; b < a.n; b += (long long)gridDim.x * PARSE_MAX_WAVES) {
         const int src_len = a.srcLen[b];
         unsigned long long cost = 0ull;
@@ -1261,9 +1270,7 @@ __device__ __forceinline__ void parse_cost_body(const BatchArgs &a, const ParseC
             const uint8_t *src = a.src + a.srcOff[b];
             ParseStats st;
             st.max_rounds = pc.max_rounds;
-            uint32_t nseq;
-            if (wave < (uint32_t)PARSE_LDS_TABLES) nseq = parse_block<1, false, true>(src, sample, nullptr, lds + 4096u * wave, seen, lane, nullptr, &st);
-            else nseq = parse_block<1, true, true>(src, sample, nullptr, far + 4096u * (wave - (uint32_t)PARSE_LDS_TABLES), seen, lane, nullptr, &st);
+            const uint32_t nseq = parse_block<1, false, true, 3>(src, sample, nullptr, lds + (uint32_t)PCOST_TABLE_DWORDS * wave, seen, lane, nullptr, &st);
             const unsigned long long ns = (unsigned long long)pc.round * st.rounds + (unsigned long long)pc.slow * st.slow + (unsigned long long)pc.seq * nseq +
                                           (unsigned long long)pc.group * st.groups + (unsigned long long)pc.lazy * st.lazies + (unsigned long long)pc.lng * st.longs;
             cost = ns * (unsigned long long)(uint32_t)src_len / (st.covered ? st.covered : 1u) + (((unsigned long long)pc.base * (unsigned long long)(uint32_t)src_len) >> 16);
@@ -1281,18 +1288,16 @@ __device__ __forceinline__ void parse_cost_body(const BatchArgs &a, const ParseC
 /* the two-step encoder's form of k4_cost_kernel (k4lz4_encode_fast.hpp); at most one workgroup per CU is worth launching */
 __global__ __launch_bounds__(64 * PARSE_MAX_WAVES) void k4_cost_kernel(BatchArgs a, ParseCost pc)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[4096 * PARSE_LDS_TABLES + PARSE_SEEN_DWORDS * PARSE_MAX_WAVES];
-    parse_cost_body(a, pc, lds, pc.tables + 4096ull * (unsigned long long)(PARSE_MAX_WAVES - PARSE_LDS_TABLES) * (unsigned long long)blockIdx.x);
+    __shared__ __attribute__((aligned(16))) uint32_t lds[PCOST_LDS_DWORDS];
+    parse_cost_body(a, pc, lds);
 }
 
 #ifdef K4_HOST_EMU
-/* the emulator launches the estimate and its order under these names (PCOST_WAVES_PER_WG waves a workgroup, 256 threads), without
- * tables in memory: static storage of the emulating thread stands in for them */
+/* the emulator launches the estimate and its order under these names (PCOST_WAVES_PER_WG waves a workgroup, 256 threads) */
 inline void k4_pcost_kernel(BatchArgs a)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[4096 * PARSE_LDS_TABLES + PARSE_SEEN_DWORDS * PARSE_MAX_WAVES];
-    __shared__ __attribute__((aligned(16))) uint32_t far[4096 * (PARSE_MAX_WAVES - PARSE_LDS_TABLES)];
-    parse_cost_body(a, PCOST_FIT, lds, far);
+    __shared__ __attribute__((aligned(16))) uint32_t lds[PCOST_LDS_DWORDS];
+    parse_cost_body(a, PCOST_FIT, lds);
 }
 inline void k4_porder_kernel(BatchArgs a) { k4_order_kernel(a, 0xffffffffu, 1); }
 #endif
