@@ -129,6 +129,10 @@ struct k4lz4_ctx {
     bool hc_chain_parts = true;           /* K4LZ4_HC_CHAIN_OLD unsets it: blocks of at most 64 KiB build their chains with sixteen waves per block (k4_hc_chain_part_kernel) */
     int hc_mem_pct = 33;                  /* K4LZ4_HC_MEM_PCT: share of an HC chunk whose chains are built with the table in memory, beside the LDS-table kernel */
     int pace_min_per_cu = 6;              /* K4LZ4_PACE_MIN: batches of more blocks per CU than this use the priorities (measured: 8 per CU +3 % encode, +7 % decode; 4 per CU -1 %, -4 %) */
+    int parse_pace_min_per_cu = 8;        /* ... and the same for k4_parse_kernel's priorities (k4lz4_parse.hpp, ParsePace; measured on 64 KiB blocks, encode launch:
+                                           * 2 and 4 per CU -1.2 %, 8 per CU level, 16 per CU +4.6 %) */
+    bool parse_pace_queue = false;        /* K4LZ4_PACE_QUEUE: ... also where every wave takes block after block from the queue (measured: 64 blocks of 64 KiB
+                                           * per CU -1.3 %, 256 of 4 KiB -3 %, so not by default) */
     bool use_pace = true;                 /* K4LZ4_NO_PACE: without the late-blocks-first priorities */
     bool prof_gtab = false;               /* K4LZ4_PROF_GTAB: the instrumented encoder keeps its table in global memory */
     uint8_t *d_parse = nullptr; size_t d_parse_cap = 0;       /* two-kernel fast encoder (k4lz4_parse.hpp): records, per-block counts, tables of the waves without an LDS table */
@@ -772,6 +776,9 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
             pa.slot_recs = slot_recs ? 1u : 0u;
             pa.migrate = ctx->parse_migrate ? 1u : 0u;
             pa.big = any_big ? 1u : 0u;
+            /* late blocks first among the waves of a SIMD (k4lz4_parse.hpp, ParsePace): its words are LDS of the workgroup, so
+             * nothing is filled or launched for it; k4_parse_kernel alone reads the switch */
+            pa.pace = parse_path && ctx->use_pace && (!queue || ctx->parse_pace_queue) && cnt > (int64_t)ctx->parse_pace_min_per_cu * (int64_t)ctx->cu_count ? 1u : 0u;
             /* eight words behind the counts: the two launches' queues (three words each) and, word 3, the number of blocks the first
              * launch leaves to the second */
             K4_HIP(ctx, hipMemsetAsync(pa.meta + 2 * cnt, 0, 32, stream));
@@ -2678,7 +2685,8 @@ int k4lz4_ctx_create(k4lz4_ctx **out, int device)
     ctx->no_pair = getenv("K4LZ4_NO_PAIR") != nullptr;
     ctx->prof_gtab = getenv("K4LZ4_PROF_GTAB") != nullptr;
     ctx->use_pace = getenv("K4LZ4_NO_PACE") == nullptr;
-    if (const char *e = getenv("K4LZ4_PACE_MIN")) ctx->pace_min_per_cu = std::max(0, atoi(e));
+    if (const char *e = getenv("K4LZ4_PACE_MIN")) ctx->pace_min_per_cu = ctx->parse_pace_min_per_cu = std::max(0, atoi(e));
+    ctx->parse_pace_queue = getenv("K4LZ4_PACE_QUEUE") != nullptr;
     if (const char *e = getenv("K4LZ4_DIRECT_SPAN_PCT")) ctx->direct_span_pct = std::max(100, atoi(e));
     if (const char *e = getenv("K4LZ4_NO_DIRECT")) ctx->no_direct = atoi(e) != 0;
     if (const char *e = getenv("K4LZ4_LDS_FLOOR")) ctx->lds_floor_per_cu = std::max(0, std::min(8, atoi(e)));

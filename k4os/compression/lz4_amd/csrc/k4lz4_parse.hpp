@@ -68,6 +68,7 @@ struct ParseArgs {
     uint32_t migrate;       /* != 0: blocks without an LDS table move into one when a block of their workgroup is done with it (ParseCtl) */
     uint32_t inline_emit;   /* != 0: the wave that parsed a block writes it out as well (k4_emit_kernel is not launched): the blocks that are
                              * through early do that while the others still parse, only the last ones' bytes come on top of the launch */
+    uint32_t pace;          /* != 0: late blocks first among the waves of a SIMD (ParsePace below; k4_parse_kernel only) */
     uint32_t *nbig;         /* nullptr, or a zeroed word: k4_parse_kernel counts the blocks it marks PARSE_BIG there, and the launch behind it leaves at
                              * once when there are none (a batch of 262 144 small blocks otherwise costs it a ticket per block for nothing) */
     uint32_t big;           /* != 0: k4_parse_big_kernel follows this launch and takes the blocks of 65 547 bytes and more (needs inline_emit) */
@@ -77,6 +78,115 @@ struct ParseArgs {
     uint32_t *queue;        /* nullptr, or three zeroed words: the launch has fewer waves than blocks and every wave takes the next block
                              * when it is done with one -- [0] tickets handed out (never more than there are blocks), [1] taken from the front
                              * of the order (the most expensive: by the waves with a table in LDS), [2] taken from its back (by the others) */
+};
+static_assert(sizeof(ParseArgs) == 64, "`pace` stands where the padding in front of `nbig` stood: the other kernels' arguments lie where they lay");
+
+/*
+ * Late blocks first inside k4_parse_kernel (k4lz4_common.hpp, Pace, says what for).  The workgroup is the CU, so the waves that
+ * compete for a SIMD's issue slots share their estimates in LDS: no slots in memory, no epochs, no fill in front of the launch.
+ *   words behind the kernel's PARSE_LDS_DWORDS:  [16 * simd + wave]  the wave's estimate F (0: none yet, or the wave has left)
+ *                                                [EST + wave]        when the wave began its block (in LDS, not in a register
+ *                                                                    the round loop is short of: Pace::begin)
+ *                                                [EST + 16]          when the workgroup began
+ * F = (start - workgroup's start) + elapsed * U / c in ticks of the 100 MHz counter, worked out at every look of the round loop
+ * (one in 16 rounds, the look at the free-table word); the wave then reads the sixteen words of its SIMD and takes its level by how
+ * close it is to the latest of them, in tiers of 1 / PARSE_PACE_DEN.  All differences of 32-bit times: the counter may wrap.
+ */
+#ifndef K4_PARSE_PACE_DEN
+#define K4_PARSE_PACE_DEN 32u
+#endif
+constexpr uint32_t PARSE_PACE_DEN = K4_PARSE_PACE_DEN;
+constexpr uint32_t PARSE_PACE_MAX = 0x03ffffffu;     /* 0.67 s: an estimate is at most this, so that one times PARSE_PACE_DEN fits a word */
+constexpr int PARSE_PACE_EST = 4 * PARSE_MAX_WAVES;  /* estimates by (SIMD, wave) */
+constexpr int PARSE_PACE_DWORDS = PARSE_PACE_EST + PARSE_MAX_WAVES + 4;
+static_assert(PARSE_PACE_DEN >= 4u && (unsigned long long)PARSE_PACE_MAX * PARSE_PACE_DEN <= 0xffffffffull, "tiers in 32-bit arithmetic");
+
+/* when the block will be done at the pace so far: `c` of its `U` bytes are behind the wave that began it at `start`; never 0 for
+ * c != 0 (0 says "no report"), never above PARSE_PACE_MAX */
+__host__ __device__ inline uint32_t parse_pace_estimate(uint32_t wg_start, uint32_t start, uint32_t now, uint32_t c, uint32_t U)
+{
+    if (c == 0u) return 0u;
+    const float own = (float)(now - start) * ((float)U / (float)c);
+    const uint32_t own_u = own < (float)PARSE_PACE_MAX ? (uint32_t)own : PARSE_PACE_MAX;
+    const uint32_t lead = start - wg_start < PARSE_PACE_MAX ? start - wg_start : PARSE_PACE_MAX;
+    const uint32_t f = lead + own_u < PARSE_PACE_MAX ? lead + own_u : PARSE_PACE_MAX;
+    return f ? f : 1u;
+}
+/* the level of a wave whose estimate is `mine` on a SIMD whose mates' latest estimate is `latest` (0: none of them has one, or all
+ * have left -- the wave is then its SIMD's latest itself); -1: the wave has no estimate, it keeps the level it has */
+__host__ __device__ inline int parse_pace_level(uint32_t mine, uint32_t latest)
+{
+    if (mine == 0u) return -1;
+    if (latest < mine) latest = mine;
+    return mine * PARSE_PACE_DEN >= latest * (PARSE_PACE_DEN - 1u) ? 3 : mine * PARSE_PACE_DEN >= latest * (PARSE_PACE_DEN - 2u) ? 2 :
+           mine * PARSE_PACE_DEN >= latest * (PARSE_PACE_DEN - 3u) ? 1 : 0;
+}
+/* before the first report, from what the deal knows: a block that starts with its table in memory pays ~13 % on every round and
+ * belongs to the group that ends the launch; of the others the first four strata of the cost order are the dearest of their SIMD */
+__host__ __device__ inline int parse_pace_first_level(uint32_t wave, bool in_lds)
+{
+    return !in_lds ? 3 : wave < 4u ? 2 : 1;
+}
+
+struct ParsePace {
+    __device__ __forceinline__ static void poke(uint32_t *p, uint32_t v)          /* an LDS store, as lds_peek is an LDS load */
+    {
+#ifndef K4_HOST_EMU
+        *(volatile __attribute__((address_space(3))) uint32_t *)p = v;
+#else
+        *(volatile uint32_t *)p = v;
+#endif
+    }
+    /* the workgroup's words, by all its threads, in front of the __syncthreads() that the free-table word has */
+    __device__ __forceinline__ static void clear(uint32_t *pace)
+    {
+        const uint32_t t = Pace::now();
+        for (uint32_t k = threadIdx.x; k < (uint32_t)PARSE_PACE_DWORDS; k += blockDim.x) poke(pace + k, k == (uint32_t)(PARSE_PACE_EST + PARSE_MAX_WAVES) ? t : 0u);
+    }
+    /* a wave begins a block: its clock, its first level; returns the index of its estimate's word (SIMD from HW_ID, as Pace::slot_of) */
+    __device__ __forceinline__ static uint32_t begin(uint32_t *pace, uint32_t wave, bool in_lds, int lane)
+    {
+#ifndef K4_HOST_EMU
+        const uint32_t hw = __builtin_amdgcn_s_getreg((16 << 11) | 4);
+        const uint32_t me = 16u * ((hw >> 4) & 3u) + wave;
+#else
+        const uint32_t me = wave;
+#endif
+        const uint32_t t = Pace::now();
+        if (lane == 0) { poke(pace + PARSE_PACE_EST + wave, t); poke(pace + me, 0u); }
+        Pace::set_level(parse_pace_first_level(wave, in_lds));
+        return me;
+    }
+    /* the latest estimate among the sixteen words of a SIMD (every lane gets it) */
+    __device__ __forceinline__ static uint32_t latest_of(const uint32_t *row, int lane)
+    {
+#ifndef K4_HOST_EMU
+        uint32_t x = lane < PARSE_MAX_WAVES ? lds_peek(row + lane) : 0u;
+        x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true));      /* row_shr:1, 2, 4, 8: lane 15 has the row's */
+        x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true));
+        x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true));
+        x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true));
+        return readlane_u32(x, 15);
+#else
+        (void)lane;
+        uint32_t x = 0u;
+        for (int k = 0; k < PARSE_MAX_WAVES; k++) x = x < row[k] ? row[k] : x;
+        return x;
+#endif
+    }
+    /* a look: `c` of `U` bytes are done */
+    __device__ __forceinline__ static void report(uint32_t *pace, uint32_t me, uint32_t c, uint32_t U, int lane)
+    {
+        const uint32_t wg_start = uni(lds_peek(pace + PARSE_PACE_EST + PARSE_MAX_WAVES)), start = uni(lds_peek(pace + PARSE_PACE_EST + (me & 15u)));
+        const uint32_t f = uni(parse_pace_estimate(wg_start, start, Pace::now(), c, U));
+        if (lane == 0) poke(pace + me, f);
+        Pace::set_level(parse_pace_level(f, latest_of(pace + (me & ~15u), lane)));
+    }
+    /* the block's parse is through: its estimate no longer counts; the wave keeps its level while it writes the block out */
+    __device__ __forceinline__ static void leave(uint32_t *pace, uint32_t me, int lane)
+    {
+        if (lane == 0) poke(pace + me, 0u);
+    }
 };
 
 /* ------------------------------------------------------------------------------------------------------------------ */
@@ -179,10 +289,17 @@ struct ParseCtl {
  * its first match end at or behind stop_at, and says whether the next run's published cut and table are that very state.  A round
  * may end at any match end (a match that runs out of the window does just that), which is all the rounds need for it: hop words of
  * matches that end at or behind the next such position carry HOP_END, and the chain's exits look at where the match ended. */
-template <int K, bool GT, bool DRY = false, int TT = 1, bool SEG = false>
+/* PACE (k4_parse_kernel's blocks only): one more argument, a ParsePaceRef -- words != nullptr: the workgroup's words of ParsePace,
+ * `me` this wave's among them.  (A parameter pack, empty for every other caller: their code has no trace of it, not even a
+ * parameter that is never looked at, and compiles to what it was before there were priorities.) */
+struct ParsePaceRef { uint32_t *words; uint32_t me, tick; };
+template <class T> __device__ __forceinline__ T &pack_first(T &t) { return t; }
+template <int K, bool GT, bool DRY = false, int TT = 1, bool SEG = false, bool PACE = false, class... PR>
 __device__ __forceinline__ uint32_t parse_block(const uint8_t *src, const uint32_t U, uint2 *recs, void *tabv, uint32_t *seen, const int lane, unsigned long long *pc = nullptr,
-                                                ParseStats *stats = nullptr, ParseCtl *ctl = nullptr, SegRun *sr = nullptr)
+                                                ParseStats *stats = nullptr, ParseCtl *ctl = nullptr, SegRun *sr = nullptr, PR... pace_ref)
 {
+    static_assert(sizeof...(PR) == (PACE ? 1 : 0), "a ParsePaceRef with PACE, nothing without");
+    static_assert(!PACE || (TT == 1 && !SEG && !DRY), "priorities: the byU16 blocks of k4_parse_kernel");
     static_assert(!SEG || (TT != 1 && K == 1 && !DRY), "segments: byU32 blocks, one sub-window per round");
     typedef FastTable<TT> Table;
     static_assert(TT == 1 || K == 1, "byU32 tables: one sub-window per round");
@@ -978,6 +1095,9 @@ __device__ __forceinline__ uint32_t parse_block(const uint8_t *src, const uint32
             ctl->claimed = PARSE_FLUSH;
             return nrec;
         }
+        /* one look every 16 rounds at the estimates of the SIMD's other waves, whatever the table: the cadence of the look at the
+         * free-table word below, on a count of its own (that one runs only where there is a table to move into) */
+        if constexpr (PACE) { ParsePaceRef &pr = pack_first(pace_ref...); if (pr.words && (++pr.tick & 15u) == 0u) ParsePace::report(pr.words, pr.me, c, U, lane); }
         if (GT && ctl && ctl->free_slots && (++mig_tick & 15u) == 0u) {
             const uint32_t fs = uni(lds_peek(ctl->free_slots));
             if (fs) {
@@ -1054,9 +1174,9 @@ __device__ __forceinline__ int emit_block(const uint8_t *src, const uint32_t U, 
  * memory until a table of the workgroup becomes free.  Returns what the encoder call returns (bytes written to dst, 0: no room); for a
  * run that stopped at its boundary (sr->state 1 / 4) that is the piece without last literals.  *nrec_out: records of the last parse call
  * (the whole block's where it fits its slot). */
-template <int K, int TT, bool SEG>
+template <int K, int TT, bool SEG, bool PACE = false, class... PR>
 __device__ __forceinline__ int parse_one(const BatchArgs &a, const ParseArgs &p, uint32_t *lds, uint32_t *seen, const bool in_lds, const uint32_t wave, const uint32_t waves,
-                                         const int lane, const long long b, const uint8_t *src, const int src_len, uint8_t *dst, const int cap, SegRun *sr, uint32_t *nrec_out)
+                                         const int lane, const long long b, const uint8_t *src, const int src_len, uint8_t *dst, const int cap, SegRun *sr, uint32_t *nrec_out, PR... pace_ref)
 {
     constexpr bool U32 = TT != 1;
     uint2 *recs = p.recs + (p.slot_recs ? (unsigned long long)blockIdx.x * waves + wave : (unsigned long long)b) * PARSE_REC_STRIDE;
@@ -1091,7 +1211,11 @@ __device__ __forceinline__ int parse_one(const BatchArgs &a, const ParseArgs &p,
     ctl.free_slots = in_lds ? nullptr : free_slots; ctl.claimed = -1; ctl.resume = false;
     ctl.rec_cap = U32 ? PARSE_REC_STRIDE : 0u;
     for (;;) {
-        if (tslot >= 0) n = parse_block<K, false, false, TT, SEG>(src, (uint32_t)src_len, recs, lds + 4096u * (uint32_t)tslot, seen, lane, pc, nullptr, (U32 || ctl.resume) ? &ctl : nullptr, sr);
+        if constexpr (PACE) {
+            if (tslot >= 0) n = parse_block<K, false, false, TT, SEG, true>(src, (uint32_t)src_len, recs, lds + 4096u * (uint32_t)tslot, seen, lane, pc, nullptr, ctl.resume ? &ctl : nullptr, sr, pace_ref...);
+            else n = parse_block<K, true, false, TT, SEG, true>(src, (uint32_t)src_len, recs, gt, seen, lane, pc, nullptr, &ctl, sr, pace_ref...);
+        }
+        else if (tslot >= 0) n = parse_block<K, false, false, TT, SEG>(src, (uint32_t)src_len, recs, lds + 4096u * (uint32_t)tslot, seen, lane, pc, nullptr, (U32 || ctl.resume) ? &ctl : nullptr, sr);
         else n = parse_block<K, true, false, TT, SEG>(src, (uint32_t)src_len, recs, gt, seen, lane, pc, nullptr, &ctl, sr);
         if (U32 && ctl.claimed == PARSE_FLUSH) {
             if (p.inline_emit) write_out(n);
@@ -1112,6 +1236,7 @@ __device__ __forceinline__ int parse_one(const BatchArgs &a, const ParseArgs &p,
         }
         break;
     }
+    if constexpr (PACE) { ParsePaceRef &pr = pack_first(pace_ref...); if (pr.words) ParsePace::leave(pr.words, pr.me, lane); }
     if (free_slots && lane == 0) {
         if (my_slot >= 0) atomicOr(free_slots, 1u << my_slot);                 /* ... and free again for the next one */
         else if (in_lds && !p.queue) atomicOr(free_slots, 1u << wave);          /* this wave's table is free now */
@@ -1140,7 +1265,8 @@ __device__ __forceinline__ int parse_one(const BatchArgs &a, const ParseArgs &p,
     return ret;
 }
 
-template <int K, int TT = 1>
+/* PACE: `lds` has PARSE_PACE_DWORDS more, behind the free-table word */
+template <int K, int TT = 1, bool PACE = false>
 __device__ __forceinline__ void parse_kernel_body(const BatchArgs &a, const ParseArgs &p, uint32_t *lds)
 {
     constexpr bool U32 = TT != 1;
@@ -1151,8 +1277,9 @@ __device__ __forceinline__ void parse_kernel_body(const BatchArgs &a, const Pars
     uint32_t *seen = lds + 4096u * (uint32_t)PARSE_LDS_TABLES + (uint32_t)PARSE_SEEN_DWORDS * wave;
     const bool in_lds = wave < lds_tables;
     if (U32 && p.nbig && uni(*(volatile uint32_t *)p.nbig) == 0u) return;          /* the launch before this one found nothing for it */
-    if (p.migrate) {
-        if (threadIdx.x == 0) lds[PARSE_LDS_DWORDS - 1] = 0u;
+    if (p.migrate || (PACE && p.pace)) {
+        if (p.migrate && threadIdx.x == 0) lds[PARSE_LDS_DWORDS - 1] = 0u;
+        if constexpr (PACE) if (p.pace) ParsePace::clear(lds + PARSE_LDS_DWORDS);
         __syncthreads();
     }
     for (long long idx = (long long)wave * (long long)p.nwg + (long long)blockIdx.x;;) {
@@ -1186,7 +1313,14 @@ __device__ __forceinline__ void parse_kernel_body(const BatchArgs &a, const Pars
             }
         } else {
             uint32_t n = 0u;
-            const int ret = parse_one<K, TT, false>(a, p, lds, seen, in_lds, wave, waves, lane, b, a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], a.dstCap[b], nullptr, &n);
+            int ret;
+            if constexpr (PACE) {
+                /* late blocks first (ParsePace): the clock starts anew with every block a wave takes */
+                ParsePaceRef pr = {nullptr, 0u, 0u};
+                if (p.pace) { pr.words = lds + PARSE_LDS_DWORDS; pr.me = uni(ParsePace::begin(pr.words, wave, in_lds, lane)); }
+                ret = parse_one<K, TT, false, true>(a, p, lds, seen, in_lds, wave, waves, lane, b, a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], a.dstCap[b], nullptr, &n, pr);
+            }
+            else ret = parse_one<K, TT, false>(a, p, lds, seen, in_lds, wave, waves, lane, b, a.src + a.srcOff[b], src_len, a.dst + a.dstOff[b], a.dstCap[b], nullptr, &n);
             if (lane == 0) {
                 meta[0] = n; meta[1] = 0u;
                 if (p.inline_emit) a.outLen[b] = codec_encode_result(src_len, ret, a.flags);
@@ -1199,8 +1333,9 @@ __device__ __forceinline__ void parse_kernel_body(const BatchArgs &a, const Pars
 
 __global__ __launch_bounds__(64 * PARSE_MAX_WAVES) void k4_parse_kernel(BatchArgs a, ParseArgs p)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[PARSE_LDS_DWORDS];
-    parse_kernel_body<K4_PARSE_K>(a, p, lds);
+    __shared__ __attribute__((aligned(16))) uint32_t lds[PARSE_LDS_DWORDS + PARSE_PACE_DWORDS];
+    static_assert((PARSE_LDS_DWORDS + PARSE_PACE_DWORDS) * 4 <= 160 * 1024, "nine tables, the `seen` sets and the priorities' words in one CU's LDS");
+    parse_kernel_body<K4_PARSE_K, 1, true>(a, p, lds);
 }
 
 /* The same for the blocks of 65 547 bytes and more (round 6): byU32 table, hash5 (LL64.fast.cs:526-544) or -- LZ4Codec.Enforce32 --
