@@ -121,7 +121,7 @@ struct k4lz4_ctx {
     int lds_floor_per_cu = 8;             /* K4LZ4_LDS_FLOOR: blocks per CU the LDS-table kernel gets at least */
     int cost_pct = 48;                    /* K4LZ4_COST_PCT: the LDS-table kernel's share of a batch's estimated cost (k4_order_kernel) */
     int dec_parts = 4, dec_parts_direct = 8;   /* K4LZ4_DEC_PARTS, K4LZ4_DEC_PARTS_DIRECT: parts of a big decode-like host-pointer call (2..MAX_PARTS); with a registered destination */
-    int last_decode_kernel = 0;           /* k4lz4_last_decode_kernel: enum k4lz4_decode_kernel of the latest KIND_DECODE / KIND_UNPICKLE launch (launch()) */
+    int last_decode_kernel = 0;           /* k4lz4_last_decode_kernel: enum k4lz4_decode_kernel of the latest KIND_DECODE / KIND_UNPICKLE launch (launch_decode_like) */
     int hop2_max_per_cu = 12;             /* K4LZ4_HOP2_MAX: pair decoders follow the token chain two links per hop in launches of up to this many blocks per CU */
     bool hc_cand_lds = true;              /* K4LZ4_HC_CAND_MEM unsets it: blocks of at most 64 KiB get their candidate records by k4_hc_cand_kernel (from memory) */
     int hc_cand_dynlds = 0;               /* K4LZ4_HC_CAND_DYNLDS (a measurement switch): bytes of unused LDS per workgroup of k4_hc_cand_kernel, i.e. fewer of them per CU */
@@ -289,7 +289,7 @@ int hip_fail(k4lz4_ctx *ctx, hipError_t e, const char *what)
 enum Kind { KIND_ENCODE, KIND_DECODE, KIND_PICKLE, KIND_UNPICKLE, KIND_WRAP };
 /* the envelope an encode is wrapped in (launch_hc): none, LZ4Pickler's, LZ4Wrapper's */
 enum Envelope { ENV_NONE, ENV_PICKLE, ENV_WRAP };
-constexpr int FLAG_SEGMENTS_OK = 1 << 20;   /* launch_inner, fast encode: big blocks may be cut into segments (k4lz4_segments.hpp); not part of the API */
+constexpr int FLAG_SEGMENTS_OK = 1 << 20;   /* launch_fast_encode: big blocks may be cut into segments (k4lz4_segments.hpp); not part of the API */
 
 /* LL.Enforce32 (Engine/LL.tools.cs:19-27): a process-wide switch in the reference, so here too */
 std::atomic<int> g_enforce32{0};
@@ -321,6 +321,32 @@ int take_device_status(k4lz4_ctx *ctx)
     return fail(ctx, nomem ? K4LZ4_E_NOMEM : K4LZ4_E_HIP, msg.c_str());
 }
 
+/* one wave per item, W waves per workgroup */
+#define K4_LAUNCH_WAVES(kernel, items, W, stream, ...) \
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(((items) + (W) - 1) / (W))), dim3(64 * (W)), 0, stream, __VA_ARGS__)
+
+/* scratch that has to grow is freed first: what still runs on it must be finished (same-stream reuse needs no wait).  For scratch
+ * that one call's own launches order on `stream`; the device forms' scratch, ordered by ev_busy, grows through grow_scratch */
+int grow_after(k4lz4_ctx *ctx, hipStream_t stream, uint8_t **p, size_t *cap, size_t need)
+{
+    if (need > *cap) K4_HIP(ctx, hipStreamSynchronize(stream));
+    return grow(ctx, p, cap, need, false);
+}
+
+/* the envelope around an encode: the encoders' slots prepared in front of them (LZ4Pickler: block = envelope + 5, cap U - 1;
+ * LZ4Wrapper: + 8, cap U - 1), the envelopes closed behind them */
+void envelope_prep(Envelope env, k4::BatchArgs a, uint64_t *encOff, int32_t *encCap, hipStream_t stream)
+{
+    if (env == ENV_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_prep_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, a, encOff, encCap);
+    if (env == ENV_WRAP) hipLaunchKernelGGL(k4::k4_wrap_prep_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, a, encOff, encCap);
+}
+
+void envelope_finish(Envelope env, k4::BatchArgs a, int32_t *encLen, hipStream_t stream)
+{
+    if (env == ENV_PICKLE) K4_LAUNCH_WAVES(k4::k4_pickle_finish_kernel, a.n, k4::PICKLE_FINISH_WAVES_PER_WG, stream, a, encLen);
+    if (env == ENV_WRAP) K4_LAUNCH_WAVES(k4::k4_wrap_finish_kernel, a.n, k4::WRAP_FINISH_WAVES_PER_WG, stream, a, encLen);
+}
+
 /* HC levels: layout -> (sync for the scratch size) -> hash-table clear -> chain kernel -> parse kernel.
  * `env`: the same around the LZ4Pickler envelope (encoder slot = envelope + 5, cap U - 1) or LZ4Wrapper's (+ 8, cap U - 1). */
 /* hostLen: the blocks' lengths when the caller has them on the host (host-pointer calls), else nullptr */
@@ -333,12 +359,9 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
     const int64_t chunk_max = 4096;   /* 128 KiB of hash table per block in flight */
     for (int64_t first = 0; first < n; first += chunk_max) {
         const int64_t cnt = std::min<int64_t>(chunk_max, n - first);
-        /* scratch that has to grow is freed first: what still runs on it must be finished (same-stream reuse needs no wait) */
-        const size_t need_hash = (size_t)cnt << (k4::HC_HASH_LOG + 2), need_meta = (size_t)(cnt + 2) * 8 + (size_t)cnt * 16 + 64;
-        if (need_hash > ctx->d_hc_hash_cap || need_meta > ctx->d_hc_meta_cap) K4_HIP(ctx, hipStreamSynchronize(stream));
-        int rc = grow(ctx, &ctx->d_hc_hash, &ctx->d_hc_hash_cap, need_hash, false);
+        int rc = grow_after(ctx, stream, &ctx->d_hc_hash, &ctx->d_hc_hash_cap, (size_t)cnt << (k4::HC_HASH_LOG + 2));
         if (rc != K4LZ4_OK) return rc;
-        rc = grow(ctx, &ctx->d_hc_meta, &ctx->d_hc_meta_cap, need_meta, false);
+        rc = grow_after(ctx, stream, &ctx->d_hc_meta, &ctx->d_hc_meta_cap, (size_t)(cnt + 2) * 8 + (size_t)cnt * 16 + 64);
         if (rc != K4LZ4_OK) return rc;
         unsigned long long *d_woff = (unsigned long long *)ctx->d_hc_meta;
         uint64_t *d_encoff = (uint64_t *)(d_woff + cnt + 2);
@@ -356,8 +379,7 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
         a.src = src; a.srcOff = h.srcOff; a.srcLen = h.srcLen; a.dst = dst; a.dstOff = h.dstOff; a.dstCap = h.dstCap;
         a.outLen = h.outLen; a.n = cnt; a.level = level; a.accel = 1; a.flags = flags;
         if (env == ENV_PICKLE || env == ENV_WRAP) {
-            if (env == ENV_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
-            else hipLaunchKernelGGL(k4::k4_wrap_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
+            envelope_prep(env, a, d_encoff, d_enccap, stream);
             h.dstOff = d_encoff; h.dstCap = d_enccap; h.outLen = d_enclen; h.flags = K4LZ4_FLAG_RAW_RETURN;
         }
         /* How much work area, and how long the longest block is: from the host's copy of the lengths, from the
@@ -379,9 +401,8 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
         } else {
             ask_device = true;
         }
-        if (!ask_device && (size_t)tail[0] + 256 > ctx->d_hc_work_cap) K4_HIP(ctx, hipStreamSynchronize(stream));
         if (!ask_device) {
-            rc = grow(ctx, &ctx->d_hc_work, &ctx->d_hc_work_cap, (size_t)tail[0] + 256, false);
+            rc = grow_after(ctx, stream, &ctx->d_hc_work, &ctx->d_hc_work_cap, (size_t)tail[0] + 256);
             if (rc != K4LZ4_OK) return rc;
         }
         hipLaunchKernelGGL(k4::k4_hc_layout_kernel, dim3(1), dim3(256), 0, stream, h);
@@ -408,16 +429,16 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
                 K4_HIP(ctx, hipMemsetAsync(ctx->d_hc_hash + ((size_t)n_lds << (k4::HC_HASH_LOG + 2)), 0, (size_t)n_mem << (k4::HC_HASH_LOG + 2), ctx->aux));
                 k4::HcArgs hm = h;
                 hm.blockBase = (unsigned)n_lds; hm.nChain = n_mem;
-                hipLaunchKernelGGL(k4::k4_hc_chain_kernel, dim3((unsigned)((n_mem + k4::HC_CHAIN_WAVES_PER_WG - 1) / k4::HC_CHAIN_WAVES_PER_WG)), dim3(64 * k4::HC_CHAIN_WAVES_PER_WG), 0, ctx->aux, hm);
+                K4_LAUNCH_WAVES(k4::k4_hc_chain_kernel, n_mem, k4::HC_CHAIN_WAVES_PER_WG, ctx->aux, hm);
                 K4_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
             }
             h.nChain = n_lds;
-            hipLaunchKernelGGL(k4::k4_hc_chain_lds_kernel, dim3((unsigned)((n_lds + k4::HC_CHAIN_LDS_WAVES_PER_WG - 1) / k4::HC_CHAIN_LDS_WAVES_PER_WG)), dim3(64 * k4::HC_CHAIN_LDS_WAVES_PER_WG), 0, stream, h);
+            K4_LAUNCH_WAVES(k4::k4_hc_chain_lds_kernel, n_lds, k4::HC_CHAIN_LDS_WAVES_PER_WG, stream, h);
             if (n_mem > 0) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_join, 0));
         } else {
             K4_HIP(ctx, hipMemsetAsync(ctx->d_hc_hash, 0, (size_t)cnt << (k4::HC_HASH_LOG + 2), stream));
             h.nChain = cnt;
-            hipLaunchKernelGGL(k4::k4_hc_chain_kernel, dim3((unsigned)((cnt + k4::HC_CHAIN_WAVES_PER_WG - 1) / k4::HC_CHAIN_WAVES_PER_WG)), dim3(64 * k4::HC_CHAIN_WAVES_PER_WG), 0, stream, h);
+            K4_LAUNCH_WAVES(k4::k4_hc_chain_kernel, cnt, k4::HC_CHAIN_WAVES_PER_WG, stream, h);
         }
         const bool optimal = level >= K4LZ4_L10_OPT;              /* clTable (LL64.high.cs:1124-1138): lz4opt strategy */
         if (tail[1] >= 13 && tail[1] <= 65536 && lds_ok && !optimal && ctx->hc_cand_lds) {
@@ -435,8 +456,7 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
                 hipLaunchKernelGGL(k4::k4_hc_cand_kernel, dim3(groups * 8u * hy.candChunks), dim3(256), (size_t)ctx->hc_cand_dynlds, stream, hy);
             }
         }
-        const hipStream_t pstream = stream;
-        if (optimal) hipLaunchKernelGGL(k4::k4_hc_parse_opt_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, h);
+        if (optimal) K4_LAUNCH_WAVES(k4::k4_hc_parse_opt_kernel, cnt, 1, stream, h);
         else {
             /* level 3 on blocks of at most 64 KiB: the parse writes 8-byte sequence records (the fast encoder's scratch, a slot per
              * block) and the same wave turns them into bytes afterwards; without room for them LZ4HC_encodeSequence stays in the loop */
@@ -448,8 +468,7 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
                 if (tail[1] < k4::HC_SEG_MIN_LEN) nseg = 1;
                 for (;;) {
                     const size_t need = (size_t)cnt * (nseg == 4 ? k4::hc_seg_rec_off(4, 4) : nseg == 2 ? k4::hc_seg_rec_off(2, 2) : k4::PARSE_REC_STRIDE) * sizeof(uint2);
-                    if (need > ctx->d_parse_cap) K4_HIP(ctx, hipStreamSynchronize(stream));
-                    if (grow(ctx, &ctx->d_parse, &ctx->d_parse_cap, need, false) == K4LZ4_OK) { h.recs = (uint2 *)ctx->d_parse; break; }
+                    if (grow_after(ctx, stream, &ctx->d_parse, &ctx->d_parse_cap, need) == K4LZ4_OK) { h.recs = (uint2 *)ctx->d_parse; break; }
                     { std::lock_guard<std::mutex> g(g_err_mu); ctx->error.clear(); }
                     if (nseg == 1) break;
                     nseg = 1;
@@ -457,15 +476,14 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
             }
             if (ctx->use_pace && ctx->d_pace && cnt > 8 * (int64_t)ctx->cu_count) {
                 h.pace = ctx->d_pace;
-                K4_HIP(ctx, hipMemsetAsync(h.pace, 0, k4::PACE_BYTES, pstream));
+                K4_HIP(ctx, hipMemsetAsync(h.pace, 0, k4::PACE_BYTES, stream));
             }
-            if (h.recs && nseg == 4) hipLaunchKernelGGL(k4::k4_hc_parse_seg4_kernel, dim3((unsigned)((cnt + 1) / 2)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, pstream, h);
-            else if (h.recs && nseg == 2) hipLaunchKernelGGL(k4::k4_hc_parse_seg2_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, pstream, h);
-            else if (h.recs) hipLaunchKernelGGL(k4::k4_hc_parse_rec_kernel, dim3((unsigned)((cnt + k4::HC_REC_WAVES_PER_WG - 1) / k4::HC_REC_WAVES_PER_WG)), dim3(64 * k4::HC_REC_WAVES_PER_WG), 0, pstream, h);
-            else hipLaunchKernelGGL(k4::k4_hc_parse_kernel, dim3((unsigned)((cnt + k4::HC_PARSE_WAVES_PER_WG - 1) / k4::HC_PARSE_WAVES_PER_WG)), dim3(64 * k4::HC_PARSE_WAVES_PER_WG), 0, pstream, h);
+            if (h.recs && nseg == 4) hipLaunchKernelGGL(k4::k4_hc_parse_seg4_kernel, dim3((unsigned)((cnt + 1) / 2)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, stream, h);
+            else if (h.recs && nseg == 2) hipLaunchKernelGGL(k4::k4_hc_parse_seg2_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, stream, h);
+            else if (h.recs) K4_LAUNCH_WAVES(k4::k4_hc_parse_rec_kernel, cnt, k4::HC_REC_WAVES_PER_WG, stream, h);
+            else K4_LAUNCH_WAVES(k4::k4_hc_parse_kernel, cnt, k4::HC_PARSE_WAVES_PER_WG, stream, h);
         }
-        if (env == ENV_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_finish_kernel, dim3((unsigned)((cnt + k4::PICKLE_FINISH_WAVES_PER_WG - 1) / k4::PICKLE_FINISH_WAVES_PER_WG)), dim3(64 * k4::PICKLE_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
-        if (env == ENV_WRAP) hipLaunchKernelGGL(k4::k4_wrap_finish_kernel, dim3((unsigned)((cnt + k4::WRAP_FINISH_WAVES_PER_WG - 1) / k4::WRAP_FINISH_WAVES_PER_WG)), dim3(64 * k4::WRAP_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
+        envelope_finish(env, a, d_enclen, stream);
         K4_HIP(ctx, hipGetLastError());
     }
     return K4LZ4_OK;
@@ -479,21 +497,8 @@ struct DictArgs {
     const signed char *mode;
 };
 
-/* how many slots the LDS-table encoder kernel is launched with for a batch of cnt blocks: a fixed share of the number
- * (K4LZ4_SPLIT_PCT), or the most the device-side split by cost (k4_order_kernel, cost_pct hundredths of the cost, at least one
- * residency) can ask for -- that kernel clamps its count to this value, so a block is never left to neither kernel */
-static int64_t lds_share(const k4lz4_ctx *ctx, int64_t cnt)
-{
-    const int64_t lds_slots = 8 * (int64_t)ctx->cu_count;
-    if (ctx->split_pct > 0) return std::min<int64_t>(cnt, std::max<int64_t>(1, cnt * ctx->split_pct / 100));
-    const int64_t pct = std::max<int64_t>(48, std::min<int64_t>(ctx->cost_pct, 100));
-    return std::min<int64_t>(cnt, std::max<int64_t>(lds_slots, (cnt * pct + 99) / 100));
-}
-
-/* enqueue the kernels for n blocks; all pointers are device pointers */
-int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
-                 const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
-                 hipStream_t stream, const DictArgs *dd, const int32_t *hostLen);
+/* the batch launcher (launch_inner and what it dispatches to): enqueues the kernels for n blocks; all pointers are device pointers */
+#include "k4lz4_launch.hpp"
 
 /* A device form's prologue: the context's scratch (dispatch order, hash tables, HC work areas, the stream formats' tables)
  * may still be in use by a call that was enqueued on another stream -- st waits for it. */
@@ -525,416 +530,6 @@ int launch(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *srcOff
     const int rc = launch_inner(ctx, kind, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, stream, dd, hostLen);
     mark_busy(ctx, stream);
     return rc;
-}
-
-int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
-                 const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
-                 hipStream_t stream, const DictArgs *dd, const int32_t *hostLen)
-{
-    int64_t chunk_max = 1 << 24;   /* blocks per launch (grid.x * blockDim.x must stay < 2^32) */
-#ifdef K4_PARSE_PROF
-    const bool parse_prof_ok = true;
-#else
-    const bool parse_prof_ok = false;
-#endif
-    const bool encode_like = kind == KIND_ENCODE || kind == KIND_PICKLE || kind == KIND_WRAP;
-    /* Fast-level LZ4Codec.Encode batches beyond what is resident at once (16 blocks per CU: the parse kernel's one workgroup per CU,
-     * nine waves with their table in LDS and seven that move into a table as one becomes free): one persistent launch (round 6,
-     * below); with K4LZ4_NO_PERSIST, or through the one-kernel encoders of rounds 1-4, equal parts of at most one residency each --
-     * a block takes its ~2-3 ms whatever the batch, so those launches are best full.  Not for batches that may be ragged (pickles,
-     * K4LZ4_FLAG_SEGMENTS): those need their one cost-ordered launch. */
-    const bool parse_path = kind == KIND_ENCODE && level < K4LZ4_L03_HC && ctx->use_parse && ctx->accel == 1 && (!ctx->prof || parse_prof_ok || ctx->prof_stamp) &&
-                            !(flags & (FLAG_SEGMENTS_OK | K4LZ4_FLAG_SEGMENTS | K4LZ4_FLAG_NO_SPLIT));
-    /* round 6: the two-step encoder takes a batch beyond one residency in ONE persistent launch -- one workgroup of sixteen waves per
-     * CU, every wave takes the next block of the cost order when it is done with one (the waves with LDS tables from the expensive
-     * end, the others from the cheap end), records in per-wave slots -- instead of launches of one residency each with their own tail */
-    /* round 6: ragged batches -- pickles, K4LZ4_FLAG_SEGMENTS -- through the two-step encoder as well: the blocks below 65 547 bytes by
-     * k4_parse_kernel, the others (and the later segments of the cut ones) by k4_parse_seg_kernel, the join as before */
-    const bool parse_seg_path = kind == KIND_ENCODE && level < K4LZ4_L03_HC && ctx->use_parse && ctx->parse_big && ctx->parse_seg && ctx->parse_inline_emit &&
-                                ctx->accel == 1 && !ctx->prof && (flags & (FLAG_SEGMENTS_OK | K4LZ4_FLAG_SEGMENTS)) != 0 &&
-                                !(flags & (K4LZ4_FLAG_NO_SPLIT | K4LZ4_FLAG_NO_REORDER | K4LZ4_FLAG_ALLOW_COPY));
-    const bool parse_persistent = parse_path && ctx->parse_persist && ctx->parse_inline_emit && !ctx->prof && n > (int64_t)k4::PARSE_MAX_WAVES * (int64_t)ctx->cu_count &&
-                                  !(flags & K4LZ4_FLAG_NO_REORDER);
-    if (kind == KIND_ENCODE && level < K4LZ4_L03_HC && !(flags & (FLAG_SEGMENTS_OK | K4LZ4_FLAG_SEGMENTS | K4LZ4_FLAG_NO_SPLIT)) &&
-        ctx->split_pct <= 0 && !ctx->prof && n > 16 * (int64_t)ctx->cu_count && !parse_persistent) {
-        const int64_t parts = (n + 16 * (int64_t)ctx->cu_count - 1) / (16 * (int64_t)ctx->cu_count);
-        chunk_max = (n + parts - 1) / parts;
-    }
-    if (parse_path && !parse_persistent) chunk_max = std::min<int64_t>(chunk_max, (int64_t)k4::PARSE_MAX_WAVES * (int64_t)ctx->cu_count);      /* (one residency) */
-    if (encode_like && level >= K4LZ4_L03_HC) {
-        const int rc = launch_hc(ctx, kind == KIND_PICKLE ? ENV_PICKLE : kind == KIND_WRAP ? ENV_WRAP : ENV_NONE, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, stream, hostLen);
-        if (rc != K4LZ4_OK || kind != KIND_ENCODE || !(flags & K4LZ4_FLAG_ALLOW_COPY)) return rc;
-        for (int64_t first = 0; first < n; first += chunk_max) {
-            const int64_t cnt = std::min<int64_t>(chunk_max, n - first);
-            k4::BatchArgs a{};
-            a.src = src; a.srcOff = srcOff + first; a.srcLen = srcLen + first;
-            a.dst = dst; a.dstOff = dstOff + first; a.dstCap = dstCap + first; a.outLen = outLen + first; a.n = cnt;
-            hipLaunchKernelGGL(k4::k4_allow_copy_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, stream, a);
-        }
-        K4_HIP(ctx, hipGetLastError());
-        return K4LZ4_OK;
-    }
-    /* (a small batch without a message big enough to be cut into segments keeps the one-kernel pickle path: the segment
-     * machinery costs a plan kernel, a 4096-workgroup launch on a second queue, a join, and -- on a context's first such
-     * call -- 269 MB of scratch; lengths the host does not know count as "may be big") */
-    bool may_cut = ctx->use_segments;
-    if (may_cut && hostLen && n <= (int64_t)ctx->pickle_split_min) {
-        may_cut = false;
-        for (int64_t i = 0; i < n && !may_cut; i++) may_cut = (uint32_t)hostLen[i] >= ctx->seg_min;
-    }
-    if ((kind == KIND_PICKLE && (n > (int64_t)ctx->pickle_split_min || may_cut) && !ctx->prof) || kind == KIND_WRAP) {
-        /* Fast-level pickles of a batch go the encoders' way: slots prepared (block = envelope + 5, cap U - 1, exactly what
-         * k4_pickle_kernel hands its encoder), the batch encoded by the two encoder kernels side by side -- the expensive
-         * messages with their tables in LDS, the others with tables in memory, which puts a ragged batch on all the
-         * chip's wave slots instead of the nine per CU that have room for a table in LDS --, envelopes closed afterwards. */
-        for (int64_t first = 0; first < n; first += chunk_max) {
-            const int64_t cnt = std::min<int64_t>(chunk_max, n - first);
-            const size_t need_meta = (size_t)cnt * 16 + 64;
-            if (need_meta > ctx->d_pk_meta_cap) K4_HIP(ctx, hipStreamSynchronize(stream));
-            int rc = grow(ctx, &ctx->d_pk_meta, &ctx->d_pk_meta_cap, need_meta, false);
-            if (rc != K4LZ4_OK) return rc;
-            uint64_t *d_encoff = (uint64_t *)ctx->d_pk_meta;
-            int32_t *d_enccap = (int32_t *)(d_encoff + cnt);
-            int32_t *d_enclen = d_enccap + cnt;
-            k4::BatchArgs a{};
-            a.src = src; a.srcOff = srcOff + first; a.srcLen = srcLen + first; a.dst = dst; a.dstOff = dstOff + first;
-            a.dstCap = dstCap + first; a.outLen = outLen + first; a.n = cnt; a.level = level; a.accel = 1;
-            a.flags = flags | (g_enforce32.load(std::memory_order_relaxed) ? K4LZ4_FLAG_X32 : 0);
-            /* (wraps take this way whatever the batch; without a message big enough to be cut, not into segments) */
-            const int seg_ok = kind == KIND_PICKLE || may_cut ? FLAG_SEGMENTS_OK : 0;
-            if (kind == KIND_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
-            else hipLaunchKernelGGL(k4::k4_wrap_prep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, a, d_encoff, d_enccap);
-            rc = launch_inner(ctx, KIND_ENCODE, src, srcOff + first, srcLen + first, dst, d_encoff, d_enccap, d_enclen, cnt, level,
-                              (flags & (K4LZ4_FLAG_NO_REORDER | K4LZ4_FLAG_X32)) | K4LZ4_FLAG_RAW_RETURN | seg_ok, stream, nullptr, hostLen ? hostLen + first : nullptr);
-            if (rc != K4LZ4_OK) return rc;
-            if (kind == KIND_PICKLE) hipLaunchKernelGGL(k4::k4_pickle_finish_kernel, dim3((unsigned)((cnt + k4::PICKLE_FINISH_WAVES_PER_WG - 1) / k4::PICKLE_FINISH_WAVES_PER_WG)), dim3(64 * k4::PICKLE_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
-            else hipLaunchKernelGGL(k4::k4_wrap_finish_kernel, dim3((unsigned)((cnt + k4::WRAP_FINISH_WAVES_PER_WG - 1) / k4::WRAP_FINISH_WAVES_PER_WG)), dim3(64 * k4::WRAP_FINISH_WAVES_PER_WG), 0, stream, a, d_enclen);
-            K4_HIP(ctx, hipGetLastError());
-        }
-        return K4LZ4_OK;
-    }
-    /* cost-ordered dispatch (most expensive blocks first): encoders by default, decoders on request */
-    const bool reorder = n > 1 &&
-                         (encode_like ? !(flags & K4LZ4_FLAG_NO_REORDER)
-                                      : ((flags & K4LZ4_FLAG_REORDER) != 0 ||
-                                         /* pickles are ragged by nature: start the long ones first unless told not to */
-                                         (kind == KIND_UNPICKLE && n > 64 && !(flags & K4LZ4_FLAG_NO_REORDER))));
-    uint32_t *d_cost = nullptr, *d_order = nullptr, *d_hist = nullptr;
-    if (reorder) {
-        const size_t cnt_max = (size_t)std::min<int64_t>(chunk_max, n);
-        const size_t hist_words = std::max<size_t>(2 * (size_t)k4::PCOST_BUCKETS, 2 * (size_t)k4::COST_BUCKETS + 16);
-        const size_t need = cnt_max * 8 + hist_words * 4 + 64;
-        if (need > ctx->d_sched_cap) K4_HIP(ctx, hipStreamSynchronize(stream));   /* scratch may still be in use */
-        int rc = grow(ctx, &ctx->d_sched, &ctx->d_sched_cap, need, false);
-        if (rc != K4LZ4_OK) return rc;
-        d_hist = (uint32_t *)ctx->d_sched;
-        d_cost = d_hist + hist_words;     /* [2 * COST_BUCKETS]: where the second encoder kernel's part of the order begins */
-        d_order = d_cost + cnt_max;
-    }
-    for (int64_t first = 0; first < n; first += chunk_max) {
-        const int64_t cnt = std::min<int64_t>(chunk_max, n - first);
-        k4::BatchArgs a{};
-        a.src = src; a.srcOff = srcOff + first; a.srcLen = srcLen + first;
-        a.dst = dst; a.dstOff = dstOff + first; a.dstCap = dstCap + first;
-        a.outLen = outLen + first; a.n = cnt; a.level = level; a.accel = ctx->accel;
-        a.flags = flags | (g_enforce32.load(std::memory_order_relaxed) ? K4LZ4_FLAG_X32 : 0);
-        /* pair decoders: the token chain two links at a time while the launch leaves wave slots free (k4lz4_decode.hpp, follow_tokens) */
-        const bool hop2 = cnt <= (int64_t)ctx->hop2_max_per_cu * (int64_t)ctx->cu_count;
-        a.prof = ctx->prof ? ctx->prof + k4::PROF_STRIDE * first : nullptr;
-        a.status = ctx->d_status;
-        if (((kind == KIND_ENCODE && !parse_path) || (K4_DEC_PACE && (kind == KIND_DECODE || kind == KIND_UNPICKLE))) && ctx->use_pace && ctx->d_pace && cnt > (int64_t)ctx->pace_min_per_cu * (int64_t)ctx->cu_count) {   /* k4lz4_common.hpp, Pace: more than two blocks per SIMD */
-            a.pace = ctx->d_pace;
-            K4_HIP(ctx, hipMemsetAsync(a.pace, 0, k4::PACE_BYTES, stream));
-        }
-        /* big blocks in several segments (k4lz4_segments.hpp): the plan is made on the device, the later segments run on a queue of
-         * their own beside the ordinary kernels (which take a cut block's first segment), the pieces are joined afterwards */
-        k4::SegArgs sg{};
-        bool seg = false;
-        if (kind == KIND_ENCODE && (flags & (FLAG_SEGMENTS_OK | K4LZ4_FLAG_SEGMENTS)) && ctx->use_segments && !a.prof && !(flags & K4LZ4_FLAG_ALLOW_COPY)) {
-            static_assert(k4::SEG_HDR_DWORDS * 4 == 256, "seg_first_of finds the header in front of the items");
-            /* how many segments the plan can come to: every item costs a 16 KiB snapshot and a 16 KiB table slot, so where the
-             * host knows the lengths the arrays are sized by them (an upper bound: the plan's segments are never shorter than
-             * seg_target, its threshold never below seg_min) instead of by the most a launch may have */
-            size_t max_items = (size_t)k4::SEG_MAX_ITEMS;
-            if (hostLen) {
-                size_t bound = 0;
-                for (int64_t i = 0; i < cnt && bound < max_items; i++) {
-                    const int32_t u = hostLen[first + i];
-                    if (u > 0 && (uint32_t)u >= ctx->seg_min) bound += ((size_t)u + ctx->seg_target - 1) / ctx->seg_target;
-                }
-                max_items = std::min(max_items, std::max<size_t>(bound, 2));
-            }
-            const size_t o_items = 256, o_work = o_items + max_items * sizeof(k4::SegItem);
-            const size_t o_blocks = o_work + max_items * 4, o_snaps = (o_blocks + (size_t)k4::SEG_MAX_BLOCKS * 4 + 255) & ~(size_t)255;
-            const size_t o_tables = o_snaps + max_items * k4::SEG_SNAP_DWORDS * 4, total = o_tables + max_items * 16384;
-            if (total > ctx->d_seg_cap || (size_t)cnt * 4 > ctx->d_seg_first_cap) {
-                K4_HIP(ctx, hipStreamSynchronize(stream));
-                K4_HIP(ctx, hipStreamSynchronize(ctx->aux2));
-            }
-            int rc = grow(ctx, &ctx->d_seg, &ctx->d_seg_cap, total, false);
-            if (rc == K4LZ4_OK) rc = grow(ctx, &ctx->d_seg_first, &ctx->d_seg_first_cap, (size_t)cnt * 4, false);
-            if (rc != K4LZ4_OK) return rc;
-            sg.hdr = (k4::SegHdr *)ctx->d_seg; sg.items = (k4::SegItem *)(ctx->d_seg + o_items); sg.work = (uint32_t *)(ctx->d_seg + o_work);
-            sg.blocks = (uint32_t *)(ctx->d_seg + o_blocks); sg.snaps = (uint32_t *)(ctx->d_seg + o_snaps); sg.tables = (uint32_t *)(ctx->d_seg + o_tables);
-            sg.first = (int32_t *)ctx->d_seg_first;
-            sg.seg_min = ctx->seg_min; sg.seg_target = ctx->seg_target; sg.seg_warm = ctx->seg_warm; sg.seg_div = ctx->seg_div; sg.seg_target_max = ctx->seg_target_max; sg.spin_max = ctx->seg_spin_max; sg.max_items = (uint32_t)max_items;
-            hipLaunchKernelGGL(k4::k4_seg_plan_kernel, dim3(1), dim3(256), 0, stream, a, sg);
-            a.seg_first = sg.first; a.seg_items = sg.items; a.seg_snaps = sg.snaps;
-            seg = true;
-        }
-        /* the later segments: on their queue, before the ordinary kernels are launched (their waves are the ones others wait for) */
-        auto segments_start = [&]() -> int {
-            if (!seg) return K4LZ4_OK;
-            K4_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
-            K4_HIP(ctx, hipStreamWaitEvent(ctx->aux2, ctx->ev_fork, 0));
-            hipLaunchKernelGGL(k4::k4_encode_seg_kernel, dim3((unsigned)((sg.max_items + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)), dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, ctx->aux2, a, sg);
-            K4_HIP(ctx, hipEventRecord(ctx->ev_join2, ctx->aux2));
-            return K4LZ4_OK;
-        };
-        auto segments_join = [&]() -> int {
-            if (!seg) return K4LZ4_OK;
-            K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_join2, 0));
-            hipLaunchKernelGGL(k4::k4_seg_join_kernel, dim3((unsigned)std::min<int64_t>(k4::SEG_MAX_BLOCKS, cnt)), dim3(64), 0, stream, a, sg);
-            return K4LZ4_OK;
-        };
-        if (dd && dd->dict) {
-            a.dict = dd->dict; a.dictOff = dd->off + first; a.dictLen = dd->len + first;
-            a.dictMode = dd->mode ? dd->mode + first : nullptr;
-        }
-        if (reorder && parse_path && kind == KIND_ENCODE && ctx->parse_pcost) {
-            /* the two-kernel encoder's own estimate and order (k4lz4_parse.hpp, ParseCost): one workgroup of sixteen waves per CU at
-             * most, every wave's table in LDS; the order's workgroups each place a stretch of the batch (k4_order_kernel) */
-            const int64_t wgs = std::min<int64_t>((cnt + k4::PARSE_MAX_WAVES - 1) / k4::PARSE_MAX_WAVES, ctx->cu_count);
-            a.cost = d_cost; a.hist = d_hist; a.order_out = d_order;
-            K4_HIP(ctx, hipMemsetAsync(d_hist, 0, k4::PCOST_BUCKETS * 4, stream));
-            hipLaunchKernelGGL(static_cast<void (*)(k4::BatchArgs, k4::ParseCost)>(k4::k4_cost_kernel), dim3((unsigned)wgs), dim3(64 * k4::PARSE_MAX_WAVES), 0, stream, a, ctx->pcost_fit);
-            hipLaunchKernelGGL(k4::k4_order_kernel, dim3(k4::order_workgroups(cnt)), dim3(256), 0, stream, a, 0xffffffffu, 1);
-            a.order = d_order;
-        }
-        else if (reorder) {
-            a.cost = d_cost; a.hist = d_hist; a.order_out = d_order;
-            K4_HIP(ctx, hipMemsetAsync(d_hist, 0, (2 * k4::COST_BUCKETS + 16) * 4, stream));
-            hipLaunchKernelGGL(k4::k4_cost_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, a, encode_like ? 0 : 1,
-                               kind == KIND_ENCODE && parse_path ? k4::COST_SAMPLE_PARSE : k4::COST_SAMPLE);
-            /* the split between the two encoder kernels by cost (see k4_order_kernel): 48 % of it, at least one residency of
-             * the LDS-table kernel; K4LZ4_SPLIT_PCT fixes a share of the NUMBER of blocks instead */
-            const bool two_kernels = kind == KIND_ENCODE && !a.prof && cnt > 512 && !(flags & K4LZ4_FLAG_NO_SPLIT) &&
-                                     cnt > 8 * (int64_t)ctx->cu_count && ctx->split_pct <= 0;
-            k4::BatchArgs ao = a;
-            ao.first = two_kernels ? (uint32_t)ctx->cost_pct : 0u;
-            ao.total = (uint32_t)((int64_t)ctx->lds_floor_per_cu * (int64_t)ctx->cu_count);
-            hipLaunchKernelGGL(k4::k4_order_kernel, dim3(k4::order_workgroups(cnt)), dim3(256), 0, stream, ao, (uint32_t)lds_share(ctx, cnt));
-            a.order = d_order;
-            if (two_kernels) a.split = d_hist + 2 * k4::COST_BUCKETS;
-        }
-        const unsigned wg4 = (unsigned)((cnt + k4::DECODE_WAVES_PER_WG - 1) / k4::DECODE_WAVES_PER_WG);
-        /* LZ4Codec.Encode's case -- acceleration 1, no segments -- goes through the two-kernel encoder (k4lz4_parse.hpp): which
-         * sequences (one wavefront per block, 64 x K positions per round, 16 blocks per workgroup = per CU dealt from the cost
-         * order, the nine most expensive of a workgroup with their table in LDS), then their bytes (a throughput kernel), then
-         * whatever block the parse left alone (65 547 bytes and more, very short ones) by the one-kernel encoder. */
-        bool parse_here = kind == KIND_ENCODE && (parse_path || (parse_seg_path && (a.order || cnt == 1)));
-        /* blocks of 65 547 bytes and more (byU32 tables) go through k4_parse_big_kernel behind the first launch -- where the parsing
-         * waves write their blocks out themselves (a big block has more sequences than a record slot holds) */
-        const bool big_ok = ctx->parse_big && ctx->parse_inline_emit;
-        bool any_small = true, any_big = big_ok;
-        if (parse_here && hostLen) {             /* nothing for the parse kernels in this part (all blocks too short): no scratch, no launch */
-            any_small = false; any_big = false;
-            for (int64_t i = 0; i < cnt && !(any_small && (any_big || !big_ok)); i++) {
-                const int32_t len = hostLen[first + i];
-                if (len >= (int32_t)k4::PARSE_MIN_LEN && len < k4::LIMIT_64K) any_small = true;
-                else if (len >= k4::LIMIT_64K && big_ok) any_big = true;
-            }
-            parse_here = any_small || any_big;
-        }
-        int64_t waves = 0, nwg = 0, nwg_seg = 0;
-        const bool seg_two_step = seg && parse_here && parse_seg_path;      /* (seg: the plan has been made above) */
-        bool queue = false, slot_recs = false;
-        size_t o_meta = 0, o_gtab = 0;
-        if (parse_here) {
-            waves = std::max<int64_t>(1, std::min<int64_t>(ctx->parse_waves, (cnt + ctx->cu_count - 1) / ctx->cu_count));
-            /* K4LZ4_PARSE_QUEUE, and every batch beyond one residency: one workgroup per CU at most, every wave takes the next block of
-             * the cost order when it is done with one */
-            queue = (ctx->parse_queue || parse_persistent || parse_seg_path) && a.order && cnt > waves * (int64_t)ctx->cu_count;
-            nwg = queue ? (int64_t)ctx->cu_count : (cnt + waves - 1) / waves;
-            /* the segments' launch: always sixteen waves per workgroup, one workgroup per CU at most, everything from its queue */
-            if (seg_two_step) nwg_seg = std::min<int64_t>(ctx->cu_count, (cnt + (int64_t)sg.max_items + k4::PARSE_MAX_WAVES - 1) / k4::PARSE_MAX_WAVES);
-            /* records: a slot per wave of the launch where the parsing waves write their blocks out themselves, else one per block */
-            slot_recs = ctx->parse_inline_emit;
-            const size_t rec_slots = slot_recs ? std::max((size_t)nwg * (size_t)waves, (size_t)nwg_seg * k4::PARSE_MAX_WAVES) : (size_t)cnt;
-            o_meta = rec_slots * k4::PARSE_REC_STRIDE * sizeof(uint2); o_gtab = (o_meta + (size_t)cnt * 8 + 64 + 255) & ~(size_t)255;
-            const size_t need = o_gtab + std::max(waves > k4::PARSE_LDS_TABLES ? (size_t)nwg * k4::PARSE_MAX_WAVES * 16384 : 0, (size_t)nwg_seg * k4::PARSE_MAX_WAVES * 16384);
-            if (need > ctx->d_parse_cap) K4_HIP(ctx, hipStreamSynchronize(stream));
-            const int rcp = grow(ctx, &ctx->d_parse, &ctx->d_parse_cap, need, false);
-            /* (no room for the records: the one-kernel encoders below need next to none -- the same bytes, a third slower) */
-            if (rcp != K4LZ4_OK) { std::lock_guard<std::mutex> g(g_err_mu); ctx->error.clear(); parse_here = false; }
-        }
-        if (parse_here) {
-            k4::ParseArgs pa{};
-            pa.recs = (uint2 *)ctx->d_parse; pa.meta = (uint32_t *)(ctx->d_parse + o_meta); pa.gtab = (uint32_t *)(ctx->d_parse + o_gtab);
-            pa.nwg = (uint32_t)nwg;
-            pa.inline_emit = ctx->parse_inline_emit ? 1u : 0u;
-            pa.slot_recs = slot_recs ? 1u : 0u;
-            pa.migrate = ctx->parse_migrate ? 1u : 0u;
-            pa.big = any_big ? 1u : 0u;
-            /* late blocks first among the waves of a SIMD (k4lz4_parse.hpp, ParsePace): its words are LDS of the workgroup, so
-             * nothing is filled or launched for it; k4_parse_kernel alone reads the switch */
-            pa.pace = parse_path && ctx->use_pace && (!queue || ctx->parse_pace_queue) && cnt > (int64_t)ctx->parse_pace_min_per_cu * (int64_t)ctx->cu_count ? 1u : 0u;
-            /* eight words behind the counts: the two launches' queues (three words each) and, word 3, the number of blocks the first
-             * launch leaves to the second */
-            K4_HIP(ctx, hipMemsetAsync(pa.meta + 2 * cnt, 0, 32, stream));
-            if (queue) pa.queue = pa.meta + 2 * cnt;
-            pa.nbig = pa.meta + 2 * cnt + 3;
-            /* (the first launch also says whose every block is -- PARSE_BIG / PARSE_REST --, so it runs even without a block of its own) */
-            hipLaunchKernelGGL(k4::k4_parse_kernel, dim3((unsigned)nwg), dim3((unsigned)(64 * waves)), 0, stream, a, pa);
-            if (seg_two_step) {
-                k4::ParseArgs pb = pa;
-                pb.queue = pa.meta + 2 * cnt + 4;
-                pb.nwg = (uint32_t)nwg_seg;
-                hipLaunchKernelGGL(k4::k4_parse_seg_kernel, dim3((unsigned)nwg_seg), dim3(64 * k4::PARSE_MAX_WAVES), 0, stream, a, pb, sg);
-            } else if (any_big) {
-                k4::ParseArgs pb = pa;
-                if (queue) pb.queue = pa.queue + 4;
-                hipLaunchKernelGGL(k4::k4_parse_big_kernel, dim3((unsigned)nwg), dim3((unsigned)(64 * waves)), 0, stream, a, pb);
-            }
-            if (!pa.inline_emit)
-                hipLaunchKernelGGL(k4::k4_emit_kernel, dim3((unsigned)((cnt + k4::EMIT_WAVES_PER_WG - 1) / k4::EMIT_WAVES_PER_WG)), dim3(64 * k4::EMIT_WAVES_PER_WG), 0, stream, a, pa);
-            bool rest = true;          /* (where the host knows the lengths it knows whether there is anything left) */
-            if (hostLen) {
-                rest = false;
-                for (int64_t i = 0; i < cnt && !rest; i++) rest = hostLen[first + i] < (int32_t)k4::PARSE_MIN_LEN || (hostLen[first + i] >= k4::LIMIT_64K && !any_big);
-            }
-            if (rest)
-                hipLaunchKernelGGL(k4::k4_encode_fast_rest_kernel, dim3((unsigned)((cnt + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)), dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, stream, a, pa);
-            if (seg_two_step)            /* the cut blocks' pieces: joined, or encoded again (k4lz4_segments.hpp) */
-                hipLaunchKernelGGL(k4::k4_seg_join_kernel, dim3((unsigned)std::min<int64_t>(k4::SEG_MAX_BLOCKS, cnt)), dim3(64), 0, stream, a, sg);
-            if (flags & K4LZ4_FLAG_ALLOW_COPY)
-                hipLaunchKernelGGL(k4::k4_allow_copy_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, stream, a);
-            K4_HIP(ctx, hipGetLastError());
-            continue;
-        }
-        switch (kind) {
-        case KIND_ENCODE:
-            if (a.prof && !ctx->prof_stamp) {
-                if (ctx->prof_gtab) {    /* diagnostics: the instrumented encoder with its table in global memory, like the global-table kernel */
-                    if ((size_t)cnt * 16384 > ctx->d_gtab_cap) {
-                        K4_HIP(ctx, hipStreamSynchronize(ctx->aux));
-                        int rc2 = grow(ctx, &ctx->d_gtab, &ctx->d_gtab_cap, (size_t)cnt * 16384, false);
-                        if (rc2 != K4LZ4_OK) return rc2;
-                    }
-                    a.gtab = (uint32_t *)ctx->d_gtab;
-                }
-                hipLaunchKernelGGL(k4::k4_encode_fast_prof_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, a);
-            }
-            else if (reorder && cnt > 512 && !(flags & K4LZ4_FLAG_NO_SPLIT)) {
-                /* Only 8 blocks per CU fit with their hash table in LDS.  The most expensive blocks
-                 * (front of the dispatch order) take those slots; the others are encoded at the same
-                 * time on a second queue by the global-memory-table variant of the kernel. */
-                /* measured on MI355X (profiles/r02_split_sweep.txt): best when the LDS-table kernel gets one full
-                 * residency of the chip (8 blocks per CU) or about 48 % of a larger batch; one block more
-                 * than a residency starts a second pass and costs 20 % */
-                const int64_t lds_slots = 8 * (int64_t)ctx->cu_count;
-                const int64_t n_lds = lds_share(ctx, cnt);
-                /* (with the split decided on the device, a.split: n_lds is the most the LDS-table kernel can get -- the share of
-                 * the cost is never a larger share of the number -- and the other kernel is sized for the least) */
-                const int64_t n_g = cnt - (a.split ? std::min<int64_t>(cnt, (int64_t)ctx->lds_floor_per_cu * (int64_t)ctx->cu_count) : n_lds);
-                const int64_t gchunk = 8192;
-                if (n_g > 0 && (size_t)std::min(n_g, gchunk) * 16384 > ctx->d_gtab_cap) {
-                    K4_HIP(ctx, hipStreamSynchronize(ctx->aux));
-                    int rc2 = grow(ctx, &ctx->d_gtab, &ctx->d_gtab_cap, (size_t)std::min(n_g, gchunk) * 16384, false);
-                    if (rc2 != K4LZ4_OK) return rc2;
-                }
-                { const int rcs = segments_start(); if (rcs != K4LZ4_OK) return rcs; }
-                K4_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
-                K4_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-                for (int64_t g0 = 0; g0 < n_g; g0 += gchunk) {
-                    k4::BatchArgs ag = a;
-                    ag.first = (uint32_t)((a.split ? 0 : n_lds) + g0);
-                    ag.total = (uint32_t)cnt;
-                    ag.gtab = (uint32_t *)ctx->d_gtab;
-                    ag.n = std::min(gchunk, n_g - g0);
-                    if (seg) hipLaunchKernelGGL(k4::k4_encode_fast_gtab_seg_kernel, dim3((unsigned)((ag.n + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)),
-                                                dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, ctx->aux, ag);
-                    else hipLaunchKernelGGL(k4::k4_encode_fast_gtab_kernel, dim3((unsigned)((ag.n + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)),
-                                       dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, ctx->aux, ag);
-                }
-                K4_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-                {
-                    k4::BatchArgs al = a;
-                    al.n = n_lds;
-                    if (seg)
-                        hipLaunchKernelGGL(k4::k4_encode_fast_seg_kernel, dim3((unsigned)((n_lds + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)),
-                                           dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, stream, al);
-                    else if (n_g == 0 && cnt <= lds_slots)
-                        hipLaunchKernelGGL(k4::k4_encode_fast_more_kernel, dim3((unsigned)((n_lds + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)),
-                                           dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, stream, al);
-                    else
-                        hipLaunchKernelGGL(k4::k4_encode_fast_kernel, dim3((unsigned)((n_lds + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)),
-                                           dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, stream, al);
-                }
-                K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_join, 0));
-                { const int rcs = segments_join(); if (rcs != K4LZ4_OK) return rcs; }
-            }
-            else if (seg) {
-                { const int rcs = segments_start(); if (rcs != K4LZ4_OK) return rcs; }
-                hipLaunchKernelGGL(k4::k4_encode_fast_seg_kernel, dim3((unsigned)((cnt + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)),
-                                   dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, stream, a);
-                { const int rcs = segments_join(); if (rcs != K4LZ4_OK) return rcs; }
-            }
-            else if (cnt <= 8 * (int64_t)ctx->cu_count)       /* a half-empty chip: the variant that buys latency with instructions */
-                hipLaunchKernelGGL(k4::k4_encode_fast_more_kernel, dim3((unsigned)((cnt + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)),
-                                   dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, stream, a);
-            else hipLaunchKernelGGL(k4::k4_encode_fast_kernel, dim3((unsigned)((cnt + k4::ENCODE_WAVES_PER_WG - 1) / k4::ENCODE_WAVES_PER_WG)),
-                                    dim3(64 * k4::ENCODE_WAVES_PER_WG), 0, stream, a);
-            break;
-        case KIND_DECODE:
-            ctx->last_decode_kernel = a.pace ? K4LZ4_DECODE_KERNEL_PACE : 0;
-            if (a.prof && ctx->prof_pair && !ctx->prof_stamp) {
-                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_PROF;
-                hipLaunchKernelGGL(k4::k4_decode_pair_prof_kernel, dim3((unsigned)((cnt + k4::DECODE_PAIRS_PER_WG - 1) / k4::DECODE_PAIRS_PER_WG)),
-                                   dim3(128 * k4::DECODE_PAIRS_PER_WG), 0, stream, a);
-            }
-            else if (a.prof && !ctx->prof_stamp) {
-                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_PROF;
-                hipLaunchKernelGGL(k4::k4_decode_prof_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
-            }
-            else if (cnt > 24 * (int64_t)ctx->cu_count) { /* more blocks than can be resident (6 waves x 4 SIMDs per CU) */
-                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_DENSE;
-                hipLaunchKernelGGL(k4::k4_decode_dense_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
-            }
-            else if (cnt <= 16 * (int64_t)ctx->cu_count && !ctx->no_pair) {
-                /* at most half the chip's wave slots (8 per SIMD at 64 VGPRs) are needed: two waves per block, one
-                 * parsing ahead of the one that copies */
-                ctx->last_decode_kernel |= hop2 ? K4LZ4_DECODE_KERNEL_PAIR2 : K4LZ4_DECODE_KERNEL_PAIR;
-                hipLaunchKernelGGL(hop2 ? k4::k4_decode_pair2_kernel : k4::k4_decode_pair_kernel, dim3((unsigned)((cnt + k4::DECODE_PAIRS_PER_WG - 1) / k4::DECODE_PAIRS_PER_WG)),
-                                   dim3(128 * k4::DECODE_PAIRS_PER_WG), 0, stream, a);
-            }
-            else {
-                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_SINGLE;
-                hipLaunchKernelGGL(k4::k4_decode_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
-            }
-            break;
-        case KIND_PICKLE:
-            hipLaunchKernelGGL(k4::k4_pickle_kernel, dim3((unsigned)cnt), dim3(64), 0, stream, a);
-            break;
-        case KIND_UNPICKLE:
-            ctx->last_decode_kernel = a.pace ? K4LZ4_DECODE_KERNEL_PACE : 0;
-            if (cnt <= 64 * (int64_t)ctx->cu_count && !ctx->no_pair) {
-                ctx->last_decode_kernel |= hop2 ? K4LZ4_DECODE_KERNEL_UNPICKLE_PAIR2 : K4LZ4_DECODE_KERNEL_UNPICKLE_PAIR;
-                hipLaunchKernelGGL(hop2 ? k4::k4_unpickle_pair2_kernel : k4::k4_unpickle_pair_kernel, dim3((unsigned)((cnt + k4::DECODE_PAIRS_PER_WG - 1) / k4::DECODE_PAIRS_PER_WG)),
-                                   dim3(128 * k4::DECODE_PAIRS_PER_WG), 0, stream, a);
-            }
-            else {
-                ctx->last_decode_kernel |= K4LZ4_DECODE_KERNEL_UNPICKLE_SINGLE;
-                hipLaunchKernelGGL(k4::k4_unpickle_kernel, dim3(wg4), dim3(64 * k4::DECODE_WAVES_PER_WG), 0, stream, a);
-            }
-            break;        case KIND_WRAP:         /* (wraps are closed above, behind the encoder kernels) */
-            break;
-        }
-        if (kind == KIND_ENCODE && (flags & K4LZ4_FLAG_ALLOW_COPY))
-            hipLaunchKernelGGL(k4::k4_allow_copy_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, stream, a);   /* 4 blocks per workgroup */
-        K4_HIP(ctx, hipGetLastError());
-    }
-    return K4LZ4_OK;
 }
 
 int grow(k4lz4_ctx *ctx, uint8_t **p, size_t *cap, size_t need, bool pinned)

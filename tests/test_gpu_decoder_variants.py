@@ -2,7 +2,7 @@
 tests/test_decoder_cases_host.py).  Everything goes through the device forms on torch tensors, so the arena a kernel wrote into is
 the arena that is read back: a write outside a slot -- behind it or in front of it, for an accepted or a rejected stream -- shows.
 
-The launcher chooses by blocks per CU (k4lz4_capi.hip, launch()): up to 12 the pair kernel that follows the token chain two links
+The launcher chooses by blocks per CU (k4lz4_launch.hpp, launch_decode_like): up to 12 the pair kernel that follows the token chain two links
 per hop, up to 16 the one-hop pair kernel, up to 24 one wave per block, beyond that the dense build; from more than 6 the pair
 kernels run with the late-blocks-first priorities.  A context reads its switches when it is created, so every variant is a
 context made under its environment; `k4lz4_last_decode_kernel` says after every launch which kernel ran, and a variant that did

@@ -83,7 +83,7 @@ def test_one_workgroup_and_a_little_more(workgroup_batch, env_vars):
     context is made --, each against the oracle byte for byte.  The default and the no-migration run also read the placement stamps
     of profile mode 4 (counters[:, 11]: 4 LDS, 5 memory, 6 memory first and an LDS table from some round on; the stamping launch
     is checked against the oracle too).  What they can show on 40 blocks is limited by the launch, not by the lengths: a batch is
-    spread over the CUs first (waves per workgroup = blocks / CUs rounded up, k4lz4_capi.hip), so on a chip of 256 CUs these 40
+    spread over the CUs first (waves per workgroup = blocks / CUs rounded up, k4lz4_launch.hpp, fast_chunk), so on a chip of 256 CUs these 40
     blocks run as 40 workgroups of ONE wave, every table in LDS, and K4LZ4_PARSE_QUEUE, which engages beyond one residency of the
     chip, repeats the default placement.  Memory tables begin at nine blocks per CU: test_ten_waves_per_workgroup below is the batch
     in which all three placements occur, and asserts it."""
