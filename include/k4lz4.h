@@ -14,7 +14,11 @@
  *     With K4LZ4_FLAG_RAW_RETURN they are the LLxx-level returns instead (Engine/LLxx.cs:17-26,
  *     :65-75): bytes written, 0 = did not fit, decode error = -(input position) - 1.
  *   - Bytes of dst[i] beyond outLen[i] are never modified on success
- *     (src/K4os.Compression.LZ4.Tests/SpanTests.cs:36-44).
+ *     (src/K4os.Compression.LZ4.Tests/SpanTests.cs:36-44) -- by the block encoders and the decoders.  Two deliberate exceptions,
+ *     both stated where they apply and both confined to the slot: the pickle and wrap calls encode in place inside the
+ *     envelope's slot (see k4lz4_pickle_batch, k4lz4_wrap_batch), and K4LZ4_FLAG_SEGMENTS.  On failure (an encode, pickle or wrap whose output did not fit
+ *     dstCap[i]) nothing outside dst + dstOff[i] .. + dstCap[i] is written, and the slot's own bytes are then undefined;
+ *     K4LZ4_FLAG_SEGMENTS may write anywhere inside the slot before outLen is final.
  *   - Call-level return: K4LZ4_OK or a negative k4lz4_status; text via k4lz4_last_error().
  *     The library never throws, aborts or calls back.  No pointer is retained after return
  *     (the *_device calls return after enqueueing on the given stream; the buffers must stay
@@ -145,6 +149,50 @@ enum k4lz4_decode_kernel {
     K4LZ4_DECODE_KERNEL_PACE = 64           /* flag: a.pace was armed for the launch */
 };
 K4LZ4_API int k4lz4_last_decode_kernel(const k4lz4_ctx *ctx);
+/* Diagnostic, no counterpart in the reference: the route ctx's most recent encode, pickle or wrap call took through the batch
+ * launcher, as a set of bits -- one per kernel family the call launched, and a few facts about the launches that bytes cannot
+ * show.  Every bit is stored on the host at the line that issues the launch, or-ed over the call's launch chunks, and cleared
+ * when the next encode, pickle or wrap call enters the launcher (a decode leaves it alone; a chained HC encode, which shares
+ * the HC launcher, clears it too and reports its own HC bits).  K4LZ4_ENCODE_ROUTE_NONE before the first such call (also for a
+ * NULL ctx).  It does not wait, and no kernel, grid or scratch depends on it. */
+enum k4lz4_encode_route {
+    K4LZ4_ENCODE_ROUTE_NONE = 0,
+    /* fast levels, the two-step encoder (k4lz4_parse.hpp) */
+    K4LZ4_ENCODE_ROUTE_PARSE = 1 << 0,         /* k4_parse_kernel */
+    K4LZ4_ENCODE_ROUTE_PARSE_BIG = 1 << 1,     /* k4_parse_big_kernel: blocks of 65 547 bytes and more */
+    K4LZ4_ENCODE_ROUTE_PARSE_SEG = 1 << 2,     /* k4_parse_seg_kernel: ragged batches, the big blocks and the later segments */
+    K4LZ4_ENCODE_ROUTE_EMIT = 1 << 3,          /* k4_emit_kernel (K4LZ4_NO_INLINE_EMIT) */
+    K4LZ4_ENCODE_ROUTE_REST = 1 << 4,          /* k4_encode_fast_rest_kernel: the blocks the parse left alone */
+    /* fast levels, the one-kernel encoders (k4lz4_encode_fast.hpp) */
+    K4LZ4_ENCODE_ROUTE_LDS = 1 << 5,           /* k4_encode_fast_kernel, or its twin k4_encode_fast_seg_kernel (then with _SEGMENTS) */
+    K4LZ4_ENCODE_ROUTE_MORE = 1 << 6,          /* k4_encode_fast_more_kernel: at most 8 blocks per CU */
+    K4LZ4_ENCODE_ROUTE_GTAB = 1 << 7,          /* k4_encode_fast_gtab_kernel beside the LDS-table kernel, or its *_seg twin */
+    K4LZ4_ENCODE_ROUTE_SEGMENTS = 1 << 8,      /* blocks cut into segments: k4_encode_seg_kernel and the *_seg twins, and the join */
+    K4LZ4_ENCODE_ROUTE_PROF = 1 << 9,          /* k4_encode_fast_prof_kernel (k4lz4_profile_batch_device, decode = 0) */
+    K4LZ4_ENCODE_ROUTE_ALLOW_COPY = 1 << 10,   /* k4_allow_copy_kernel behind the encoders (K4LZ4_FLAG_ALLOW_COPY) */
+    K4LZ4_ENCODE_ROUTE_PICKLE = 1 << 11,       /* k4_pickle_kernel: a small batch of pickles by one kernel */
+    K4LZ4_ENCODE_ROUTE_ENVELOPE = 1 << 12,     /* pickles and wraps through the encoders: the prep and finish kernels around them */
+    /* HC levels (k4lz4_encode_hc.hpp) */
+    K4LZ4_ENCODE_ROUTE_HC_CHAIN_PART = 1 << 13, /* k4_hc_chain_part_kernel */
+    K4LZ4_ENCODE_ROUTE_HC_CHAIN_LDS = 1 << 14,  /* k4_hc_chain_lds_kernel (K4LZ4_HC_CHAIN_OLD) */
+    K4LZ4_ENCODE_ROUTE_HC_CHAIN_MEM = 1 << 15,  /* k4_hc_chain_kernel: tables in memory */
+    K4LZ4_ENCODE_ROUTE_HC_CAND_LDS = 1 << 16,   /* k4_hc_walk_lds_kernel + k4_hc_cand_lds_kernel */
+    K4LZ4_ENCODE_ROUTE_HC_CAND_MEM = 1 << 17,   /* k4_hc_cand_kernel (K4LZ4_HC_CAND_MEM, blocks over 64 KiB) */
+    K4LZ4_ENCODE_ROUTE_HC_PARSE = 1 << 18,      /* k4_hc_parse_kernel */
+    K4LZ4_ENCODE_ROUTE_HC_PARSE_REC = 1 << 19,  /* k4_hc_parse_rec_kernel: level 3, one wave per block */
+    K4LZ4_ENCODE_ROUTE_HC_PARSE_SEG2 = 1 << 20, /* k4_hc_parse_seg2_kernel: two waves per block */
+    K4LZ4_ENCODE_ROUTE_HC_PARSE_SEG4 = 1 << 21, /* k4_hc_parse_seg4_kernel: four waves per block */
+    K4LZ4_ENCODE_ROUTE_HC_PARSE_OPT = 1 << 22,  /* k4_hc_parse_opt_kernel: levels 10 and up */
+    /* facts about the fast-level launches */
+    K4LZ4_ENCODE_ROUTE_QUEUE = 1 << 23,        /* k4_parse_kernel's waves took their blocks from the queue */
+    K4LZ4_ENCODE_ROUTE_PERSISTENT = 1 << 24,   /* ... in one persistent launch for a batch beyond one residency */
+    K4LZ4_ENCODE_ROUTE_PARSE_PACE = 1 << 25,   /* k4_parse_kernel ran with the late-blocks-first priorities */
+    K4LZ4_ENCODE_ROUTE_PCOST_ORDER = 1 << 26,  /* the dispatch order came from the parse's own cost estimate */
+    K4LZ4_ENCODE_ROUTE_TWO_KERNELS = 1 << 27,  /* the order was split between the two one-kernel encoders on the device */
+    K4LZ4_ENCODE_ROUTE_MIGRATE = 1 << 28,      /* k4_parse_kernel's blocks may move into an LDS table that became free */
+    K4LZ4_ENCODE_ROUTE_CHUNKS = 1 << 29        /* the call took more than one launch chunk */
+};
+K4LZ4_API int k4lz4_last_encode_route(const k4lz4_ctx *ctx);
 
 /* LZ4Codec.MaximumOutputSize (LZ4Codec.cs:30-31) == LL.LZ4_compressBound (Engine/LL.tools.cs:38-40).
  * Pure host arithmetic. */
@@ -213,7 +261,14 @@ K4LZ4_API int k4lz4_decode_dict_batch_device(k4lz4_ctx *ctx, const uint8_t *src,
  *           k4lz4_pickle_bound(srcLen[i]); 0 for an empty message (Pickle returns an empty array).
  * unpickle: dstCap[i] must equal the size k4lz4_unpickle_size reports (the reference allocates
  *           exactly that); outLen[i] = that size, or -1 where the reference throws
- *           InvalidDataException (bad version, short header, size mismatch, corrupt block).  */
+ *           InvalidDataException (bad version, short header, size mismatch, corrupt block).
+ * A deliberate deviation from "bytes beyond outLen are never modified on success": there is no scratch buffer, the block
+ * encoder works in place inside the envelope's slot (at +5, capacity srcLen - 1) and the envelope is closed around its bytes
+ * afterwards (the reference encodes into a rented buffer and copies).  So behind a pickle's outLen[i] bytes the slot may hold
+ * what the encoder wrote: the last 4 - sizeOfDiff bytes of a block that was moved down to its header; up to 4 + srcLen[i] where
+ * the block did not shrink (a raw envelope of 1 + srcLen[i] bytes) or the message was cut into segments.  Nothing beyond
+ * 4 + srcLen[i], and nothing outside the slot where dstCap[i] is too small (outLen[i] = -1).  A caller that needs the slack
+ * untouched sizes the slot by outLen after the call, as LZ4Pickler.Pickle's callers receive an array of exactly that size.  */
 K4LZ4_API int k4lz4_pickle_bound(int srcLen);
 /* host arithmetic on one envelope: unpickled size, or -1 when the header is corrupt */
 K4LZ4_API int k4lz4_unpickle_size(const uint8_t *pickle, int pickleLen);
@@ -529,7 +584,10 @@ K4LZ4_API int k4lz4_decode_frames(k4lz4_ctx *ctx, const uint8_t *src, const uint
  * bytes] when the block is not shorter than U; 8 zero bytes for an empty message), -1 when dstCap[i] < k4lz4_wrap_bound(srcLen[i]).
  * high = 0: L00_FAST, else L09_HC.  flags: K4LZ4_FLAG_X32, K4LZ4_FLAG_NO_REORDER.  The encoder writes straight into the slot
  * (cap U - 1); fast batches take the pickles' two-step encoder and segments, HC the pickles' envelope path.  Scratch: the
- * encoders' (d_pk_meta, 16 bytes per message; HC as k4lz4_pickle_batch). */
+ * encoders' (d_pk_meta, 16 bytes per message; HC as k4lz4_pickle_batch).  As with pickles (the same deliberate deviation), behind
+ * outLen[i] the slot may hold what the encoder wrote in place at +8 where the block did not shrink or the message was cut into
+ * segments, up to 7 + srcLen[i]; a block that shrank leaves nothing behind outLen[i] (the header is always 8 bytes).  Where the
+ * slot is too small nothing outside it is written. */
 K4LZ4_API int k4lz4_wrap_bound(int srcLen);
 K4LZ4_API int k4lz4_wrap_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
                                const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int high, int flags);

@@ -25,6 +25,44 @@ FLAG_SEGMENTS = 256
 DECODE_KERNEL_NONE, DECODE_KERNEL_PAIR2, DECODE_KERNEL_PAIR, DECODE_KERNEL_SINGLE, DECODE_KERNEL_DENSE, DECODE_KERNEL_PROF = 0, 1, 2, 3, 4, 5
 DECODE_KERNEL_UNPICKLE_PAIR2, DECODE_KERNEL_UNPICKLE_PAIR, DECODE_KERNEL_UNPICKLE_SINGLE = 9, 10, 11
 DECODE_KERNEL_PACE = 64
+# enum k4lz4_encode_route (k4lz4_last_encode_route, a diagnostic): one bit per kernel family and launch fact
+ENCODE_ROUTE_NONE = 0
+ENCODE_ROUTE_PARSE = 1 << 0
+ENCODE_ROUTE_PARSE_BIG = 1 << 1
+ENCODE_ROUTE_PARSE_SEG = 1 << 2
+ENCODE_ROUTE_EMIT = 1 << 3
+ENCODE_ROUTE_REST = 1 << 4
+ENCODE_ROUTE_LDS = 1 << 5
+ENCODE_ROUTE_MORE = 1 << 6
+ENCODE_ROUTE_GTAB = 1 << 7
+ENCODE_ROUTE_SEGMENTS = 1 << 8
+ENCODE_ROUTE_PROF = 1 << 9
+ENCODE_ROUTE_ALLOW_COPY = 1 << 10
+ENCODE_ROUTE_PICKLE = 1 << 11
+ENCODE_ROUTE_ENVELOPE = 1 << 12
+ENCODE_ROUTE_HC_CHAIN_PART = 1 << 13
+ENCODE_ROUTE_HC_CHAIN_LDS = 1 << 14
+ENCODE_ROUTE_HC_CHAIN_MEM = 1 << 15
+ENCODE_ROUTE_HC_CAND_LDS = 1 << 16
+ENCODE_ROUTE_HC_CAND_MEM = 1 << 17
+ENCODE_ROUTE_HC_PARSE = 1 << 18
+ENCODE_ROUTE_HC_PARSE_REC = 1 << 19
+ENCODE_ROUTE_HC_PARSE_SEG2 = 1 << 20
+ENCODE_ROUTE_HC_PARSE_SEG4 = 1 << 21
+ENCODE_ROUTE_HC_PARSE_OPT = 1 << 22
+ENCODE_ROUTE_QUEUE = 1 << 23
+ENCODE_ROUTE_PERSISTENT = 1 << 24
+ENCODE_ROUTE_PARSE_PACE = 1 << 25
+ENCODE_ROUTE_PCOST_ORDER = 1 << 26
+ENCODE_ROUTE_TWO_KERNELS = 1 << 27
+ENCODE_ROUTE_MIGRATE = 1 << 28
+ENCODE_ROUTE_CHUNKS = 1 << 29
+ENCODE_ROUTE_NAMES = ("PARSE", "PARSE_BIG", "PARSE_SEG", "EMIT", "REST", "LDS", "MORE", "GTAB", "SEGMENTS", "PROF", "ALLOW_COPY", "PICKLE", "ENVELOPE", "HC_CHAIN_PART", "HC_CHAIN_LDS", "HC_CHAIN_MEM", "HC_CAND_LDS", "HC_CAND_MEM", "HC_PARSE", "HC_PARSE_REC", "HC_PARSE_SEG2", "HC_PARSE_SEG4", "HC_PARSE_OPT", "QUEUE", "PERSISTENT", "PARSE_PACE", "PCOST_ORDER", "TWO_KERNELS", "MIGRATE", "CHUNKS")      # bit i is ENCODE_ROUTE_<ENCODE_ROUTE_NAMES[i]>
+
+
+def encode_route_names(route: int) -> str:
+    """the bits of a k4lz4_last_encode_route value by name, for messages"""
+    return "+".join(n.lower() for i, n in enumerate(ENCODE_ROUTE_NAMES) if route >> i & 1) or "none"
 
 _u8p = C.c_void_p
 _BATCH = [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
@@ -48,6 +86,7 @@ SYMBOLS = {
     "k4lz4_host_unregister": (C.c_int, [C.c_void_p]),
     "k4lz4_selftest_chains": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]),
     "k4lz4_last_decode_kernel": (C.c_int, [C.c_void_p]),
+    "k4lz4_last_encode_route": (C.c_int, [C.c_void_p]),
     "k4lz4_set_enforce32": (None, [C.c_int]),
     "k4lz4_get_enforce32": (C.c_int, []),
     "k4lz4_compress_bound": (C.c_int, [C.c_int]),
@@ -277,6 +316,11 @@ class Context:
     def last_decode_kernel(self) -> int:
         """DECODE_KERNEL_* of this context's most recent decode / unpickle launch, DECODE_KERNEL_PACE or-ed in (a diagnostic)"""
         return int(self.lib.k4lz4_last_decode_kernel(self.handle))
+
+    def last_encode_route(self) -> int:
+        """ENCODE_ROUTE_* bits of this context's most recent encode / pickle / wrap call: the kernel families it launched and a few
+        facts about the launches, or-ed over its launch chunks (a diagnostic)"""
+        return int(self.lib.k4lz4_last_encode_route(self.handle))
 
     def close(self):
         if getattr(self, "handle", None):

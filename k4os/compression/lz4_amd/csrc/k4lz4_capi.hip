@@ -122,6 +122,7 @@ struct k4lz4_ctx {
     int cost_pct = 48;                    /* K4LZ4_COST_PCT: the LDS-table kernel's share of a batch's estimated cost (k4_order_kernel) */
     int dec_parts = 4, dec_parts_direct = 8;   /* K4LZ4_DEC_PARTS, K4LZ4_DEC_PARTS_DIRECT: parts of a big decode-like host-pointer call (2..MAX_PARTS); with a registered destination */
     int last_decode_kernel = 0;           /* k4lz4_last_decode_kernel: enum k4lz4_decode_kernel of the latest KIND_DECODE / KIND_UNPICKLE launch (launch_decode_like) */
+    int last_encode_route = 0;            /* k4lz4_last_encode_route: enum k4lz4_encode_route bits of the latest encode / pickle / wrap call, or-ed over its launch chunks */
     int hop2_max_per_cu = 12;             /* K4LZ4_HOP2_MAX: pair decoders follow the token chain two links per hop in launches of up to this many blocks per CU */
     bool hc_cand_lds = true;              /* K4LZ4_HC_CAND_MEM unsets it: blocks of at most 64 KiB get their candidate records by k4_hc_cand_kernel (from memory) */
     int hc_cand_dynlds = 0;               /* K4LZ4_HC_CAND_DYNLDS (a measurement switch): bytes of unused LDS per workgroup of k4_hc_cand_kernel, i.e. fewer of them per CU */
@@ -379,6 +380,7 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
         a.src = src; a.srcOff = h.srcOff; a.srcLen = h.srcLen; a.dst = dst; a.dstOff = h.dstOff; a.dstCap = h.dstCap;
         a.outLen = h.outLen; a.n = cnt; a.level = level; a.accel = 1; a.flags = flags;
         if (env == ENV_PICKLE || env == ENV_WRAP) {
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_ENVELOPE;
             envelope_prep(env, a, d_encoff, d_enccap, stream);
             h.dstOff = d_encoff; h.dstCap = d_enccap; h.outLen = d_enclen; h.flags = K4LZ4_FLAG_RAW_RETURN;
         }
@@ -416,6 +418,7 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
         if (tail[1] <= 65536 && lds_ok && ctx->hc_chain_parts) {
             /* no block over 64 KiB: eight waves per block, each with an eighth of the hash values and of the table (round 6) */
             h.nChain = cnt;
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_PART;
             hipLaunchKernelGGL(k4::k4_hc_chain_part_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_CHAIN_PARTS), 0, stream, h);
         } else if (tail[1] <= 65536 && lds_ok) {
             /* (rounds 3-5, K4LZ4_HC_CHAIN_OLD) no block over 64 KiB (known from the host lengths, the reservation or the device): hash tables in LDS -- two blocks
@@ -429,24 +432,29 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
                 K4_HIP(ctx, hipMemsetAsync(ctx->d_hc_hash + ((size_t)n_lds << (k4::HC_HASH_LOG + 2)), 0, (size_t)n_mem << (k4::HC_HASH_LOG + 2), ctx->aux));
                 k4::HcArgs hm = h;
                 hm.blockBase = (unsigned)n_lds; hm.nChain = n_mem;
+                ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_MEM;
                 K4_LAUNCH_WAVES(k4::k4_hc_chain_kernel, n_mem, k4::HC_CHAIN_WAVES_PER_WG, ctx->aux, hm);
                 K4_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
             }
             h.nChain = n_lds;
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_LDS;
             K4_LAUNCH_WAVES(k4::k4_hc_chain_lds_kernel, n_lds, k4::HC_CHAIN_LDS_WAVES_PER_WG, stream, h);
             if (n_mem > 0) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_join, 0));
         } else {
             K4_HIP(ctx, hipMemsetAsync(ctx->d_hc_hash, 0, (size_t)cnt << (k4::HC_HASH_LOG + 2), stream));
             h.nChain = cnt;
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_MEM;
             K4_LAUNCH_WAVES(k4::k4_hc_chain_kernel, cnt, k4::HC_CHAIN_WAVES_PER_WG, stream, h);
         }
         const bool optimal = level >= K4LZ4_L10_OPT;              /* clTable (LL64.high.cs:1124-1138): lz4opt strategy */
         if (tail[1] >= 13 && tail[1] <= 65536 && lds_ok && !optimal && ctx->hc_cand_lds) {
             /* no block over 64 KiB: the candidates' records out of LDS (k4_hc_walk_lds_kernel, k4_hc_cand_lds_kernel; round 6) */
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CAND_LDS;
             hipLaunchKernelGGL(k4::k4_hc_walk_lds_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_LDS_WAVES), 0, stream, h);
             hipLaunchKernelGGL(k4::k4_hc_cand_lds_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_CAND_LDS_WAVES), 0, stream, h);
         } else if (tail[1] >= 13 && !optimal) {
             const unsigned gy = (unsigned)((tail[1] + k4::HC_CAND_POS_PER_WG - 1) / k4::HC_CAND_POS_PER_WG);
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CAND_MEM;
             const unsigned groups = (unsigned)((cnt + 7) / 8);                     /* eight blocks, one per XCD (k4_hc_cand_kernel) */
             const unsigned per = std::max(1u, (1u << 30) / (8u * groups));         /* chunks per launch: the grid stays below 2^31 workgroups */
             for (unsigned y0 = 0; y0 < gy; y0 += per) {
@@ -456,8 +464,10 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
                 hipLaunchKernelGGL(k4::k4_hc_cand_kernel, dim3(groups * 8u * hy.candChunks), dim3(256), (size_t)ctx->hc_cand_dynlds, stream, hy);
             }
         }
-        if (optimal) K4_LAUNCH_WAVES(k4::k4_hc_parse_opt_kernel, cnt, 1, stream, h);
-        else {
+        if (optimal) {
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_PARSE_OPT;
+            K4_LAUNCH_WAVES(k4::k4_hc_parse_opt_kernel, cnt, 1, stream, h);
+        } else {
             /* level 3 on blocks of at most 64 KiB: the parse writes 8-byte sequence records (the fast encoder's scratch, a slot per
              * block) and the same wave turns them into bytes afterwards; without room for them LZ4HC_encodeSequence stays in the loop */
             /* ... by two or four waves per block while the chip has the wave slots for them (k4lz4_encode_hc.hpp, HcSegs; round 6) */
@@ -478,6 +488,8 @@ int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *
                 h.pace = ctx->d_pace;
                 K4_HIP(ctx, hipMemsetAsync(h.pace, 0, k4::PACE_BYTES, stream));
             }
+            ctx->last_encode_route |= h.recs && nseg == 4 ? K4LZ4_ENCODE_ROUTE_HC_PARSE_SEG4 : h.recs && nseg == 2 ? K4LZ4_ENCODE_ROUTE_HC_PARSE_SEG2 :
+                                      h.recs ? K4LZ4_ENCODE_ROUTE_HC_PARSE_REC : K4LZ4_ENCODE_ROUTE_HC_PARSE;
             if (h.recs && nseg == 4) hipLaunchKernelGGL(k4::k4_hc_parse_seg4_kernel, dim3((unsigned)((cnt + 1) / 2)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, stream, h);
             else if (h.recs && nseg == 2) hipLaunchKernelGGL(k4::k4_hc_parse_seg2_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, stream, h);
             else if (h.recs) K4_LAUNCH_WAVES(k4::k4_hc_parse_rec_kernel, cnt, k4::HC_REC_WAVES_PER_WG, stream, h);
@@ -1248,6 +1260,7 @@ int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, con
     K4_HIP(ctx, order_after_ctx(ctx, stream));
     K4_HIP(ctx, hipMemcpyAsync(ctx->d_chain, ctx->h_chain.data(), bytes, hipMemcpyHostToDevice, stream));
     K4_HIP(ctx, hipEventRecord(ctx->ev_chain, stream));
+    ctx->last_encode_route = K4LZ4_ENCODE_ROUTE_NONE;    /* (this call reaches launch_hc without passing launch_inner) */
     rc = launch_hc(ctx, ENV_NONE, src, d.woff, d.wlen, dst, d.doff, d.cap, outLen, nb, level, 0, stream, h.wlen, d.hist);
     if (rc == K4LZ4_OK && (flags & K4LZ4_FLAG_ALLOW_COPY)) {
         /* LZ4EncoderBase.Encode(allowCopy): a block that did not shrink is stored raw -- its bytes stay in the history all the same */
@@ -2486,6 +2499,7 @@ int k4lz4_selftest_chains(k4lz4_ctx *ctx, int waves, int rounds, uint32_t seed, 
 }
 
 int k4lz4_last_decode_kernel(const k4lz4_ctx *ctx) { return ctx ? ctx->last_decode_kernel : K4LZ4_DECODE_KERNEL_NONE; }
+int k4lz4_last_encode_route(const k4lz4_ctx *ctx) { return ctx ? ctx->last_encode_route : K4LZ4_ENCODE_ROUTE_NONE; }
 
 int k4lz4_last_status(void) { return tl_status; }
 

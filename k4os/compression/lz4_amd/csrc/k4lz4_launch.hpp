@@ -18,8 +18,9 @@ k4::BatchArgs slice(k4::BatchArgs b, int64_t first, int64_t cnt)
 }
 
 /* K4LZ4_FLAG_ALLOW_COPY: blocks that did not shrink are stored raw, behind whatever encoded them */
-void allow_copy(k4::BatchArgs a, hipStream_t stream)
+void allow_copy(k4lz4_ctx *ctx, k4::BatchArgs a, hipStream_t stream)
 {
+    ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_ALLOW_COPY;
     K4_LAUNCH_WAVES(k4::k4_allow_copy_kernel, a.n, 4, stream, a);
 }
 
@@ -261,6 +262,7 @@ int segments_start(k4lz4_ctx *ctx, hipStream_t stream, k4::BatchArgs a, k4::SegA
 {
     K4_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
     K4_HIP(ctx, hipStreamWaitEvent(ctx->aux2, ctx->ev_fork, 0));
+    ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_SEGMENTS;
     K4_LAUNCH_WAVES(k4::k4_encode_seg_kernel, sg.max_items, k4::ENCODE_WAVES_PER_WG, ctx->aux2, a, sg);
     K4_HIP(ctx, hipEventRecord(ctx->ev_join2, ctx->aux2));
     return K4LZ4_OK;
@@ -289,6 +291,7 @@ int one_kernel_chunk(k4lz4_ctx *ctx, const FastRoute &r, const FastChunk &c, k4:
             if ((rc = grow_after(ctx, ctx->aux, &ctx->d_gtab, &ctx->d_gtab_cap, (size_t)cnt * 16384)) != K4LZ4_OK) return rc;
             a.gtab = (uint32_t *)ctx->d_gtab;
         }
+        ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_PROF;
         K4_LAUNCH_WAVES(k4::k4_encode_fast_prof_kernel, cnt, 1, stream, a);
         return K4LZ4_OK;
     }
@@ -297,6 +300,7 @@ int one_kernel_chunk(k4lz4_ctx *ctx, const FastRoute &r, const FastChunk &c, k4:
     if (r.segments && (rc = segments_start(ctx, stream, a, sg)) != K4LZ4_OK) return rc;
     k4::BatchArgs al = a;
     if (c.pair) {
+        if (c.n_g > 0) ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_GTAB | (r.segments ? K4LZ4_ENCODE_ROUTE_SEGMENTS : 0) | (c.two_kernels ? K4LZ4_ENCODE_ROUTE_TWO_KERNELS : 0);
         K4_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
         K4_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
         for (int64_t g0 = 0; g0 < c.n_g; g0 += gchunk) {
@@ -311,6 +315,7 @@ int one_kernel_chunk(k4lz4_ctx *ctx, const FastRoute &r, const FastChunk &c, k4:
         K4_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
         al.n = c.n_lds;
     }
+    ctx->last_encode_route |= r.segments ? K4LZ4_ENCODE_ROUTE_LDS | K4LZ4_ENCODE_ROUTE_SEGMENTS : c.more ? K4LZ4_ENCODE_ROUTE_MORE : K4LZ4_ENCODE_ROUTE_LDS;
     if (r.segments) K4_LAUNCH_WAVES(k4::k4_encode_fast_seg_kernel, al.n, k4::ENCODE_WAVES_PER_WG, stream, al);
     else if (c.more) K4_LAUNCH_WAVES(k4::k4_encode_fast_more_kernel, al.n, k4::ENCODE_WAVES_PER_WG, stream, al);
     else K4_LAUNCH_WAVES(k4::k4_encode_fast_kernel, al.n, k4::ENCODE_WAVES_PER_WG, stream, al);
@@ -346,17 +351,22 @@ int two_step_chunk(k4lz4_ctx *ctx, const FastRoute &r, const FastChunk &c, k4::B
     if (c.queue) pa.queue = pa.meta + 2 * cnt;
     pa.nbig = pa.meta + 2 * cnt + 3;
     /* (the first launch also says whose every block is -- PARSE_BIG / PARSE_REST --, so it runs even without a block of its own) */
+    ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_PARSE | (c.queue ? K4LZ4_ENCODE_ROUTE_QUEUE : 0) | (r.persistent ? K4LZ4_ENCODE_ROUTE_PERSISTENT : 0) |
+                              (c.parse_pace ? K4LZ4_ENCODE_ROUTE_PARSE_PACE : 0) | (pa.migrate ? K4LZ4_ENCODE_ROUTE_MIGRATE : 0);
     hipLaunchKernelGGL(k4::k4_parse_kernel, dim3((unsigned)c.nwg), dim3((unsigned)(64 * c.waves)), 0, stream, a, pa);
     if (c.seg_two_step) {
         k4::ParseArgs pb = pa;
         pb.queue = pa.meta + 2 * cnt + 4;
         pb.nwg = (uint32_t)c.nwg_seg;
+        ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_PARSE_SEG;
         hipLaunchKernelGGL(k4::k4_parse_seg_kernel, dim3((unsigned)c.nwg_seg), dim3(64 * k4::PARSE_MAX_WAVES), 0, stream, a, pb, sg);
     } else if (c.any_big) {
         k4::ParseArgs pb = pa;
         if (c.queue) pb.queue = pa.queue + 4;
+        ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_PARSE_BIG;
         hipLaunchKernelGGL(k4::k4_parse_big_kernel, dim3((unsigned)c.nwg), dim3((unsigned)(64 * c.waves)), 0, stream, a, pb);
     }
+    ctx->last_encode_route |= (pa.inline_emit ? 0 : K4LZ4_ENCODE_ROUTE_EMIT) | (c.rest ? K4LZ4_ENCODE_ROUTE_REST : 0) | (c.seg_two_step ? K4LZ4_ENCODE_ROUTE_SEGMENTS : 0);
     if (!pa.inline_emit) K4_LAUNCH_WAVES(k4::k4_emit_kernel, cnt, k4::EMIT_WAVES_PER_WG, stream, a, pa);
     if (c.rest) K4_LAUNCH_WAVES(k4::k4_encode_fast_rest_kernel, cnt, k4::ENCODE_WAVES_PER_WG, stream, a, pa);
     if (c.seg_two_step) segments_join_launch(stream, a, sg);
@@ -378,6 +388,7 @@ int launch_fast_encode(k4lz4_ctx *ctx, k4::BatchArgs b, hipStream_t stream, cons
         const FastChunk c = fast_chunk(ctx, r, cnt, hostLen ? hostLen + first : nullptr);
         k4::BatchArgs a = slice(b, first, cnt);
         a.prof = ctx->prof ? ctx->prof + k4::PROF_STRIDE * first : nullptr;
+        ctx->last_encode_route |= (first > 0 ? K4LZ4_ENCODE_ROUTE_CHUNKS : 0) | (r.pcost_order ? K4LZ4_ENCODE_ROUTE_PCOST_ORDER : 0);
         if (c.pace) {
             a.pace = ctx->d_pace;
             K4_HIP(ctx, hipMemsetAsync(a.pace, 0, k4::PACE_BYTES, stream));
@@ -391,7 +402,7 @@ int launch_fast_encode(k4lz4_ctx *ctx, k4::BatchArgs b, hipStream_t stream, cons
         if (r.reorder && (rc = order_prelude(ctx, stream, a, s, r.pcost_order, 0, r.cost_sample, c.two_kernels)) != K4LZ4_OK) return rc;
         rc = c.parse_here ? two_step_chunk(ctx, r, c, a, sg, stream) : one_kernel_chunk(ctx, r, c, a, sg, stream);
         if (rc != K4LZ4_OK) return rc;
-        if (r.allow_copy) allow_copy(a, stream);
+        if (r.allow_copy) allow_copy(ctx, a, stream);
         K4_HIP(ctx, hipGetLastError());
     }
     return K4LZ4_OK;
@@ -429,6 +440,7 @@ int launch_envelope(k4lz4_ctx *ctx, Envelope env, k4::BatchArgs b, hipStream_t s
         int32_t *d_enccap = (int32_t *)(d_encoff + cnt);
         int32_t *d_enclen = d_enccap + cnt;
         const k4::BatchArgs a = slice(b, first, cnt);
+        ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_ENVELOPE;
         envelope_prep(env, a, d_encoff, d_enccap, stream);
         k4::BatchArgs e{};
         e.src = a.src; e.srcOff = a.srcOff; e.srcLen = a.srcLen; e.dst = a.dst; e.dstOff = d_encoff; e.dstCap = d_enccap; e.outLen = d_enclen;
@@ -474,6 +486,7 @@ int launch_decode_like(k4lz4_ctx *ctx, Kind kind, k4::BatchArgs b, hipStream_t s
         }
         if (reorder && (rc = order_prelude(ctx, stream, a, s, false, kind == KIND_PICKLE ? 0 : 1, k4::COST_SAMPLE, false)) != K4LZ4_OK) return rc;
         if (kind == KIND_PICKLE) {
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_PICKLE;
             K4_LAUNCH_WAVES(k4::k4_pickle_kernel, cnt, 1, stream, a);
         } else if (kind == KIND_DECODE) {
             ctx->last_decode_kernel = a.pace ? K4LZ4_DECODE_KERNEL_PACE : 0;
@@ -527,10 +540,11 @@ int launch_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *
     k4::BatchArgs b{};
     b.src = src; b.srcOff = srcOff; b.srcLen = srcLen; b.dst = dst; b.dstOff = dstOff; b.dstCap = dstCap; b.outLen = outLen;
     b.n = n; b.level = level; b.flags = flags;
+    if (kind == KIND_ENCODE || env != ENV_NONE) ctx->last_encode_route = K4LZ4_ENCODE_ROUTE_NONE;
     if ((kind == KIND_ENCODE || env != ENV_NONE) && level >= K4LZ4_L03_HC) {
         const int rc = launch_hc(ctx, env, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, stream, hostLen);
         if (rc != K4LZ4_OK || kind != KIND_ENCODE || !(flags & K4LZ4_FLAG_ALLOW_COPY)) return rc;
-        for (int64_t first = 0; first < n; first += LAUNCH_CHUNK_MAX) allow_copy(slice(b, first, std::min<int64_t>(LAUNCH_CHUNK_MAX, n - first)), stream);
+        for (int64_t first = 0; first < n; first += LAUNCH_CHUNK_MAX) allow_copy(ctx, slice(b, first, std::min<int64_t>(LAUNCH_CHUNK_MAX, n - first)), stream);
         K4_HIP(ctx, hipGetLastError());
         return K4LZ4_OK;
     }
