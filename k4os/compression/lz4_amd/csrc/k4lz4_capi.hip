@@ -295,12 +295,6 @@ constexpr int FLAG_SEGMENTS_OK = 1 << 20;   /* launch_fast_encode: big blocks ma
 /* LL.Enforce32 (Engine/LL.tools.cs:19-27): a process-wide switch in the reference, so here too */
 std::atomic<int> g_enforce32{0};
 
-int check_level(k4lz4_ctx *ctx, int level)
-{
-    (void)ctx; (void)level;   /* < L03_HC -> fast (LZ4Codec.cs:48); L03..L09 hash chain; L10..L12 optimal parser; above: as L12 (LL64.high.cs:1160) */
-    return K4LZ4_OK;
-}
-
 int grow(k4lz4_ctx *ctx, uint8_t **p, size_t *cap, size_t need, bool pinned);
 
 /* After a synchronisation of the call's stream: did a kernel launched through THIS context report call-level trouble?
@@ -346,159 +340,6 @@ void envelope_finish(Envelope env, k4::BatchArgs a, int32_t *encLen, hipStream_t
 {
     if (env == ENV_PICKLE) K4_LAUNCH_WAVES(k4::k4_pickle_finish_kernel, a.n, k4::PICKLE_FINISH_WAVES_PER_WG, stream, a, encLen);
     if (env == ENV_WRAP) K4_LAUNCH_WAVES(k4::k4_wrap_finish_kernel, a.n, k4::WRAP_FINISH_WAVES_PER_WG, stream, a, encLen);
-}
-
-/* HC levels: layout -> (sync for the scratch size) -> hash-table clear -> chain kernel -> parse kernel.
- * `env`: the same around the LZ4Pickler envelope (encoder slot = envelope + 5, cap U - 1) or LZ4Wrapper's (+ 8, cap U - 1). */
-/* hostLen: the blocks' lengths when the caller has them on the host (host-pointer calls), else nullptr */
-/* hist: chained HC streams (k4::HcArgs::hist, device pointer), else nullptr -- such a batch takes the memory paths: the LDS
- * kernels are built around blocks of at most 64 KiB that start at their position 0 */
-int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
-              const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
-              hipStream_t stream, const int32_t *hostLen, const int32_t *hist = nullptr)
-{
-    const int64_t chunk_max = 4096;   /* 128 KiB of hash table per block in flight */
-    for (int64_t first = 0; first < n; first += chunk_max) {
-        const int64_t cnt = std::min<int64_t>(chunk_max, n - first);
-        int rc = grow_after(ctx, stream, &ctx->d_hc_hash, &ctx->d_hc_hash_cap, (size_t)cnt << (k4::HC_HASH_LOG + 2));
-        if (rc != K4LZ4_OK) return rc;
-        rc = grow_after(ctx, stream, &ctx->d_hc_meta, &ctx->d_hc_meta_cap, (size_t)(cnt + 2) * 8 + (size_t)cnt * 16 + 64);
-        if (rc != K4LZ4_OK) return rc;
-        unsigned long long *d_woff = (unsigned long long *)ctx->d_hc_meta;
-        uint64_t *d_encoff = (uint64_t *)(d_woff + cnt + 2);
-        int32_t *d_enccap = (int32_t *)(d_encoff + cnt);
-        int32_t *d_enclen = d_enccap + cnt;
-        k4::HcArgs h{};
-        h.status = ctx->d_status;
-        h.src = src; h.srcOff = srcOff + first; h.srcLen = srcLen + first;
-        h.dst = dst; h.dstOff = dstOff + first; h.dstCap = dstCap + first; h.outLen = outLen + first;
-        h.n = cnt; h.level = level; h.flags = flags;
-        h.hash = (uint32_t *)ctx->d_hc_hash; h.workOff = d_woff;
-        h.hist = hist ? hist + first : nullptr;
-        const bool lds_ok = hist == nullptr;
-        k4::BatchArgs a{};
-        a.src = src; a.srcOff = h.srcOff; a.srcLen = h.srcLen; a.dst = dst; a.dstOff = h.dstOff; a.dstCap = h.dstCap;
-        a.outLen = h.outLen; a.n = cnt; a.level = level; a.accel = 1; a.flags = flags;
-        if (env == ENV_PICKLE || env == ENV_WRAP) {
-            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_ENVELOPE;
-            envelope_prep(env, a, d_encoff, d_enccap, stream);
-            h.dstOff = d_encoff; h.dstCap = d_enccap; h.outLen = d_enclen; h.flags = K4LZ4_FLAG_RAW_RETURN;
-        }
-        /* How much work area, and how long the longest block is: from the host's copy of the lengths, from the
-         * reservation (k4lz4_ctx_reserve_hc), or -- the only case that synchronises -- from the device. */
-        unsigned long long tail[2] = {0, 0};   /* total work bytes, longest block */
-        bool ask_device = false;
-        if (hostLen) {
-            for (int64_t i = 0; i < cnt; i++) {
-                const int32_t len = hostLen[first + i];
-                if (len > 0) {
-                    tail[0] += (((unsigned long long)len + 3u) & ~3ull) * k4::HC_WORK_PER_BYTE;
-                    tail[1] = std::max<unsigned long long>(tail[1], (unsigned long long)len);
-                }
-            }
-        } else if (ctx->hc_res_total) {
-            tail[0] = (ctx->hc_res_total + 4u * (unsigned long long)cnt) * k4::HC_WORK_PER_BYTE;
-            tail[1] = ctx->hc_res_longest;
-            h.workCap = tail[0]; h.maxLen = ctx->hc_res_longest;
-        } else {
-            ask_device = true;
-        }
-        if (!ask_device) {
-            rc = grow_after(ctx, stream, &ctx->d_hc_work, &ctx->d_hc_work_cap, (size_t)tail[0] + 256);
-            if (rc != K4LZ4_OK) return rc;
-        }
-        hipLaunchKernelGGL(k4::k4_hc_layout_kernel, dim3(1), dim3(256), 0, stream, h);
-        if (ask_device) {
-            K4_HIP(ctx, hipMemcpyAsync(tail, d_woff + cnt, 16, hipMemcpyDeviceToHost, stream));
-            K4_HIP(ctx, hipStreamSynchronize(stream));
-            rc = grow(ctx, &ctx->d_hc_work, &ctx->d_hc_work_cap, (size_t)tail[0] + 256, false);
-            if (rc != K4LZ4_OK) return rc;
-        }
-        h.work = ctx->d_hc_work;
-        if (tail[1] <= 65536 && lds_ok && ctx->hc_chain_parts) {
-            /* no block over 64 KiB: eight waves per block, each with an eighth of the hash values and of the table (round 6) */
-            h.nChain = cnt;
-            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_PART;
-            hipLaunchKernelGGL(k4::k4_hc_chain_part_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_CHAIN_PARTS), 0, stream, h);
-        } else if (tail[1] <= 65536 && lds_ok) {
-            /* (rounds 3-5, K4LZ4_HC_CHAIN_OLD) no block over 64 KiB (known from the host lengths, the reservation or the device): hash tables in LDS -- two blocks
-             * per CU, a wave each, which leaves the CU's other wave slots empty; so the last third of a big chunk goes through the
-             * table-in-memory kernel on the second queue at the same time (its tables: 128 KiB per block, cleared here) */
-            const int64_t n_mem = cnt >= 8 * (int64_t)ctx->cu_count ? cnt * ctx->hc_mem_pct / 100 : 0;
-            const int64_t n_lds = cnt - n_mem;
-            if (n_mem > 0) {
-                K4_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
-                K4_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-                K4_HIP(ctx, hipMemsetAsync(ctx->d_hc_hash + ((size_t)n_lds << (k4::HC_HASH_LOG + 2)), 0, (size_t)n_mem << (k4::HC_HASH_LOG + 2), ctx->aux));
-                k4::HcArgs hm = h;
-                hm.blockBase = (unsigned)n_lds; hm.nChain = n_mem;
-                ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_MEM;
-                K4_LAUNCH_WAVES(k4::k4_hc_chain_kernel, n_mem, k4::HC_CHAIN_WAVES_PER_WG, ctx->aux, hm);
-                K4_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-            }
-            h.nChain = n_lds;
-            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_LDS;
-            K4_LAUNCH_WAVES(k4::k4_hc_chain_lds_kernel, n_lds, k4::HC_CHAIN_LDS_WAVES_PER_WG, stream, h);
-            if (n_mem > 0) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_join, 0));
-        } else {
-            K4_HIP(ctx, hipMemsetAsync(ctx->d_hc_hash, 0, (size_t)cnt << (k4::HC_HASH_LOG + 2), stream));
-            h.nChain = cnt;
-            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_MEM;
-            K4_LAUNCH_WAVES(k4::k4_hc_chain_kernel, cnt, k4::HC_CHAIN_WAVES_PER_WG, stream, h);
-        }
-        const bool optimal = level >= K4LZ4_L10_OPT;              /* clTable (LL64.high.cs:1124-1138): lz4opt strategy */
-        if (tail[1] >= 13 && tail[1] <= 65536 && lds_ok && !optimal && ctx->hc_cand_lds) {
-            /* no block over 64 KiB: the candidates' records out of LDS (k4_hc_walk_lds_kernel, k4_hc_cand_lds_kernel; round 6) */
-            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CAND_LDS;
-            hipLaunchKernelGGL(k4::k4_hc_walk_lds_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_LDS_WAVES), 0, stream, h);
-            hipLaunchKernelGGL(k4::k4_hc_cand_lds_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_CAND_LDS_WAVES), 0, stream, h);
-        } else if (tail[1] >= 13 && !optimal) {
-            const unsigned gy = (unsigned)((tail[1] + k4::HC_CAND_POS_PER_WG - 1) / k4::HC_CAND_POS_PER_WG);
-            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CAND_MEM;
-            const unsigned groups = (unsigned)((cnt + 7) / 8);                     /* eight blocks, one per XCD (k4_hc_cand_kernel) */
-            const unsigned per = std::max(1u, (1u << 30) / (8u * groups));         /* chunks per launch: the grid stays below 2^31 workgroups */
-            for (unsigned y0 = 0; y0 < gy; y0 += per) {
-                k4::HcArgs hy = h;
-                hy.posBase = y0 * (unsigned)k4::HC_CAND_POS_PER_WG;
-                hy.candChunks = std::min(per, gy - y0);
-                hipLaunchKernelGGL(k4::k4_hc_cand_kernel, dim3(groups * 8u * hy.candChunks), dim3(256), (size_t)ctx->hc_cand_dynlds, stream, hy);
-            }
-        }
-        if (optimal) {
-            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_PARSE_OPT;
-            K4_LAUNCH_WAVES(k4::k4_hc_parse_opt_kernel, cnt, 1, stream, h);
-        } else {
-            /* level 3 on blocks of at most 64 KiB: the parse writes 8-byte sequence records (the fast encoder's scratch, a slot per
-             * block) and the same wave turns them into bytes afterwards; without room for them LZ4HC_encodeSequence stays in the loop */
-            /* ... by two or four waves per block while the chip has the wave slots for them (k4lz4_encode_hc.hpp, HcSegs; round 6) */
-            int nseg = 1;
-            if (level <= K4LZ4_L03_HC && tail[1] <= 65536 && lds_ok && ctx->hc_records) {
-                const int64_t slots = 32 * (int64_t)ctx->cu_count;
-                nseg = ctx->hc_segs > 0 ? ctx->hc_segs : (cnt * 2 <= slots ? 4 : 1);      /* (measured, profiles/r6_hc_ab.txt: four waves per block beat two even when they take turns -- 4096 blocks: 9.5 against 12.2-13.3 ms, one wave 13.9) */
-                if (tail[1] < k4::HC_SEG_MIN_LEN) nseg = 1;
-                for (;;) {
-                    const size_t need = (size_t)cnt * (nseg == 4 ? k4::hc_seg_rec_off(4, 4) : nseg == 2 ? k4::hc_seg_rec_off(2, 2) : k4::PARSE_REC_STRIDE) * sizeof(uint2);
-                    if (grow_after(ctx, stream, &ctx->d_parse, &ctx->d_parse_cap, need) == K4LZ4_OK) { h.recs = (uint2 *)ctx->d_parse; break; }
-                    { std::lock_guard<std::mutex> g(g_err_mu); ctx->error.clear(); }
-                    if (nseg == 1) break;
-                    nseg = 1;
-                }
-            }
-            if (ctx->use_pace && ctx->d_pace && cnt > 8 * (int64_t)ctx->cu_count) {
-                h.pace = ctx->d_pace;
-                K4_HIP(ctx, hipMemsetAsync(h.pace, 0, k4::PACE_BYTES, stream));
-            }
-            ctx->last_encode_route |= h.recs && nseg == 4 ? K4LZ4_ENCODE_ROUTE_HC_PARSE_SEG4 : h.recs && nseg == 2 ? K4LZ4_ENCODE_ROUTE_HC_PARSE_SEG2 :
-                                      h.recs ? K4LZ4_ENCODE_ROUTE_HC_PARSE_REC : K4LZ4_ENCODE_ROUTE_HC_PARSE;
-            if (h.recs && nseg == 4) hipLaunchKernelGGL(k4::k4_hc_parse_seg4_kernel, dim3((unsigned)((cnt + 1) / 2)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, stream, h);
-            else if (h.recs && nseg == 2) hipLaunchKernelGGL(k4::k4_hc_parse_seg2_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, stream, h);
-            else if (h.recs) K4_LAUNCH_WAVES(k4::k4_hc_parse_rec_kernel, cnt, k4::HC_REC_WAVES_PER_WG, stream, h);
-            else K4_LAUNCH_WAVES(k4::k4_hc_parse_kernel, cnt, k4::HC_PARSE_WAVES_PER_WG, stream, h);
-        }
-        envelope_finish(env, a, d_enclen, stream);
-        K4_HIP(ctx, hipGetLastError());
-    }
-    return K4LZ4_OK;
 }
 
 /* per-block dictionaries for decode (device pointers) */
@@ -801,10 +642,6 @@ int run_host_inner(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t
 {
     int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
     if (rc != K4LZ4_OK) return rc;
-    if (kind == KIND_ENCODE || kind == KIND_PICKLE || kind == KIND_WRAP) {
-        rc = check_level(ctx, level);
-        if (rc != K4LZ4_OK) return rc;
-    }
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
     const auto tr0 = std::chrono::steady_clock::now();
@@ -1085,10 +922,6 @@ int run_device(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *sr
 {
     int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
     if (rc != K4LZ4_OK) return rc;
-    if (kind == KIND_ENCODE || kind == KIND_PICKLE || kind == KIND_WRAP) {
-        rc = check_level(ctx, level);
-        if (rc != K4LZ4_OK) return rc;
-    }
     if (n == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
     return launch(ctx, kind, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n, level, flags, (hipStream_t)stream, dd);
@@ -1151,6 +984,28 @@ struct HcChainPlan {
 /* LZ4EncoderBase's block size: rounded up to a whole KiB, at least 1 KiB (LZ4EncoderBase.cs:23) */
 int64_t hc_chain_block_size(int32_t blockSize) { const int64_t b = std::max<int64_t>(blockSize, 1024); return (b + 1023) / 1024 * 1024; }
 
+/* A whole stream as block lengths for the one ring model (k4lz4_chain_encoder.hpp: ce_hc_rows, ce_fast_rows): its `fresh` bytes
+ * behind the dictionary are B repeated, then the remainder; none when there are none */
+struct WholeLens {
+    int64_t fresh, B;
+    int64_t count() const { return fresh / B + (fresh % B != 0); }
+    int64_t operator[](int64_t j) const { return std::min(B, fresh - j * B); }
+};
+
+/* one stream's rows of the table, from row k on, out of its block lengths; block j goes to dstOff + j * k4lz4_compress_bound(B) */
+template <class Len>
+void hc_chain_rows(HcChainPlan *fill, int64_t k, uint64_t srcOff, uint64_t dstOff, int64_t D, Len len, int64_t count, int64_t B, int64_t extra)
+{
+    const int64_t slot = B + B / 255 + 16;                            /* k4lz4_compress_bound(B) */
+    k4::ce_hc_rows(D, len, count, B, extra, [&](int64_t j, int64_t ws, int64_t pos, int64_t n, int64_t) {
+        const int64_t r = k + j;
+        fill->woff[r] = srcOff + (uint64_t)ws; fill->boff[r] = srcOff + (uint64_t)pos;
+        fill->doff[r] = dstOff + (uint64_t)(j * slot);
+        fill->wlen[r] = (int32_t)(pos - ws + n); fill->hist[r] = (int32_t)(pos - ws);
+        fill->blen[r] = (int32_t)n; fill->cap[r] = (int32_t)slot;
+    });
+}
+
 /* counts the blocks (fill == nullptr) or lays the table out in `fill`; the streams' contents start at srcOff[s], their first dictLen[s]
  * bytes are what the encoder's ring buffer already holds (ptr = dictLen, dictLimit at the content's start), block j of stream s goes to
  * dstOff[s] + j * k4lz4_compress_bound(B) */
@@ -1166,36 +1021,19 @@ int hc_chain_table(k4lz4_ctx *ctx, const uint64_t *srcOff, const int64_t *srcLen
         if (N < 0) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: negative content length");
         if (D < 0 || D > N) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: dictLen outside the content");
         if (B > k4::MAX_INPUT_SIZE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: block size above the input size limit");
-        const int64_t L = 65536 + (1 + extra) * B + 32;                   /* the ring buffer (LZ4EncoderBase.cs:25) */
-        const int64_t slot = B + B / 255 + 16;                            /* k4lz4_compress_bound(B) */
-        int64_t ptr = D, dl = 0, pos = D, j = 0;
-        while (pos < N) {
-            /* LZ4_compressHC_continue_generic renormalises once end - base > 2 GB (LL64.high.cs:1271-1276): not offered */
-            if (65536 + pos > ((int64_t)1 << 31))
-                return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
-            const int64_t len = std::min(B, N - pos);
-            const int64_t ws = std::max(dl, pos - 65536);
-            if (fill) {
-                fill->woff[k] = srcOff[si] + (uint64_t)ws; fill->boff[k] = srcOff[si] + (uint64_t)pos;
-                fill->doff[k] = dstOff[si] + (uint64_t)(j * slot);
-                fill->wlen[k] = (int32_t)(pos - ws + len); fill->hist[k] = (int32_t)(pos - ws);
-                fill->blen[k] = (int32_t)len; fill->cap[k] = (int32_t)slot;
-            }
-            k++; j++;
-            pos += len; ptr += len;
-            if (ptr + B > L) {                                            /* Commit -> LZ4_saveDictHC(ctx, buf, ptr) */
-                int64_t d = std::min<int64_t>(65536, std::min(ptr, pos - dl));
-                if (d < 4) d = 0;
-                dl = pos - d; ptr = d;
-            }
-        }
+        const WholeLens lens{N - D, B};
+        /* LZ4_compressHC_continue_generic renormalises once end - base > 2 GB (LL64.high.cs:1271-1276): not offered (the last block starts furthest in) */
+        if (lens.count() > 0 && 65536 + D + (lens.count() - 1) * B > ((int64_t)1 << 31))
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
+        if (fill) hc_chain_rows(fill, k, srcOff[si], dstOff[si], D, lens, lens.count(), B, extra);
+        k += lens.count();
     }
     nb = k;
     return K4LZ4_OK;
 }
 
-/* the same table with explicit block lengths (k4lz4_chain_encoder.hpp: ce_hc_rows): stream s has blocks lens.len[lens.first[s] ..
- * + lens.count[s]), which may be shorter than B in mid-stream; its content is dictLen[s] bytes and the blocks behind them */
+/* the same table with explicit block lengths: stream s has blocks lens.len[lens.first[s] .. + lens.count[s]), which may be shorter
+ * than B in mid-stream; its content is dictLen[s] bytes and the blocks behind them */
 struct ChainLens { const int64_t *first; const int32_t *count; const int32_t *len; };
 
 int hc_chain_table_lens(k4lz4_ctx *ctx, const uint64_t *srcOff, const ChainLens &lens, const int32_t *blockSize, const int32_t *extraBlocks,
@@ -1211,15 +1049,7 @@ int hc_chain_table_lens(k4lz4_ctx *ctx, const uint64_t *srcOff, const ChainLens 
         if (B > k4::MAX_INPUT_SIZE) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: block size above the input size limit");
         for (int64_t j = 0; j < lens.count[si]; j++)
             if (len[j] <= 0 || len[j] > B) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a block length outside 1 .. BlockSize");
-        const int64_t slot = B + B / 255 + 16;
-        if (fill)
-            k4::ce_hc_rows(D, len, lens.count[si], B, extra, [&](int64_t j, int64_t ws, int64_t pos, int64_t n, int64_t) {
-                const int64_t r = k + j;
-                fill->woff[r] = srcOff[si] + (uint64_t)ws; fill->boff[r] = srcOff[si] + (uint64_t)pos;
-                fill->doff[r] = dstOff[si] + (uint64_t)(j * slot);
-                fill->wlen[r] = (int32_t)(pos - ws + n); fill->hist[r] = (int32_t)(pos - ws);
-                fill->blen[r] = (int32_t)n; fill->cap[r] = (int32_t)slot;
-            });
+        if (fill) hc_chain_rows(fill, k, srcOff[si], dstOff[si], D, len, lens.count[si], B, extra);
         k += lens.count[si];
     }
     nb = k;
@@ -1301,6 +1131,21 @@ struct FastChainPlan {
     }
 };
 
+/* stream si's words and its rows of the table, from row k on, out of its block lengths (`total` bytes in all); cur: its currentOffset */
+template <class Len>
+void fast_chain_rows(FastChainPlan *fill, int64_t si, int64_t k, uint64_t srcOff, uint64_t dstOff, int64_t D, int64_t cur, Len len, int64_t count,
+                     int64_t total, int64_t B, int64_t extra)
+{
+    const int64_t slot = B + B / 255 + 16;                            /* k4lz4_compress_bound(B) */
+    const int64_t dict = k4::ce_fast_rows(D, cur, len, count, B, extra, [&](int64_t j, int64_t pos, int64_t n, int64_t d, bool) {
+        const int64_t r = k + j;
+        fill->bpos[r] = (uint32_t)pos; fill->blen[r] = (int32_t)n; fill->bdict[r] = (uint32_t)d;
+        fill->doff[r] = dstOff + (uint64_t)(j * slot); fill->cap[r] = (int32_t)slot;
+    });
+    fill->soff[si] = srcOff; fill->slen[si] = (uint64_t)(D + total); fill->first[si] = k; fill->nblk[si] = (uint32_t)count;
+    fill->idx0[si] = (uint32_t)(cur - D); fill->dict_end[si] = (uint32_t)dict;
+}
+
 /* counts the blocks (fill == nullptr) or lays the table out in `fill`.  cur0 / sdict: the streams' state (currentOffset, dictSize), or
  * nullptr for fresh streams; the content's first dictLen[s] bytes are what the ring buffer holds (dictLen == dictSize) */
 int fast_chain_table(k4lz4_ctx *ctx, const uint64_t *srcOff, const int64_t *srcLen, const int32_t *blockSize, const int32_t *extraBlocks,
@@ -1324,30 +1169,12 @@ int fast_chain_table(k4lz4_ctx *ctx, const uint64_t *srcOff, const int64_t *srcL
         } else if (D != 0) {
             return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: dictLen without a state (the table is what continues a stream)");
         }
-        const int64_t L = 65536 + (1 + extra) * B + 32;                   /* the ring buffer (LZ4EncoderBase.cs:25) */
-        const int64_t slot = B + B / 255 + 16;                            /* k4lz4_compress_bound(B) */
-        const int64_t first = k;
-        int64_t ptr = D, dict = D, pos = D, j = 0;
-        while (pos < N) {
-            const int64_t len = std::min(B, N - pos);
-            /* LZ4_renormDictT (LL64.tools.cs:157-173) rescales the table once currentOffset + inputSize > 2 GB: not offered */
-            if (cur + len > ((int64_t)1 << 31))
-                return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
-            if (fill) {
-                fill->bpos[k] = (uint32_t)pos; fill->blen[k] = (int32_t)len; fill->bdict[k] = (uint32_t)dict;
-                fill->doff[k] = dstOff[si] + (uint64_t)(j * slot); fill->cap[k] = (int32_t)slot;
-            }
-            k++; j++;
-            pos += len; ptr += len; dict += len; cur += len;
-            if (ptr + B > L) {                                            /* Commit -> LZ4_saveDict(ctx, buf, ptr); ptr == dictSize */
-                dict = std::min<int64_t>(65536, dict);
-                ptr = dict;
-            }
-        }
-        if (fill) {
-            fill->soff[si] = srcOff[si]; fill->slen[si] = (uint64_t)N; fill->first[si] = first; fill->nblk[si] = (uint32_t)(k - first);
-            fill->idx0[si] = (uint32_t)((cur0 ? (int64_t)cur0[si] : 0) - D); fill->dict_end[si] = (uint32_t)dict;
-        }
+        const WholeLens lens{N - D, B};
+        /* LZ4_renormDictT (LL64.tools.cs:157-173) rescales the table once currentOffset + inputSize > 2 GB: not offered (the last block ends furthest in) */
+        if (lens.count() > 0 && N - D > ((int64_t)1 << 31) - cur)
+            return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
+        if (fill) fast_chain_rows(fill, si, k, srcOff[si], dstOff[si], D, cur, lens, lens.count(), N - D, B, extra);
+        k += lens.count();
     }
     nb = k;
     return K4LZ4_OK;
@@ -1374,16 +1201,7 @@ int fast_chain_table_lens(k4lz4_ctx *ctx, const uint64_t *srcOff, const ChainLen
         }
         if ((int64_t)cur0[si] + total > ((int64_t)1 << 31))
             return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: a chained stream longer than 2 GB (the encoder's renormalisation) is not supported");
-        const int64_t slot = B + B / 255 + 16;
-        if (fill) {
-            const int64_t dict = k4::ce_fast_rows(D, (int64_t)cur0[si], len, lens.count[si], B, extra, [&](int64_t j, int64_t pos, int64_t n, int64_t d, bool) {
-                const int64_t r = k + j;
-                fill->bpos[r] = (uint32_t)pos; fill->blen[r] = (int32_t)n; fill->bdict[r] = (uint32_t)d;
-                fill->doff[r] = dstOff[si] + (uint64_t)(j * slot); fill->cap[r] = (int32_t)slot;
-            });
-            fill->soff[si] = srcOff[si]; fill->slen[si] = (uint64_t)(D + total); fill->first[si] = k; fill->nblk[si] = (uint32_t)lens.count[si];
-            fill->idx0[si] = (uint32_t)((int64_t)cur0[si] - D); fill->dict_end[si] = (uint32_t)dict;
-        }
+        if (fill) fast_chain_rows(fill, si, k, srcOff[si], dstOff[si], D, (int64_t)cur0[si], len, lens.count[si], total, B, extra);
         k += lens.count[si];
     }
     nb = k;

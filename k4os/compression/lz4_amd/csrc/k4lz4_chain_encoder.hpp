@@ -12,9 +12,9 @@
  * A stream's store: for chained fast streams its k4lz4_fast_chain_state, then the encoder's ring buffer.
  *
  * Two pieces of host arithmetic describe the same ring and must agree: ce_model, which walks the records, and ce_hc_rows /
- * ce_fast_rows, which walk block lengths the way hc_chain_table / fast_chain_table do and fill the chained encoders' plans.
- * k4lz4_chain_encode_blocks and k4lz4_chain_table_rows expose both; tests/test_chain_encoder_host.py compares them with each other
- * and with the witness.
+ * ce_fast_rows, which walk block lengths and fill every chained encoder's plan (k4lz4_capi.hip: hc_chain_table / fast_chain_table,
+ * whose whole streams have every length BlockSize but the last, and their _lens twins).  k4lz4_chain_encode_blocks and
+ * k4lz4_chain_table_rows expose both; tests/test_chain_encoder_host.py compares them with each other and with the witness.
  */
 #pragma once
 #include <algorithm>
@@ -166,11 +166,11 @@ inline void ce_advance(k4lz4_chain_encoder &e, const CeAfter &a)
     if (e.kind == 2) { e.currentOffset = a.cur; e.dictSize = a.dict; }
 }
 
-/* ---- the chained encoders' block tables with explicit block lengths, beside hc_chain_table / fast_chain_table (k4lz4_capi.hip):
- * the content's first D bytes are what the ring buffer holds, block j is the next len[j] bytes.  With every length but the last B
- * the rows are those tables'. */
-template <class Row>   /* row(j, ws, pos, len, dictLimit): the block sees [ws, pos) in front of it, ws = max(dictLimit, pos - 64 KiB) */
-inline void ce_hc_rows(int64_t D, const int32_t *len, int64_t n, int64_t B, int64_t extra, Row row)
+/* ---- the chained encoders' block tables, the one walk over LZ4EncoderBase's ring that hc_chain_table / fast_chain_table and their
+ * _lens twins (k4lz4_capi.hip) fill their plans through: the content's first D bytes are what the ring buffer holds, block j
+ * is the next len[j] bytes (len: an array, or anything else with []).  A whole stream has every length B but the last. */
+template <class Len, class Row>   /* row(j, ws, pos, len, dictLimit): the block sees [ws, pos) in front of it, ws = max(dictLimit, pos - 64 KiB) */
+inline void ce_hc_rows(int64_t D, Len len, int64_t n, int64_t B, int64_t extra, Row row)
 {
     const int64_t L = 65536 + (1 + extra) * B + 32;
     int64_t ptr = D, dl = 0, pos = D;
@@ -185,8 +185,8 @@ inline void ce_hc_rows(int64_t D, const int32_t *len, int64_t n, int64_t B, int6
     }
 }
 
-template <class Row>   /* row(j, pos, len, dictSize, dictSmall) -> the dictSize after the last block's Commit; cur0: currentOffset */
-inline int64_t ce_fast_rows(int64_t D, int64_t cur0, const int32_t *len, int64_t n, int64_t B, int64_t extra, Row row)
+template <class Len, class Row>   /* row(j, pos, len, dictSize, dictSmall) -> the dictSize after the last block's Commit; cur0: currentOffset */
+inline int64_t ce_fast_rows(int64_t D, int64_t cur0, Len len, int64_t n, int64_t B, int64_t extra, Row row)
 {
     const int64_t L = 65536 + (1 + extra) * B + 32;
     int64_t ptr = D, dict = D, pos = D, cur = cur0;

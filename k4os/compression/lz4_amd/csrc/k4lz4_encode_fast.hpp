@@ -348,7 +348,7 @@ constexpr uint32_t SEG_NONE = 0xffffffffu;
 constexpr uint32_t SEG_ITEM_WORDS = 10u;          /* a segment's record (k4lz4_segments.hpp, SegItem) as the words the encoder kernels read and write */
 constexpr int SEG_SNAP_DWORDS = 4096 + 16;          /* [0] cut + 1 (0: not there yet, SEG_NONE: this run never found one), [16..] the table */
 constexpr uint32_t SEG_ITEMS_MAX = 8192u;           /* = SEG_MAX_ITEMS (k4lz4_segments.hpp): segments of all cut blocks of a launch, at most */
-constexpr uint32_t SEG_HDR_DWORDS = 64u;            /* k4lz4_capi.hip lays a launch's segment scratch out as header (256 bytes), then the items */
+constexpr uint32_t SEG_HDR_DWORDS = 64u;            /* segment_plan (k4lz4_launch.hpp) lays a launch's segment scratch out as header (256 bytes), then the items */
 constexpr uint32_t SEG_SPIN_MAX = 1u << 20;          /* polls (with s_sleep 8 between them: some tenths of a second) before a run stops waiting for the next one's cut */
 struct SegRun {
     uint32_t begin;             /* where the run starts probing: 0, or the start of the warm-up */

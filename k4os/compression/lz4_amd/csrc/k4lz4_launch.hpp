@@ -1,7 +1,9 @@
 /* The batch launcher: which kernels a batch of blocks gets, and their launches.  A part of k4lz4_capi.hip -- included there, inside
- * its unnamed namespace, behind launch_hc (the HC levels) and the helpers they share -- and of no other file.
+ * its unnamed namespace, behind the helpers the launchers share (grow_after, envelope_prep / envelope_finish, DictArgs) -- and of
+ * no other file.
  *
  *   launch_inner          the dispatcher
+ *   launch_hc             the HC levels: hc_chunk() decides once per launch chunk which kernels run, launch_hc sizes the scratch and launches them
  *   launch_envelope       fast-level pickles and wraps the encoders' way: prep, launch_fast_encode on the slots, finish
  *   launch_fast_encode    LZ4Codec.Encode below level 3: fast_route() decides once per call and fast_chunk() once per launch chunk
  *                         which kernels run; order_prelude, segment_plan, two_step_chunk and one_kernel_chunk launch what they say
@@ -526,6 +528,185 @@ int launch_decode_like(k4lz4_ctx *ctx, Kind kind, k4::BatchArgs b, hipStream_t s
                 K4_LAUNCH_WAVES(k4::k4_unpickle_kernel, cnt, k4::DECODE_WAVES_PER_WG, stream, a);
             }
         }
+        K4_HIP(ctx, hipGetLastError());
+    }
+    return K4LZ4_OK;
+}
+
+/* ---- the HC levels: the route ---- */
+/* what is decided per launch chunk of cnt blocks once the longest of them is known */
+struct HcChunk {
+    enum Chain { CHAIN_PART, CHAIN_LDS, CHAIN_MEM } chain;      /* which kernel builds the chains */
+    int64_t n_lds, n_mem;           /* CHAIN_LDS: its blocks, and those the table-in-memory kernel takes beside it on the second queue */
+    enum Cand { CAND_NONE, CAND_LDS, CAND_MEM } cand;           /* where the candidates' records come from */
+    unsigned gy, groups, per;       /* CAND_MEM: position chunks per block, groups of eight blocks, chunks per launch */
+    bool optimal, pace;             /* k4_hc_parse_opt_kernel; else the parse's late-blocks-first priorities (k4lz4_common.hpp, Pace) */
+    int nseg;                       /* the parse writes sequence records by this many waves per block if there is room for them; 0: none */
+};
+
+/* longest: the chunk's longest block; chained: its blocks have a history in front of them (k4::HcArgs::hist) -- such a batch takes
+ * the memory paths: the LDS kernels are built around blocks of at most 64 KiB that start at their position 0 */
+HcChunk hc_chunk(const k4lz4_ctx *ctx, int64_t cnt, unsigned long long longest, int level, bool chained)
+{
+    const int64_t cu = ctx->cu_count;
+    const bool lds_ok = longest <= 65536 && !chained;
+    HcChunk c{};
+    /* no block over 64 KiB: eight waves per block, each with an eighth of the hash values and of the table (round 6) */
+    if (lds_ok && ctx->hc_chain_parts) c.chain = HcChunk::CHAIN_PART;
+    else if (lds_ok) {
+        /* (rounds 3-5, K4LZ4_HC_CHAIN_OLD) no block over 64 KiB (known from the host lengths, the reservation or the device): hash tables in LDS -- two blocks
+         * per CU, a wave each, which leaves the CU's other wave slots empty; so the last third of a big chunk goes through the
+         * table-in-memory kernel on the second queue at the same time (its tables: 128 KiB per block, cleared by launch_hc) */
+        c.chain = HcChunk::CHAIN_LDS;
+        c.n_mem = cnt >= 8 * cu ? cnt * ctx->hc_mem_pct / 100 : 0;
+        c.n_lds = cnt - c.n_mem;
+    } else c.chain = HcChunk::CHAIN_MEM;
+    c.optimal = level >= K4LZ4_L10_OPT;              /* clTable (LL64.high.cs:1124-1138): lz4opt strategy */
+    /* no block over 64 KiB: the candidates' records out of LDS (k4_hc_walk_lds_kernel, k4_hc_cand_lds_kernel; round 6) */
+    if (longest >= 13 && lds_ok && !c.optimal && ctx->hc_cand_lds) c.cand = HcChunk::CAND_LDS;
+    else if (longest >= 13 && !c.optimal) {
+        c.cand = HcChunk::CAND_MEM;
+        c.gy = (unsigned)((longest + k4::HC_CAND_POS_PER_WG - 1) / k4::HC_CAND_POS_PER_WG);
+        c.groups = (unsigned)((cnt + 7) / 8);                            /* eight blocks, one per XCD (k4_hc_cand_kernel) */
+        c.per = std::max(1u, (1u << 30) / (8u * c.groups));              /* chunks per launch: the grid stays below 2^31 workgroups */
+    }
+    if (c.optimal) return c;
+    /* level 3 on blocks of at most 64 KiB: the parse writes 8-byte sequence records (the fast encoder's scratch, a slot per
+     * block) and the same wave turns them into bytes afterwards; without room for them LZ4HC_encodeSequence stays in the loop */
+    /* ... by two or four waves per block while the chip has the wave slots for them (k4lz4_encode_hc.hpp, HcSegs; round 6) */
+    if (level <= K4LZ4_L03_HC && lds_ok && ctx->hc_records)      /* (measured, profiles/r6_hc_ab.txt: four waves per block beat two even when they take turns -- 4096 blocks: 9.5 against 12.2-13.3 ms, one wave 13.9) */
+        c.nseg = longest < k4::HC_SEG_MIN_LEN ? 1 : ctx->hc_segs > 0 ? ctx->hc_segs : (cnt * 2 <= 32 * cu ? 4 : 1);
+    c.pace = ctx->use_pace && ctx->d_pace && cnt > 8 * cu;
+    return c;
+}
+
+/* HC levels: layout -> (sync for the scratch size) -> hash-table clear -> chain kernel -> parse kernel.
+ * `env`: the same around the LZ4Pickler envelope (encoder slot = envelope + 5, cap U - 1) or LZ4Wrapper's (+ 8, cap U - 1). */
+/* hostLen: the blocks' lengths when the caller has them on the host (host-pointer calls), else nullptr; hist: chained HC streams
+ * (k4::HcArgs::hist, device pointer), else nullptr */
+int launch_hc(k4lz4_ctx *ctx, Envelope env, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+              const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, int level, int flags,
+              hipStream_t stream, const int32_t *hostLen, const int32_t *hist = nullptr)
+{
+    const int64_t chunk_max = 4096;   /* 128 KiB of hash table per block in flight */
+    for (int64_t first = 0; first < n; first += chunk_max) {
+        const int64_t cnt = std::min<int64_t>(chunk_max, n - first);
+        int rc = grow_after(ctx, stream, &ctx->d_hc_hash, &ctx->d_hc_hash_cap, (size_t)cnt << (k4::HC_HASH_LOG + 2));
+        if (rc != K4LZ4_OK) return rc;
+        rc = grow_after(ctx, stream, &ctx->d_hc_meta, &ctx->d_hc_meta_cap, (size_t)(cnt + 2) * 8 + (size_t)cnt * 16 + 64);
+        if (rc != K4LZ4_OK) return rc;
+        unsigned long long *d_woff = (unsigned long long *)ctx->d_hc_meta;
+        uint64_t *d_encoff = (uint64_t *)(d_woff + cnt + 2);
+        int32_t *d_enccap = (int32_t *)(d_encoff + cnt);
+        int32_t *d_enclen = d_enccap + cnt;
+        k4::HcArgs h{};
+        h.status = ctx->d_status;
+        h.src = src; h.srcOff = srcOff + first; h.srcLen = srcLen + first;
+        h.dst = dst; h.dstOff = dstOff + first; h.dstCap = dstCap + first; h.outLen = outLen + first;
+        h.n = cnt; h.level = level; h.flags = flags;
+        h.hash = (uint32_t *)ctx->d_hc_hash; h.workOff = d_woff;
+        h.hist = hist ? hist + first : nullptr;
+        k4::BatchArgs a{};
+        a.src = src; a.srcOff = h.srcOff; a.srcLen = h.srcLen; a.dst = dst; a.dstOff = h.dstOff; a.dstCap = h.dstCap;
+        a.outLen = h.outLen; a.n = cnt; a.level = level; a.accel = 1; a.flags = flags;
+        if (env == ENV_PICKLE || env == ENV_WRAP) {
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_ENVELOPE;
+            envelope_prep(env, a, d_encoff, d_enccap, stream);
+            h.dstOff = d_encoff; h.dstCap = d_enccap; h.outLen = d_enclen; h.flags = K4LZ4_FLAG_RAW_RETURN;
+        }
+        /* How much work area, and how long the longest block is: from the host's copy of the lengths, from the
+         * reservation (k4lz4_ctx_reserve_hc), or -- the only case that synchronises -- from the device. */
+        unsigned long long tail[2] = {0, 0};   /* total work bytes, longest block */
+        bool ask_device = false;
+        if (hostLen) {
+            for (int64_t i = 0; i < cnt; i++) {
+                const int32_t len = hostLen[first + i];
+                if (len > 0) {
+                    tail[0] += (((unsigned long long)len + 3u) & ~3ull) * k4::HC_WORK_PER_BYTE;
+                    tail[1] = std::max<unsigned long long>(tail[1], (unsigned long long)len);
+                }
+            }
+        } else if (ctx->hc_res_total) {
+            tail[0] = (ctx->hc_res_total + 4u * (unsigned long long)cnt) * k4::HC_WORK_PER_BYTE;
+            tail[1] = ctx->hc_res_longest;
+            h.workCap = tail[0]; h.maxLen = ctx->hc_res_longest;
+        } else {
+            ask_device = true;
+        }
+        if (!ask_device) {
+            rc = grow_after(ctx, stream, &ctx->d_hc_work, &ctx->d_hc_work_cap, (size_t)tail[0] + 256);
+            if (rc != K4LZ4_OK) return rc;
+        }
+        hipLaunchKernelGGL(k4::k4_hc_layout_kernel, dim3(1), dim3(256), 0, stream, h);
+        if (ask_device) {
+            K4_HIP(ctx, hipMemcpyAsync(tail, d_woff + cnt, 16, hipMemcpyDeviceToHost, stream));
+            K4_HIP(ctx, hipStreamSynchronize(stream));
+            rc = grow(ctx, &ctx->d_hc_work, &ctx->d_hc_work_cap, (size_t)tail[0] + 256, false);
+            if (rc != K4LZ4_OK) return rc;
+        }
+        h.work = ctx->d_hc_work;
+        const HcChunk c = hc_chunk(ctx, cnt, tail[1], level, hist != nullptr);
+        if (c.chain == HcChunk::CHAIN_PART) {
+            h.nChain = cnt;
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_PART;
+            hipLaunchKernelGGL(k4::k4_hc_chain_part_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_CHAIN_PARTS), 0, stream, h);
+        } else if (c.chain == HcChunk::CHAIN_LDS) {
+            if (c.n_mem > 0) {
+                K4_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
+                K4_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
+                K4_HIP(ctx, hipMemsetAsync(ctx->d_hc_hash + ((size_t)c.n_lds << (k4::HC_HASH_LOG + 2)), 0, (size_t)c.n_mem << (k4::HC_HASH_LOG + 2), ctx->aux));
+                k4::HcArgs hm = h;
+                hm.blockBase = (unsigned)c.n_lds; hm.nChain = c.n_mem;
+                ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_MEM;
+                K4_LAUNCH_WAVES(k4::k4_hc_chain_kernel, c.n_mem, k4::HC_CHAIN_WAVES_PER_WG, ctx->aux, hm);
+                K4_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
+            }
+            h.nChain = c.n_lds;
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_LDS;
+            K4_LAUNCH_WAVES(k4::k4_hc_chain_lds_kernel, c.n_lds, k4::HC_CHAIN_LDS_WAVES_PER_WG, stream, h);
+            if (c.n_mem > 0) K4_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_join, 0));
+        } else {
+            K4_HIP(ctx, hipMemsetAsync(ctx->d_hc_hash, 0, (size_t)cnt << (k4::HC_HASH_LOG + 2), stream));
+            h.nChain = cnt;
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CHAIN_MEM;
+            K4_LAUNCH_WAVES(k4::k4_hc_chain_kernel, cnt, k4::HC_CHAIN_WAVES_PER_WG, stream, h);
+        }
+        if (c.cand == HcChunk::CAND_LDS) {
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CAND_LDS;
+            hipLaunchKernelGGL(k4::k4_hc_walk_lds_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_LDS_WAVES), 0, stream, h);
+            hipLaunchKernelGGL(k4::k4_hc_cand_lds_kernel, dim3((unsigned)cnt), dim3(64 * k4::HC_CAND_LDS_WAVES), 0, stream, h);
+        } else if (c.cand == HcChunk::CAND_MEM) {
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_CAND_MEM;
+            for (unsigned y0 = 0; y0 < c.gy; y0 += c.per) {
+                k4::HcArgs hy = h;
+                hy.posBase = y0 * (unsigned)k4::HC_CAND_POS_PER_WG;
+                hy.candChunks = std::min(c.per, c.gy - y0);
+                hipLaunchKernelGGL(k4::k4_hc_cand_kernel, dim3(c.groups * 8u * hy.candChunks), dim3(256), (size_t)ctx->hc_cand_dynlds, stream, hy);
+            }
+        }
+        if (c.optimal) {
+            ctx->last_encode_route |= K4LZ4_ENCODE_ROUTE_HC_PARSE_OPT;
+            K4_LAUNCH_WAVES(k4::k4_hc_parse_opt_kernel, cnt, 1, stream, h);
+        } else {
+            int nseg = c.nseg;      /* the records the route wants: fewer waves per block, or none, where d_parse cannot grow that far */
+            while (nseg) {
+                const size_t need = (size_t)cnt * (nseg == 4 ? k4::hc_seg_rec_off(4, 4) : nseg == 2 ? k4::hc_seg_rec_off(2, 2) : k4::PARSE_REC_STRIDE) * sizeof(uint2);
+                if (grow_after(ctx, stream, &ctx->d_parse, &ctx->d_parse_cap, need) == K4LZ4_OK) { h.recs = (uint2 *)ctx->d_parse; break; }
+                { std::lock_guard<std::mutex> g(g_err_mu); ctx->error.clear(); }
+                nseg = nseg > 1 ? 1 : 0;
+            }
+            if (c.pace) {
+                h.pace = ctx->d_pace;
+                K4_HIP(ctx, hipMemsetAsync(h.pace, 0, k4::PACE_BYTES, stream));
+            }
+            ctx->last_encode_route |= h.recs && nseg == 4 ? K4LZ4_ENCODE_ROUTE_HC_PARSE_SEG4 : h.recs && nseg == 2 ? K4LZ4_ENCODE_ROUTE_HC_PARSE_SEG2 :
+                                      h.recs ? K4LZ4_ENCODE_ROUTE_HC_PARSE_REC : K4LZ4_ENCODE_ROUTE_HC_PARSE;
+            if (h.recs && nseg == 4) hipLaunchKernelGGL(k4::k4_hc_parse_seg4_kernel, dim3((unsigned)((cnt + 1) / 2)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, stream, h);
+            else if (h.recs && nseg == 2) hipLaunchKernelGGL(k4::k4_hc_parse_seg2_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(64 * k4::HC_SEG_WAVES_PER_WG), 0, stream, h);
+            else if (h.recs) K4_LAUNCH_WAVES(k4::k4_hc_parse_rec_kernel, cnt, k4::HC_REC_WAVES_PER_WG, stream, h);
+            else K4_LAUNCH_WAVES(k4::k4_hc_parse_kernel, cnt, k4::HC_PARSE_WAVES_PER_WG, stream, h);
+        }
+        envelope_finish(env, a, d_enclen, stream);
         K4_HIP(ctx, hipGetLastError());
     }
     return K4LZ4_OK;

@@ -152,7 +152,8 @@ HC_CHAIN_LIMIT = (1 << 31) - 65536      # LZ4_compressHC_continue_generic renorm
 def hc_chain_blocks(length: int, blockSize: int, extraBlocks: int = 0, dictLen: int = 0) -> List[Tuple[int, int, int]]:
     """LZ4HighChainEncoder's blocks of a content in content coordinates: (start, length, dictLimit) per block -- the model
     LZ4EncoderBase's ring buffer reduces to (Topup / Encode / Commit -> LZ4_saveDictHC).  dictLen: the content's first bytes are
-    what the ring buffer already holds (no block for them).  The library builds the same table (k4lz4_capi.hip, hc_chain_table)."""
+    what the ring buffer already holds (no block for them).  The library builds the same table (k4lz4_capi.hip,
+    hc_chain_table: the stream's block lengths through k4lz4_chain_encoder.hpp's ce_hc_rows)."""
     B = _round_block_size(blockSize)
     L = 65536 + (1 + max(int(extraBlocks), 0)) * B + 32
     ptr = s = int(dictLen)
@@ -311,7 +312,8 @@ def fast_chain_blocks(length: int, blockSize: int, extraBlocks: int = 0, dictLen
     model LZ4EncoderBase's ring buffer reduces to (Topup / Encode / Commit -> LZ4_saveDict).  dictLen: the content's first bytes are
     what the ring buffer already holds (= the stream context's dictSize); currentOffset: the context's index at that point (default:
     dictLen, a stream from its start).  dictSize is what the ring holds in front of the block, dictSmall LZ4_compress_fast_continue's
-    choice of dictIssue (LL64.fast.cs:617, :650).  The library builds the same table (k4lz4_capi.hip, fast_chain_table)."""
+    choice of dictIssue (LL64.fast.cs:617, :650).  The library builds the same table (k4lz4_capi.hip, fast_chain_table:
+    the stream's block lengths through k4lz4_chain_encoder.hpp's ce_fast_rows)."""
     B = _round_block_size(blockSize)
     L = 65536 + (1 + max(int(extraBlocks), 0)) * B + 32
     s = ptr = d = int(dictLen)

@@ -271,7 +271,7 @@ int k4emu_pickle_seg_batch(const uint8_t *src, const uint64_t *srcOff, const int
     k4emu::launch_fn(dim3((unsigned)((n + 255) / 256)), dim3(256), [=] { k4::k4_pickle_prep_kernel(a, eo, ec); }, 1);
     k4::BatchArgs e = a;
     e.dstOff = encOff.data(); e.dstCap = encCap.data(); e.outLen = encLen.data(); e.flags = (flags & k4::FLAG_X32) | k4::FLAG_RAW_RETURN;
-    /* header and items in one piece of memory, the header SEG_HDR_DWORDS in front of the items, as k4lz4_capi.hip lays them out
+    /* header and items in one piece of memory, the header SEG_HDR_DWORDS in front of the items, as segment_plan (k4lz4_launch.hpp) lays them out
      * (seg_first_of finds SegHdr::spin_max there) */
     std::vector<uint32_t> segmem((size_t)k4::SEG_HDR_DWORDS + (size_t)k4::SEG_MAX_ITEMS * k4::SEG_ITEM_WORDS, 0u);
     k4::SegHdr &hdr = *(k4::SegHdr *)segmem.data();

@@ -115,6 +115,73 @@ def test_explicit_length_tables_equal_the_cut_at_B_tables(B, extra, D, total):
     assert table_rows(lens, B, extra, D, 2, cur=D + 70000) == E.fast_chain_blocks(total, B, extra, D, currentOffset=D + 70000)
 
 
+@pytest.mark.parametrize("B", [K1, K64])
+@pytest.mark.parametrize("extra", [0, 2])
+@pytest.mark.parametrize("D", [0, 3, 4, K64 - 1, K64])
+def test_whole_stream_tables_where_the_ring_cuts(B, extra, D):
+    """ce_hc_rows / ce_fast_rows (through k4lz4_chain_table_rows) over a whole stream's block lengths, formed here as the library's
+    whole-stream tables form them -- B repeated, then the remainder, none for a stream that is all dictionary: the rows equal the
+    package's own tables at the lengths where the ring cuts -- nothing or one byte behind the dictionary, a block less or more
+    than a byte, the first Commit (pointer + B > L) a byte early and a byte late and the block behind it, and dictionaries around
+    the 4 bytes below which LZ4_saveDictHC keeps nothing and around 64 KiB.  (hc_chain_table / fast_chain_table themselves fill
+    plans only in front of a launch: the GPU chain tests compare their blocks with the witness; their counting pass is below.)"""
+    L = K64 + (1 + extra) * B + 32
+    sizes = [D, D + 1, B - 1, B, B + 1, L - B - 1, L - B + 1, L + 1]
+    for N in sorted({n for n in sizes if n >= D} | {D + n for n in sizes[2:]}):
+        lens = [B] * ((N - D) // B) + ([(N - D) % B] if (N - D) % B else [])
+        assert table_rows(lens, B, extra, D, 1) == E.hc_chain_blocks(N, B, extra, D)
+        assert table_rows(lens, B, extra, D, 2) == E.fast_chain_blocks(N, B, extra, D)
+        assert table_rows(lens, B, extra, D, 2, cur=D + 70000) == E.fast_chain_blocks(N, B, extra, D, currentOffset=D + 70000)
+
+
+G2 = 1 << 31
+
+
+def whole_stream_answer(kind, N, B, D, cur):
+    """hc_chain_table / fast_chain_table themselves, without a GPU: the host forms of the one-shot chained encoders count the
+    blocks before they look at the context, so without one a stream the table accepts is answered "ctx is NULL" and one it
+    refuses with the table's own message"""
+    lib = _native.load_library()
+    byte = (C.c_ubyte * 16)()
+    off, out = np.zeros(1, np.uint64), np.zeros(1, np.int32)
+    n, bs, extra, dl = np.array([N], np.int64), np.array([B], np.int32), np.zeros(1, np.int32), np.array([D], np.int32)
+    streams = (None, byte, off.ctypes.data, n.ctypes.data, bs.ctypes.data, extra.ctypes.data, dl.ctypes.data, 1)
+    if kind == 1:
+        rc = lib.k4lz4_encode_hc_chain_batch(*streams, byte, off.ctypes.data, out.ctypes.data, 1, 9, 0)
+    else:
+        st = np.zeros(1, E.FAST_CHAIN_STATE)
+        st["currentOffset"], st["dictSize"] = cur or 0, D
+        rc = lib.k4lz4_encode_fast_chain_batch(*streams, st.ctypes.data if cur is not None else None, None, byte, off.ctypes.data,
+                                               out.ctypes.data, 1, 0)
+    assert rc != 0
+    return lib.k4lz4_last_error(None).decode()
+
+
+@pytest.mark.parametrize("B", [K64, 16 * K1])
+@pytest.mark.parametrize("D,cur", [(0, None), (0, 70000), (5, 70000), (K64, 3 * K64)])
+def test_whole_stream_tables_refuse_2_gb_where_the_block_walk_does(B, D, cur):
+    """The refusals stand as they were: LZ4HC on 65536 + a block's start, the fast chain on currentOffset + a block's end, past
+    2^31.  The model is the walk block by block; the streams end a block, a byte and nothing around the last one either accepts,
+    and one is all dictionary with a state already past 2 GB (no block: nothing to refuse)."""
+    def walk(kind, N):
+        at = (cur or 0) if kind == 2 else K64 + D
+        for pos in range(D, N, B):
+            if (at + min(B, N - pos) if kind == 2 else K64 + pos) > G2:
+                return True
+            at += min(B, N - pos)
+        return False
+    for kind in (1, 2):
+        edge = G2 - K64 if kind == 1 else G2 - (cur or 0) + D        # the stream position where a start (HC) or an end (fast) reaches 2^31
+        seen = set()
+        for N in (edge - B, edge - 1, edge, edge + 1, edge + B - 1, edge + B, edge + B + 1):
+            want = walk(kind, N)
+            answer = whole_stream_answer(kind, N, B, D, cur)
+            assert ("longer than 2 GB" in answer) == want and (answer == "ctx is NULL") == (not want), (kind, N, answer)
+            seen.add(want)
+        assert seen == {False, True}
+    assert whole_stream_answer(2, D, B, D, G2 + 5 if cur is not None else None) == "ctx is NULL"
+
+
 @pytest.mark.parametrize("B,extra", [(K1, 0), (K1, 3), (4 * K1, 1), (K64, 0)])
 def test_table_codecs_hold_with_short_blocks_in_mid_stream(B, extra):
     """4.9's argument for the new case: blocks contiguous, lowLimit == dictLimit, dictLimit <= s - 65536 after a save -- and the

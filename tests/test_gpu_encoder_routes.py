@@ -3,7 +3,7 @@
 torch tensors, so the arena a kernel wrote into is the arena that is read back: a write outside a slot -- behind it or in front of
 it, for an accepted or a REJECTED block -- shows.
 
-The launcher chooses by switches, flags and blocks per CU (k4lz4_launch.hpp: fast_route, fast_chunk; k4lz4_capi.hip: launch_hc).
+The launcher chooses by switches, flags and blocks per CU (k4lz4_launch.hpp: fast_route, fast_chunk, hc_chunk).
 A context reads its switches when it is created, so every variant is a context made under its environment; every batch count is
 derived from the CU count the device reports; `k4lz4_last_encode_route` says after every call which kernel families it launched
 and how (queue, persistent, priorities, cost order, device split, migration, more than one chunk), and a variant whose call did
