@@ -7,7 +7,7 @@ using System.Runtime.InteropServices;
 
 namespace K4os.Compression.LZ4.Engine
 {
-	internal static unsafe class LLNative
+	internal static unsafe partial class LLNative      // (the other part: LZ4Frame.DictSet.cs)
 	{
 		private const string Lib = "k4lz4"; // libk4lz4.so on the probing path
 

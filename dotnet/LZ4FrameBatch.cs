@@ -70,18 +70,28 @@ namespace K4os.Compression.LZ4.Streams.Frames
 			else
 				using (var encoder = new LZ4BlockEncoder(settings.CompressionLevel, blockSize))
 					encoder.EncodeBlocks(content, arena, encoded, allowCopy: true);
+			return Assemble(content, settings, bdCode, arena, slot, encoded, n, null);
+		}
 
-			// sizes: header 7 (+8 content length), per block 4 + stored (+4), EndMark 4 (+4)
-			long total = 7 + (settings.ContentLength.HasValue ? 8 : 0) + 4 + (settings.ContentChecksum ? 4 : 0);
+		/// <summary>The frame around n encoded blocks (block i in arena[i * slot ..], encoded[i] negative: stored raw): header, records
+		/// with their checksums, EndMark, content checksum.  dictId: the DictID the header names (FLG bit 0, after the content size) --
+		/// only LZ4FrameDictSet passes one.</summary>
+		internal static byte[] Assemble(
+			ReadOnlySpan<byte> content, LZ4EncoderSettings settings, int bdCode, byte[] arena, int slot, int[] encoded, int n, uint? dictId)
+		{
+			var chained = settings.ChainBlocks;
+			// sizes: header 7 (+8 content length, +4 DictID), per block 4 + stored (+4), EndMark 4 (+4)
+			long total = 7 + (settings.ContentLength.HasValue ? 8 : 0) + (dictId.HasValue ? 4 : 0) + 4 + (settings.ContentChecksum ? 4 : 0);
 			for (var i = 0; i < n; i++) total += 4 + Math.Abs(encoded[i]) + (settings.BlockChecksum ? 4 : 0);
 			var frame = new byte[total];
 			var at = 0;
 			BinaryPrimitives.WriteUInt32LittleEndian(frame.AsSpan(at), Magic); at += 4;
 			var headerStart = at;
 			frame[at++] = (byte) ((1 << 6) | (chained ? 0 : 1 << 5) /* FLG bit 5: independent blocks */ | (settings.BlockChecksum ? 1 << 4 : 0) |
-				(settings.ContentLength.HasValue ? 1 << 3 : 0) | (settings.ContentChecksum ? 1 << 2 : 0));
+				(settings.ContentLength.HasValue ? 1 << 3 : 0) | (settings.ContentChecksum ? 1 << 2 : 0) | (dictId.HasValue ? 1 : 0));
 			frame[at++] = (byte) (bdCode << 4);
 			if (settings.ContentLength.HasValue) { BinaryPrimitives.WriteUInt64LittleEndian(frame.AsSpan(at), (ulong) settings.ContentLength.Value); at += 8; }
+			if (dictId.HasValue) { BinaryPrimitives.WriteUInt32LittleEndian(frame.AsSpan(at), dictId.Value); at += 4; }
 			frame[at] = (byte) (Digest(frame.AsSpan(headerStart, at - headerStart)) >> 8); at++;          // LZ4FrameWriter.cs:100
 
 			// payloads first, then every block checksum of the frame in one XXH32 launch
@@ -154,7 +164,7 @@ namespace K4os.Compression.LZ4.Streams.Frames
 
 		/// <summary>The reference reader's exception for a K4LZ4_FRAME_* code (Frames/LZ4FrameReader.blocking.cs ReadHeader / ReadBlock,
 		/// Internal/Stash: EndOfStream).</summary>
-		private static Exception FrameError(long code) => code switch {
+		internal static Exception FrameError(long code) => code switch {
 			LLNative.FRAME_EOF => new System.IO.EndOfStreamException("Unexpected end of stream"),
 			LLNative.FRAME_MAGIC => new System.IO.InvalidDataException("LZ4 frame magic number expected"),
 			LLNative.FRAME_VERSION => new System.IO.InvalidDataException("LZ4 frame version unknown: 0"),
@@ -168,7 +178,7 @@ namespace K4os.Compression.LZ4.Streams.Frames
 			_ => new InvalidOperationException($"unknown frame result {code}"),
 		};
 
-		private static int MaxBlockSize(int requested, out int bdCode)
+		internal static int MaxBlockSize(int requested, out int bdCode)
 		{   // LZ4FrameWriter.cs:176-189
 			if (requested <= 1 << 16) { bdCode = 4; return 1 << 16; }
 			if (requested <= 1 << 18) { bdCode = 5; return 1 << 18; }

@@ -1245,6 +1245,58 @@ K4LZ4_API int k4lz4_chain_decoder_open_dictset_device(k4lz4_ctx *ctx, const k4lz
                                                       const uint64_t *storeOff, const int32_t *dictIdx, const k4lz4_dict_set *set,
                                                       int64_t *outLen, int64_t n, void *stream);
 
+/* ---- frames with a predefined dictionary read against a set ---------------------------------------------------
+ * The frame reader above (k4lz4_frame_sizes*, k4lz4_decode_frames*) with a k4lz4_dict_set beside it: frames whose FLG has the
+ * dictionary bit (what `lz4 -D` and LZ4F_compressFrame_usingCDict write) are decoded against an entry of the set instead of being
+ * reported as K4LZ4_FRAME_DICTIONARY.  The set stays as it is; the ids are the call's: dictIds is a HOST array of set->nDict
+ * uint32_t in both forms, entry e answers to DictID dictIds[e], and it is copied to the context's scratch per call.
+ *   - a frame's DictID resolves to the FIRST entry whose id equals it (duplicate ids: the later entries are never chosen);
+ *   - a frame without the bit decodes without a dictionary, as in the plain calls;
+ *   - a DictID that resolves to nothing is K4LZ4_FRAME_DICTIONARY at its place in the defect order: after the header checksum
+ *     (which covers the DictID: a flipped DictID byte is K4LZ4_FRAME_HEADER_SUM, a header cut inside it K4LZ4_FRAME_EOF), before
+ *     the first block.  No code is new.
+ * Independent-block frames: every compressed block is decoded against the entry's kept bytes (the last 64 KiB of the dictionary)
+ * as an external dictionary, in parallel and straight into place; blocks never see each other.  Chained frames: in order, one
+ * wave per frame, the history being the kept bytes followed by the output so far.  An offset that reaches before the first kept
+ * byte is K4LZ4_FRAME_BLOCK.  Content checksum and ContentLength cover the content only.  Result codes, defect order and what
+ * may be written are those of k4lz4_decode_frames_device.
+ * outDictIdx (optional, NULL: not wanted): per frame the entry it resolved to, -1 for none (no bit, a header defect, unknown id).
+ * K4LZ4_E_ARG before anything is enqueued: a set on another device than the context; NULL dictIds with a non-NULL set.  A NULL
+ * set (dictIds is then ignored) behaves exactly like the plain call: DictID frames report K4LZ4_FRAME_DICTIONARY.
+ * The _device forms take device pointers for everything but dictIds; k4lz4_decode_frames_dictset_device waits for `stream` once
+ * like k4lz4_decode_frames_device.  In-order work is dealt to two decoders: frames without an entry (no DictID, or an entry of no bytes)
+ * keep k4lz4_decode_chain_batch_device's kernels, frames with one go to a one-wave kernel bounded at sixteen waves per compute unit
+ * (measured on 4096 chained single-block frames: 1.18 ms against the plain kernels' 1.05 ms).  Only when a chained frame resolved to
+ * an entry does that kernel get windows in the context's scratch, grow-only: 64 KiB per frame of the call up to sixteen per compute
+ * unit (256 MiB on a 256-CU device).
+ * Writing such frames needs no call of its own: the header is FLG bit 0 and the DictID (LE32) after the content size -- at most 14
+ * descriptor bytes, which fit the 16-byte hdr rows of k4lz4_frame_assemble_device -- and the blocks are those of
+ * k4lz4_encode_dictset_batch with the allowCopy rule (independent frames) or of a chain encoder opened from the entry with
+ * k4lz4_chain_encoder_open_dictset (chained frames); frames.py composes them.
+ * Refused, exactly: by every call that takes no set, and by these with a NULL set, every DictID (K4LZ4_FRAME_DICTIONARY); by the
+ * incremental frame readers and writers (k4lz4_frame_read_batch, k4lz4_frame_read_fed_batch, k4lz4_frame_write_batch and their
+ * _device forms) the dictionary bit, with or without a set anywhere; by the encoders the writer is made of,
+ * K4LZ4_L10_OPT .. K4LZ4_L12_MAX with a dictionary and the 32-bit engine (K4LZ4_FLAG_X32, k4lz4_set_enforce32). */
+/* The allowCopy rule (LZ4EncoderBase.Encode(allowCopy: true)) behind an encoder that takes no flags, on device pointers: block i
+ * with outLen[i] >= srcLen[i] is stored raw (its srcLen[i] bytes copied to dst + dstOff[i], outLen[i] = -srcLen[i]; 0 when
+ * dstCap[i] is too small for that), outLen[i] <= 0 becomes 0 -- what K4LZ4_FLAG_ALLOW_COPY does behind k4lz4_encode_batch_device.
+ * The writer of dictionary frames on device-resident contents runs it behind k4lz4_encode_dictset_batch_device.  Asynchronous. */
+K4LZ4_API int k4lz4_allow_copy_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen,
+                                            uint8_t *dst, const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n,
+                                            void *stream);
+K4LZ4_API int k4lz4_frame_sizes_dictset_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen,
+                                               int64_t n, uint64_t *outSize, int32_t *outStatus, int32_t *outDictIdx,
+                                               const k4lz4_dict_set *set, const uint32_t *dictIds, void *stream);
+K4LZ4_API int k4lz4_decode_frames_dictset_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen,
+                                                 int64_t n, uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen,
+                                                 const k4lz4_dict_set *set, const uint32_t *dictIds, void *stream);
+K4LZ4_API int k4lz4_frame_sizes_dictset(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                                        uint64_t *outSize, int32_t *outStatus, int32_t *outDictIdx, const k4lz4_dict_set *set,
+                                        const uint32_t *dictIds);
+K4LZ4_API int k4lz4_decode_frames_dictset(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                                          uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen,
+                                          const k4lz4_dict_set *set, const uint32_t *dictIds);
+
 #ifdef __cplusplus
 }
 #endif

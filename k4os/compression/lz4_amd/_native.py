@@ -123,6 +123,15 @@ SYMBOLS = {
                                              C.c_void_p, C.c_void_p]),
     "k4lz4_frame_sizes": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "k4lz4_decode_frames": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_allow_copy_batch_device": (C.c_int, _BATCH + [C.c_void_p]),
+    "k4lz4_frame_sizes_dictset_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_decode_frames_dictset_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_frame_sizes_dictset": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "k4lz4_decode_frames_dictset": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_int64, _u8p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "k4lz4_encode_hc_chain_batch": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _u8p,
                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]),
     "k4lz4_encode_hc_chain_batch_device": (C.c_int, [C.c_void_p, _u8p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _u8p,

@@ -51,6 +51,7 @@
 #include "k4lz4_dict_encode_hc.hpp"
 #include "k4lz4_dict_set.hpp"
 #include "k4lz4_chain_open.hpp"
+#include "k4lz4_frame_dict.hpp"
 
 constexpr int MAX_PARTS = 8;      /* a big host-pointer call is staged, run and brought back in up to this many parts */
 
@@ -182,6 +183,12 @@ struct k4lz4_ctx {
     } dict_fast, dict_hc;
     /* k4lz4_decode_dictset_batch_device: the per-message dictionary words k4_dict_pick_kernel writes, and its copy of dstCap; grow-only */
     uint8_t *d_dpick = nullptr; size_t d_dpick_cap = 0;
+    /* frames with a DictID (k4lz4_frame_dict.hpp): the call's id table and the entry of every frame; the blocks' dictionary words
+     * and the in-order decoder's windows; both grow-only.  h_fdict: the ids on their way up, rewritten only after ev_fdict */
+    uint8_t *d_fdx = nullptr; size_t d_fdx_cap = 0;
+    uint8_t *d_fdb = nullptr; size_t d_fdb_cap = 0;
+    std::vector<uint32_t> h_fdict;
+    hipEvent_t ev_fdict = nullptr;
 };
 
 /* k4lz4_dict_set: one device allocation that nothing writes after create.  Carved at 64-byte steps in this order:
@@ -2213,6 +2220,9 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     }
     if (ctx->d_pk_meta) (void)hipFree(ctx->d_pk_meta);
     if (ctx->d_dpick) (void)hipFree(ctx->d_dpick);
+    if (ctx->d_fdx) (void)hipFree(ctx->d_fdx);
+    if (ctx->d_fdb) (void)hipFree(ctx->d_fdb);
+    if (ctx->ev_fdict) (void)hipEventDestroy(ctx->ev_fdict);
     delete ctx;
 }
 
@@ -2986,8 +2996,61 @@ int k4lz4_decode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_
 
 /* ---- frame reader (k4lz4_frame_read.hpp) ---------------------------------------------------------------- */
 
-int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
-                             uint64_t *outSize, int32_t *outStatus, void *stream)
+/* frames with a DictID against a set (k4lz4_frame_dict.hpp): the refusals, and the call's scratch -- the id table
+ * (a host array in both forms, through ctx->h_fdict) and the entry every frame resolves to */
+constexpr int64_t FRAME_DICT_WAVES_PER_CU = 16;      /* of the in-order decoder, a 64 KiB window each: one residency at four waves per SIMD */
+
+static int frame_dict_args(k4lz4_ctx *ctx, const k4lz4_dict_set *set, const uint32_t *dictIds, const char *what)
+{
+    if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
+    if (!set) return K4LZ4_OK;
+    if (set->device != ctx->device) return fail(ctx, K4LZ4_E_ARG, std::string(what) + ": the set lives on another device than the context");
+    if (!dictIds) return fail(ctx, K4LZ4_E_ARG, std::string(what) + ": NULL dictIds with a set");
+    return K4LZ4_OK;
+}
+
+static int frame_dict_ids(k4lz4_ctx *ctx, const k4lz4_dict_set *set, const uint32_t *dictIds, int64_t n, hipStream_t st, uint32_t **ids,
+                          int32_t **idx)
+{
+    const size_t nd = (size_t)set->nDict;
+    auto layout = [&](Carve &cv) { cv.take(*ids, nd); cv.take(*idx, (size_t)n); };
+    Carve m{nullptr};
+    layout(m);
+    int rc;
+    if ((rc = grow_scratch(ctx, &ctx->d_fdx, &ctx->d_fdx_cap, m.at + 64)) != K4LZ4_OK) return rc;
+    Carve dv{ctx->d_fdx};
+    layout(dv);
+    if (!nd) return K4LZ4_OK;
+    if (!ctx->ev_fdict) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fdict, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fdict));        /* the previous upload of the host copy is over */
+    try { ctx->h_fdict.assign(dictIds, dictIds + nd); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    K4_HIP(ctx, hipMemcpyAsync(*ids, ctx->h_fdict.data(), nd * 4, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipEventRecord(ctx->ev_fdict, st));
+    return K4LZ4_OK;
+}
+
+/* the walk of a call: the plain one, or with a set the one that resolves DictIDs (w.counters, w.outSize, w.outStatus as the call wants) */
+static int frame_walk(k4lz4_ctx *ctx, k4::FrameWalkArgs w, const k4lz4_dict_set *set, const uint32_t *dictIds, int32_t *outDictIdx,
+                      hipStream_t st, int32_t **idx)
+{
+    const dim3 grid((unsigned)((w.n + 255) / 256));
+    *idx = nullptr;
+    if (!set) {
+        hipLaunchKernelGGL(k4::k4_frame_walk_kernel, grid, dim3(256), 0, st, w);
+        if (outDictIdx) K4_HIP(ctx, hipMemsetAsync(outDictIdx, 0xff, (size_t)w.n * 4, st));      /* -1: none */
+        return K4LZ4_OK;
+    }
+    uint32_t *ids = nullptr;
+    int rc;
+    if ((rc = frame_dict_ids(ctx, set, dictIds, w.n, st, &ids, idx)) != K4LZ4_OK) return rc;
+    const k4::FrameWalkIds wd{ids, set->nDict, *idx, outDictIdx, w.counters ? w.counters + k4::FRC_DICT_CHAINED : nullptr};
+    hipLaunchKernelGGL(k4::k4_frame_walk_dict_kernel, grid, dim3(256), 0, st, w, wd);
+    return K4LZ4_OK;
+}
+
+static int frame_sizes_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                           uint64_t *outSize, int32_t *outStatus, int32_t *outDictIdx, const k4lz4_dict_set *set, const uint32_t *dictIds,
+                           void *stream)
 {
     if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
     if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
@@ -2998,16 +3061,34 @@ int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t 
     k4::FrameTab t;
     unsigned long long *cnt;
     int rc;
+    int32_t *idx;
     if ((rc = frame_scratch(ctx, n, &t, &cnt)) != K4LZ4_OK) return rc;
     k4::FrameWalkArgs w{src, frameOff, frameLen, n, t, nullptr, outSize, outStatus};
-    hipLaunchKernelGGL(k4::k4_frame_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w);
+    if ((rc = frame_walk(ctx, w, set, dictIds, outDictIdx, st, &idx)) != K4LZ4_OK) return rc;
     K4_HIP(ctx, hipGetLastError());
     mark_busy(ctx, st);
     return K4LZ4_OK;
 }
 
-int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
-                               uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, void *stream)
+int k4lz4_frame_sizes_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                             uint64_t *outSize, int32_t *outStatus, void *stream)
+{
+    return frame_sizes_run(ctx, src, frameOff, frameLen, n, outSize, outStatus, nullptr, nullptr, nullptr, stream);
+}
+
+int k4lz4_frame_sizes_dictset_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                                     uint64_t *outSize, int32_t *outStatus, int32_t *outDictIdx, const k4lz4_dict_set *set,
+                                     const uint32_t *dictIds, void *stream)
+{
+    const int rc = frame_dict_args(ctx, set, dictIds, "k4lz4_frame_sizes_dictset");
+    if (rc != K4LZ4_OK) return rc;
+    return frame_sizes_run(ctx, src, frameOff, frameLen, n, outSize, outStatus, outDictIdx, set, dictIds, stream);
+}
+
+/* set == nullptr: k4lz4_decode_frames_device as it always was; with a set, k4lz4_decode_frames_dictset_device */
+static int decode_frames_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                             uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, const k4lz4_dict_set *set,
+                             const uint32_t *dictIds, void *stream)
 {
     if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
     if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !dst || !dstOff || !dstCap || !outLen)))
@@ -3020,19 +3101,41 @@ int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_
     k4::BlockTab b;
     unsigned long long *cnt;
     int rc;
+    int32_t *idx;
     if ((rc = frame_scratch(ctx, n, &t, &cnt)) != K4LZ4_OK) return rc;
     const unsigned fgrid = (unsigned)((n + 255) / 256);
     K4_HIP(ctx, hipMemsetAsync(cnt, 0, 64, st));
     k4::FrameWalkArgs w{src, frameOff, frameLen, n, t, cnt, nullptr, nullptr};
-    hipLaunchKernelGGL(k4::k4_frame_walk_kernel, dim3(fgrid), dim3(256), 0, st, w);
+    if ((rc = frame_walk(ctx, w, set, dictIds, nullptr, st, &idx)) != K4LZ4_OK) return rc;
     hipLaunchKernelGGL(k4::k4_frame_scan_kernel, dim3(1), dim3(k4::FRAME_SCAN_THREADS), 0, st, t.nblk, t.first, (long long)n, cnt);
     K4_HIP(ctx, hipGetLastError());
     /* the one wait: the block count sizes the table (and says which passes have work) */
-    unsigned long long h[k4::FRC_COUNT];
+    unsigned long long h[k4::FRC_DICT_COUNT];       /* (the last word stays 0 without a set) */
     K4_HIP(ctx, hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
     K4_HIP(ctx, hipStreamSynchronize(st));
     const int64_t nb = (int64_t)h[k4::FRC_BLOCKS];
     if ((rc = block_scratch(ctx, nb, &b)) != K4LZ4_OK) return rc;
+    /* with a set: every block's dictionary words, the in-order work dealt to the two decoders, and the windows of the dictionary
+     * decoder's waves -- none when no chained frame resolved to an entry: only such frames use them */
+    k4::FrameDictRowsArgs ra{};
+    uint8_t *windows = nullptr;
+    uint32_t *n_plain = nullptr, *n_dict = nullptr;
+    const int64_t cwaves = (std::min<int64_t>(n, FRAME_DICT_WAVES_PER_CU * (int64_t)ctx->cu_count) + k4::DECODE_WAVES_PER_WG - 1) / k4::DECODE_WAVES_PER_WG *
+                           k4::DECODE_WAVES_PER_WG;                 /* whole workgroups: every wave of the grid has a window */
+    if (set) {
+        const size_t rows = (size_t)std::max<int64_t>(nb, 1);
+        auto layout = [&](Carve &cv) {
+            cv.take(ra.dictOff, rows); cv.take(ra.dictLen, rows); cv.take(ra.dictMode, rows);
+            cv.take(n_plain, (size_t)n); cv.take(n_dict, (size_t)n);
+            cv.take(windows, h[k4::FRC_DICT_CHAINED] ? (size_t)cwaves * k4::FRAME_DICT_WINDOW : 0);
+        };
+        Carve m{nullptr};
+        layout(m);
+        if ((rc = grow_scratch(ctx, &ctx->d_fdb, &ctx->d_fdb_cap, m.at + 64)) != K4LZ4_OK) return rc;
+        Carve dv{ctx->d_fdb};
+        layout(dv);
+        ra.owner = b.owner; ra.dictIdx = idx; ra.entryOff = set->dec_off; ra.entryLen = set->dec_len; ra.nb = nb;
+    }
     k4::FrameFillArgs fa{src, frameOff, dstOff, dstCap, n, t, b};
     hipLaunchKernelGGL(k4::k4_frame_fill_kernel, dim3(fgrid), dim3(256), 0, st, fa);
     K4_HIP(ctx, hipGetLastError());
@@ -3041,15 +3144,28 @@ int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_
         hipLaunchKernelGGL(k4::k4_frame_bsum_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, t, b, (long long)nb);
     }
     if (nb && h[k4::FRC_INDEP_BLOCKS]) {
-        if ((rc = launch(ctx, KIND_DECODE, src, b.off, b.srcLen, dst, b.dstOff, b.dstCap, b.outLen, nb, 0, 0, st)) != K4LZ4_OK) return rc;
+        if (set) hipLaunchKernelGGL(k4::k4_frame_dict_rows_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, ra);
+        const DictArgs dd{set ? set->buf : nullptr, ra.dictOff, ra.dictLen, ra.dictMode};
+        if ((rc = launch(ctx, KIND_DECODE, src, b.off, b.srcLen, dst, b.dstOff, b.dstCap, b.outLen, nb, 0, 0, st, set ? &dd : nullptr)) != K4LZ4_OK)
+            return rc;
     }
     if (nb) hipLaunchKernelGGL(k4::k4_frame_place_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, src, dst, t, b, (long long)nb);
     hipLaunchKernelGGL(k4::k4_frame_route_kernel, dim3(fgrid), dim3(256), 0, st, t, (long long)n);
     K4_HIP(ctx, hipGetLastError());
     /* chained frames, and independent ones whose blocks did not fill their places: in order, one stream per frame (frames
      * without such work have no blocks there) */
-    if ((rc = k4lz4_decode_chain_batch_device(ctx, src, b.off, b.len, t.first, t.nSerial, t.bsize, t.chained, dst, dstOff, dstCap,
-                                              t.serialOut, n, st)) != K4LZ4_OK)
+    if (set) {
+        /* frames without an entry (or with an empty one) keep the plain call's decoders; those with one follow, and write only their own results */
+        hipLaunchKernelGGL(k4::k4_frame_dict_split_kernel, dim3(fgrid), dim3(256), 0, st, t.nSerial, idx, set->dec_len, n_plain, n_dict, (long long)n);
+        if ((rc = k4lz4_decode_chain_batch_device(ctx, src, b.off, b.len, t.first, n_plain, t.bsize, t.chained, dst, dstOff, dstCap, t.serialOut, n,
+                                                  st)) != K4LZ4_OK)
+            return rc;
+        k4::ChainDictArgs ca{{src, b.off, b.len, t.first, n_dict, t.bsize, t.chained, dst, dstOff, dstCap, (long long *)t.serialOut, n, ctx->d_status},
+                             idx, set->buf, set->dec_off, set->dec_len, windows};
+        K4_LAUNCH_WAVES(k4::k4_decode_chain_dict_kernel, cwaves, k4::DECODE_WAVES_PER_WG, st, ca);
+        K4_HIP(ctx, hipGetLastError());
+    } else if ((rc = k4lz4_decode_chain_batch_device(ctx, src, b.off, b.len, t.first, t.nSerial, t.bsize, t.chained, dst, dstOff, dstCap,
+                                                     t.serialOut, n, st)) != K4LZ4_OK)
         return rc;
     hipLaunchKernelGGL(k4::k4_frame_settle_kernel, dim3(fgrid), dim3(256), 0, st, t, dstCap, (long long)n);
     if (h[k4::FRC_CSUM_FRAMES]) {
@@ -3060,6 +3176,21 @@ int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_
     K4_HIP(ctx, hipGetLastError());
     mark_busy(ctx, st);
     return K4LZ4_OK;
+}
+
+int k4lz4_decode_frames_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                               uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, void *stream)
+{
+    return decode_frames_run(ctx, src, frameOff, frameLen, n, dst, dstOff, dstCap, outLen, nullptr, nullptr, stream);
+}
+
+int k4lz4_decode_frames_dictset_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                                       uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen,
+                                       const k4lz4_dict_set *set, const uint32_t *dictIds, void *stream)
+{
+    const int rc = frame_dict_args(ctx, set, dictIds, "k4lz4_decode_frames_dictset");
+    if (rc != K4LZ4_OK) return rc;
+    return decode_frames_run(ctx, src, frameOff, frameLen, n, dst, dstOff, dstCap, outLen, set, dictIds, stream);
 }
 
 int k4lz4_frame_sizes(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
@@ -3073,6 +3204,57 @@ int k4lz4_decode_frames(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *fram
 {
     return host_streams(k4lz4_decode_frames_device, ctx, src, frameOff, frameLen, n, dst, dstOff, dstCap, outLen, /* zero */ true,
                         /* capped */ true);
+}
+
+/* the allowCopy rule behind an encoder that takes no flags (the dictionary encoders): k4_allow_copy_kernel over the call's blocks */
+int k4lz4_allow_copy_batch_device(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
+                                  const uint64_t *dstOff, const int32_t *dstCap, int32_t *outLen, int64_t n, void *stream)
+{
+    const int rc = check_batch_args(ctx, src, srcOff, srcLen, dst, dstOff, dstCap, outLen, n);
+    if (rc != K4LZ4_OK || n == 0) return rc;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    for (int64_t first = 0; first < n; first += (int64_t)1 << 24) {
+        const int64_t cnt = std::min<int64_t>((int64_t)1 << 24, n - first);
+        k4::BatchArgs a{};
+        a.src = src; a.srcOff = srcOff + first; a.srcLen = srcLen + first;
+        a.dst = dst; a.dstOff = dstOff + first; a.dstCap = dstCap + first; a.outLen = outLen + first; a.n = cnt;
+        hipLaunchKernelGGL(k4::k4_allow_copy_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, a);
+    }
+    K4_HIP(ctx, hipGetLastError());
+    return K4LZ4_OK;
+}
+
+int k4lz4_frame_sizes_dictset(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                              uint64_t *outSize, int32_t *outStatus, int32_t *outDictIdx, const k4lz4_dict_set *set, const uint32_t *dictIds)
+{
+    int rc = frame_dict_args(ctx, set, dictIds, "k4lz4_frame_sizes_dictset");
+    if (rc != K4LZ4_OK) return rc;
+    if (n < 0 || (n > 0 && (!src || !frameOff || !frameLen || !outSize || !outStatus))) return fail(ctx, K4LZ4_E_ARG, "bad argument");
+    if (n == 0) return K4LZ4_OK;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    HostStage s(ctx);
+    s.span(src, frameOff, n, [&](int64_t i) { return frameLen[i]; });
+    uint64_t *d_off, *d_len, *d_size;
+    int32_t *d_status, *d_idx;
+    s.meta(&d_off, n, s.in_off.data()); s.meta(&d_len, n, frameLen); s.meta(&d_size, n); s.meta(&d_status, n); s.meta(&d_idx, n);
+    if ((rc = s.upload()) != K4LZ4_OK ||
+        (rc = frame_sizes_run(ctx, ctx->d_src, d_off, d_len, n, d_size, d_status, d_idx, set, dictIds, s.st)) != K4LZ4_OK)
+        return rc;
+    return s.finish({{outSize, d_size, (size_t)n * 8}, {outStatus, d_status, (size_t)n * 4}, {outDictIdx, d_idx, outDictIdx ? (size_t)n * 4 : 0}});
+}
+
+int k4lz4_decode_frames_dictset(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
+                                uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen, const k4lz4_dict_set *set,
+                                const uint32_t *dictIds)
+{
+    const int rc = frame_dict_args(ctx, set, dictIds, "k4lz4_decode_frames_dictset");
+    if (rc != K4LZ4_OK) return rc;
+    auto device = [&](k4lz4_ctx *c, const uint8_t *s, const uint64_t *off, const uint64_t *len, int64_t count, uint8_t *d, const uint64_t *dOff,
+                      const uint64_t *dCap, int64_t *out, void *st) {
+        return decode_frames_run(c, s, off, len, count, d, dOff, dCap, out, set, dictIds, st);
+    };
+    return host_streams(device, ctx, src, frameOff, frameLen, n, dst, dstOff, dstCap, outLen, /* zero */ true, /* capped */ true);
 }
 
 /* ---- legacy formats: LZ4Wrapper, LZ4Stream (k4lz4_legacy.hpp) ------------------------------------------ */

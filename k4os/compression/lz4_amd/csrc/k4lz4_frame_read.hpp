@@ -109,11 +109,25 @@ struct FrameWalkArgs {
     int32_t *outStatus;
 };
 
-__global__ __launch_bounds__(256) void k4_frame_walk_kernel(FrameWalkArgs a)
+/* the id table of a call with a dictionary set (k4lz4_frame_dict.hpp): entry e answers to DictID ids[e] */
+struct FrameWalkIds {
+    const uint32_t *ids;
+    int nDict;
+    int32_t *dictIdx;                /* per frame, out: the entry, -1: none */
+    int32_t *outDictIdx;             /* the caller's copy, or nullptr */
+    unsigned long long *chained;     /* counter: chained frames that resolved to an entry, or nullptr */
+};
+
+/* the walk of one frame per thread.  WITH_IDS: a DictID is looked up in the call's id table once the header checksum has passed
+ * (it covers those bytes) -- the first entry whose id equals it, FR_DICT when there is none; without, every DictID is FR_DICT */
+template <bool WITH_IDS>
+__device__ __forceinline__ void frame_walk_body(const FrameWalkArgs &a, const FrameWalkIds &d)
 {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool live = f < a.n;
     int st = 0;
+    int32_t entry = -1;
+    uint64_t id_at = 0;
     uint32_t flg = 0, bd = 0, hdr_end = 0, nb = 0, csum = 0, indep = 0;
     uint64_t clen = 0, bound = 0;
     int bs = 64 << 10;
@@ -133,12 +147,19 @@ __global__ __launch_bounds__(256) void k4_frame_walk_kernel(FrameWalkArgs a)
             }
             if (flg & FLG_DICT) {
                 if (end - pos < 4) { st = FR_EOF; break; }
-                pos += 4;
+                id_at = pos; pos += 4;
             }
             if (end - pos < 1) { st = FR_EOF; break; }
             if (((xxh32_short(p + 4, (uint32_t)(pos - 4)) >> 8) & 0xffu) != p[pos]) { st = FR_HEADER; break; }
             pos += 1;
-            if (flg & FLG_DICT) { st = FR_DICT; break; }
+            if (flg & FLG_DICT) {
+                if (WITH_IDS) {
+                    const uint32_t id = ld32u(p + id_at);
+                    for (int e = 0; e < d.nDict; e++)
+                        if (d.ids[e] == id) { entry = e; break; }
+                }
+                if (entry < 0) { st = FR_DICT; break; }
+            }
             hdr_end = (uint32_t)pos;
             bs = frame_block_size(bd);
             const uint64_t trailer = (flg & FLG_BLOCK_SUM) ? 4 : 0;
@@ -173,6 +194,11 @@ __global__ __launch_bounds__(256) void k4_frame_walk_kernel(FrameWalkArgs a)
         a.t.bsize[f] = bs;
         a.t.csum[f] = csum;
         a.t.hdrEnd[f] = hdr_end;
+        if (WITH_IDS) {
+            if (!hdr_end) entry = -1;
+            d.dictIdx[f] = entry;
+            if (d.outDictIdx) d.outDictIdx[f] = entry;
+        }
         if (a.outSize) a.outSize[f] = bound;
         if (a.outStatus) a.outStatus[f] = st;
     }
@@ -186,6 +212,15 @@ __global__ __launch_bounds__(256) void k4_frame_walk_kernel(FrameWalkArgs a)
             if (cs) atomicAdd(a.counters + FRC_CSUM_FRAMES, cs);
         }
     }
+    if (WITH_IDS && d.chained) {
+        const unsigned long long dc = wave_sum64(hdr_end && entry >= 0 && !(flg & FLG_INDEPENDENT) ? 1ull : 0ull);
+        if (dc && lane_id() == 0) atomicAdd(d.chained, dc);
+    }
+}
+
+__global__ __launch_bounds__(256) void k4_frame_walk_kernel(FrameWalkArgs a)
+{
+    frame_walk_body<false>(a, FrameWalkIds{});
 }
 
 constexpr int FRAME_SCAN_THREADS = 256;

@@ -118,16 +118,20 @@ def max_block_size(code: int) -> int:                     # LZ4FrameReader.cs:56
     return {7: M4, 6: M1, 5: K256, 4: K64}.get(code, K64)
 
 
-def frame_header(d: LZ4Descriptor) -> bytes:
-    """FLG, BD [, content size] -- the bytes covered by the header checksum (LZ4FrameWriter.cs:65-100)"""
-    if d.Dictionary is not None:
+def frame_header(d: LZ4Descriptor, dictionary: bool = False) -> bytes:
+    """FLG, BD [, content size] [, DictID] -- the bytes covered by the header checksum (LZ4FrameWriter.cs:65-100).  A descriptor's
+    Dictionary is written (FLG bit 0, the id after the content size) only for the writer with a DictionarySet (dictionary=True,
+    DESIGN.md 4.24); otherwise it is refused as the reference refuses it."""
+    if d.Dictionary is not None and not dictionary:
         raise NotImplementedException("Predefined dictionaries feature is not implemented")
     flg = (1 << 6) | ((0 if d.Chaining else 1) << 5) | ((1 if d.BlockChecksum else 0) << 4) | \
-          ((1 if d.ContentLength is not None else 0) << 3) | ((1 if d.ContentChecksum else 0) << 2)
+          ((1 if d.ContentLength is not None else 0) << 3) | ((1 if d.ContentChecksum else 0) << 2) | (1 if d.Dictionary is not None else 0)
     bd = max_block_size_code(d.BlockSize) << 4
     out = bytes([flg & 0xFF, bd & 0xFF])
     if d.ContentLength is not None:
         out += struct.pack("<Q", d.ContentLength)
+    if d.Dictionary is not None:
+        out += struct.pack("<I", d.Dictionary)
     return out
 
 
@@ -194,9 +198,9 @@ def parse_frame(frame, start: int = 0) -> FrameInfo:
 
 
 def assemble_frame(d: LZ4Descriptor, header_hash: int, payloads: Sequence[bytes], raw: Sequence[bool],
-                   block_hashes: Optional[Sequence[int]], content_hash: Optional[int]) -> bytes:
-    """lays the pieces out as the writer does (LZ4FrameWriter.async.cs:15-27,:75-90)"""
-    parts = [struct.pack("<I", MAGIC), frame_header(d), bytes([(header_hash >> 8) & 0xFF])]
+                   block_hashes: Optional[Sequence[int]], content_hash: Optional[int], dictionary: bool = False) -> bytes:
+    """lays the pieces out as the writer does (LZ4FrameWriter.async.cs:15-27,:75-90); dictionary: as frame_header"""
+    parts = [struct.pack("<I", MAGIC), frame_header(d, dictionary), bytes([(header_hash >> 8) & 0xFF])]
     for i, p in enumerate(payloads):
         parts.append(struct.pack("<I", len(p) | (0x80000000 if raw[i] else 0)))     # BlockLengthCode
         parts.append(p)
@@ -222,9 +226,10 @@ def xxh32_many(buffers: Sequence, ctx: Optional[_native.Context] = None) -> np.n
     return out
 
 
-def _assemble_frames(s: "LZ4EncoderSettings", contents, out, arena, aoff, owner, ctx) -> List[bytes]:
+def _assemble_frames(s: "LZ4EncoderSettings", contents, out, arena, aoff, owner, ctx, dict_ids=None) -> List[bytes]:
     """the frames of a batch from its encoded blocks (outLen per block, negative: stored raw; arena slots; owning frame per block):
-    header, block records with their checksums, EndMark, content checksum -- every XXH32 in one launch"""
+    header, block records with their checksums, EndMark, content checksum -- every XXH32 in one launch.  dict_ids: per frame the
+    DictID its header names (the writer with a DictionarySet)"""
     bs = int(s.BlockSize)
     payloads, raw = [], []
     for n, o in zip(out, aoff if len(out) else []):
@@ -232,9 +237,11 @@ def _assemble_frames(s: "LZ4EncoderSettings", contents, out, arena, aoff, owner,
             raise RuntimeError("Failed to encode chunk. Target buffer too small.")       # LZ4EncoderBase.cs:75-77
         payloads.append(arena[int(o):int(o) + abs(int(n))])
         raw.append(n < 0)
-    descs = [LZ4Descriptor(s.ContentLength, s.ContentChecksum, bool(s.ChainBlocks), s.BlockChecksum, None, bs) for _ in contents]
+    with_id = dict_ids is not None
+    descs = [LZ4Descriptor(s.ContentLength, s.ContentChecksum, bool(s.ChainBlocks), s.BlockChecksum, int(dict_ids[f]) if with_id else None, bs)
+             for f, _ in enumerate(contents)]
     # every XXH32 of the batch in one launch: headers, then block payloads, then contents
-    to_hash = [np.frombuffer(frame_header(d), np.uint8) for d in descs]
+    to_hash = [np.frombuffer(frame_header(d, with_id), np.uint8) for d in descs]
     if s.BlockChecksum:
         to_hash += payloads
     if s.ContentChecksum:
@@ -251,7 +258,7 @@ def _assemble_frames(s: "LZ4EncoderSettings", contents, out, arena, aoff, owner,
             k += 1
         frames.append(assemble_frame(d, int(hashes[f]), [payloads[i].tobytes() for i in range(k0, k)], raw[k0:k],
                                      None if bh is None else [int(x) for x in bh[k0:k]],
-                                     None if ch is None else int(ch[f])))
+                                     None if ch is None else int(ch[f]), with_id))
     return frames
 
 
@@ -260,15 +267,21 @@ class LZ4Frame:
 
     # ---- encode -----------------------------------------------------------------------------------
     @staticmethod
-    def Encode(source, settings: Optional[LZ4EncoderSettings] = None, level: Optional[LZ4Level] = None) -> bytes:
-        return LZ4Frame.EncodeBatch([source], settings, level)[0]
+    def Encode(source, settings: Optional[LZ4EncoderSettings] = None, level: Optional[LZ4Level] = None, dictionary=None,
+               dict_index: int = -1) -> bytes:
+        return LZ4Frame.EncodeBatch([source], settings, level, dictionary=dictionary,
+                                    dict_index=None if dictionary is None else [dict_index])[0]
 
     @staticmethod
     def EncodeBatch(sources: Sequence, settings: Optional[LZ4EncoderSettings] = None, level: Optional[LZ4Level] = None,
-                    ctx: Optional[_native.Context] = None) -> List[bytes]:
+                    ctx: Optional[_native.Context] = None, dictionary=None, dict_index=None) -> List[bytes]:
+        """dictionary=(DictionarySet, ids) with dict_index[f] (an entry of the set, -1: a plain frame): frame f names the entry's id
+        as its DictID and its blocks are encoded against the entry (_encode_frames_dictset)"""
         s = settings or LZ4EncoderSettings()
         if level is not None:
             s = LZ4EncoderSettings(**{**s.__dict__, "CompressionLevel": LZ4Level(level)})
+        if dictionary is not None:
+            return _encode_frames_dictset(sources, s, ctx, dictionary, dict_index)
         if s.ChainBlocks and int(s.CompressionLevel) < int(LZ4Level.L03_HC):
             raise NotImplementedException(FAST_CHAIN_REFUSED)
         max_block_size_code(s.BlockSize)
@@ -298,12 +311,16 @@ class LZ4Frame:
 
     # ---- decode -----------------------------------------------------------------------------------
     @staticmethod
-    def Decode(source, settings=None) -> bytes:
-        return LZ4Frame.DecodeBatch([source])[0]
+    def Decode(source, settings=None, dictionary=None) -> bytes:
+        return LZ4Frame.DecodeBatch([source], dictionary=dictionary)[0]
 
     @staticmethod
-    def DecodeBatch(sources: Sequence, ctx: Optional[_native.Context] = None) -> List[bytes]:
-        """every element holds one frame (bytes after it are ignored, as a reader that stops at EndMark does)"""
+    def DecodeBatch(sources: Sequence, ctx: Optional[_native.Context] = None, dictionary=None) -> List[bytes]:
+        """every element holds one frame (bytes after it are ignored, as a reader that stops at EndMark does).
+        dictionary=(DictionarySet, ids): frames with a DictID are decoded against the first entry whose id equals it
+        (k4lz4_decode_frames_dictset); without it such a frame raises NotImplementedException as before."""
+        if dictionary is not None:
+            return _decode_frames_dictset_host(sources, ctx, dictionary)
         ctx = ctx or _native.default_context()
         bufs = [_ro_view(x, "source") for x in sources]
         infos = [parse_frame(b) for b in bufs]
@@ -420,24 +437,42 @@ class LZ4Frame:
         return res
 
 
-def encode_frames_device(dc, data, off: np.ndarray, length: np.ndarray, settings: Optional[LZ4EncoderSettings] = None):
+def encode_frames_device(dc, data, off: np.ndarray, length: np.ndarray, settings: Optional[LZ4EncoderSettings] = None, dictionary=None,
+                         dict_index=None):
     """LZ4Frame.EncodeBatch on HBM-resident contents, nothing leaves the device: `data` is a uint8 torch tensor holding
     the contents, content f = data[off[f] : off[f]+length[f]] (off / length: host arrays -- the block split is host index
     work).  Returns (frames, frame_off, frame_len): frame f = frames[frame_off[f] : frame_off[f] + frame_len[f]], with
     frame_off a host array of (worst-case spaced) positions and frame_len a device tensor.  Asynchronous on the current
-    torch stream; `dc` is a device.DeviceCodec."""
+    torch stream; `dc` is a device.DeviceCodec.
+    dictionary=(DictionarySet, ids) with dict_index[f] (a host array; an entry of the set, -1: a plain frame): frame f names the
+    entry's id as its DictID; its independent blocks are k4lz4_encode_dictset_batch_device's with the allowCopy rule behind them
+    (k4lz4_allow_copy_batch_device), its chained blocks those of a ChainEncoderDevice opened from the entry, one record (Topup and a
+    forced Encode) per block.  Levels 10 - 12 and Enforce32 are refused when a frame names an entry."""
     import ctypes as C
     import torch
     from ._native import FLAG_ALLOW_COPY
-    from .device import DeviceBatch, _dp
+    from .device import DeviceBatch, ChainEncoderDevice, _dp
     s = settings or LZ4EncoderSettings()
-    if s.ChainBlocks and int(s.CompressionLevel) < int(LZ4Level.L03_HC):
-        raise NotImplementedException(FAST_CHAIN_REFUSED)
-    bs = int(s.BlockSize)
-    max_block_size_code(bs)
     off = np.asarray(off, dtype=np.int64)
     length = np.asarray(length, dtype=np.int64)
     nf = len(off)
+    entry = np.full(nf, -1, np.int64)
+    ids = None
+    if dictionary is not None:
+        dset, ids = _dictionary_ids(dictionary)
+        entry = np.asarray(dict_index if dict_index is not None else [], np.int64)
+        if entry.shape != (nf,):
+            raise ValueError("dict_index must have one entry per content")
+        if nf and (int(entry.min()) < -1 or int(entry.max()) >= dset.n):
+            raise ValueError("a dict_index outside the DictionarySet")
+    named = entry >= 0
+    if named.any() and (int(s.CompressionLevel) >= int(LZ4Level.L10_OPT) or LZ4Codec.Enforce32):
+        raise NotImplementedException(DICT_WRITER_REFUSED)
+    fast_chain = s.ChainBlocks and int(s.CompressionLevel) < int(LZ4Level.L03_HC)
+    if fast_chain and (dictionary is None or not named.all()):
+        raise NotImplementedException(FAST_CHAIN_REFUSED)
+    bs = int(s.BlockSize)
+    max_block_size_code(bs)
     eb = _round_block_size(bs) if s.ChainBlocks else bs          # (the chained encoder's blocks: its ring buffer's, whole KiB)
     nblk = (length + eb - 1) // eb
     first = np.concatenate(([0], np.cumsum(nblk)))[:-1]
@@ -445,48 +480,79 @@ def encode_frames_device(dc, data, off: np.ndarray, length: np.ndarray, settings
     owner = np.repeat(np.arange(nf), nblk)
     bound = LZ4Codec.MaximumOutputSize(eb)
     dev = dc.device
+    k_in = np.arange(nb) - first[owner]
+    boff = off[owner] + k_in * eb
+    blen = np.minimum(eb, length[owner] - k_in * eb).astype(np.int32)
+    stream = C.c_void_p(dc._stream())
+    out_len = torch.zeros(nb, dtype=torch.int32, device=dev)
     if not s.ChainBlocks:
         arena = DeviceBatch.empty_slots(np.full(nb, bound, np.int64), dev)
+        slot_off = arena.off
+        for which in (np.flatnonzero(~named[owner]), np.flatnonzero(named[owner])):
+            if not which.size:
+                continue
+            sel = torch.from_numpy(which).to(dev)
+            src = DeviceBatch(data, torch.from_numpy(boff[which]).to(dev), torch.from_numpy(blen[which]).to(dev))
+            dst = DeviceBatch(arena.data, arena.off[sel], arena.length[sel])
+            if named[owner[which[0]]]:
+                got = dc.encode_dictset(src, dst, torch.from_numpy(entry[owner[which]].astype(np.int32)).to(dev), dset, level=s.CompressionLevel)
+                dc.ctx.check(dc.lib.k4lz4_allow_copy_batch_device(dc.ctx.handle, _dp(src.data), _dp(src.off), _dp(src.length), _dp(dst.data),
+                                                                  _dp(dst.off), _dp(dst.length), _dp(got), src.n, stream))
+            else:
+                got = dc.encode(src, dst, level=s.CompressionLevel, flags=FLAG_ALLOW_COPY)
+            out_len[sel] = got
     else:
-        # every frame one stream whose blocks' slots lie behind each other, `bound` bytes apart (k4lz4_encode_hc_chain_batch_device)
+        # every frame one stream whose blocks' slots lie behind each other
         frame_slots = np.zeros(nf, np.int64)
         if nf > 1:
             frame_slots[1:] = np.cumsum((nblk * bound + 15) // 16 * 16)[:-1]
-        slot_off = frame_slots[owner] + (np.arange(nb) - first[owner]) * bound
-        arena = DeviceBatch(torch.empty(int(((nblk * bound + 15) // 16 * 16).sum()) + 64, dtype=torch.uint8, device=dev),
-                            torch.from_numpy(slot_off).to(dev), torch.full((nb,), bound, dtype=torch.int32, device=dev))
-    if not nb:
-        out_len = torch.zeros(0, dtype=torch.int32, device=dev)
-    elif s.ChainBlocks:
-        out_len = torch.empty(nb, dtype=torch.int32, device=dev)
-        c_off, c_len, c_dst = off.astype(np.uint64), np.ascontiguousarray(length), frame_slots.astype(np.uint64)
-        bsz = np.full(nf, bs, np.int32)
-        ext = np.full(nf, _extra_blocks(bs, int(s.ExtraMemory)), np.int32)
-        rc = dc.lib.k4lz4_encode_hc_chain_batch_device(dc.ctx.handle, _dp(data), c_off.ctypes.data, c_len.ctypes.data, bsz.ctypes.data,
-                                                       ext.ctypes.data, None, nf, _dp(arena.data), c_dst.ctypes.data, _dp(out_len), nb,
-                                                       int(s.CompressionLevel), FLAG_ALLOW_COPY, C.c_void_p(dc._stream()))
-        dc.ctx.check(rc)
-    else:
-        k_in = np.arange(nb) - first[owner]
-        boff = off[owner] + k_in * bs
-        blen = np.minimum(bs, length[owner] - k_in * bs).astype(np.int32)
-        src = DeviceBatch(data, torch.from_numpy(boff).to(dev), torch.from_numpy(blen).to(dev))
-        out_len = dc.encode(src, arena, level=s.CompressionLevel, flags=FLAG_ALLOW_COPY)
+        arena = DeviceBatch(torch.empty(int(((nblk * bound + 15) // 16 * 16).sum()) + 64, dtype=torch.uint8, device=dev), None, None)
+        slot_off = torch.from_numpy(frame_slots[owner] + k_in * bound).to(dev)          # the whole-stream call: `bound` bytes apart
+        plain, pb = np.flatnonzero(~named), np.flatnonzero(~named[owner])
+        if pb.size:
+            got = torch.empty(pb.size, dtype=torch.int32, device=dev)
+            c_off, c_len, c_dst = off[plain].astype(np.uint64), np.ascontiguousarray(length[plain]), frame_slots[plain].astype(np.uint64)
+            bsz = np.full(plain.size, bs, np.int32)
+            ext = np.full(plain.size, _extra_blocks(bs, int(s.ExtraMemory)), np.int32)
+            dc.ctx.check(dc.lib.k4lz4_encode_hc_chain_batch_device(dc.ctx.handle, _dp(data), c_off.ctypes.data, c_len.ctypes.data, bsz.ctypes.data,
+                                                                   ext.ctypes.data, None, plain.size, _dp(arena.data), c_dst.ctypes.data, _dp(got),
+                                                                   pb.size, int(s.CompressionLevel), FLAG_ALLOW_COPY, stream))
+            out_len[torch.from_numpy(pb).to(dev)] = got
+        mine = np.flatnonzero(named & (nblk > 0))
+        if mine.size:
+            # open encoders primed from the entries; one record per block, each a Topup and a forced Encode: the blocks lie packed
+            from .encoders import CENC_FORCE, CENC_ALLOW_COPY
+            enc = ChainEncoderDevice([(True, s.CompressionLevel, bs, _extra_blocks(bs, int(s.ExtraMemory)))] * mine.size, dc)
+            enc.open(entry[mine].astype(np.int32), dset)
+            mb = np.flatnonzero(named[owner])
+            sel = torch.from_numpy(mb).to(dev)
+            rec_first = np.concatenate(([0], np.cumsum(nblk[mine])))[:-1]
+            got = torch.zeros(mb.size, dtype=torch.int32, device=dev)
+            loaded = torch.zeros(mb.size, dtype=torch.int32, device=dev)
+            total = torch.zeros(mine.size, dtype=torch.int64, device=dev)
+            enc.run(data, boff[mb], blen[mb], np.full(mb.size, CENC_FORCE | CENC_ALLOW_COPY, np.uint32), rec_first, nblk[mine], arena.data,
+                    frame_slots[mine], nblk[mine] * bound, loaded, got, total)
+            out_len[sel] = got
+            size = got.abs().to(torch.int64)
+            excl = torch.cumsum(size, 0) - size
+            start = excl[torch.from_numpy(rec_first).to(dev)]
+            rank = torch.from_numpy(np.repeat(np.arange(mine.size), nblk[mine])).to(dev)
+            slot_off[sel] = torch.from_numpy(frame_slots[owner[mb]]).to(dev) + excl - start[rank]
     stored = out_len.abs().to(torch.int64)
-    # header bytes (host: two to ten bytes per frame) and every XXH32 of the batch
+    # header bytes (host: two to fourteen bytes per frame) and every XXH32 of the batch
     hdrs = [frame_header(LZ4Descriptor(int(length[f]) if s.ContentLength is not None else None, s.ContentChecksum, bool(s.ChainBlocks),
-                                       s.BlockChecksum, None, bs)) for f in range(nf)]
-    hl = len(hdrs[0]) if nf else 2
+                                       s.BlockChecksum, int(ids[entry[f]]) if named[f] else None, bs), bool(named[f])) for f in range(nf)]
+    hl = np.array([len(h) for h in hdrs] if nf else [2], np.int64)
     hdr_h = np.zeros((max(nf, 1), 16), np.uint8)
     for f, h in enumerate(hdrs):
-        hdr_h[f, :hl] = np.frombuffer(h, np.uint8)
+        hdr_h[f, :len(h)] = np.frombuffer(h, np.uint8)
     hdr_d = torch.from_numpy(hdr_h.reshape(-1)).to(dev)
-    hdr_len = torch.full((max(nf, 1),), hl, dtype=torch.int64, device=dev)
+    hdr_len = torch.from_numpy(hl).to(dev)
     hdr_sum = dc.xxh32(hdr_d, torch.arange(max(nf, 1), dtype=torch.int64, device=dev) * 16, hdr_len)
-    blk_sum = dc.xxh32(arena.data, arena.off, stored) if (s.BlockChecksum and nb) else None
+    blk_sum = dc.xxh32(arena.data, slot_off, stored) if (s.BlockChecksum and nb) else None
     con_sum = dc.xxh32(data, torch.from_numpy(off).to(dev), torch.from_numpy(length).to(dev)) if (s.ContentChecksum and nf) else None
     # layout: frames sit at worst-case spaced bases (known without a sync), records are packed inside each frame
-    head = 4 + hl + 1
+    head = 4 + hl[:nf] + 1
     per_block = 4 + bound + (4 if s.BlockChecksum else 0)
     frame_cap = head + nblk * per_block + 8
     frame_off = np.concatenate(([0], np.cumsum(frame_cap)))[:-1].astype(np.int64)
@@ -494,19 +560,19 @@ def encode_frames_device(dc, data, off: np.ndarray, length: np.ndarray, settings
     excl = torch.cumsum(rec_size, 0) - rec_size if nb else rec_size
     owner_d = torch.from_numpy(owner).to(dev)
     first_d = torch.from_numpy(np.minimum(first, max(nb - 1, 0))).to(dev)
-    base_d = torch.from_numpy(frame_off).to(dev)
+    base_d = torch.from_numpy(frame_off + head).to(dev)          # behind the header
     start_of_frame = excl[first_d] if nb else torch.zeros(nf, dtype=torch.int64, device=dev)
-    rec_off = (base_d[owner_d] + head + excl - start_of_frame[owner_d]) if nb else torch.zeros(0, dtype=torch.int64, device=dev)
+    rec_off = (base_d[owner_d] + excl - start_of_frame[owner_d]) if nb else torch.zeros(0, dtype=torch.int64, device=dev)
     total = torch.zeros(nf, dtype=torch.int64, device=dev)
     if nb:
         total.index_add_(0, owner_d, rec_size)
-    tail_off = base_d + head + total
+    tail_off = base_d + total
     frames = torch.empty(int(frame_cap.sum()) + 64, dtype=torch.uint8, device=dev)
     frame_len = torch.zeros(max(nf, 1), dtype=torch.int64, device=dev)
     hdr_len32 = hdr_len.to(torch.int32)
-    rc = dc.lib.k4lz4_frame_assemble_device(dc.ctx.handle, _dp(arena.data), _dp(arena.off), _dp(out_len), _dp(blk_sum), _dp(rec_off), nb,
-                                            _dp(hdr_d), _dp(hdr_len32), _dp(hdr_sum), _dp(base_d), _dp(tail_off), _dp(con_sum), _dp(frames),
-                                            _dp(frame_len), nf, C.c_void_p(dc._stream()))
+    rc = dc.lib.k4lz4_frame_assemble_device(dc.ctx.handle, _dp(arena.data), _dp(slot_off), _dp(out_len), _dp(blk_sum), _dp(rec_off), nb,
+                                            _dp(hdr_d), _dp(hdr_len32), _dp(hdr_sum), _dp(torch.from_numpy(frame_off).to(dev)), _dp(tail_off),
+                                            _dp(con_sum), _dp(frames), _dp(frame_len), nf, stream)
     dc.ctx.check(rc)
     return frames, frame_off, frame_len[:nf]
 
@@ -541,11 +607,120 @@ def _dev_i64(x, dev):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.int64))).to(dev)
 
 
-def frame_sizes_device(dc, frames, off, length):
+def _dictionary_ids(dictionary):
+    """dictionary=(DictionarySet, ids) -> (the set, its ids as a uint32 host array: entry e answers to DictID ids[e])"""
+    dset, ids = dictionary
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32))
+    if ids.ndim != 1 or ids.size != dset.n:
+        raise ValueError("dictionary=(DictionarySet, ids): one id per entry of the set")
+    return dset, ids
+
+
+DICT_WRITER_REFUSED = ("frames with a predefined dictionary are written at L00_FAST .. L09_HC by the 64-bit engine: the dictionary "
+                       "encoders have no witness at L10_OPT and above, nor under Enforce32")
+
+
+def _encode_frames_dictset(sources: Sequence, s: "LZ4EncoderSettings", ctx, dictionary, dict_index) -> List[bytes]:
+    """LZ4Frame.EncodeBatch(dictionary=..., dict_index=...).  Frame f with dict_index[f] = e >= 0 carries DictID ids[e]; its blocks are
+    independent frames: the blocks k4lz4_encode_dictset_batch writes for entry e (each block one message), with the allowCopy rule
+                        (a block that does not shrink is stored raw);
+    chained frames:     the blocks of an encoder opened from entry e (k4lz4_chain_encoder_open_dictset: LZ4FastChainEncoder below
+                        L03_HC, LZ4HighChainEncoder from there), fed the whole content and flushed, block size and ExtraMemory as
+                        the chained writers have them.
+    Frames with dict_index -1 are the plain writers' (LZ4Frame.EncodeBatch, encode_fast_chain_frames)."""
+    from .encoders import LZ4EncoderBatch
+    dset, ids = _dictionary_ids(dictionary)
+    ctx = ctx or dset.ctx
+    contents = [_ro_view(x, "source") for x in sources]
+    idx = np.asarray(dict_index if dict_index is not None else [], np.int64)
+    if idx.shape != (len(contents),):
+        raise ValueError("dict_index must have one entry per source")
+    if idx.size and (int(idx.min()) < -1 or int(idx.max()) >= dset.n):
+        raise ValueError("a dict_index outside the DictionarySet")
+    if (idx >= 0).any() and (int(s.CompressionLevel) >= int(LZ4Level.L10_OPT) or LZ4Codec.Enforce32):
+        raise NotImplementedException(DICT_WRITER_REFUSED)          # (a batch of plain frames is the plain writers' at any level)
+    bs = int(s.BlockSize)
+    max_block_size_code(bs)
+    for c in contents:
+        if s.ContentLength is not None and s.ContentLength != c.size:
+            raise ValueError("ContentLength does not match the source length")
+    res: List[Optional[bytes]] = [None] * len(contents)
+    plain = [f for f in range(len(contents)) if idx[f] < 0]
+    if plain:
+        fast_chain = s.ChainBlocks and int(s.CompressionLevel) < int(LZ4Level.L03_HC)
+        made = encode_fast_chain_frames([contents[f] for f in plain], s, ctx) if fast_chain else LZ4Frame.EncodeBatch([contents[f] for f in plain], s, ctx=ctx)
+        for f, fr in zip(plain, made):
+            res[f] = fr
+    named = [f for f in range(len(contents)) if idx[f] >= 0]
+    if named:
+        mine = [contents[f] for f in named]
+        payloads, out, owner = [], [], []
+        if s.ChainBlocks:
+            enc = LZ4EncoderBatch([(True, s.CompressionLevel, bs, _extra_blocks(bs, int(s.ExtraMemory)))] * len(named), ctx)
+            enc.open(idx[named].astype(np.int32), dset)
+            written = enc.Write(mine, force=False, allowCopy=True)
+            for k, last in enumerate(enc.Flush(allowCopy=True)):
+                for n, b in written[k] + last:
+                    payloads.append(np.frombuffer(b, np.uint8))
+                    out.append(int(n))
+                    owner.append(k)
+        else:
+            blocks = [c[p:p + bs] for c in mine for p in range(0, c.size, bs)]
+            owner = [k for k, c in enumerate(mine) for _ in range(0, c.size, bs)]
+            if blocks:
+                src, soff, slen = pack_blocks(blocks)
+                caps = np.array([LZ4Codec.MaximumOutputSize(b.size) for b in blocks], np.int32)
+                dst, doff = make_arena(caps)
+                got = LZ4Codec.EncodeDictBatchPacked(src, soff, slen, dst, doff, caps, idx[named][owner].astype(np.int32), dset,
+                                                     level=s.CompressionLevel, ctx=ctx)
+                for b, n, o in zip(blocks, got, doff):                   # LZ4EncoderBase.Encode(allowCopy: true), LZ4EncoderBase.cs:66-88
+                    if n <= 0:
+                        raise RuntimeError("Failed to encode chunk. Target buffer too small.")
+                    raw = int(n) >= b.size
+                    payloads.append(b if raw else dst[int(o):int(o) + int(n)])
+                    out.append(-b.size if raw else int(n))
+        arena, aoff = (np.concatenate(payloads), np.concatenate(([0], np.cumsum([p.size for p in payloads])))[:-1]) if payloads else (None, [])
+        frames = _assemble_frames(s, mine, np.array(out, np.int64), arena, aoff, owner, ctx, dict_ids=[int(ids[idx[f]]) for f in named])
+        for f, fr in zip(named, frames):
+            res[f] = fr
+    return res
+
+
+def _decode_frames_dictset_host(sources: Sequence, ctx, dictionary) -> List[bytes]:
+    """LZ4Frame.DecodeBatch(dictionary=...): k4lz4_frame_sizes_dictset sizes the targets, k4lz4_decode_frames_dictset reads the
+    frames; the lowest-index failing frame raises what LZ4FrameReader raises"""
+    dset, ids = _dictionary_ids(dictionary)
+    ctx = ctx or dset.ctx
+    bufs = [_ro_view(x, "source") for x in sources]
+    n = len(bufs)
+    if not n:
+        return []
+    src, foff, flen = pack_blocks(bufs)
+    flen = flen.astype(np.uint64)
+    size, status, idx = np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    ip = ids.ctypes.data if ids.size else None
+    ctx.check(ctx.lib.k4lz4_frame_sizes_dictset(ctx.handle, src.ctypes.data_as(_native._u8p), foff.ctypes.data, flen.ctypes.data, n,
+                                                size.ctypes.data, status.ctypes.data, idx.ctypes.data, dset.handle, ip))
+    doff = np.zeros(n, np.uint64)
+    doff[1:] = np.cumsum(size[:-1])
+    dst = np.zeros(max(int(size.sum()), 1), np.uint8)
+    out = np.zeros(n, np.int64)
+    ctx.check(ctx.lib.k4lz4_decode_frames_dictset(ctx.handle, src.ctypes.data_as(_native._u8p), foff.ctypes.data, flen.ctypes.data, n,
+                                                  dst.ctypes.data_as(_native._u8p), doff.ctypes.data, size.ctypes.data, out.ctypes.data,
+                                                  dset.handle, ip))
+    bad = np.flatnonzero(out < 0)
+    if bad.size:
+        raise frame_exception(int(out[bad[0]]))
+    return [dst[int(o):int(o) + int(k)].tobytes() for o, k in zip(doff, out)]
+
+
+def frame_sizes_device(dc, frames, off, length, dictionary=None):
     """k4lz4_frame_sizes_device: frame f = frames[off[f] : off[f]+length[f]] (frames: uint8 device tensor; off / length: host arrays or
     device tensors).  Returns (size, status), int64 / int32 device tensors: the most frame f can decode to without trusting its
     header (per block min(blockSize, 255 * stored + 32), stored if raw; capped by ContentLength), and 0 or the walk's K4LZ4_FRAME_*
-    code.  Asynchronous on the current torch stream."""
+    code.  Asynchronous on the current torch stream.
+    dictionary=(DictionarySet, ids): k4lz4_frame_sizes_dictset_device -- a DictID that one of the ids answers to is no defect, and a
+    third tensor comes back: dict_index (int32), the entry every frame resolved to, -1 for none."""
     import ctypes as C
     import torch
     from .device import _dp
@@ -554,12 +729,19 @@ def frame_sizes_device(dc, frames, off, length):
     n = off_d.numel()
     size = torch.zeros(n, dtype=torch.int64, device=dev)
     status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if dictionary is not None:
+        dset, ids = _dictionary_ids(dictionary)
+        idx = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        dc.ctx.check(dc.lib.k4lz4_frame_sizes_dictset_device(dc.ctx.handle, _dp(frames), _dp(off_d), _dp(len_d), n, _dp(size), _dp(status),
+                                                             _dp(idx), dset.handle, ids.ctypes.data if ids.size else None,
+                                                             C.c_void_p(dc._stream())))
+        return size, status, idx
     dc.ctx.check(dc.lib.k4lz4_frame_sizes_device(dc.ctx.handle, _dp(frames), _dp(off_d), _dp(len_d), n, _dp(size), _dp(status),
                                                  C.c_void_p(dc._stream())))
     return size, status
 
 
-def decode_frames_device(dc, frames, off, length, out=None, raise_errors: bool = True):
+def decode_frames_device(dc, frames, off, length, out=None, raise_errors: bool = True, dictionary=None):
     """LZ4Frame.DecodeBatch on HBM-resident frames, nothing goes through the host: frame f = frames[off[f] : off[f]+length[f]]
     (off / length: host arrays or device tensors, e.g. encode_frames_device's frame_off and frame_len as they are).
     out: None, or (buffer, out_off, out_cap) -- a uint8 device tensor and per-frame positions / capacities (host arrays or device
@@ -567,7 +749,9 @@ def decode_frames_device(dc, frames, off, length, out=None, raise_errors: bool =
     Returns (out, out_off, out_len): frame f decoded = out[out_off[f] : out_off[f]+out_len[f]], out_len an int64 device tensor
     holding a negative K4LZ4_FRAME_* code for a frame that does not decode.  k4lz4_decode_frames_device waits for the stream once
     (it reads the batch's block count back).  raise_errors: raise what LZ4FrameReader raises for the lowest-index failing frame
-    (reads out_len back); otherwise the caller reads out_len."""
+    (reads out_len back); otherwise the caller reads out_len.
+    dictionary=(DictionarySet, ids): k4lz4_decode_frames_dictset_device -- frames with a DictID are decoded against the first entry of
+    the set whose id equals it; a DictID none of the ids answers to is FRAME_DICTIONARY, as every DictID is without it."""
     import ctypes as C
     import torch
     from .device import _dp
@@ -575,7 +759,7 @@ def decode_frames_device(dc, frames, off, length, out=None, raise_errors: bool =
     off_d, len_d = _dev_i64(off, dev), _dev_i64(length, dev)
     n = off_d.numel()
     if out is None:
-        size, _ = frame_sizes_device(dc, frames, off_d, len_d)
+        size = frame_sizes_device(dc, frames, off_d, len_d, dictionary=dictionary)[0]
         cap = size.cpu().numpy() if n else np.zeros(0, np.int64)
         out_off = np.zeros(n, np.int64)
         if n > 1:
@@ -586,7 +770,12 @@ def decode_frames_device(dc, frames, off, length, out=None, raise_errors: bool =
         buf, out_off, out_cap = out
         off_o, cap_o = _dev_i64(out_off, dev), _dev_i64(out_cap, dev)
     out_len = torch.zeros(n, dtype=torch.int64, device=dev)
-    if n:
+    if n and dictionary is not None:
+        dset, ids = _dictionary_ids(dictionary)
+        dc.ctx.check(dc.lib.k4lz4_decode_frames_dictset_device(dc.ctx.handle, _dp(frames), _dp(off_d), _dp(len_d), n, _dp(buf), _dp(off_o),
+                                                               _dp(cap_o), _dp(out_len), dset.handle, ids.ctypes.data if ids.size else None,
+                                                               C.c_void_p(dc._stream())))
+    elif n:
         dc.ctx.check(dc.lib.k4lz4_decode_frames_device(dc.ctx.handle, _dp(frames), _dp(off_d), _dp(len_d), n, _dp(buf), _dp(off_o),
                                                        _dp(cap_o), _dp(out_len), C.c_void_p(dc._stream())))
     if raise_errors and n:
