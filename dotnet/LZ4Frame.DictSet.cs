@@ -5,8 +5,9 @@
 // a set (NotImplementedException).  The writer: Encode / EncodeBatch name the entry's id as the frame's DictID and take the blocks
 // from LZ4Codec.EncodeBatch(..., set, dictionaryIndex) with the allowCopy rule (independent frames) or from an LZ4EncoderBatch opened
 // from the entry, one record -- Topup and a forced Encode -- per block (chained frames); the layout is LZ4FrameBatch.Assemble's.  Not
-// at L10_OPT and up, not under LZ4Codec.Enforce32.  The incremental readers and writers (LZ4FrameReaderBatch, LZ4FrameWriterBatch)
-// keep refusing the dictionary bit.  The executable form of all of it is frames.py.  Compile-unverified.
+// at L10_OPT and up, not under LZ4Codec.Enforce32.  The incremental readers take a set of their own (LZ4FrameReaderBatch.DictSet.cs,
+// LZ4FrameFedReaderBatch.DictSet.cs, DESIGN.md 4.25); the incremental writer (LZ4FrameWriterBatch) keeps refusing the dictionary bit.
+// The executable form of all of it is frames.py.  Compile-unverified.
 using System;
 using K4os.Compression.LZ4.Encoders;
 using K4os.Compression.LZ4.Engine;

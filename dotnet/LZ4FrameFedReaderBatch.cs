@@ -13,7 +13,7 @@ using K4os.Compression.LZ4.Engine;
 
 namespace K4os.Compression.LZ4.Streams.Frames
 {
-	public sealed unsafe class LZ4FrameFedReaderBatch: IDisposable
+	public sealed unsafe partial class LZ4FrameFedReaderBatch: IDisposable
 	{
 		[DllImport("amdhip64")] private static extern int hipSetDevice(int device);
 		[DllImport("amdhip64")] private static extern int hipMalloc(out IntPtr ptr, UIntPtr size);
@@ -31,8 +31,12 @@ namespace K4os.Compression.LZ4.Streams.Frames
 		/// <summary>Per stream after the last call: the further bytes with which the field a starved read stands at is complete; 0: not starved.</summary>
 		public long[] Need { get; private set; }
 
-		public LZ4FrameFedReaderBatch(int n, int maxBlockSize = 4 << 20)
+		public LZ4FrameFedReaderBatch(int n, int maxBlockSize = 4 << 20): this(n, maxBlockSize, null, default) { }
+
+		// (the form with a dictionary set is in LZ4FrameFedReaderBatch.DictSet.cs)
+		private LZ4FrameFedReaderBatch(int n, int maxBlockSize, LZ4DictionarySet dictionaries, ReadOnlySpan<uint> dictionaryIds)
 		{
+			SetDictionaries(dictionaries, dictionaryIds);
 			_lease = NativeContext.Rent();
 			var settings = new LLNative.k4lz4_frame_reader_settings { maxBlockSize = maxBlockSize, flags = LLNative.FREADER_FED };
 			fixed (LLNative.k4lz4_frame_reader* r = &_record)
@@ -79,8 +83,13 @@ namespace K4os.Compression.LZ4.Streams.Frames
 			fixed (byte* ps = src, pd = dst)
 			fixed (ulong* pso = srcOff, psl = srcLen, pdo = dstOff, pst = _storeOff)
 			fixed (long* pc = counts, pol = outLen, pf = _final, pcs = consumed, pn = need)
-				LLNative.ThrowIfFailed(LLNative.k4lz4_frame_read_fed_batch(_lease.Handle, r, _store, pst, ps, pso, psl, pf, pd, pdo, pc, pol, pcs, pn, n,
-					op, interactive ? LLNative.FREAD_INTERACTIVE : 0), _lease.Handle);
+			fixed (uint* ids = _dictionaryIds)
+				LLNative.ThrowIfFailed(_dictionaries is null
+					? LLNative.k4lz4_frame_read_fed_batch(_lease.Handle, r, _store, pst, ps, pso, psl, pf, pd, pdo, pc, pol, pcs, pn, n,
+						op, interactive ? LLNative.FREAD_INTERACTIVE : 0)
+					: LLNative.k4lz4_frame_read_fed_dictset_batch(_lease.Handle, r, _store, pst, ps, pso, psl, pf, pd, pdo, pc, pol, pcs, pn, n,
+						op, interactive ? LLNative.FREAD_INTERACTIVE : 0, _dictionaries.Handle, ids), _lease.Handle);
+			GC.KeepAlive(_dictionaries);
 			var codes = new long[n];
 			for (var i = 0; i < n; i++)
 			{

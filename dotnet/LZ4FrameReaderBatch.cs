@@ -10,7 +10,7 @@ using K4os.Compression.LZ4.Engine;
 
 namespace K4os.Compression.LZ4.Streams.Frames
 {
-	public sealed unsafe class LZ4FrameReaderBatch: IDisposable
+	public sealed unsafe partial class LZ4FrameReaderBatch: IDisposable
 	{
 		[DllImport("amdhip64")] private static extern int hipSetDevice(int device);
 		[DllImport("amdhip64")] private static extern int hipMalloc(out IntPtr ptr, UIntPtr size);
@@ -25,8 +25,12 @@ namespace K4os.Compression.LZ4.Streams.Frames
 		/// <summary>Per-stream codes of the last call: 0, or a K4LZ4_FRAME_* code for a stream that failed (it stays failed).</summary>
 		public long[] LastCodes { get; private set; }
 
-		public LZ4FrameReaderBatch(byte[][] sources, int maxBlockSize = 4 << 20)
+		public LZ4FrameReaderBatch(byte[][] sources, int maxBlockSize = 4 << 20): this(sources, maxBlockSize, null, default) { }
+
+		// (the form with a dictionary set is in LZ4FrameReaderBatch.DictSet.cs)
+		private LZ4FrameReaderBatch(byte[][] sources, int maxBlockSize, LZ4DictionarySet dictionaries, ReadOnlySpan<uint> dictionaryIds)
 		{
+			SetDictionaries(dictionaries, dictionaryIds);
 			var n = sources.Length;
 			_lease = NativeContext.Rent();
 			var settings = new LLNative.k4lz4_frame_reader_settings { maxBlockSize = maxBlockSize };
@@ -61,8 +65,13 @@ namespace K4os.Compression.LZ4.Streams.Frames
 			fixed (byte* ps = _src, pd = dst)
 			fixed (ulong* pso = _srcOff, psl = _srcLen, pdo = dstOff, pst = _storeOff)
 			fixed (long* pc = counts, pol = outLen)
-				LLNative.ThrowIfFailed(LLNative.k4lz4_frame_read_batch(_lease.Handle, r, _store, pst, ps, pso, psl, pd, pdo, pc, pol, n, op,
-					interactive ? LLNative.FREAD_INTERACTIVE : 0), _lease.Handle);
+			fixed (uint* ids = _dictionaryIds)
+				LLNative.ThrowIfFailed(_dictionaries is null
+					? LLNative.k4lz4_frame_read_batch(_lease.Handle, r, _store, pst, ps, pso, psl, pd, pdo, pc, pol, n, op,
+						interactive ? LLNative.FREAD_INTERACTIVE : 0)
+					: LLNative.k4lz4_frame_read_dictset_batch(_lease.Handle, r, _store, pst, ps, pso, psl, pd, pdo, pc, pol, n, op,
+						interactive ? LLNative.FREAD_INTERACTIVE : 0, _dictionaries.Handle, ids), _lease.Handle);
+			GC.KeepAlive(_dictionaries);
 			var codes = new long[n];
 			for (var i = 0; i < n; i++) codes[i] = counts[i] < 0 ? 0 : Math.Min(outLen[i], 0);
 			LastCodes = codes;

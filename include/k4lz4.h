@@ -1273,10 +1273,11 @@ K4LZ4_API int k4lz4_chain_decoder_open_dictset_device(k4lz4_ctx *ctx, const k4lz
  * descriptor bytes, which fit the 16-byte hdr rows of k4lz4_frame_assemble_device -- and the blocks are those of
  * k4lz4_encode_dictset_batch with the allowCopy rule (independent frames) or of a chain encoder opened from the entry with
  * k4lz4_chain_encoder_open_dictset (chained frames); frames.py composes them.
- * Refused, exactly: by every call that takes no set, and by these with a NULL set, every DictID (K4LZ4_FRAME_DICTIONARY); by the
- * incremental frame readers and writers (k4lz4_frame_read_batch, k4lz4_frame_read_fed_batch, k4lz4_frame_write_batch and their
- * _device forms) the dictionary bit, with or without a set anywhere; by the encoders the writer is made of,
- * K4LZ4_L10_OPT .. K4LZ4_L12_MAX with a dictionary and the 32-bit engine (K4LZ4_FLAG_X32, k4lz4_set_enforce32). */
+ * Refused, exactly: by every call that takes no set, and by these with a NULL set, every DictID (K4LZ4_FRAME_DICTIONARY) -- the
+ * incremental frame readers have calls of their own that take one (k4lz4_frame_read_dictset_batch, k4lz4_frame_read_fed_dictset_batch
+ * below); by the incremental frame writer (k4lz4_frame_write_batch and its _device form) the
+ * dictionary bit, with or without a set anywhere; by the encoders the writer is made of, K4LZ4_L10_OPT .. K4LZ4_L12_MAX with a
+ * dictionary and the 32-bit engine (K4LZ4_FLAG_X32, k4lz4_set_enforce32). */
 /* The allowCopy rule (LZ4EncoderBase.Encode(allowCopy: true)) behind an encoder that takes no flags, on device pointers: block i
  * with outLen[i] >= srcLen[i] is stored raw (its srcLen[i] bytes copied to dst + dstOff[i], outLen[i] = -srcLen[i]; 0 when
  * dstCap[i] is too small for that), outLen[i] <= 0 becomes 0 -- what K4LZ4_FLAG_ALLOW_COPY does behind k4lz4_encode_batch_device.
@@ -1296,6 +1297,50 @@ K4LZ4_API int k4lz4_frame_sizes_dictset(k4lz4_ctx *ctx, const uint8_t *src, cons
 K4LZ4_API int k4lz4_decode_frames_dictset(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *frameOff, const uint64_t *frameLen, int64_t n,
                                           uint8_t *dst, const uint64_t *dstOff, const uint64_t *dstCap, int64_t *outLen,
                                           const k4lz4_dict_set *set, const uint32_t *dictIds);
+
+/* ---- the incremental frame readers against a set --------------------------------------------------------------
+ * k4lz4_frame_read_batch[_device] and k4lz4_frame_read_fed_batch[_device] with a k4lz4_dict_set beside them:
+ * each call is its counterpart's argument list with `set, dictIds` added (in front of `stream` in the _device forms), and everything
+ * said of the counterpart holds -- ops, flags, codes, what is written, maxCount, the two ways through a READ, starving and need.
+ * Records and stores are the counterparts': k4lz4_frame_reader_store_bytes does not change, a store made for one works with the other.
+ * dictIds is a HOST array of set->nDict uint32_t in both forms and goes up per call through the context (the caller may free it when
+ * the call returns; the _device forms stay asynchronous).  The rules are 4.24's:
+ *   - a frame's DictID resolves to the FIRST entry whose id equals it; a frame without the dictionary bit is read as in the plain calls;
+ *   - a DictID nothing answers to is K4LZ4_FRAME_DICTIONARY where the plain calls report every DictID: behind the header checksum (a
+ *     flipped DictID byte is K4LZ4_FRAME_HEADER_SUM), before the first block; an OPEN reports it too.  A source that ends inside the
+ *     DictID is K4LZ4_FRAME_EOF; a fed stream that is not final starves there with need the bytes that complete the header;
+ *   - independent-block frames: every compressed block is decoded against the entry's kept bytes (the last 64 KiB) as an external
+ *     dictionary, on both ways through a READ; chained frames: the kept bytes are the history in front of the first block, as
+ *     LZ4ChainDecoder's after Inject.  The kept bytes are never delivered, never counted in K4LZ4_FRQ_BYTES_READ and never enter the
+ *     content checksum.  An offset that reaches before the first kept byte is K4LZ4_FRAME_BLOCK; an entry of no bytes reads as a
+ *     plain frame (whose id still has to resolve).
+ * The store remembers which entry the open frame resolved to, from the header to the frame's end; a source of several frames may
+ * name another entry, or none, per frame.  THE CALLER PASSES THE SAME SET AND THE SAME IDS FOR AS LONG AS A FRAME IS OPEN.  A call that
+ * brings a set which does not have the remembered entry fails the stream with K4LZ4_FRAME_DICTIONARY and reads nothing of the set;
+ * a set that has it but holds other bytes there is not noticed.
+ * A NULL set (dictIds is then ignored) makes each call exactly its counterpart.  K4LZ4_E_ARG before anything is enqueued: a set on
+ * another device than the context, NULL dictIds with a set, and what the counterpart refuses (a record of the other kind).
+ * No status code and no query word is new.  Not here: the incremental frame writer with a dictionary. */
+K4LZ4_API int k4lz4_frame_read_dictset_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                             const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                             const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags,
+                                             const k4lz4_dict_set *set, const uint32_t *dictIds);
+K4LZ4_API int k4lz4_frame_read_dictset_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                                    const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                                    const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op,
+                                                    int flags, int64_t maxCount, const k4lz4_dict_set *set, const uint32_t *dictIds,
+                                                    void *stream);
+K4LZ4_API int k4lz4_frame_read_fed_dictset_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                                 const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final,
+                                                 uint8_t *dst, const uint64_t *dstOff, const int64_t *count, int64_t *outLen,
+                                                 int64_t *consumed, int64_t *need, int64_t n, int op, int flags,
+                                                 const k4lz4_dict_set *set, const uint32_t *dictIds);
+K4LZ4_API int k4lz4_frame_read_fed_dictset_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store,
+                                                        const uint64_t *storeOff, const uint8_t *src, const uint64_t *srcOff,
+                                                        const uint64_t *srcLen, const int64_t *final, uint8_t *dst, const uint64_t *dstOff,
+                                                        const int64_t *count, int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n,
+                                                        int op, int flags, int64_t maxCount, const k4lz4_dict_set *set,
+                                                        const uint32_t *dictIds, void *stream);
 
 #ifdef __cplusplus
 }

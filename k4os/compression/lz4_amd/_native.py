@@ -188,6 +188,12 @@ SYMBOLS = {
     "k4lz4_frame_read_table_rows": (C.c_int64, [C.c_int64]),
     "k4lz4_frame_read_fed_batch": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int]),
     "k4lz4_frame_read_fed_batch_device": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    # ... set, dictIds [, stream]
+    "k4lz4_frame_read_dictset_batch": (C.c_int, _FREAD + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "k4lz4_frame_read_dictset_batch_device": (C.c_int, _FREAD + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "k4lz4_frame_read_fed_dictset_batch": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "k4lz4_frame_read_fed_dictset_batch_device": (C.c_int, [C.c_void_p] * 14 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p]),
     "k4lz4_frame_reader_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "k4lz4_frame_reader_query_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "k4lz4_legacy_writer_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

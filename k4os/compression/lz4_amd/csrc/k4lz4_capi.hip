@@ -52,6 +52,7 @@
 #include "k4lz4_dict_set.hpp"
 #include "k4lz4_chain_open.hpp"
 #include "k4lz4_frame_dict.hpp"
+#include "k4lz4_frame_reader_dict.hpp"
 
 constexpr int MAX_PARTS = 8;      /* a big host-pointer call is staged, run and brought back in up to this many parts */
 
@@ -1849,6 +1850,21 @@ void direct_layout(Carve &c, k4::FrFeedFastArgs &ff, size_t n, size_t nr)
     direct_layout(c, ff.f, n, nr);
     c.take(ff.tail, n); c.take(ff.want, n);
 }
+void direct_layout(Carve &c, k4::FrDictRows &w, size_t n, size_t nr)
+{
+    c.take(w.dictOff, nr); c.take(w.dictLen, nr); c.take(w.dictMode, nr);
+    c.take(w.sDictOff, n); c.take(w.sDictLen, n); c.take(w.sDictMode, n); c.take(w.entry, n);
+}
+void direct_layout(Carve &c, k4::FrDictFastArgs &d, size_t n, size_t nr)
+{
+    direct_layout(c, d.f, n, nr);
+    direct_layout(c, d.w, n, nr);
+}
+void direct_layout(Carve &c, k4::FrDictFeedFastArgs &d, size_t n, size_t nr)
+{
+    direct_layout(c, d.f, n, nr);
+    direct_layout(c, d.w, n, nr);
+}
 void direct_layout(Carve &c, k4::LsDirectArgs &f, size_t n, size_t nr)
 {
     c.take(f.plan, n); c.take(f.done, n);
@@ -1862,14 +1878,15 @@ void direct_layout(Carve &c, k4::LsFeedDirectArgs &f, size_t n, size_t nr)
     c.take(f.srcAddr, nr); c.take(f.dstAddr, nr); c.take(f.srcLen, nr); c.take(f.dstCap, nr); c.take(f.outLen, nr); c.take(f.rawLen, nr);
 }
 
-/* What tells the four readers apart on the host.  Args: what the per-stream reader kernel (READ) takes; Direct: what the direct
+/* What tells the readers apart on the host.  Args: what the per-stream reader kernel (READ) takes; Direct: what the direct
  * path's PLAN and COMMIT kernels take, table(d) the part of it that holds the tables; begin() hands the call's arrays to the direct
  * path and served() hands the reader kernel what the commit left for it.  SUMS: block checksums between plan and decode.
- * ADDRESSES: the rows hold addresses -- a row's source may be the stash, which TOPUP completes first --, the decoder's bases are null. */
+ * ADDRESSES: the rows hold addresses -- a row's source may be the stash, which TOPUP completes first --, the decoder's bases are null.
+ * DICT: the call has a dictionary set -- words(d) are the plan's dictionary words for the batch decoder. */
 struct FrameReader {
     using Args = k4::FrReadArgs; using Direct = k4::FrFastArgs;
     static constexpr int WAVES = k4::FR_WAVES_PER_WG;
-    static constexpr bool SUMS = true, ADDRESSES = false;
+    static constexpr bool SUMS = true, ADDRESSES = false, DICT = false;
     static constexpr const char *ROWS_PASS = "k4lz4_frame_read_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows";
     static constexpr auto PLAN = k4::k4_fr_plan_kernel, COMMIT = k4::k4_fr_commit_kernel;
     static constexpr auto READ = k4::k4_fr_read_kernel;
@@ -1881,7 +1898,7 @@ struct FrameReader {
 struct FedFrameReader {
     using Args = k4::FrFeedArgs; using Direct = k4::FrFeedFastArgs;
     static constexpr int WAVES = k4::FR_WAVES_PER_WG;
-    static constexpr bool SUMS = true, ADDRESSES = false;
+    static constexpr bool SUMS = true, ADDRESSES = false, DICT = false;
     static constexpr const char *ROWS_PASS = "k4lz4_frame_read_fed_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows";
     static constexpr auto PLAN = k4::k4_fr_feed_plan_kernel, COMMIT = k4::k4_fr_feed_commit_kernel;
     static constexpr auto READ = k4::k4_fr_feed_kernel;
@@ -1890,10 +1907,36 @@ struct FedFrameReader {
     static void begin(Direct &d, const Args &a) { d.f.r = a.r; d.final = a.final; d.consumed = a.consumed; d.need = a.need; }
     static void served(Args &a, const Direct &d) { a.r.done = d.f.done; }
 };
+struct DictFrameReader {
+    using Args = k4::FrDictReadArgs; using Direct = k4::FrDictFastArgs;
+    static constexpr int WAVES = k4::FR_WAVES_PER_WG;
+    static constexpr bool SUMS = true, ADDRESSES = false, DICT = true;
+    static constexpr const char *ROWS_PASS = "k4lz4_frame_read_dictset_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows";
+    static constexpr auto PLAN = k4::k4_fr_dict_plan_kernel, COMMIT = k4::k4_fr_dict_commit_kernel;
+    static constexpr auto READ = k4::k4_fr_dict_read_kernel;
+    static k4::FrReadArgs &reader(Args &a) { return a.r; }
+    static k4::FrFastArgs &table(Direct &d) { return d.f; }
+    static const k4::FrDictRows &words(const Direct &d) { return d.w; }
+    static void begin(Direct &d, const Args &a) { d.f.r = a.r; d.w.d = a.d; }
+    static void served(Args &a, const Direct &d) { a.r.done = d.f.done; }
+};
+struct DictFedFrameReader {
+    using Args = k4::FrDictFeedArgs; using Direct = k4::FrDictFeedFastArgs;
+    static constexpr int WAVES = k4::FR_WAVES_PER_WG;
+    static constexpr bool SUMS = true, ADDRESSES = false, DICT = true;
+    static constexpr const char *ROWS_PASS = "k4lz4_frame_read_fed_dictset_batch: maxCount / 64 KiB + 2 rows per stream pass 2^31 rows";
+    static constexpr auto PLAN = k4::k4_fr_dict_feed_plan_kernel, COMMIT = k4::k4_fr_dict_feed_commit_kernel;
+    static constexpr auto READ = k4::k4_fr_dict_feed_kernel;
+    static k4::FrReadArgs &reader(Args &a) { return a.f.r; }
+    static k4::FrFastArgs &table(Direct &d) { return d.f.f; }
+    static const k4::FrDictRows &words(const Direct &d) { return d.w; }
+    static void begin(Direct &d, const Args &a) { FedFrameReader::begin(d.f, a.f); d.w.d = a.d; }
+    static void served(Args &a, const Direct &d) { a.f.r.done = d.f.f.done; }
+};
 struct LegacyReader {
     using Args = k4::LsReadArgs; using Direct = k4::LsDirectArgs;
     static constexpr int WAVES = k4::LS_WAVES_PER_WG;
-    static constexpr bool SUMS = false, ADDRESSES = false;
+    static constexpr bool SUMS = false, ADDRESSES = false, DICT = false;
     static constexpr const char *ROWS_PASS = "k4lz4_legacy_read_batch: the chunk table passes 2^31 rows";
     static constexpr auto PLAN = k4::k4_ls_plan_kernel, COMMIT = k4::k4_ls_commit_kernel;
     static constexpr auto READ = k4::k4_ls_read_kernel;
@@ -1905,7 +1948,7 @@ struct LegacyReader {
 struct FedLegacyReader {
     using Args = k4::LsFeedArgs; using Direct = k4::LsFeedDirectArgs;
     static constexpr int WAVES = k4::LS_WAVES_PER_WG;
-    static constexpr bool SUMS = false, ADDRESSES = true;
+    static constexpr bool SUMS = false, ADDRESSES = true, DICT = false;
     static constexpr const char *ROWS_PASS = "k4lz4_legacy_read_fed_batch: the chunk table passes 2^31 rows";
     static constexpr auto TOPUP = k4::k4_ls_feed_topup_kernel, PLAN = k4::k4_ls_feed_plan_kernel, COMMIT = k4::k4_ls_feed_commit_kernel;
     static constexpr auto READ = k4::k4_ls_feed_kernel;
@@ -1945,13 +1988,21 @@ int read_device(k4lz4_ctx *ctx, typename F::Args a, long long rows, void *stream
         K4_HIP(ctx, hipGetLastError());
         if constexpr (F::SUMS)
             if ((rc = k4lz4_xxh32_batch_device(ctx, r.src, t.srcOff, t.hlen, t.got, (int64_t)nr, 0, st)) != K4LZ4_OK) return rc;
+        DictArgs rows_dict{}, stores_dict{};               /* DICT: every row against its stream's entry, the set's bytes as dict */
+        if constexpr (F::DICT) {
+            const k4::FrDictRows &w = F::words(d);
+            rows_dict = DictArgs{w.d.dict, w.dictOff, w.dictLen, w.dictMode};
+            stores_dict = DictArgs{w.d.dict, w.sDictOff, w.sDictLen, w.sDictMode};
+        }
         if constexpr (F::ADDRESSES) {
             if ((rc = launch(ctx, KIND_DECODE, nullptr, t.srcAddr, t.srcLen, nullptr, t.dstAddr, t.dstCap, t.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
                 (rc = launch(ctx, KIND_DECODE, nullptr, t.sSrcAddr, t.sSrcLen, nullptr, t.sDstAddr, t.sDstCap, t.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
                 return rc;
         } else {
-            if ((rc = launch(ctx, KIND_DECODE, r.src, t.srcOff, t.srcLen, r.dst, t.dstOff, t.dstCap, t.outLen, (int64_t)nr, 0, 0, st)) != K4LZ4_OK ||
-                (rc = launch(ctx, KIND_DECODE, r.src, t.sSrcOff, t.sSrcLen, r.store, t.sDstOff, t.sDstCap, t.sOutLen, n, 0, 0, st)) != K4LZ4_OK)
+            if ((rc = launch(ctx, KIND_DECODE, r.src, t.srcOff, t.srcLen, r.dst, t.dstOff, t.dstCap, t.outLen, (int64_t)nr, 0, 0, st,
+                             F::DICT ? &rows_dict : nullptr)) != K4LZ4_OK ||
+                (rc = launch(ctx, KIND_DECODE, r.src, t.sSrcOff, t.sSrcLen, r.store, t.sDstOff, t.sDstCap, t.sOutLen, n, 0, 0, st,
+                             F::DICT ? &stores_dict : nullptr)) != K4LZ4_OK)
                 return rc;
         }
         hipLaunchKernelGGL(F::COMMIT, waves, wg, 0, st, d);
@@ -3839,10 +3890,25 @@ int k4lz4_frame_reader_init(k4lz4_frame_reader *r, const k4lz4_frame_reader_sett
 int64_t k4lz4_frame_reader_store_bytes(const k4lz4_frame_reader *r) { return r ? r->storeBytes : 0; }
 int64_t k4lz4_frame_read_table_rows(int64_t maxCount) { return k4::fr_table_rows(maxCount); }
 
-int k4lz4_frame_read_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
-                                  const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
-                                  const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags,
-                                  int64_t maxCount, void *stream)
+/* the readers against a dictionary set (k4lz4_frame_reader_dict.hpp): the set's words and the call's id table -- a
+ * host array in both forms, staged like k4lz4_decode_frames_dictset's -- for the kernels */
+static int reader_dict(k4lz4_ctx *ctx, const k4lz4_dict_set *set, const uint32_t *dictIds, hipStream_t st, k4::FrDict *d)
+{
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    K4_HIP(ctx, order_after_ctx(ctx, st));
+    uint32_t *ids = nullptr;
+    int32_t *idx = nullptr;
+    const int rc = frame_dict_ids(ctx, set, dictIds, 0, st, &ids, &idx);
+    if (rc != K4LZ4_OK) return rc;
+    *d = k4::FrDict{set->buf, set->dec_off, set->dec_len, ids, set->nDict};
+    return K4LZ4_OK;
+}
+
+/* set == nullptr: k4lz4_frame_read_batch_device as it always was; with a set, k4lz4_frame_read_dictset_batch_device */
+static int frame_read_run(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                          const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const int64_t *count,
+                          int64_t *outLen, int64_t n, int op, int flags, int64_t maxCount, const k4lz4_dict_set *set, const uint32_t *dictIds,
+                          void *stream)
 {
     if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
     if (op < K4LZ4_FREAD_READ || op > K4LZ4_FREAD_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: unknown op");
@@ -3854,14 +3920,37 @@ int k4lz4_frame_read_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, u
         return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: the record was not made by k4lz4_frame_reader_init");
     if (n == 0) return K4LZ4_OK;
     const int interactive = (flags & K4LZ4_FREAD_INTERACTIVE) ? 1 : 0;
-    return read_device<FrameReader>(ctx, {src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op, interactive,
-                                          r->settings.maxBlockSize, nullptr},
-                                    op == K4LZ4_FREAD_READ && !interactive ? k4::fr_table_rows(maxCount) : 0, stream);
+    const k4::FrReadArgs a{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op, interactive, r->settings.maxBlockSize,
+                           nullptr};
+    const long long rows = op == K4LZ4_FREAD_READ && !interactive ? k4::fr_table_rows(maxCount) : 0;
+    if (!set) return read_device<FrameReader>(ctx, a, rows, stream);
+    k4::FrDict d;
+    const int rc = reader_dict(ctx, set, dictIds, (hipStream_t)stream, &d);
+    if (rc != K4LZ4_OK) return rc;
+    return read_device<DictFrameReader>(ctx, {a, d}, rows, stream);
 }
 
-int k4lz4_frame_read_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+int k4lz4_frame_read_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                  const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                  const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags,
+                                  int64_t maxCount, void *stream)
+{
+    return frame_read_run(ctx, r, store, storeOff, src, srcOff, srcLen, dst, dstOff, count, outLen, n, op, flags, maxCount, nullptr, nullptr, stream);
+}
+
+int k4lz4_frame_read_dictset_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                          const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst,
+                                          const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t n, int op, int flags,
+                                          int64_t maxCount, const k4lz4_dict_set *set, const uint32_t *dictIds, void *stream)
+{
+    const int rc = frame_dict_args(ctx, set, dictIds, "k4lz4_frame_read_dictset_batch");
+    if (rc != K4LZ4_OK) return rc;
+    return frame_read_run(ctx, r, store, storeOff, src, srcOff, srcLen, dst, dstOff, count, outLen, n, op, flags, maxCount, set, dictIds, stream);
+}
+
+static int frame_read_host(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
                            const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const int64_t *count,
-                           int64_t *outLen, int64_t n, int op, int flags)
+                           int64_t *outLen, int64_t n, int op, int flags, const k4lz4_dict_set *set, const uint32_t *dictIds)
 {
     if (!ctx) return fail(nullptr, K4LZ4_E_ARG, "ctx is NULL");
     if (op < K4LZ4_FREAD_READ || op > K4LZ4_FREAD_RESET) return fail(ctx, K4LZ4_E_ARG, "k4lz4_frame_read_batch: unknown op");
@@ -3875,9 +3964,25 @@ int k4lz4_frame_read_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t 
     return host_read(ctx, {storeOff, src, srcOff, srcLen, nullptr, dst, dstOff, count, outLen, nullptr, nullptr}, n,
                      /* sends */ op != K4LZ4_FREAD_RESET, /* fills */ op == K4LZ4_FREAD_READ,
                      [&](const ReadArrays &d, int64_t maxCount, hipStream_t st) {
-                         return k4lz4_frame_read_batch_device(ctx, r, store, d.storeOff, d.src, d.srcOff, d.srcLen, d.dst, d.dstOff, d.count,
-                                                              d.outLen, n, op, flags, maxCount, st);
+                         return frame_read_run(ctx, r, store, d.storeOff, d.src, d.srcOff, d.srcLen, d.dst, d.dstOff, d.count, d.outLen, n, op,
+                                               flags, maxCount, set, dictIds, st);
                      });
+}
+
+int k4lz4_frame_read_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                           const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const int64_t *count,
+                           int64_t *outLen, int64_t n, int op, int flags)
+{
+    return frame_read_host(ctx, r, store, storeOff, src, srcOff, srcLen, dst, dstOff, count, outLen, n, op, flags, nullptr, nullptr);
+}
+
+int k4lz4_frame_read_dictset_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                                   const uint64_t *srcOff, const uint64_t *srcLen, uint8_t *dst, const uint64_t *dstOff, const int64_t *count,
+                                   int64_t *outLen, int64_t n, int op, int flags, const k4lz4_dict_set *set, const uint32_t *dictIds)
+{
+    const int rc = frame_dict_args(ctx, set, dictIds, "k4lz4_frame_read_dictset_batch");
+    if (rc != K4LZ4_OK) return rc;
+    return frame_read_host(ctx, r, store, storeOff, src, srcOff, srcLen, dst, dstOff, count, outLen, n, op, flags, set, dictIds);
 }
 
 int k4lz4_frame_reader_query_device(k4lz4_ctx *ctx, const uint8_t *store, const uint64_t *storeOff, int64_t n, int64_t *out, void *stream)
@@ -3907,24 +4012,51 @@ static int fed_args(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, const void *sto
     return K4LZ4_OK;
 }
 
-int k4lz4_frame_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
-                                      const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final,
-                                      uint8_t *dst, const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t *consumed,
-                                      int64_t *need, int64_t n, int op, int flags, int64_t maxCount, void *stream)
+/* set == nullptr: k4lz4_frame_read_fed_batch_device as it always was; with a set, k4lz4_frame_read_fed_dictset_batch_device */
+static int frame_read_fed_run(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                              const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final, uint8_t *dst, const uint64_t *dstOff,
+                              const int64_t *count, int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags,
+                              int64_t maxCount, const k4lz4_dict_set *set, const uint32_t *dictIds, void *stream)
 {
     int rc;
     if ((rc = fed_args(ctx, r, store, storeOff, srcOff, srcLen, dst, dstOff, count, outLen, consumed, need, n, op, flags)) != K4LZ4_OK) return rc;
     if (n > 0 && op != K4LZ4_FREAD_RESET && !src) return fail(ctx, K4LZ4_E_ARG, "bad argument");
     if (n == 0) return K4LZ4_OK;
     const int interactive = (flags & K4LZ4_FREAD_INTERACTIVE) ? 1 : 0;
-    return read_device<FedFrameReader>(ctx, {{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op, interactive,
-                                              r->settings.maxBlockSize, nullptr}, final, consumed, need},
-                                       op == K4LZ4_FREAD_READ && !interactive ? k4::fr_table_rows(maxCount) : 0, stream);
+    const k4::FrFeedArgs a{{src, srcOff, srcLen, store, storeOff, dst, dstOff, count, outLen, (long long)n, op, interactive, r->settings.maxBlockSize,
+                            nullptr}, final, consumed, need};
+    const long long rows = op == K4LZ4_FREAD_READ && !interactive ? k4::fr_table_rows(maxCount) : 0;
+    if (!set) return read_device<FedFrameReader>(ctx, a, rows, stream);
+    k4::FrDict d;
+    if ((rc = reader_dict(ctx, set, dictIds, (hipStream_t)stream, &d)) != K4LZ4_OK) return rc;
+    return read_device<DictFedFrameReader>(ctx, {a, d}, rows, stream);
 }
 
-int k4lz4_frame_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+int k4lz4_frame_read_fed_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                      const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final,
+                                      uint8_t *dst, const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t *consumed,
+                                      int64_t *need, int64_t n, int op, int flags, int64_t maxCount, void *stream)
+{
+    return frame_read_fed_run(ctx, r, store, storeOff, src, srcOff, srcLen, final, dst, dstOff, count, outLen, consumed, need, n, op, flags, maxCount,
+                              nullptr, nullptr, stream);
+}
+
+int k4lz4_frame_read_fed_dictset_batch_device(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff,
+                                              const uint8_t *src, const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final,
+                                              uint8_t *dst, const uint64_t *dstOff, const int64_t *count, int64_t *outLen, int64_t *consumed,
+                                              int64_t *need, int64_t n, int op, int flags, int64_t maxCount, const k4lz4_dict_set *set,
+                                              const uint32_t *dictIds, void *stream)
+{
+    const int rc = frame_dict_args(ctx, set, dictIds, "k4lz4_frame_read_fed_dictset_batch");
+    if (rc != K4LZ4_OK) return rc;
+    return frame_read_fed_run(ctx, r, store, storeOff, src, srcOff, srcLen, final, dst, dstOff, count, outLen, consumed, need, n, op, flags, maxCount,
+                              set, dictIds, stream);
+}
+
+static int frame_read_fed_host(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
                                const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final, uint8_t *dst, const uint64_t *dstOff,
-                               const int64_t *count, int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags)
+                               const int64_t *count, int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags,
+                               const k4lz4_dict_set *set, const uint32_t *dictIds)
 {
     int rc;
     if ((rc = fed_args(ctx, r, store, storeOff, srcOff, srcLen, dst, dstOff, count, outLen, consumed, need, n, op, flags)) != K4LZ4_OK) return rc;
@@ -3932,9 +4064,28 @@ int k4lz4_frame_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint
     return host_read(ctx, {storeOff, src, srcOff, srcLen, final, dst, dstOff, count, outLen, consumed, need}, n,
                      /* sends */ op != K4LZ4_FREAD_RESET, /* fills */ op == K4LZ4_FREAD_READ,
                      [&](const ReadArrays &d, int64_t maxCount, hipStream_t st) {
-                         return k4lz4_frame_read_fed_batch_device(ctx, r, store, d.storeOff, d.src, d.srcOff, d.srcLen, d.final, d.dst, d.dstOff,
-                                                                  d.count, d.outLen, d.consumed, d.need, n, op, flags, maxCount, st);
+                         return frame_read_fed_run(ctx, r, store, d.storeOff, d.src, d.srcOff, d.srcLen, d.final, d.dst, d.dstOff, d.count,
+                                                   d.outLen, d.consumed, d.need, n, op, flags, maxCount, set, dictIds, st);
                      });
+}
+
+int k4lz4_frame_read_fed_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                               const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final, uint8_t *dst, const uint64_t *dstOff,
+                               const int64_t *count, int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags)
+{
+    return frame_read_fed_host(ctx, r, store, storeOff, src, srcOff, srcLen, final, dst, dstOff, count, outLen, consumed, need, n, op, flags,
+                               nullptr, nullptr);
+}
+
+int k4lz4_frame_read_fed_dictset_batch(k4lz4_ctx *ctx, const k4lz4_frame_reader *r, uint8_t *store, const uint64_t *storeOff, const uint8_t *src,
+                                       const uint64_t *srcOff, const uint64_t *srcLen, const int64_t *final, uint8_t *dst, const uint64_t *dstOff,
+                                       const int64_t *count, int64_t *outLen, int64_t *consumed, int64_t *need, int64_t n, int op, int flags,
+                                       const k4lz4_dict_set *set, const uint32_t *dictIds)
+{
+    const int rc = frame_dict_args(ctx, set, dictIds, "k4lz4_frame_read_fed_dictset_batch");
+    if (rc != K4LZ4_OK) return rc;
+    return frame_read_fed_host(ctx, r, store, storeOff, src, srcOff, srcLen, final, dst, dstOff, count, outLen, consumed, need, n, op, flags, set,
+                               dictIds);
 }
 
 /* ---- LZ4Stream written and read piece by piece (k4lz4_legacy_stream.hpp) ---------------------------------- */

@@ -103,190 +103,13 @@ struct FrFeedArgs {
     int64_t *consumed, *need;
 };
 
+/* the loop's text is k4lz4_frame_feed_loop.hpp, which k4_fr_dict_feed_kernel (k4lz4_frame_reader_dict.hpp) includes as well */
 __global__ __launch_bounds__(64 * FR_WAVES_PER_WG) void k4_fr_feed_kernel(FrFeedArgs fa)
 {
     __shared__ uint32_t lds[FR_WAVES_PER_WG][DECODE_LDS_DWORDS];
-    const FrReadArgs &a = fa.r;
-    const int lane = lane_id();
-    const uint32_t wave = uni(threadIdx.x >> 6);
-    const long long s = (long long)blockIdx.x * FR_WAVES_PER_WG + (long long)wave;
-    if (s >= a.n) return;
-    if (a.done && a.done[s] == FR_PLAN_DONE) return;
-    const int64_t want = a.count ? a.count[s] : 0;
-    if (want < 0) {                                          /* untouched */
-        if (lane == 0) { a.outLen[s] = 0; fa.consumed[s] = 0; fa.need[s] = 0; }
-        return;
-    }
-    FrState *st = (FrState *)(a.store + a.storeOff[s]);
-    uint8_t *buf = (uint8_t *)st + FR_STATE_BYTES;
-    if (a.op == FR_OP_RESET) {
-        uint32_t *w = (uint32_t *)st;
-        if (lane < (int)(FR_STATE_BYTES / 4)) w[lane] = 0u;
-        if (lane == 0) { a.outLen[s] = 0; fa.consumed[s] = 0; fa.need[s] = 0; }
-        return;
-    }
-    /* the state, the same in every lane */
-    uint64_t bytes_read = st->bytesRead, clen = st->clen, blocks = st->blocks;
-    int phase = st->phase, code = st->code;
-    uint32_t flg = st->flg, bd = st->bd, pending = st->pending, tail = st->tail, direct = st->direct;
-    int bs = st->bsize;
-    const uint32_t fill0 = st->stashFill;
-    wave_sync();
-    if (phase == FR_PHASE_FAILED) {                          /* failed streams stay failed and touch nothing */
-        if (lane == 0) { a.outLen[s] = code; fa.consumed[s] = 0; fa.need[s] = 0; }
-        return;
-    }
-    FrFeedSrc f{a.src ? a.src + a.srcOff[s] : nullptr, 0u, a.srcLen[s], (uint8_t *)st + fr_store_bytes(a.maxBlock), fill0};
-    const bool fin = fa.final && fa.final[s] != 0;
-    uint8_t *out = a.dst ? a.dst + a.dstOff[s] : nullptr;
-    const uint32_t buf_bytes = (uint32_t)fr_buffer_bytes(a.maxBlock);
-    int fail = 0;
-    int64_t result = 0;
-    uint32_t need = 0, awaited = 0;                          /* starved: bytes missing of the field, and the field's length */
-    bool has_frame = phase == FR_PHASE_OPEN;
-
-    /* ---- EnsureHeader -> ReadHeader (.async.cs:46-108): the magic, FLG / BD and the rest are three fields of one stash run */
-    if (!has_frame) {
-        const uint8_t *h;
-        uint32_t have;
-        int hw;
-        for (;;) {
-            h = f.fill ? f.stash : f.p + f.at;
-            have = f.fill ? f.fill : (f.end - f.at > 32u ? 32u : (uint32_t)(f.end - f.at));
-            hw = have ? fr_header_want(h, have) : 4;
-            if (hw <= 0 || !fr_feed_field(f, (uint32_t)hw, lane)) break;
-        }
-        if (hw < 0) {
-            fail = hw;
-        } else if (hw > 0) {                                 /* the header is not all there */
-            if (!fin) { awaited = (uint32_t)hw; need = fr_feed_keep(f, awaited, lane); }
-            else if (have) fail = FR_EOF;                    /* nothing left is a clean end (ReaderExtensions.cs:20-21) */
-        } else {
-            FrHeader hd{flg, bd, 0u, bs, clen};
-            fail = fr_parse_header(h, have, a.maxBlock, hd);
-            flg = hd.flg; bd = hd.bd;
-            if (!fail) {
-                clen = hd.clen; bs = hd.bs;
-                if (flg & FLG_CONTENT_SUM) fr_xxh_update(&st->content, h, 0, true, lane);   /* InitializeContentChecksum */
-                fr_feed_take(f, hd.len);
-                pending = 0; tail = 0;
-                phase = FR_PHASE_OPEN;
-                has_frame = true;
-            }
-        }
-    }
-
-    if (!fail && a.op == FR_OP_OPEN) result = has_frame ? 1 : 0;
-    if (!fail && a.op == FR_OP_READ && has_frame) {
-        const bool chained = !(flg & FLG_INDEPENDENT);
-        uint64_t offset = 0, count = (uint64_t)want;
-        while (count > 0) {
-            if (pending == 0) {
-                /* ---- ReadBlock (.async.cs:110-137) */
-                const uint8_t *rec = fr_feed_field(f, 4u, lane);
-                if (!rec) {
-                    if (fin) fail = FR_EOF; else { awaited = 4u; need = fr_feed_keep(f, 4u, lane); }
-                    break;
-                }
-                const uint32_t lc = ld32u(rec);
-                if (lc == 0) {                                                      /* EndMark */
-                    if (flg & FLG_CONTENT_SUM) {
-                        rec = fr_feed_field(f, 8u, lane);
-                        if (!rec) {
-                            if (fin) fail = FR_EOF; else { awaited = 8u; need = fr_feed_keep(f, 8u, lane); }
-                            break;
-                        }
-                        const uint32_t stored = ld32u(rec + 4);
-                        fr_feed_take(f, 8u);
-                        if (fw_xxh32_digest(st->content) != stored) { fail = FR_CONTENT_SUM; break; }
-                    } else {
-                        fr_feed_take(f, 4u);
-                    }
-                    phase = FR_PHASE_NONE;                                          /* CloseFrame: this read ends with what it has */
-                    break;
-                }
-                const uint32_t sn = lc & 0x7fffffffu;
-                const bool raw = (lc & 0x80000000u) != 0;
-                if (sn > (uint32_t)bs) { fail = FR_BLOCK; break; }                  /* does not fit AllocBuffer(blockSize) */
-                const uint32_t rl = 4u + sn + ((flg & FLG_BLOCK_SUM) ? 4u : 0u);
-                rec = fr_feed_field(f, rl, lane);
-                if (!rec) {
-                    if (fin) fail = FR_EOF; else { awaited = rl; need = fr_feed_keep(f, rl, lane); }
-                    break;
-                }
-                const uint8_t *payload = rec + 4;
-                fr_feed_take(f, rl);
-                if (flg & FLG_BLOCK_SUM) {
-                    const uint32_t stored = ld32u(payload + sn);
-                    fr_xxh_update(&st->scratch, payload, sn, true, lane);
-                    if (fw_xxh32_digest(st->scratch) != stored) { fail = FR_BLOCK_SUM; break; }
-                }
-                blocks++;
-                /* ---- InjectOrDecode, as k4_fr_read_kernel */
-                uint32_t got = 0;
-                const uint8_t *made = buf;
-                bool to_dst = false;
-                if (chained) {
-                    const uint32_t room = raw ? sn : (uint32_t)bs;
-                    if (tail + room > buf_bytes) {
-                        const uint32_t keep = tail < FR_HISTORY ? tail : FR_HISTORY;
-                        wave_sync();
-                        wave_shift_down(buf, buf + tail - keep, keep, lane);
-                        tail = keep;
-                    }
-                    made = buf + tail;
-                }
-                if (raw) {
-                    got = sn;
-                    if (!chained && count >= sn) { to_dst = true; made = out + offset; }
-                    wave_sync();
-                    if (sn) wave_copy((uint8_t *)made, payload, sn, lane);
-                    wave_sync();
-                } else {
-                    const int cap = chained ? bs : bs + 8;
-                    DecodeDict dict{nullptr, 0u, 0};
-                    if (chained && tail) {
-                        const uint32_t hist = tail < FR_HISTORY ? tail : FR_HISTORY;
-                        dict = DecodeDict{made, hist >= 65535u ? 65536u : hist, 1};
-                    }
-                    if (!chained && count >= (uint64_t)cap) { to_dst = true; made = out + offset; }
-                    wave_sync();
-                    const int ret = decode_block(payload, (int)sn, (uint8_t *)made, cap, lane, lds[wave], nullptr, false, dict);
-                    wave_sync();
-                    if (ret < 0 || (!chained && ret == 0)) { fail = FR_BLOCK; break; }
-                    got = (uint32_t)ret;
-                }
-                if (chained) tail += got; else if (!to_dst) tail = got;
-                if ((flg & FLG_CONTENT_SUM) && got) fr_xxh_update(&st->content, made, got, false, lane);   /* UpdateContentChecksum */
-                if (got == 0) break;                                                /* .async.cs:162-163: the frame stays open */
-                if (to_dst) {
-                    direct++;
-                    bytes_read += got; offset += got; count -= got;
-                    if (a.interactive) break;
-                    continue;
-                }
-                pending = got;
-            }
-            /* ---- Drain (LZ4FrameReader.cs:98-112) */
-            const uint32_t n = count < pending ? (uint32_t)count : pending;
-            wave_sync();
-            wave_copy(out + offset, buf + tail - pending, n, lane);
-            bytes_read += n; pending -= n; offset += n; count -= n;
-            if (a.interactive) break;
-        }
-        result = (int64_t)offset;
-    }
-    if (fail) { phase = FR_PHASE_FAILED; code = fail; result = fail; need = 0; awaited = 0; }
-    wave_sync();
-    if (lane == 0) {
-        st->pos += f.at; st->bytesRead = bytes_read; st->clen = clen; st->blocks = blocks;
-        st->phase = phase; st->code = code; st->flg = flg; st->bd = bd; st->bsize = bs;
-        st->pending = pending; st->tail = tail; st->direct = direct;
-        st->stashFill = need ? f.fill : 0u; st->stashWant = need ? awaited : 0u;
-        a.outLen[s] = result;
-        fa.consumed[s] = (int64_t)f.at;
-        fa.need[s] = (int64_t)need;
-    }
+#define FR_LOOP_DICT 0
+#include "k4lz4_frame_feed_loop.hpp"
+#undef FR_LOOP_DICT
 }
 
 /* ---- the fast path for pieces -------------------------------------------------------------------------------------------------
@@ -299,7 +122,9 @@ struct FrFeedFastArgs {
     uint32_t *tail, *want;
 };
 
-__global__ __launch_bounds__(256) void k4_fr_feed_plan_kernel(FrFeedFastArgs fa)
+/* k4_fr_feed_plan_kernel's body; DICT (k4_fr_dict_feed_plan_kernel) as in fr_plan_body */
+template <bool DICT>
+__device__ __forceinline__ void fr_feed_plan_body(const FrFeedFastArgs &fa, const FrDictRows &w)
 {
     const FrFastArgs &a = fa.f;
     const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -309,7 +134,7 @@ __global__ __launch_bounds__(256) void k4_fr_feed_plan_kernel(FrFeedFastArgs fa)
     const long long row0 = s * a.rows;
     const int64_t want = a.r.count[s];
     const FrState *st = (const FrState *)(a.r.store + a.r.storeOff[s]);
-    uint32_t used = 0, tl = 0, tw = 0;
+    uint32_t used = 0, tl = 0, tw = 0, entry1 = 0;
     do {
         if (want <= 0 || a.r.interactive || st->phase == FR_PHASE_FAILED || st->pending != 0 || st->stashFill != 0) break;
         const uint8_t *p = a.r.src + a.r.srcOff[s];
@@ -317,9 +142,12 @@ __global__ __launch_bounds__(256) void k4_fr_feed_plan_kernel(FrFeedFastArgs fa)
         uint64_t pos = 0;
         FrHeader hd{st->flg, st->bd, 0u, st->bsize, st->clen};
         if (st->phase != FR_PHASE_OPEN) {
-            if (end == 0 || fr_parse_header(p, end, a.r.maxBlock, hd) != 0) break;
+            if (end == 0 || fr_parse_header_ids<DICT>(p, end, a.r.maxBlock, hd, w.d, entry1) != 0) break;
             pos += hd.len;
             pl.opened = 1;
+        } else if (DICT) {
+            entry1 = st->dictEntry;
+            if (entry1 > (uint32_t)w.d.nDict) break;
         }
         if (!(hd.flg & FLG_INDEPENDENT)) break;
         const uint64_t bs = (uint64_t)hd.bs, need = (uint64_t)want;
@@ -376,9 +204,17 @@ __global__ __launch_bounds__(256) void k4_fr_feed_plan_kernel(FrFeedFastArgs fa)
     a.plan[s] = pl;
     a.done[s] = FR_PLAN_NONE;
     fa.tail[s] = tl; fa.want[s] = tw;
+    if (DICT) fr_plan_dict_rows(w, s, row0, a.rows, pl.state == FR_PLAN_FAST ? entry1 : 0u);
 }
 
-__global__ __launch_bounds__(64 * FR_WAVES_PER_WG) void k4_fr_feed_commit_kernel(FrFeedFastArgs fa)
+__global__ __launch_bounds__(256) void k4_fr_feed_plan_kernel(FrFeedFastArgs fa)
+{
+    fr_feed_plan_body<false>(fa, FrDictRows{});
+}
+
+/* k4_fr_feed_commit_kernel's body; entry (k4_fr_dict_feed_commit_kernel) as in fr_commit_body */
+template <bool DICT>
+__device__ __forceinline__ void fr_feed_commit_body(const FrFeedFastArgs &fa, const uint32_t *entry)
 {
     const FrFastArgs &a = fa.f;
     const int lane = lane_id();
@@ -430,11 +266,17 @@ __global__ __launch_bounds__(64 * FR_WAVES_PER_WG) void k4_fr_feed_commit_kernel
         st->bytesRead += (uint64_t)pl.nfull * bs + pl.part;
         st->blocks += pl.nblk; st->fastBlocks += pl.nblk;
         st->stashFill = tl; st->stashWant = tw;
+        if (DICT) st->dictEntry = entry[s];
         a.r.outLen[s] = (int64_t)((uint64_t)pl.nfull * bs + pl.part);
         fa.consumed[s] = (int64_t)(pl.posAfter + tl);
         fa.need[s] = tw ? (int64_t)(tw - tl) : 0;
         a.done[s] = FR_PLAN_DONE;
     }
+}
+
+__global__ __launch_bounds__(64 * FR_WAVES_PER_WG) void k4_fr_feed_commit_kernel(FrFeedFastArgs fa)
+{
+    fr_feed_commit_body<false>(fa, nullptr);
 }
 
 }  // namespace k4

@@ -61,6 +61,8 @@ struct FrState {
     FwXxhState scratch;              /* a block checksum in the making */
     uint32_t stashFill;              /* fed records (k4lz4_frame_feed.hpp): bytes of an incomplete field kept behind the buffer */
     uint32_t stashWant;              /* ... and the length with which that field is complete (0: nothing is awaited) */
+    uint32_t dictEntry;              /* calls with a dictionary set (k4lz4_frame_reader_dict.hpp): the entry the open frame's DictID resolved
+                                      * to, + 1 (0: none) -- set where the header is accepted, cleared where the frame closes */
 };
 static_assert(sizeof(FrState) <= (size_t)FR_STATE_BYTES, "FrState outgrew its slot");
 
@@ -142,9 +144,22 @@ __device__ __forceinline__ void fr_xxh_update(FwXxhState *st, const uint8_t *p, 
     wave_sync();
 }
 
-/* ReadHeader (.async.cs:50-108) over h[0 .. left), left >= 1: 0 and the fields, or the code of the first defect */
+/* the dictionary set of a call that has one (k4lz4_frame_reader_dict.hpp): entry e answers to DictID ids[e], its kept
+ * bytes are dict[entryOff[e] .. + entryLen[e]) */
+struct FrDict {
+    const uint8_t *dict;
+    const uint64_t *entryOff;
+    const int32_t *entryLen;
+    const uint32_t *ids;
+    int nDict;
+};
+
+/* ReadHeader (.async.cs:50-108) over h[0 .. left), left >= 1: 0 and the fields, or the code of the first defect.  WITH_IDS: a DictID is
+ * looked up in the call's id table where it is refused otherwise -- entry1 is the first entry whose id equals it, + 1 (0: the frame
+ * names none), FR_DICT when there is none */
 struct FrHeader { uint32_t flg, bd, len; int bs; uint64_t clen; };
-__device__ __forceinline__ int fr_parse_header(const uint8_t *h, uint64_t left, int32_t maxBlock, FrHeader &o)
+template <bool WITH_IDS>
+__device__ __forceinline__ int fr_parse_header_ids(const uint8_t *h, uint64_t left, int32_t maxBlock, FrHeader &o, const FrDict &d, uint32_t &entry1)
 {
     uint64_t at;
     if (left < 4) return FR_EOF;
@@ -164,11 +179,34 @@ __device__ __forceinline__ int fr_parse_header(const uint8_t *h, uint64_t left, 
     if (left - at < 1) return FR_EOF;
     if (((xxh32_short(h + 4, (uint32_t)(at - 4)) >> 8) & 0xffu) != h[at]) return FR_HEADER;
     at += 1;
-    if (o.flg & FLG_DICT) return FR_DICT;
+    if (WITH_IDS) {
+        entry1 = 0u;
+        if (o.flg & FLG_DICT) {
+            const uint32_t id = ld32u(h + at - 5);
+            for (int e = 0; e < d.nDict; e++)
+                if (d.ids[e] == id) { entry1 = (uint32_t)e + 1u; break; }
+            if (!entry1) return FR_DICT;
+        }
+    } else if (o.flg & FLG_DICT) return FR_DICT;
     o.bs = frame_block_size(o.bd);
     if (o.bs > maxBlock) return FR_BLOCK_SIZE;                              /* where the reference creates its decoder */
     o.len = (uint32_t)at;
     return 0;
+}
+__device__ __forceinline__ int fr_parse_header(const uint8_t *h, uint64_t left, int32_t maxBlock, FrHeader &o)
+{
+    uint32_t none;
+    return fr_parse_header_ids<false>(h, left, maxBlock, o, FrDict{}, none);
+}
+
+/* the kept bytes of entry1 - 1 (their end and how many), nothing for entry1 == 0; entry1 <= d.nDict.  The same in every lane. */
+__device__ __forceinline__ uint32_t fr_dict_kept(const FrDict &d, uint32_t entry1, const uint8_t *&end)
+{
+    end = nullptr;
+    if (!entry1) return 0u;
+    const uint32_t len = uni((uint32_t)d.entryLen[entry1 - 1u]);
+    end = d.dict + d.entryOff[entry1 - 1u] + len;
+    return len;
 }
 
 struct FrReadArgs {
@@ -189,162 +227,14 @@ struct FrReadArgs {
 
 constexpr int FR_WAVES_PER_WG = DECODE_WAVES_PER_WG;
 
+/* the loop described at the top: its text is k4lz4_frame_reader_loop.hpp, which k4_fr_dict_read_kernel (k4lz4_frame_reader_dict.hpp)
+ * includes as well, with the dictionary's lines switched on */
 __global__ __launch_bounds__(64 * FR_WAVES_PER_WG) void k4_fr_read_kernel(FrReadArgs a)
 {
     __shared__ uint32_t lds[FR_WAVES_PER_WG][DECODE_LDS_DWORDS];
-    const int lane = lane_id();
-    const uint32_t wave = uni(threadIdx.x >> 6);
-    const long long s = (long long)blockIdx.x * FR_WAVES_PER_WG + (long long)wave;
-    if (s >= a.n) return;
-    if (a.done && a.done[s] == FR_PLAN_DONE) return;
-    const int64_t want = a.count ? a.count[s] : 0;
-    if (want < 0) {                                          /* untouched, as srcLen[s] < 0 in the writer */
-        if (lane == 0) a.outLen[s] = 0;
-        return;
-    }
-    FrState *st = (FrState *)(a.store + a.storeOff[s]);
-    uint8_t *buf = (uint8_t *)st + FR_STATE_BYTES;
-    if (a.op == FR_OP_RESET) {
-        uint32_t *w = (uint32_t *)st;
-        if (lane < (int)(FR_STATE_BYTES / 4)) w[lane] = 0u;
-        if (lane == 0) a.outLen[s] = 0;
-        return;
-    }
-    /* the state, the same in every lane */
-    uint64_t pos = st->pos, bytes_read = st->bytesRead, clen = st->clen, blocks = st->blocks;
-    int phase = st->phase, code = st->code;
-    uint32_t flg = st->flg, bd = st->bd, pending = st->pending, tail = st->tail, direct = st->direct;
-    int bs = st->bsize;
-    wave_sync();
-    if (phase == FR_PHASE_FAILED) {                          /* failed streams stay failed and touch nothing */
-        if (lane == 0) a.outLen[s] = code;
-        return;
-    }
-    const uint8_t *p = a.src + a.srcOff[s];
-    const uint64_t end = a.srcLen[s];
-    uint8_t *out = a.dst ? a.dst + a.dstOff[s] : nullptr;
-    const uint32_t buf_bytes = (uint32_t)fr_buffer_bytes(a.maxBlock);
-    int fail = 0;
-    int64_t result = 0;
-    bool has_frame = phase == FR_PHASE_OPEN;
-
-    /* ---- EnsureHeader -> ReadHeader (.async.cs:46-108) */
-    if (!has_frame && pos < end) {                           /* TryPeek4: nothing left is a clean end (ReaderExtensions.cs:20-21) */
-        FrHeader hd{flg, bd, 0u, bs, clen};
-        fail = fr_parse_header(p + pos, end - pos, a.maxBlock, hd);
-        flg = hd.flg; bd = hd.bd;
-        if (!fail) {
-            clen = hd.clen; bs = hd.bs;
-            if (flg & FLG_CONTENT_SUM) fr_xxh_update(&st->content, p + pos, 0, true, lane);   /* InitializeContentChecksum */
-            pos += hd.len;
-            pending = 0; tail = 0;
-            phase = FR_PHASE_OPEN;
-            has_frame = true;
-        }
-    }
-
-    if (!fail && a.op == FR_OP_OPEN) result = has_frame ? 1 : 0;
-    if (!fail && a.op == FR_OP_READ && has_frame) {
-        const bool chained = !(flg & FLG_INDEPENDENT);
-        uint64_t offset = 0, count = (uint64_t)want;
-        while (count > 0) {
-            if (pending == 0) {
-                /* ---- ReadBlock (.async.cs:110-137) */
-                if (end - pos < 4) { fail = FR_EOF; break; }
-                const uint32_t lc = ld32u(p + pos);
-                pos += 4;
-                if (lc == 0) {                                                      /* EndMark */
-                    if (flg & FLG_CONTENT_SUM) {
-                        if (end - pos < 4) { fail = FR_EOF; break; }
-                        const uint32_t stored = ld32u(p + pos);
-                        pos += 4;
-                        if (fw_xxh32_digest(st->content) != stored) { fail = FR_CONTENT_SUM; break; }
-                    }
-                    phase = FR_PHASE_NONE;                                          /* CloseFrame: this read ends with what it has */
-                    break;
-                }
-                const uint32_t sn = lc & 0x7fffffffu;
-                const bool raw = (lc & 0x80000000u) != 0;
-                if (sn > (uint32_t)bs) { fail = FR_BLOCK; break; }                  /* does not fit AllocBuffer(blockSize): see above */
-                if (end - pos < sn) { fail = FR_EOF; break; }
-                const uint8_t *payload = p + pos;
-                pos += sn;
-                if (flg & FLG_BLOCK_SUM) {
-                    if (end - pos < 4) { fail = FR_EOF; break; }
-                    const uint32_t stored = ld32u(p + pos);
-                    pos += 4;
-                    fr_xxh_update(&st->scratch, payload, sn, true, lane);
-                    if (fw_xxh32_digest(st->scratch) != stored) { fail = FR_BLOCK_SUM; break; }
-                }
-                blocks++;
-                /* ---- InjectOrDecode */
-                uint32_t got = 0;
-                const uint8_t *made = buf;                                          /* where the block's bytes are */
-                bool to_dst = false;
-                if (chained) {
-                    /* LZ4ChainDecoder.Prepare / Inject: the block goes behind the bytes so far; the last 64 KiB move to the front first
-                     * when it would not fit */
-                    const uint32_t need = raw ? sn : (uint32_t)bs;
-                    if (tail + need > buf_bytes) {
-                        const uint32_t keep = tail < FR_HISTORY ? tail : FR_HISTORY;
-                        wave_sync();
-                        wave_shift_down(buf, buf + tail - keep, keep, lane);
-                        tail = keep;
-                    }
-                    made = buf + tail;
-                }
-                if (raw) {
-                    /* Inject: LZ4BlockDecoder.cs:58-71 (<= blockSize + 8), LZ4ChainDecoder.cs:64-93 (<= max(blockSize, 64 KiB)): the
-                     * stored length is at most blockSize here.  Nothing (0x80000000) ends the read without closing the frame */
-                    got = sn;
-                    if (!chained && count >= sn) { to_dst = true; made = out + offset; }
-                    wave_sync();
-                    if (sn) wave_copy((uint8_t *)made, payload, sn, lane);
-                    wave_sync();
-                } else {
-                    const int cap = chained ? bs : bs + 8;
-                    DecodeDict dict{nullptr, 0u, 0};
-                    if (chained && tail) {
-                        const uint32_t hist = tail < FR_HISTORY ? tail : FR_HISTORY;
-                        dict = DecodeDict{made, hist >= 65535u ? 65536u : hist, 1};
-                    }
-                    if (!chained && count >= (uint64_t)cap) { to_dst = true; made = out + offset; }
-                    wave_sync();
-                    const int ret = decode_block(payload, (int)sn, (uint8_t *)made, cap, lane, lds[wave], nullptr, false, dict);
-                    wave_sync();
-                    /* LZ4ChainDecoder.Decode: < 0 throws, 0 is a block of nothing; LZ4BlockDecoder.Decode through LZ4Codec.Decode: <= 0
-                     * is -1 and throws (LZ4BlockDecoder.cs:49-51) */
-                    if (ret < 0 || (!chained && ret == 0)) { fail = FR_BLOCK; break; }
-                    got = (uint32_t)ret;
-                }
-                if (chained) tail += got; else if (!to_dst) tail = got;
-                if ((flg & FLG_CONTENT_SUM) && got) fr_xxh_update(&st->content, made, got, false, lane);   /* UpdateContentChecksum */
-                if (got == 0) break;                                                /* .async.cs:162-163: the frame stays open */
-                if (to_dst) {                                                       /* decoded in place: Drain has nothing to move */
-                    direct++;
-                    bytes_read += got; offset += got; count -= got;
-                    if (a.interactive) break;
-                    continue;
-                }
-                pending = got;
-            }
-            /* ---- Drain (LZ4FrameReader.cs:98-112) */
-            const uint32_t n = count < pending ? (uint32_t)count : pending;
-            wave_sync();
-            wave_copy(out + offset, buf + tail - pending, n, lane);
-            bytes_read += n; pending -= n; offset += n; count -= n;
-            if (a.interactive) break;
-        }
-        result = (int64_t)offset;
-    }
-    if (fail) { phase = FR_PHASE_FAILED; code = fail; result = fail; }
-    wave_sync();
-    if (lane == 0) {
-        st->pos = pos; st->bytesRead = bytes_read; st->clen = clen; st->blocks = blocks;
-        st->phase = phase; st->code = code; st->flg = flg; st->bd = bd; st->bsize = bs;
-        st->pending = pending; st->tail = tail; st->direct = direct;
-        a.outLen[s] = result;
-    }
+#define FR_LOOP_DICT 0
+#include "k4lz4_frame_reader_loop.hpp"
+#undef FR_LOOP_DICT
 }
 
 /* ---- the fast path for what real writers produce: independent-block frames whose blocks are full -------------
@@ -386,7 +276,34 @@ struct FrFastArgs {
 
 __host__ __device__ inline long long fr_table_rows(long long maxCount) { return maxCount > 0 ? maxCount / 65536 + 2 : 0; }
 
-__global__ __launch_bounds__(256) void k4_fr_plan_kernel(FrFastArgs a)
+/* the fast path's words of a call with a dictionary set: the batch decoder's dictionary arguments for the rows into dst and for the
+ * straddling blocks, and what the plan resolved for the commit to store */
+struct FrDictRows {
+    FrDict d;
+    uint64_t *dictOff;               /* per row */
+    int32_t *dictLen;
+    signed char *dictMode;
+    uint64_t *sDictOff;              /* per stream: the straddling block */
+    int32_t *sDictLen;
+    signed char *sDictMode;
+    uint32_t *entry;                 /* per stream: the frame's entry + 1 (0: none) */
+};
+
+/* every row of stream s and its straddling block decode against entry1 - 1's kept bytes -- the set's memory is never the bytes in
+ * front of a target (mode 2) */
+__device__ __forceinline__ void fr_plan_dict_rows(const FrDictRows &w, long long s, long long row0, long long rows, uint32_t entry1)
+{
+    const uint64_t off = entry1 ? w.d.entryOff[entry1 - 1u] : 0ull;
+    const int32_t len = entry1 ? w.d.entryLen[entry1 - 1u] : 0;
+    for (long long j = 0; j < rows; j++) { w.dictOff[row0 + j] = off; w.dictLen[row0 + j] = len; w.dictMode[row0 + j] = 2; }
+    w.sDictOff[s] = off; w.sDictLen[s] = len; w.sDictMode[s] = 2;
+    w.entry[s] = entry1;
+}
+
+/* k4_fr_plan_kernel's body.  DICT (k4_fr_dict_plan_kernel): the walk resolves a DictID when it reads a header, or takes the entry the
+ * open frame has; a stored entry the set does not have is the general reader's to report */
+template <bool DICT>
+__device__ __forceinline__ void fr_plan_body(const FrFastArgs &a, const FrDictRows &w)
 {
     const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
     if (s >= a.r.n) return;
@@ -395,7 +312,7 @@ __global__ __launch_bounds__(256) void k4_fr_plan_kernel(FrFastArgs a)
     const long long row0 = s * a.rows;
     const int64_t want = a.r.count[s];
     const FrState *st = (const FrState *)(a.r.store + a.r.storeOff[s]);
-    uint32_t used = 0;
+    uint32_t used = 0, entry1 = 0;
     do {
         if (want <= 0 || a.r.interactive || st->phase == FR_PHASE_FAILED || st->pending != 0) break;
         const uint8_t *p = a.r.src + a.r.srcOff[s];
@@ -403,9 +320,12 @@ __global__ __launch_bounds__(256) void k4_fr_plan_kernel(FrFastArgs a)
         uint64_t pos = st->pos;
         FrHeader hd{st->flg, st->bd, 0u, st->bsize, st->clen};
         if (st->phase != FR_PHASE_OPEN) {
-            if (pos >= end || fr_parse_header(p + pos, end - pos, a.r.maxBlock, hd) != 0) break;
+            if (pos >= end || fr_parse_header_ids<DICT>(p + pos, end - pos, a.r.maxBlock, hd, w.d, entry1) != 0) break;
             pos += hd.len;
             pl.opened = 1;
+        } else if (DICT) {
+            entry1 = st->dictEntry;
+            if (entry1 > (uint32_t)w.d.nDict) break;
         }
         if (!(hd.flg & FLG_INDEPENDENT)) break;
         const uint64_t bs = (uint64_t)hd.bs, need = (uint64_t)want;
@@ -451,9 +371,17 @@ __global__ __launch_bounds__(256) void k4_fr_plan_kernel(FrFastArgs a)
     for (long long j = used; j < a.rows; j++) { a.srcLen[row0 + j] = 0; a.dstCap[row0 + j] = 0; a.hlen[row0 + j] = 0; a.srcOff[row0 + j] = 0; a.dstOff[row0 + j] = 0; }
     a.plan[s] = pl;
     a.done[s] = FR_PLAN_NONE;
+    if (DICT) fr_plan_dict_rows(w, s, row0, a.rows, pl.state == FR_PLAN_FAST ? entry1 : 0u);
 }
 
-__global__ __launch_bounds__(64 * FR_WAVES_PER_WG) void k4_fr_commit_kernel(FrFastArgs a)
+__global__ __launch_bounds__(256) void k4_fr_plan_kernel(FrFastArgs a)
+{
+    fr_plan_body<false>(a, FrDictRows{});
+}
+
+/* k4_fr_commit_kernel's body.  entry (k4_fr_dict_commit_kernel): per stream the word the plan resolved, committed with the state */
+template <bool DICT>
+__device__ __forceinline__ void fr_commit_body(const FrFastArgs &a, const uint32_t *entry)
 {
     const int lane = lane_id();
     const long long s = (long long)blockIdx.x * FR_WAVES_PER_WG + (long long)uni(threadIdx.x >> 6);
@@ -500,9 +428,15 @@ __global__ __launch_bounds__(64 * FR_WAVES_PER_WG) void k4_fr_commit_kernel(FrFa
         st->tail = pl.part ? bs : 0u;
         st->bytesRead += (uint64_t)pl.nfull * bs + pl.part;
         st->blocks += pl.nblk; st->fastBlocks += pl.nblk;
+        if (DICT) st->dictEntry = entry[s];
         a.r.outLen[s] = (int64_t)((uint64_t)pl.nfull * bs + pl.part);
         a.done[s] = FR_PLAN_DONE;
     }
+}
+
+__global__ __launch_bounds__(64 * FR_WAVES_PER_WG) void k4_fr_commit_kernel(FrFastArgs a)
+{
+    fr_commit_body<false>(a, nullptr);
 }
 
 /* per stream: bytes read, the open frame's ContentLength (-1: no frame open, or it declares none), phase, code, blocks read, blocks

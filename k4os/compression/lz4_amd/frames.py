@@ -616,6 +616,15 @@ def _dictionary_ids(dictionary):
     return dset, ids
 
 
+def _reader_dictionary(dictionary):
+    """the incremental readers' dictionary=(DictionarySet, ids), or None -> (the set and the id array, kept alive by the reader; the two
+    arguments the _dictset calls take behind their counterparts')"""
+    if dictionary is None:
+        return None, []
+    dset, ids = _dictionary_ids(dictionary)
+    return (dset, ids), [dset.handle, ids.ctypes.data if ids.size else None]
+
+
 DICT_WRITER_REFUSED = ("frames with a predefined dictionary are written at L00_FAST .. L09_HC by the 64-bit engine: the dictionary "
                        "encoders have no witness at L10_OPT and above, nor under Enforce32")
 
@@ -977,11 +986,15 @@ class LZ4FrameReaderBatch:
     frame and at the end of the source, None where the count is None or negative); Open() is one OpenFrame.  The readers' state lives
     in device memory; every call sends the sources up and brings the bytes back (k4lz4_frame_read_batch).  A stream that fails raises
     the reader's exception (the lowest-index one) when raise_errors, else reports None and its K4LZ4_FRAME_* code in LastCodes; it
-    stays failed.  maxBlockSize: the largest block size a frame may declare (the stores are sized by it)."""
+    stays failed.  maxBlockSize: the largest block size a frame may declare (the stores are sized by it).
+    dictionary=(DictionarySet, ids): k4lz4_frame_read_dictset_batch -- frames with a DictID are read against the first entry of the set
+    whose id equals it; without it every DictID is FRAME_DICTIONARY."""
 
-    def __init__(self, sources, maxBlockSize: int = 4 << 20, ctx: Optional[_native.Context] = None, raise_errors: bool = True):
+    def __init__(self, sources, maxBlockSize: int = 4 << 20, ctx: Optional[_native.Context] = None, raise_errors: bool = True,
+                 dictionary=None):
         import torch
         self.ctx = ctx or _native.default_context()
+        self.dictionary, self._dict_args = _reader_dictionary(dictionary)
         self.views = [_ro_view(s, "source") for s in sources]
         self.n = len(self.views)
         self.raise_errors = raise_errors
@@ -1002,10 +1015,11 @@ class LZ4FrameReaderBatch:
             doff[1:] = np.cumsum(caps[:-1])
         dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
         out = np.zeros(max(self.n, 1), np.int64)
-        self.ctx.check(self.ctx.lib.k4lz4_frame_read_batch(
+        call = self.ctx.lib.k4lz4_frame_read_dictset_batch if self.dictionary else self.ctx.lib.k4lz4_frame_read_batch
+        self.ctx.check(call(
             self.ctx.handle, _C.byref(self.record), self.store.data_ptr(), self.store_off.ctypes.data, self.src.ctypes.data,
             self.src_off.ctypes.data, self.src_len.ctypes.data, dst.ctypes.data, doff.ctypes.data, counts.ctypes.data, out.ctypes.data,
-            self.n, op, FREAD_INTERACTIVE if interactive else 0))
+            self.n, op, FREAD_INTERACTIVE if interactive else 0, *self._dict_args))
         out = out[:self.n]
         self.LastCodes = np.where(counts >= 0, np.minimum(out, 0), 0)
         bad = np.flatnonzero(self.LastCodes < 0)
@@ -1055,11 +1069,13 @@ class FrameReaderDevice:
     this call are out[out_off[s] : out_off[s] + out_len[s]], out_len an int64 device tensor (negative: a K4LZ4_FRAME_* code).  With
     out=(buffer, out_off) the bytes go to buffer[out_off[s] : out_off[s] + counts[s]] (host array or device tensor), and with
     device tensors throughout the call touches no host memory.  Asynchronous on the current torch stream: one kernel, no
-    synchronisation; `dc` is a device.DeviceCodec."""
+    synchronisation; `dc` is a device.DeviceCodec.  dictionary=(DictionarySet, ids): k4lz4_frame_read_dictset_batch_device, as
+    LZ4FrameReaderBatch; the ids are a host array and go up with every call."""
 
-    def __init__(self, dc, data, off, length, maxBlockSize: int = 4 << 20):
+    def __init__(self, dc, data, off, length, maxBlockSize: int = 4 << 20, dictionary=None):
         import torch
         self.dc = dc
+        self.dictionary, self._dict_args = _reader_dictionary(dictionary)
         self.data = data
         self.off, self.length = _dev_i64(off, dc.device), _dev_i64(length, dc.device)
         self.n = int(self.off.numel())
@@ -1074,10 +1090,11 @@ class FrameReaderDevice:
         from .device import _dp
         out_len = torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.dc.device)
         if self.n:
-            self.dc.ctx.check(self.dc.lib.k4lz4_frame_read_batch_device(
+            call = self.dc.lib.k4lz4_frame_read_dictset_batch_device if self.dictionary else self.dc.lib.k4lz4_frame_read_batch_device
+            self.dc.ctx.check(call(
                 self.dc.ctx.handle, _C.byref(self.record), _dp(self.store), _dp(self.store_off), _dp(self.data), _dp(self.off),
                 _dp(self.length), _dp(buf), _dp(out_off), _dp(counts), _dp(out_len), self.n, op, FREAD_INTERACTIVE if interactive else 0,
-                int(max_count),
+                int(max_count), *self._dict_args,
                 _C.c_void_p(self.dc._stream())))
         return out_len[:self.n]
 
@@ -1123,11 +1140,13 @@ class LZ4FrameFedReaderBatch:
     bytes to one ReadManyBytes per stream, drops what was consumed and returns the bytes delivered; Need[s] > 0 then says that the
     read is starved: the field it stands at wants that many further bytes, and the same read is to be issued again with the count
     reduced by what it delivered once more has been fed.  ReadAll(counts) does that over what is queued.  Every source byte goes up
-    once.  Errors as LZ4FrameReaderBatch."""
+    once.  Errors and dictionary=(DictionarySet, ids) (k4lz4_frame_read_fed_dictset_batch) as LZ4FrameReaderBatch."""
 
-    def __init__(self, n: int, maxBlockSize: int = 4 << 20, ctx: Optional[_native.Context] = None, raise_errors: bool = True):
+    def __init__(self, n: int, maxBlockSize: int = 4 << 20, ctx: Optional[_native.Context] = None, raise_errors: bool = True,
+                 dictionary=None):
         import torch
         self.ctx = ctx or _native.default_context()
+        self.dictionary, self._dict_args = _reader_dictionary(dictionary)
         self.n = int(n)
         self.raise_errors = raise_errors
         self.record = frame_reader_record(maxBlockSize, self.ctx.lib, fed=True)
@@ -1156,10 +1175,11 @@ class LZ4FrameFedReaderBatch:
             doff[1:] = np.cumsum(caps[:-1])
         dst = np.zeros(max(int(caps.sum()), 1), np.uint8)
         out, consumed, need = (np.zeros(max(n, 1), np.int64) for _ in range(3))
-        self.ctx.check(self.ctx.lib.k4lz4_frame_read_fed_batch(
+        call = self.ctx.lib.k4lz4_frame_read_fed_dictset_batch if self.dictionary else self.ctx.lib.k4lz4_frame_read_fed_batch
+        self.ctx.check(call(
             self.ctx.handle, _C.byref(self.record), self.store.data_ptr(), self.store_off.ctypes.data, src.ctypes.data,
             src_off.ctypes.data, src_len.ctypes.data, final.ctypes.data, dst.ctypes.data, doff.ctypes.data, counts.ctypes.data,
-            out.ctypes.data, consumed.ctypes.data, need.ctypes.data, n, op, FREAD_INTERACTIVE if interactive else 0))
+            out.ctypes.data, consumed.ctypes.data, need.ctypes.data, n, op, FREAD_INTERACTIVE if interactive else 0, *self._dict_args))
         out = out[:n]
         data = [dst[int(doff[i]):int(doff[i]) + max(int(out[i]), 0)].tobytes() if op == FREAD_READ else b"" for i in range(n)]
         return out, data, consumed[:n], need[:n]
@@ -1231,11 +1251,13 @@ class FrameFedReaderDevice:
     """n fed LZ4FrameReaders over pieces in HBM (k4lz4_frame_read_fed_batch_device).  Per call stream s is given
     data[off[s] : off[s] + length[s]], the part of its source it has not consumed yet, and final[s] (None: none is final); read()
     returns (out, out_off, out_len, consumed, need), the last three int64 device tensors.  Arguments as FrameReaderDevice.read;
-    asynchronous on the current torch stream, nothing is read back."""
+    asynchronous on the current torch stream, nothing is read back.  dictionary=(DictionarySet, ids):
+    k4lz4_frame_read_fed_dictset_batch_device, as FrameReaderDevice."""
 
-    def __init__(self, dc, n: int, maxBlockSize: int = 4 << 20):
+    def __init__(self, dc, n: int, maxBlockSize: int = 4 << 20, dictionary=None):
         import torch
         self.dc = dc
+        self.dictionary, self._dict_args = _reader_dictionary(dictionary)
         self.n = int(n)
         self.record = frame_reader_record(maxBlockSize, dc.lib, fed=True)
         self.store_off = torch.from_numpy(_store_offsets(self.n, self.record).astype(np.int64)).to(dc.device)
@@ -1248,10 +1270,11 @@ class FrameFedReaderDevice:
         from .device import _dp
         out_len, consumed, need = (torch.zeros(max(self.n, 1), dtype=torch.int64, device=self.dc.device) for _ in range(3))
         if self.n:
-            self.dc.ctx.check(self.dc.lib.k4lz4_frame_read_fed_batch_device(
+            call = self.dc.lib.k4lz4_frame_read_fed_dictset_batch_device if self.dictionary else self.dc.lib.k4lz4_frame_read_fed_batch_device
+            self.dc.ctx.check(call(
                 self.dc.ctx.handle, _C.byref(self.record), _dp(self.store), _dp(self.store_off), _dp(data), _dp(off), _dp(length),
                 _dp(final), _dp(buf), _dp(out_off), _dp(counts), _dp(out_len), _dp(consumed), _dp(need), self.n, op,
-                FREAD_INTERACTIVE if interactive else 0, int(max_count), _C.c_void_p(self.dc._stream())))
+                FREAD_INTERACTIVE if interactive else 0, int(max_count), *self._dict_args, _C.c_void_p(self.dc._stream())))
         return out_len[:self.n], consumed[:self.n], need[:self.n]
 
     def _pieces(self, off, length, final):
