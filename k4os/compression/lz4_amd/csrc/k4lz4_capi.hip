@@ -56,6 +56,15 @@
 
 constexpr int MAX_PARTS = 8;      /* a big host-pointer call is staged, run and brought back in up to this many parts */
 
+/* What a device form builds on the host and sends up with its launches (a block table, a writer's plan, a list's words): the host
+ * copy is rewritten only after ev says the previous upload of it is over (plan_begin, plan_send).  dev: the grow-only device
+ * scratch the plan is laid out in, grown by grow_scratch. */
+struct PlanUpload {
+    std::vector<uint8_t> host;
+    uint8_t *dev = nullptr; size_t cap = 0;
+    hipEvent_t ev = nullptr;
+};
+
 struct k4lz4_ctx {
     int device = -1;
     std::string error;
@@ -152,11 +161,8 @@ struct k4lz4_ctx {
     k4::ParseCost pcost_fit = k4::PCOST_FIT;      /* K4LZ4_PCOST_FIT: sample,max_rounds,round,slow,seq,group,lazy,long,base (the fields of ParseCost) for trying another fit */
     int parse_waves = 16;                 /* K4LZ4_PARSE_WAVES: blocks per workgroup (= per CU) of the parse kernel, at most PARSE_MAX_WAVES */
     bool trace = false;         /* K4LZ4_TRACE: host-pointer calls print where their time went (stderr) */
-    /* chained HC streams (k4lz4_encode_hc_chain_batch*): the block table, built on the host, and its copy on the device; the
-     * host copy is rewritten only after ev_chain says the previous upload of it is over */
-    std::vector<uint8_t> h_chain;
-    uint8_t *d_chain = nullptr; size_t d_chain_cap = 0;
-    hipEvent_t ev_chain = nullptr;
+    /* chained HC and fast streams (k4lz4_encode_hc_chain_batch*, k4lz4_encode_fast_chain_batch*): the block table */
+    PlanUpload chain_plan;
     /* frame reader (k4lz4_frame_read.hpp): per-frame words and the block table, both grow-only */
     uint8_t *d_fr = nullptr; size_t d_fr_cap = 0;
     uint8_t *d_fb = nullptr; size_t d_fb_cap = 0;
@@ -165,32 +171,75 @@ struct k4lz4_ctx {
     uint8_t *d_frd = nullptr; size_t d_frd_cap = 0;      /* the incremental reader's fast path: plans and block table */
     uint8_t *d_lgr = nullptr; size_t d_lgr_cap = 0;
     uint8_t *d_lga = nullptr; size_t d_lga_cap = 0;
-    /* incremental frame writer (k4lz4_frame_write.hpp): the call's plan, built on the host (rewritten only after ev_fw says the
-     * previous upload is over), and the device scratch it is laid out in with the windows, the arena and the fast-chain states */
-    std::vector<uint8_t> h_fw;
-    uint8_t *d_fw = nullptr; size_t d_fw_cap = 0;
-    hipEvent_t ev_fw = nullptr;
+    /* incremental frame writer (k4lz4_frame_write.hpp): the call's plan, and the device scratch it is laid out in with the windows,
+     * the arena and the fast-chain states.  The LZ4Stream writer, the chain encoder and its open from a set share it. */
+    PlanUpload fw_plan;
     /* messages against shared dictionaries, per family of levels (fast: k4lz4_dict_encode.hpp, 16 KiB of tables per distinct
-     * dictionary; HC: k4lz4_dict_encode_hc.hpp, 256 KiB each and as much per wave of the encode launch).  dev: the tables, the
-     * list's words, the dispatch order and the wave slots, grow-only (dict_layout); host: the copy of the words that goes up,
-     * rewritten only after ev says the previous upload is over; table, kept: which table and what kept length the most recent
-     * call gave every entry of its list (the state queries) -- empty after a call against a k4lz4_dict_set.  The families share
-     * nothing: neither disturbs what the other left for its query. */
+     * dictionary; HC: k4lz4_dict_encode_hc.hpp, 256 KiB each and as much per wave of the encode launch).  plan.dev: the tables,
+     * the list's words, the dispatch order and the wave slots (dict_layout); plan.host: the copy of the words that goes up;
+     * table, kept: which table and what kept length the most recent call gave every entry of its list (the state queries) --
+     * empty after a call against a k4lz4_dict_set.  The families share nothing: neither disturbs what the other left for its
+     * query. */
     struct DictScratch {
-        std::vector<uint8_t> host;
-        uint8_t *dev = nullptr; size_t cap = 0;
-        hipEvent_t ev = nullptr;
+        PlanUpload plan;
         std::vector<uint32_t> table, kept;
     } dict_fast, dict_hc;
     /* k4lz4_decode_dictset_batch_device: the per-message dictionary words k4_dict_pick_kernel writes, and its copy of dstCap; grow-only */
     uint8_t *d_dpick = nullptr; size_t d_dpick_cap = 0;
     /* frames with a DictID (k4lz4_frame_dict.hpp): the call's id table and the entry of every frame; the blocks' dictionary words
-     * and the in-order decoder's windows; both grow-only.  h_fdict: the ids on their way up, rewritten only after ev_fdict */
+     * and the in-order decoder's windows; both grow-only.  fdict_plan: the ids on their way up into d_fdx (it has no scratch of its own) */
     uint8_t *d_fdx = nullptr; size_t d_fdx_cap = 0;
     uint8_t *d_fdb = nullptr; size_t d_fdb_cap = 0;
-    std::vector<uint32_t> h_fdict;
-    hipEvent_t ev_fdict = nullptr;
+    PlanUpload fdict_plan;
 };
+
+/* the switches above, read from the environment once, when a context is created */
+static void read_switches(k4lz4_ctx &c)
+{
+    if (const char *pct = getenv("K4LZ4_SPLIT_PCT")) { const int v = atoi(pct); c.split_pct = v < 1 ? 1 : (v > 100 ? 100 : v); }
+    c.no_pair = getenv("K4LZ4_NO_PAIR") != nullptr;
+    c.prof_gtab = getenv("K4LZ4_PROF_GTAB") != nullptr;
+    c.use_pace = getenv("K4LZ4_NO_PACE") == nullptr;
+    if (const char *e = getenv("K4LZ4_PACE_MIN")) c.pace_min_per_cu = c.parse_pace_min_per_cu = std::max(0, atoi(e));
+    c.parse_pace_queue = getenv("K4LZ4_PACE_QUEUE") != nullptr;
+    if (const char *e = getenv("K4LZ4_DIRECT_SPAN_PCT")) c.direct_span_pct = std::max(100, atoi(e));
+    if (const char *e = getenv("K4LZ4_NO_DIRECT")) c.no_direct = atoi(e) != 0;
+    if (const char *e = getenv("K4LZ4_LDS_FLOOR")) c.lds_floor_per_cu = std::max(0, std::min(8, atoi(e)));
+    if (const char *e = getenv("K4LZ4_COST_PCT")) c.cost_pct = std::max(1, std::min(99, atoi(e)));
+    if (const char *e = getenv("K4LZ4_DEC_PARTS")) c.dec_parts = std::max(2, std::min(MAX_PARTS, atoi(e)));
+    if (const char *e = getenv("K4LZ4_DEC_PARTS_DIRECT")) c.dec_parts_direct = std::max(2, std::min(MAX_PARTS, atoi(e)));
+    if (const char *e = getenv("K4LZ4_HOP2_MAX")) c.hop2_max_per_cu = std::max(0, atoi(e));
+    c.hc_chain_parts = getenv("K4LZ4_HC_CHAIN_OLD") == nullptr;
+    c.hc_cand_lds = getenv("K4LZ4_HC_CAND_MEM") == nullptr;
+    if (const char *e = getenv("K4LZ4_HC_CAND_DYNLDS")) c.hc_cand_dynlds = std::max(0, std::min(65536, atoi(e)));
+    if (const char *e = getenv("K4LZ4_HC_SEGS")) { const int v = atoi(e); c.hc_segs = v >= 4 ? 4 : (v >= 2 ? 2 : (v == 1 ? 1 : 0)); }
+    if (const char *e = getenv("K4LZ4_HC_MEM_PCT")) c.hc_mem_pct = std::max(0, std::min(100, atoi(e)));
+    c.use_segments = getenv("K4LZ4_NO_SEGMENTS") == nullptr;
+    if (const char *e = getenv("K4LZ4_SEG_MIN")) c.seg_min = (uint32_t)std::max(65536 + 4096, atoi(e));
+    if (const char *e = getenv("K4LZ4_SEG_TARGET")) c.seg_target = c.seg_target_max = (uint32_t)std::max(8192, atoi(e));
+    if (const char *e = getenv("K4LZ4_SEG_TARGET_MAX")) c.seg_target_max = (uint32_t)std::max(8192, atoi(e));
+    if (const char *e = getenv("K4LZ4_SEG_WARM")) c.seg_warm = (uint32_t)std::max(0, atoi(e));
+    if (const char *e = getenv("K4LZ4_SEG_SPIN_MAX")) c.seg_spin_max = (uint32_t)std::max(0, atoi(e));
+    if (const char *e = getenv("K4LZ4_SEG_DIV")) c.seg_div = (uint32_t)std::max(0, atoi(e));
+    if (const char *e = getenv("K4LZ4_PICKLE_SPLIT_MIN")) c.pickle_split_min = std::max(0, atoi(e));
+    if (const char *e = getenv("K4LZ4_STAGE_THREADS")) c.stage_threads = std::max(0, std::min(63, atoi(e) - 1));
+    c.use_parse = getenv("K4LZ4_NO_PARSE") == nullptr;
+    c.parse_queue = getenv("K4LZ4_PARSE_QUEUE") != nullptr;
+    c.parse_persist = getenv("K4LZ4_NO_PERSIST") == nullptr;
+    c.parse_big = getenv("K4LZ4_NO_PARSE_BIG") == nullptr;
+    c.parse_seg = getenv("K4LZ4_NO_PARSE_SEG") == nullptr;
+    c.hc_records = getenv("K4LZ4_NO_HC_RECORDS") == nullptr;
+    c.parse_pcost = getenv("K4LZ4_NO_PCOST") == nullptr || getenv("K4LZ4_PCOST") != nullptr;
+    if (const char *e = getenv("K4LZ4_PCOST_FIT")) {
+        unsigned v[9];
+        if (sscanf(e, "%u,%u,%u,%u,%u,%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8]) == 9 && v[0] >= k4::PARSE_MIN_LEN && v[0] < 65536u)
+            c.pcost_fit = k4::ParseCost{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
+    }
+    c.parse_migrate = getenv("K4LZ4_NO_MIGRATE") == nullptr;
+    c.parse_inline_emit = getenv("K4LZ4_NO_INLINE_EMIT") == nullptr;
+    if (const char *e = getenv("K4LZ4_PARSE_WAVES")) c.parse_waves = std::max(1, std::min(k4::PARSE_MAX_WAVES, atoi(e)));
+    c.trace = getenv("K4LZ4_TRACE") != nullptr;
+}
 
 /* k4lz4_dict_set: one device allocation that nothing writes after create.  Carved at 64-byte steps in this order:
  * the kept bytes of every distinct dictionary; the entries' words for the decoders; per family the words and tables its load and
@@ -380,6 +429,26 @@ int grow_scratch(k4lz4_ctx *ctx, uint8_t **p, size_t *cap, size_t need)
 {
     if (need > *cap && ctx->busy) K4_HIP(ctx, hipEventSynchronize(ctx->ev_busy));
     return grow(ctx, p, cap, need, false);
+}
+
+/* The plan upload, first half: the previous upload of p's host copy is over (the event is made on first use), and the copy has
+ * `bytes` bytes -- zeroed: all of them 0; otherwise what was there stays and the caller writes every byte it sends. */
+int plan_begin(k4lz4_ctx *ctx, PlanUpload &p, size_t bytes, bool zeroed)
+{
+    if (!p.ev) K4_HIP(ctx, hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
+    else K4_HIP(ctx, hipEventSynchronize(p.ev));
+    try { if (zeroed) p.host.assign(bytes, 0); else p.host.resize(bytes); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    return K4LZ4_OK;
+}
+
+/* ... second half: the first `bytes` of the host copy go to dev on `stream`, behind the context's earlier work, and the event
+ * says when they have left. */
+int plan_send(k4lz4_ctx *ctx, PlanUpload &p, void *dev, size_t bytes, hipStream_t stream)
+{
+    K4_HIP(ctx, order_after_ctx(ctx, stream));
+    K4_HIP(ctx, hipMemcpyAsync(dev, p.host.data(), bytes, hipMemcpyHostToDevice, stream));
+    K4_HIP(ctx, hipEventRecord(p.ev, stream));
+    return K4LZ4_OK;
 }
 
 int launch(k4lz4_ctx *ctx, Kind kind, const uint8_t *src, const uint64_t *srcOff, const int32_t *srcLen, uint8_t *dst,
@@ -1084,20 +1153,17 @@ int hc_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, con
     if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_hc_chain_batch: outLen has fewer entries than the streams have blocks");
     if (nb == 0) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->ev_chain) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
-    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_chain));        /* the previous upload of the host table is over */
+    PlanUpload &plan = ctx->chain_plan;
     const size_t bytes = (size_t)nb * HcChainPlan::PER_BLOCK;
-    try { ctx->h_chain.resize(bytes); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    if ((rc = plan_begin(ctx, plan, bytes, false)) != K4LZ4_OK) return rc;
     HcChainPlan h;
-    h.place(ctx->h_chain.data(), nb);
+    h.place(plan.host.data(), nb);
     rc = table(&h);
     if (rc != K4LZ4_OK) return rc;
-    if ((rc = grow_scratch(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &plan.dev, &plan.cap, bytes)) != K4LZ4_OK) return rc;
     HcChainPlan d;
-    d.place(ctx->d_chain, nb);
-    K4_HIP(ctx, order_after_ctx(ctx, stream));
-    K4_HIP(ctx, hipMemcpyAsync(ctx->d_chain, ctx->h_chain.data(), bytes, hipMemcpyHostToDevice, stream));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_chain, stream));
+    d.place(plan.dev, nb);
+    if ((rc = plan_send(ctx, plan, plan.dev, bytes, stream)) != K4LZ4_OK) return rc;
     ctx->last_encode_route = K4LZ4_ENCODE_ROUTE_NONE;    /* (this call reaches launch_hc without passing launch_inner) */
     rc = launch_hc(ctx, ENV_NONE, src, d.woff, d.wlen, dst, d.doff, d.cap, outLen, nb, level, 0, stream, h.wlen, d.hist);
     if (rc == K4LZ4_OK && (flags & K4LZ4_FLAG_ALLOW_COPY)) {
@@ -1240,12 +1306,11 @@ int fast_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, c
     if (nb > nBlocks) return fail(ctx, K4LZ4_E_ARG, "k4lz4_encode_fast_chain_batch: outLen has fewer entries than the streams have blocks");
     if (nStreams == 0 || (nb == 0 && !stateOut)) return K4LZ4_OK;
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->ev_chain) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
-    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_chain));        /* the previous upload of the host table is over */
+    PlanUpload &plan = ctx->chain_plan;
     const size_t bytes = FastChainPlan::bytes(nStreams, nb);
-    try { ctx->h_chain.assign(bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    if ((rc = plan_begin(ctx, plan, bytes, true)) != K4LZ4_OK) return rc;
     FastChainPlan h;
-    h.place(ctx->h_chain.data(), nStreams, nb);
+    h.place(plan.host.data(), nStreams, nb);
     rc = table(&h);
     if (rc != K4LZ4_OK) return rc;
     {   /* longest first: a wave that is done takes the next stream (the ticket) */
@@ -1254,12 +1319,10 @@ int fast_chain_run(k4lz4_ctx *ctx, const uint8_t *src, const uint64_t *srcOff, c
         std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return srcLen[x] - (dictLen ? dictLen[x] : 0) > srcLen[y] - (dictLen ? dictLen[y] : 0); });
         memcpy(h.order, ord.data(), ord.size() * 4);
     }
-    if ((rc = grow_scratch(ctx, &ctx->d_chain, &ctx->d_chain_cap, bytes)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &plan.dev, &plan.cap, bytes)) != K4LZ4_OK) return rc;
     FastChainPlan d;
-    d.place(ctx->d_chain, nStreams, nb);
-    K4_HIP(ctx, order_after_ctx(ctx, stream));
-    K4_HIP(ctx, hipMemcpyAsync(ctx->d_chain, ctx->h_chain.data(), bytes, hipMemcpyHostToDevice, stream));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_chain, stream));
+    d.place(plan.dev, nStreams, nb);
+    if ((rc = plan_send(ctx, plan, plan.dev, bytes, stream)) != K4LZ4_OK) return rc;
     k4::FastChainArgs a{};
     a.src = src; a.soff = d.soff; a.slen = d.slen; a.first = d.first; a.nblk = d.nblk; a.idx0 = d.idx0; a.dict_end = d.dict_end; a.order = d.order;
     a.bpos = d.bpos; a.blen = d.blen; a.bdict = d.bdict; a.doff = d.doff; a.cap = d.cap; a.dst = dst; a.outLen = outLen;
@@ -1565,7 +1628,7 @@ struct DictSource {
     const uint8_t *dict; const uint64_t *dictOff; const int32_t *dictLen; int32_t nDict;
 };
 
-/* a family's scratch (k4lz4_ctx::DictScratch::dev), at 64-byte steps in this order: [ticket, hist] [tables] [per table: keptOff,
+/* a family's scratch (k4lz4_ctx::DictScratch::plan.dev), at 64-byte steps in this order: [ticket, hist] [tables] [per table: keptOff,
  * keptLen] [per entry: keptOff, keptLen, table] [cost[n], order[n]] [wave slots].  What goes up from the host lies between the
  * tables and cost[].  A call against a set finds tables and words in the set: nt = nd = 0, and those parts take no room. */
 constexpr size_t DICT_HEAD_WORDS = 64 + 2 * k4::COST_BUCKETS + 16;
@@ -1659,11 +1722,15 @@ void dict_words(const DictList &l, uint64_t *toff, uint32_t *tlen, uint64_t *eof
     for (size_t d = 0; d < l.table.size(); d++) { eoff[d] = l.keptOff[d]; elen[d] = l.keptLen[d]; etab[d] = l.table[d]; }
 }
 
-void dict_layout(Carve &c, DictLayout &w, const DictFamily &fam, size_t nt, size_t nd, size_t n, size_t nslots)
+/* returns the bytes that go up from the host: from toff to cost[] */
+size_t dict_layout(Carve &c, DictLayout &w, const DictFamily &fam, size_t nt, size_t nd, size_t n, size_t nslots)
 {
     c.take(w.head, DICT_HEAD_WORDS); c.take(w.tables, nt * fam.table_bytes);
+    const size_t up = c.at;
     c.take(w.toff, nt); c.take(w.tlen, nt); c.take(w.eoff, nd); c.take(w.elen, nd); c.take(w.etab, nd);
+    const size_t up_bytes = c.at - up;
     c.take(w.cost, n); c.take(w.order, n); c.take(w.slots, nslots * fam.table_bytes);
+    return up_bytes;
 }
 
 /* every refusal of the six encode calls that needs no device; b's and s's pointers are the caller's */
@@ -1710,30 +1777,22 @@ int dict_encode_run(k4lz4_ctx *ctx, const DictFamily &fam, int level, const Dict
     const size_t nd = list ? list->table.size() : 0, nt = list ? std::max<size_t>(list->rep.size(), 1) : 0;
     const int64_t wgs = std::min<int64_t>((n + fam.waves_per_wg - 1) / fam.waves_per_wg, (int64_t)ctx->cu_count * fam.wgs_per_cu);
     const size_t nslots = fam.slots ? (size_t)wgs * (size_t)fam.waves_per_wg : 0;
-    if (list) {
-        if (!sc.ev) K4_HIP(ctx, hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming));
-        else K4_HIP(ctx, hipEventSynchronize(sc.ev));               /* the previous upload of the host words is over */
-    }
     DictLayout w;
     Carve m{nullptr};
-    dict_layout(m, w, fam, nt, nd, (size_t)n, nslots);
+    const size_t up_bytes = dict_layout(m, w, fam, nt, nd, (size_t)n, nslots);
     int rc;
-    if ((rc = grow_scratch(ctx, &sc.dev, &sc.cap, m.at + 64)) != K4LZ4_OK) return rc;
-    Carve dv{sc.dev};
+    if (list && (rc = plan_begin(ctx, sc.plan, up_bytes, true)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &sc.plan.dev, &sc.plan.cap, m.at + 64)) != K4LZ4_OK) return rc;
+    Carve dv{sc.plan.dev};
     dict_layout(dv, w, fam, nt, nd, (size_t)n, nslots);
-    const size_t up_bytes = (size_t)((uint8_t *)w.cost - (uint8_t *)w.toff);
     if (list) {
-        try { sc.host.assign(up_bytes, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
-        auto host = [&](auto *p) { return (decltype(p))(sc.host.data() + ((uint8_t *)p - (uint8_t *)w.toff)); };      /* host image of the same layout */
+        auto host = [&](auto *p) { return (decltype(p))(sc.plan.host.data() + ((uint8_t *)p - (uint8_t *)w.toff)); };      /* host image of the same layout */
         dict_words(*list, host(w.toff), host(w.tlen), host(w.eoff), host(w.elen), host(w.etab));
         sc.table = list->table; sc.kept = list->keptLen;
+        if ((rc = plan_send(ctx, sc.plan, w.toff, up_bytes, stream)) != K4LZ4_OK) return rc;
     } else {
         sc.table.clear(); sc.kept.clear();
-    }
-    K4_HIP(ctx, order_after_ctx(ctx, stream));
-    if (list) {
-        K4_HIP(ctx, hipMemcpyAsync(w.toff, sc.host.data(), up_bytes, hipMemcpyHostToDevice, stream));
-        K4_HIP(ctx, hipEventRecord(sc.ev, stream));
+        K4_HIP(ctx, order_after_ctx(ctx, stream));
     }
     K4_HIP(ctx, hipMemsetAsync(w.head, 0, DICT_HEAD_WORDS * 4, stream));
     if (list) fam.load(stream, (unsigned)nt, dict, w.toff, w.tlen, w.tables);
@@ -1814,8 +1873,8 @@ int dict_encode_host(k4lz4_ctx *ctx, const DictFamily &fam, int level, int flags
 const uint8_t *dict_loaded_table(k4lz4_ctx *ctx, const DictFamily &fam, int32_t d)
 {
     const k4lz4_ctx::DictScratch &sc = ctx->*fam.scratch;
-    if (d < 0 || (size_t)d >= sc.table.size() || sc.table[(size_t)d] == 0xffffffffu || !sc.dev) return nullptr;
-    Carve c{sc.dev};
+    if (d < 0 || (size_t)d >= sc.table.size() || sc.table[(size_t)d] == 0xffffffffu || !sc.plan.dev) return nullptr;
+    Carve c{sc.plan.dev};
     DictLayout w;
     dict_layout(c, w, fam, 1, 0, 0, 0);
     return w.tables + fam.table_bytes * sc.table[(size_t)d];
@@ -2099,6 +2158,14 @@ using k4::fw_advance;
 
 size_t fw_take(size_t &at, size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
 
+/* numbers the chunks of the pieces k4_fw_copy_kernel takes (a workgroup per chunk, an empty piece has one); returns their count */
+unsigned long long fw_chunks(k4::FwPiece *p, size_t cnt)
+{
+    unsigned long long c = 0;
+    for (size_t k = 0; k < cnt; k++) { p[k].chunk0 = c; c += std::max<unsigned long long>(1, (p[k].len + k4::FW_CHUNK - 1) / k4::FW_CHUNK); }
+    return c;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2165,49 +2232,7 @@ int k4lz4_ctx_create(k4lz4_ctx **out, int device)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_len[b], hipEventDisableTiming);
     }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->dlq, hipStreamNonBlocking);
-    if (const char *pct = getenv("K4LZ4_SPLIT_PCT")) { const int v = atoi(pct); ctx->split_pct = v < 1 ? 1 : (v > 100 ? 100 : v); }
-    ctx->no_pair = getenv("K4LZ4_NO_PAIR") != nullptr;
-    ctx->prof_gtab = getenv("K4LZ4_PROF_GTAB") != nullptr;
-    ctx->use_pace = getenv("K4LZ4_NO_PACE") == nullptr;
-    if (const char *e = getenv("K4LZ4_PACE_MIN")) ctx->pace_min_per_cu = ctx->parse_pace_min_per_cu = std::max(0, atoi(e));
-    ctx->parse_pace_queue = getenv("K4LZ4_PACE_QUEUE") != nullptr;
-    if (const char *e = getenv("K4LZ4_DIRECT_SPAN_PCT")) ctx->direct_span_pct = std::max(100, atoi(e));
-    if (const char *e = getenv("K4LZ4_NO_DIRECT")) ctx->no_direct = atoi(e) != 0;
-    if (const char *e = getenv("K4LZ4_LDS_FLOOR")) ctx->lds_floor_per_cu = std::max(0, std::min(8, atoi(e)));
-    if (const char *e = getenv("K4LZ4_COST_PCT")) ctx->cost_pct = std::max(1, std::min(99, atoi(e)));
-    if (const char *e = getenv("K4LZ4_DEC_PARTS")) ctx->dec_parts = std::max(2, std::min(MAX_PARTS, atoi(e)));
-    if (const char *e = getenv("K4LZ4_DEC_PARTS_DIRECT")) ctx->dec_parts_direct = std::max(2, std::min(MAX_PARTS, atoi(e)));
-    if (const char *e = getenv("K4LZ4_HOP2_MAX")) ctx->hop2_max_per_cu = std::max(0, atoi(e));
-    ctx->hc_chain_parts = getenv("K4LZ4_HC_CHAIN_OLD") == nullptr;
-    ctx->hc_cand_lds = getenv("K4LZ4_HC_CAND_MEM") == nullptr;
-    if (const char *e = getenv("K4LZ4_HC_CAND_DYNLDS")) ctx->hc_cand_dynlds = std::max(0, std::min(65536, atoi(e)));
-    if (const char *e = getenv("K4LZ4_HC_SEGS")) { const int v = atoi(e); ctx->hc_segs = v >= 4 ? 4 : (v >= 2 ? 2 : (v == 1 ? 1 : 0)); }
-    if (const char *e = getenv("K4LZ4_HC_MEM_PCT")) ctx->hc_mem_pct = std::max(0, std::min(100, atoi(e)));
-    ctx->use_segments = getenv("K4LZ4_NO_SEGMENTS") == nullptr;
-    if (const char *e = getenv("K4LZ4_SEG_MIN")) ctx->seg_min = (uint32_t)std::max(65536 + 4096, atoi(e));
-    if (const char *e = getenv("K4LZ4_SEG_TARGET")) ctx->seg_target = ctx->seg_target_max = (uint32_t)std::max(8192, atoi(e));
-    if (const char *e = getenv("K4LZ4_SEG_TARGET_MAX")) ctx->seg_target_max = (uint32_t)std::max(8192, atoi(e));
-    if (const char *e = getenv("K4LZ4_SEG_WARM")) ctx->seg_warm = (uint32_t)std::max(0, atoi(e));
-    if (const char *e = getenv("K4LZ4_SEG_SPIN_MAX")) ctx->seg_spin_max = (uint32_t)std::max(0, atoi(e));
-    if (const char *e = getenv("K4LZ4_SEG_DIV")) ctx->seg_div = (uint32_t)std::max(0, atoi(e));
-    if (const char *e = getenv("K4LZ4_PICKLE_SPLIT_MIN")) ctx->pickle_split_min = std::max(0, atoi(e));
-    if (const char *e = getenv("K4LZ4_STAGE_THREADS")) ctx->stage_threads = std::max(0, std::min(63, atoi(e) - 1));
-    ctx->use_parse = getenv("K4LZ4_NO_PARSE") == nullptr;
-    ctx->parse_queue = getenv("K4LZ4_PARSE_QUEUE") != nullptr;
-    ctx->parse_persist = getenv("K4LZ4_NO_PERSIST") == nullptr;
-    ctx->parse_big = getenv("K4LZ4_NO_PARSE_BIG") == nullptr;
-    ctx->parse_seg = getenv("K4LZ4_NO_PARSE_SEG") == nullptr;
-    ctx->hc_records = getenv("K4LZ4_NO_HC_RECORDS") == nullptr;
-    ctx->parse_pcost = getenv("K4LZ4_NO_PCOST") == nullptr || getenv("K4LZ4_PCOST") != nullptr;
-    if (const char *e = getenv("K4LZ4_PCOST_FIT")) {
-        unsigned v[9];
-        if (sscanf(e, "%u,%u,%u,%u,%u,%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8]) == 9 && v[0] >= k4::PARSE_MIN_LEN && v[0] < 65536u)
-            ctx->pcost_fit = k4::ParseCost{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
-    }
-    ctx->parse_migrate = getenv("K4LZ4_NO_MIGRATE") == nullptr;
-    ctx->parse_inline_emit = getenv("K4LZ4_NO_INLINE_EMIT") == nullptr;
-    if (const char *e = getenv("K4LZ4_PARSE_WAVES")) ctx->parse_waves = std::max(1, std::min(k4::PARSE_MAX_WAVES, atoi(e)));
-    ctx->trace = getenv("K4LZ4_TRACE") != nullptr;
+    read_switches(*ctx);
     if (e != hipSuccess) { delete ctx; return hip_fail(nullptr, e, "hipStreamCreate"); }
     *out = ctx;
     return K4LZ4_OK;
@@ -2261,19 +2286,14 @@ void k4lz4_ctx_destroy(k4lz4_ctx *ctx)
     if (ctx->d_hc_hash) (void)hipFree(ctx->d_hc_hash);
     if (ctx->d_hc_work) (void)hipFree(ctx->d_hc_work);
     if (ctx->d_hc_meta) (void)hipFree(ctx->d_hc_meta);
-    if (ctx->d_chain) (void)hipFree(ctx->d_chain);
-    if (ctx->d_fw) (void)hipFree(ctx->d_fw);
-    if (ctx->ev_fw) (void)hipEventDestroy(ctx->ev_fw);
-    if (ctx->ev_chain) (void)hipEventDestroy(ctx->ev_chain);
-    for (k4lz4_ctx::DictScratch *sc : {&ctx->dict_fast, &ctx->dict_hc}) {
-        if (sc->dev) (void)hipFree(sc->dev);
-        if (sc->ev) (void)hipEventDestroy(sc->ev);
+    for (PlanUpload *p : {&ctx->chain_plan, &ctx->fw_plan, &ctx->fdict_plan, &ctx->dict_fast.plan, &ctx->dict_hc.plan}) {
+        if (p->dev) (void)hipFree(p->dev);
+        if (p->ev) (void)hipEventDestroy(p->ev);
     }
     if (ctx->d_pk_meta) (void)hipFree(ctx->d_pk_meta);
     if (ctx->d_dpick) (void)hipFree(ctx->d_dpick);
     if (ctx->d_fdx) (void)hipFree(ctx->d_fdx);
     if (ctx->d_fdb) (void)hipFree(ctx->d_fdb);
-    if (ctx->ev_fdict) (void)hipEventDestroy(ctx->ev_fdict);
     delete ctx;
 }
 
@@ -3048,7 +3068,7 @@ int k4lz4_decode_dictset_batch(k4lz4_ctx *ctx, const uint8_t *src, const uint64_
 /* ---- frame reader (k4lz4_frame_read.hpp) ---------------------------------------------------------------- */
 
 /* frames with a DictID against a set (k4lz4_frame_dict.hpp): the refusals, and the call's scratch -- the id table
- * (a host array in both forms, through ctx->h_fdict) and the entry every frame resolves to */
+ * (a host array in both forms, through ctx->fdict_plan) and the entry every frame resolves to */
 constexpr int64_t FRAME_DICT_WAVES_PER_CU = 16;      /* of the in-order decoder, a 64 KiB window each: one residency at four waves per SIMD */
 
 static int frame_dict_args(k4lz4_ctx *ctx, const k4lz4_dict_set *set, const uint32_t *dictIds, const char *what)
@@ -3072,11 +3092,11 @@ static int frame_dict_ids(k4lz4_ctx *ctx, const k4lz4_dict_set *set, const uint3
     Carve dv{ctx->d_fdx};
     layout(dv);
     if (!nd) return K4LZ4_OK;
-    if (!ctx->ev_fdict) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fdict, hipEventDisableTiming));
-    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fdict));        /* the previous upload of the host copy is over */
-    try { ctx->h_fdict.assign(dictIds, dictIds + nd); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
-    K4_HIP(ctx, hipMemcpyAsync(*ids, ctx->h_fdict.data(), nd * 4, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_fdict, st));
+    if ((rc = plan_begin(ctx, ctx->fdict_plan, nd * 4, false)) != K4LZ4_OK) return rc;
+    memcpy(ctx->fdict_plan.host.data(), dictIds, nd * 4);
+    /* (not plan_send: the callers have put st behind the context's work already, in front of their own scratch) */
+    K4_HIP(ctx, hipMemcpyAsync(*ids, ctx->fdict_plan.host.data(), nd * 4, hipMemcpyHostToDevice, st));
+    K4_HIP(ctx, hipEventRecord(ctx->fdict_plan.ev, st));
     return K4LZ4_OK;
 }
 
@@ -3682,12 +3702,11 @@ int k4lz4_frame_write_batch_device(k4lz4_ctx *ctx, k4lz4_frame_writer *w, uint8_
     const size_t total_bytes = at + 64;
 
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->ev_fw) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fw, hipEventDisableTiming));
-    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fw));        /* the previous upload of the host plan is over */
-    try { ctx->h_fw.assign(plan_bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    PlanUpload &plan = ctx->fw_plan;
     int rc;
-    if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, total_bytes)) != K4LZ4_OK) return rc;
-    uint8_t *h = ctx->h_fw.data(), *d = ctx->d_fw;
+    if ((rc = plan_begin(ctx, plan, plan_bytes + 64, true)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &plan.dev, &plan.cap, total_bytes)) != K4LZ4_OK) return rc;
+    uint8_t *h = plan.host.data(), *d = plan.dev;
     k4::FwStream *hs = (k4::FwStream *)(h + o_streams);
     k4::FwHashItem *hh = (k4::FwHashItem *)(h + o_hash);
     k4::FwPiece *hstage = (k4::FwPiece *)(h + o_stage), *hback = (k4::FwPiece *)(h + o_back);
@@ -3752,17 +3771,10 @@ int k4lz4_frame_write_batch_device(k4lz4_ctx *ctx, k4lz4_frame_writer *w, uint8_
             hstage[ks++] = k4::FwPiece{ring + r.pointer, src + srcOff[i], (unsigned long long)len, 0};
         }
     }
-    auto chunks = [](k4::FwPiece *p, int64_t cnt) {
-        unsigned long long c = 0;
-        for (int64_t k = 0; k < cnt; k++) { p[k].chunk0 = c; c += std::max<unsigned long long>(1, (p[k].len + k4::FW_CHUNK - 1) / k4::FW_CHUNK); }
-        return c;
-    };
-    const unsigned long long stage_chunks = chunks(hstage, ks), back_chunks = chunks(hback, kb);
+    const unsigned long long stage_chunks = fw_chunks(hstage, (size_t)ks), back_chunks = fw_chunks(hback, (size_t)kb);
 
     /* ---- enqueue: plan up, hash, stage, encode, write back, records, edges */
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    K4_HIP(ctx, hipMemcpyAsync(d, h, plan_bytes, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
+    if ((rc = plan_send(ctx, plan, d, plan_bytes, st)) != K4LZ4_OK) return rc;
     const k4::FwStream *d_streams = (const k4::FwStream *)(d + o_streams);
     int32_t *d_out = (int32_t *)(d + o_out);
     unsigned long long *d_stored = (unsigned long long *)(d + o_stored), *d_rec = (unsigned long long *)(d + o_rec),
@@ -4130,19 +4142,15 @@ int k4lz4_legacy_write_batch_device(k4lz4_ctx *ctx, k4lz4_legacy_writer *w, uint
     try { k4::ls_w_layout(w, srcLen, dstCap, n, op, code, L); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
     if (L.rows > 0xffffffffll) return fail(ctx, K4LZ4_E_ARG, "k4lz4_legacy_write_batch: more than 2^32 chunks in one call");
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    /* the writers share the plan buffers: the previous upload of a host plan is over before this one is written */
-    if (!ctx->ev_fw) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fw, hipEventDisableTiming));
-    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fw));
-    try { ctx->h_fw.assign(L.plan_bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
+    PlanUpload &plan = ctx->fw_plan;      /* the writers share the plan buffers */
     int rc;
-    if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, L.total)) != K4LZ4_OK) return rc;
-    uint8_t *h = ctx->h_fw.data(), *d = ctx->d_fw;
+    if ((rc = plan_begin(ctx, plan, L.plan_bytes + 64, true)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &plan.dev, &plan.cap, L.total)) != K4LZ4_OK) return rc;
+    uint8_t *h = plan.host.data(), *d = plan.dev;
     k4::ls_w_fill(w, store, storeOff, src, srcOff, srcLen, dstOff, n, op, code, L, h, d);
 
     /* ---- enqueue: plan up, stage, encode (a batch per level), records, assembly, tails, lengths */
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    K4_HIP(ctx, hipMemcpyAsync(d, h, L.plan_bytes, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
+    if ((rc = plan_send(ctx, plan, d, L.plan_bytes, st)) != K4LZ4_OK) return rc;
     k4::LsWriteArgs a{};
     a.streams = (const k4::LsWStream *)(d + L.o_streams); a.n = n; a.rows = L.rows;
     a.cSrc = (const uint64_t *)(d + L.o_src); a.cEnc = (const uint64_t *)(d + L.o_enc); a.cLen = (const int32_t *)(d + L.o_len);
@@ -4603,17 +4611,7 @@ int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, ui
     const bool x32 = (flags & K4LZ4_FLAG_X32) || g_enforce32.load(std::memory_order_relaxed);
     hipStream_t st = (hipStream_t)stream;
     std::vector<k4::FwPiece> stage, back;
-    auto chunks = [](std::vector<k4::FwPiece> &p) {
-        unsigned long long c = 0;
-        for (k4::FwPiece &x : p) { x.chunk0 = c; c += std::max<unsigned long long>(1, (x.len + k4::FW_CHUNK - 1) / k4::FW_CHUNK); }
-        return c;
-    };
-    auto sync_plan = [&]() -> int {
-        K4_HIP(ctx, hipSetDevice(ctx->device));
-        if (!ctx->ev_fw) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fw, hipEventDisableTiming));
-        else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fw));        /* the previous upload of the host plan is over */
-        return K4LZ4_OK;
-    };
+    PlanUpload &plan = ctx->fw_plan;      /* the writers' */
     int rc;
 
     if (op == K4LZ4_CENC_RESET) {
@@ -4621,16 +4619,14 @@ int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, ui
             if (enc[i].kind == 2)
                 stage.push_back(k4::FwPiece{store + storeOff[i], nullptr, sizeof(k4lz4_fast_chain_state), 0});
         if (!stage.empty()) {
-            const unsigned long long c = chunks(stage);
+            const unsigned long long c = fw_chunks(stage.data(), stage.size());
             const size_t bytes = stage.size() * sizeof(k4::FwPiece);
-            if ((rc = sync_plan()) != K4LZ4_OK) return rc;
-            try { ctx->h_fw.assign(bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
-            if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, bytes + 64)) != K4LZ4_OK) return rc;
-            memcpy(ctx->h_fw.data(), stage.data(), bytes);
-            K4_HIP(ctx, order_after_ctx(ctx, st));
-            K4_HIP(ctx, hipMemcpyAsync(ctx->d_fw, ctx->h_fw.data(), bytes, hipMemcpyHostToDevice, st));
-            K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
-            hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)c), dim3(k4::FW_THREADS), 0, st, (const k4::FwPiece *)ctx->d_fw, (long long)stage.size());
+            K4_HIP(ctx, hipSetDevice(ctx->device));
+            if ((rc = plan_begin(ctx, plan, bytes + 64, true)) != K4LZ4_OK) return rc;
+            if ((rc = grow_scratch(ctx, &plan.dev, &plan.cap, bytes + 64)) != K4LZ4_OK) return rc;
+            memcpy(plan.host.data(), stage.data(), bytes);
+            if ((rc = plan_send(ctx, plan, plan.dev, bytes, st)) != K4LZ4_OK) return rc;
+            hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)c), dim3(k4::FW_THREADS), 0, st, (const k4::FwPiece *)plan.dev, (long long)stage.size());
             K4_HIP(ctx, hipGetLastError());
             mark_busy(ctx, st);
         }
@@ -4704,10 +4700,10 @@ int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, ui
                  o_stout = fw_take(at, (size_t)nfast * sizeof(k4lz4_fast_chain_state));
     const size_t total_bytes = at + 64;
 
-    if ((rc = sync_plan()) != K4LZ4_OK) return rc;
-    try { ctx->h_fw.assign(plan_bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
-    if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, total_bytes)) != K4LZ4_OK) return rc;
-    uint8_t *h = ctx->h_fw.data(), *d = ctx->d_fw;
+    K4_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = plan_begin(ctx, plan, plan_bytes + 64, true)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &plan.dev, &plan.cap, total_bytes)) != K4LZ4_OK) return rc;
+    uint8_t *h = plan.host.data(), *d = plan.dev;
     k4::CeStream *hs = (k4::CeStream *)(h + o_streams);
     k4::CeRec *hr = (k4::CeRec *)(h + o_recs);
     k4::CeBlock *hb = (k4::CeBlock *)(h + o_blocks);
@@ -4760,14 +4756,12 @@ int k4lz4_chain_encode_batch_device(k4lz4_ctx *ctx, k4lz4_chain_encoder *enc, ui
         }
     }
     if (stage.size() > npiece_max || back.size() > 2 * (size_t)n) return fail(ctx, K4LZ4_E_ARG, "k4lz4_chain_encode_batch: internal: piece table overflow");
-    const unsigned long long stage_chunks = chunks(stage), back_chunks = chunks(back);
+    const unsigned long long stage_chunks = fw_chunks(stage.data(), stage.size()), back_chunks = fw_chunks(back.data(), back.size());
     if (!stage.empty()) memcpy(h + o_stage, stage.data(), stage.size() * sizeof(k4::FwPiece));
     if (!back.empty()) memcpy(h + o_back, back.data(), back.size() * sizeof(k4::FwPiece));
 
     /* ---- enqueue: plan up, stage, encode, write back, place */
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    K4_HIP(ctx, hipMemcpyAsync(d, h, plan_bytes, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
+    if ((rc = plan_send(ctx, plan, d, plan_bytes, st)) != K4LZ4_OK) return rc;
     int32_t *d_out = (int32_t *)(d + o_out);
     if (!stage.empty())
         hipLaunchKernelGGL(k4::k4_fw_copy_kernel, dim3((unsigned)stage_chunks), dim3(k4::FW_THREADS), 0, st, (const k4::FwPiece *)(d + o_stage), (long long)stage.size());
@@ -4948,15 +4942,12 @@ int k4lz4_chain_encoder_open_dictset_device(k4lz4_ctx *ctx, k4lz4_chain_encoder 
     hipStream_t st = (hipStream_t)stream;
     int rc;
     K4_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->ev_fw) K4_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fw, hipEventDisableTiming));
-    else K4_HIP(ctx, hipEventSynchronize(ctx->ev_fw));           /* the previous upload of the host plan is over */
-    try { ctx->h_fw.assign(bytes + 64, 0); } catch (...) { return fail(ctx, K4LZ4_E_NOMEM, "out of host memory"); }
-    if ((rc = grow_scratch(ctx, &ctx->d_fw, &ctx->d_fw_cap, bytes + 64)) != K4LZ4_OK) return rc;
-    memcpy(ctx->h_fw.data(), rows.data(), bytes);
-    K4_HIP(ctx, order_after_ctx(ctx, st));
-    K4_HIP(ctx, hipMemcpyAsync(ctx->d_fw, ctx->h_fw.data(), bytes, hipMemcpyHostToDevice, st));
-    K4_HIP(ctx, hipEventRecord(ctx->ev_fw, st));
-    hipLaunchKernelGGL(k4::k4_ce_open_kernel, dim3((unsigned)n), dim3(k4::OPEN_WAVE), 0, st, (const k4::CeOpenStream *)ctx->d_fw, store,
+    PlanUpload &plan = ctx->fw_plan;      /* the writers' */
+    if ((rc = plan_begin(ctx, plan, bytes + 64, true)) != K4LZ4_OK) return rc;
+    if ((rc = grow_scratch(ctx, &plan.dev, &plan.cap, bytes + 64)) != K4LZ4_OK) return rc;
+    memcpy(plan.host.data(), rows.data(), bytes);
+    if ((rc = plan_send(ctx, plan, plan.dev, bytes, st)) != K4LZ4_OK) return rc;
+    hipLaunchKernelGGL(k4::k4_ce_open_kernel, dim3((unsigned)n), dim3(k4::OPEN_WAVE), 0, st, (const k4::CeOpenStream *)plan.dev, store,
                        (const uint8_t *)set->buf, (long long)n);
     K4_HIP(ctx, hipGetLastError());
     mark_busy(ctx, st);
